@@ -7,7 +7,12 @@ already resident in HBM; the CSR hit lists are left in HBM.  Index construction 
 outside the timed region (the reference's own timer also starts after index load,
 src/guidescan.cxx:239).
 
-    python bench.py --gpus N --steps K --warmup W [--workload chr1|hg38|saccer3]
+    python bench.py --gpus N --steps K --warmup W [--workload chr1|hg38|saccer3] [--dump-outputs DIR] [--full]
+
+A plain run sets up (genome, index, guides), warms up, times the K steps and prints one
+JSON line.  --full adds everything else the bench measures or checks: the roofline (the
+reference-order walk and the counting passes), the side steps, the CPU baseline and the
+extra rows.  --dump-outputs DIR writes what the last timed step returned as .npy files.
 
 N>1: launched by torch.distributed.run, one rank per GPU; the index is replicated
 into every GPU's HBM and each rank enumerates its own shard of the guide batch
@@ -30,6 +35,8 @@ for p in (str(ROOT), str(ROOT / "tests")):
         sys.path.insert(0, p)
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
+GUIDE_POOL = 4_000_000  # guides drawn at most per rank (see main: a longer run cycles through the sets drawn)
+DUMP_BYTES = 64_000_000   # --dump-outputs: at most this much in all (64 MB)
 
 WORKLOADS = {
     # name: (chromosome lengths, guides per step per GPU, base probabilities)
@@ -64,7 +71,8 @@ def main():
     ap.add_argument("--workload", default=os.environ.get("GS_BENCH_WORKLOAD", "hg38"))
     ap.add_argument("--mismatches", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="guides per step per GPU (0 = workload default)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="guides timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="guides timed on the CPU oracle (0 = skip; default: an automatic sample with --full, none without)")
     ap.add_argument("--cpu-kind", choices=["auto", "port", "reference"], default="auto",
                     help="cpu_baseline: the reference itself (oracle/_ref/gs_ref_enumerate, compiled "
                          "from the reference's sources; its SDSL index files are written first, about "
@@ -87,7 +95,8 @@ def main():
     ap.add_argument("--hwpopcnt", action="store_true", help="also time the reference built with hardware POPCNT")
     ap.add_argument("--extra-rows", choices=["auto", "on", "off", "e2e"], default="auto",
                     help="after the headline: the repeat-rich genome at <= 3 mismatches and <= 6 mismatches + CFD on this "
-                         "genome, 20 k guides each (auto: with the default hg38 workload on one GPU; e2e: the end-to-end row alone)")
+                         "genome, 20 k guides each (auto: with --full and the default hg38 workload on one GPU; e2e: the "
+                         "end-to-end row alone)")
     ap.add_argument("--e2e-guides", type=int, default=1_000_000,
                     help="guides of the end-to-end row among the extra rows (the built `guidescan enumerate`, kmers CSV -> CSV; 0 = skip)")
     ap.add_argument("--n-gaps", type=int, default=0,
@@ -95,7 +104,16 @@ def main():
                          "three literal-N windows per run and strand for k_search to look through)")
     ap.add_argument("--verify", action="store_true",
                     help="after timing, check full-size properties of the last batch (on-target found, order)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the roofline (reference-order walk, counting passes), the side steps, the CPU "
+                         "baseline and the extra rows (extra-rows auto); without it a run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (CSR hit counts and hits; CFD and "
+                         "specificity with --score) as DIR/<name>.npy in float64/float32, at most 64 MB (a fixed, seeded "
+                         "sample of the guides when the hits are more)")
     args = ap.parse_args()
+    if args.cpu_sample is None:
+        args.cpu_sample = -1 if args.full else 0
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` by itself: this process never touches the GPU; it starts the
@@ -137,39 +155,63 @@ def main():
         for at in np.sort(rng.integers(1_000_000, text.shape[0] - 1_000_000, size=args.n_gaps)):
             text[at:at + int(rng.integers(100, 50_000))] = ord("N")
     t_gen = time.time() - t0
-    t0 = time.time()
-    gidx = api.GenomeIndex.build(text, device=local_rank)
-    torch.cuda.synchronize()
-    t_index = time.time() - t0
-    # HBM left on this rank's GPU next to the index (RCCL's buffers exist by now: the rendezvous and the
-    # barriers of shared_genome ran before the build), again after the timed steps (PAM-pair tables + workspace)
-    free_after_index = int(torch.cuda.mem_get_info()[0])
 
     nb = args.steps + args.warmup
     parallel = import_module("guidescan-cli_amd.parallel")
     batch_all = batch * world   # guides per step over all ranks
     if args.scaling == "strong":
-        # one seeded guide set per step for the whole job, rank r takes the contiguous shard r of every step
-        # (src/guidescan.cxx:226-251 deals guides to threads; here to GPUs, each with the whole index)
-        batch_all = batch
-        all_seqs, all_pams, _, _ = synth.sample_guides(text, batch_all * nb, seed=1000)
-        if args.deal:
-            seqs, pams = all_seqs, all_pams   # every rank holds the step's guides and enumerates the chunks it draws
-        else:
-            b = parallel.shard_bounds(batch_all, world)
-            lo, hi = b[rank], b[rank + 1]
-            batch = hi - lo
-            pick = np.concatenate([np.arange(i * batch_all + lo, i * batch_all + hi) for i in range(nb)])
-            seqs, pams = np.ascontiguousarray(all_seqs[pick]), np.ascontiguousarray(all_pams[pick])
-        del all_seqs, all_pams
-    else:
-        # every step and every rank gets its own guides (seeded): shard r of the global batch
-        seqs, pams, _, _ = synth.sample_guides(text, batch * nb, seed=1000 + rank)
+        batch_all = batch   # --batch is the whole job's guides per step
+    per_set = batch_all if args.scaling == "strong" else batch
+    # guide sets drawn: one per step while they come to at most GUIDE_POOL guides, else as many as fit and step i takes
+    # set i mod n_sets (drawing costs seconds per 10^6 guides on one core, a run of many steps would spend minutes on it)
+    n_sets = nb if per_set * nb <= GUIDE_POOL else max(1, GUIDE_POOL // max(1, per_set))
+    drawn = {}
+
+    def draw_guides():
+        try:
+            if args.scaling == "strong":
+                # one seeded guide set per step for the whole job, rank r takes the contiguous shard r of every step
+                # (src/guidescan.cxx:226-251 deals guides to threads; here to GPUs, each with the whole index)
+                all_seqs, all_pams, _, _ = synth.sample_guides(text, batch_all * n_sets, seed=1000)
+                if args.deal:
+                    drawn["sp"] = all_seqs, all_pams   # every rank holds the step's guides and enumerates the chunks it draws
+                else:
+                    b = parallel.shard_bounds(batch_all, world)
+                    lo, hi = b[rank], b[rank + 1]
+                    pick = np.concatenate([np.arange(i * batch_all + lo, i * batch_all + hi) for i in range(n_sets)])
+                    drawn["sp"] = np.ascontiguousarray(all_seqs[pick]), np.ascontiguousarray(all_pams[pick])
+            else:
+                # every step and every rank gets its own guides (seeded): shard r of the global batch
+                drawn["sp"] = synth.sample_guides(text, batch * n_sets, seed=1000 + rank)[:2]
+        except BaseException as e:
+            drawn["err"] = e
+
+    # the guides are drawn on the host while the index is built on the device
+    import threading
+    drawer = threading.Thread(target=draw_guides)
+    t0 = time.time()
+    drawer.start()
+    try:
+        gidx = api.GenomeIndex.build(text, device=local_rank)
+        torch.cuda.synchronize()
+        t_index = time.time() - t0
+    finally:
+        drawer.join()
+    if "err" in drawn:
+        raise drawn["err"]
+    seqs, pams = drawn.pop("sp")
+    if args.scaling == "strong" and not args.deal:
+        b = parallel.shard_bounds(batch_all, world)
+        batch = b[rank + 1] - b[rank]
+    # HBM left on this rank's GPU next to the index (RCCL's buffers exist by now: the rendezvous and the
+    # barriers of shared_genome ran before the build), again after the timed steps (PAM-pair tables + workspace)
+    free_after_index = int(torch.cuda.mem_get_info()[0])
     d_seqs = torch.from_numpy(seqs).cuda()
     d_pams = torch.from_numpy(pams).cuda()
     L, P = seqs.shape[1], pams.shape[1]
     gs_struct = api.make_genome_structure(names, lengths) if args.score else None
     score_buf = {}
+    last_call = {}   # what the last call returned to its caller (--dump-outputs)
 
     def one_call(s, p, n):
         d_off, d_hits, st = gidx.enumerate_device(s.data_ptr(), n, L, p.data_ptr(), P, mismatches=m)
@@ -181,13 +223,16 @@ def main():
                 score_buf["spec"] = torch.empty(n, dtype=torch.float32, device="cuda")
             gidx.score_device(gs_struct, s.data_ptr(), n, L, P, d_off, d_hits, score_buf["cfd"].data_ptr(),
                               score_buf["spec"].data_ptr())
+        last_call.update(n=n, d_off=d_off, d_hits=d_hits, n_hits=st["n_hits"], cfd=score_buf.get("cfd"),
+                         spec=score_buf.get("spec"))
         return d_off, d_hits, st
 
     busy = {"s": 0.0, "chunks": 0}
 
     def step(i):
-        s = d_seqs[i * batch:(i + 1) * batch]
-        p = d_pams[i * batch:(i + 1) * batch]
+        k = i % n_sets   # the guide set of step i
+        s = d_seqs[k * batch:(k + 1) * batch]
+        p = d_pams[k * batch:(k + 1) * batch]
         if args.scaling == "strong" and args.deal:
             # chunks of the step's guides from the shared counter; what the step returns is the sum over this rank's chunks
             acc = {"st": None, "last": (None, None)}
@@ -216,39 +261,44 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # N_ext is a property of the input under the REFERENCE's traversal
-    # rules.  The timed path skips the input-independent top of the tree through the prefix
-    # table, so it is measured here, untimed, with the reference-order walk on a sample (sized so
-    # that the walk stays around a second: it is ~10^5 extensions per guide at m = 3, 3.5e7 at m = 6).
-    ns = min(batch, args.stream or batch, {0: 20000, 1: 20000, 2: 20000, 3: 20000, 4: 4000}.get(m, 0))
-    if ns:
-        _, _, st_ref = gidx.enumerate_device(d_seqs.data_ptr(), ns, L, d_pams.data_ptr(), P, mismatches=m,
-                                             faithful=True)
-        n_ext_ref_per_guide = st_ref["n_ext"] / ns
-    else:
-        # m >= 5: one item of the walk is 10^7 extensions on ONE wavefront (16 s at m = 6 whatever the
-        # sample); SURVEY App. C's closed form, within 7 % of the measured walk at three genome sizes
-        from math import comb
-        n_rows = float(text.shape[0])
-        n_ext_ref_per_guide = 2.0 * sum(min(1.0, n_rows / 4.0 ** d) * sum(comb(d, k) * 3 ** k for k in range(min(m, d) + 1))
-                                        for d in range(L + 1))
-    # The bytes THIS algorithm asks the memory system for: one untimed pass of the first batch
-    # through the counting instantiation of k_search (same code, plus a tally of the distinct
-    # 64-byte lines every load instruction requests; include/guidescan_amd.h GS_FLAG_COUNT_REQUESTS)
     n_cnt = min(batch, args.stream) if args.stream else batch   # guides of one launch
     launches_per_step = (batch + n_cnt - 1) // n_cnt if n_cnt else 1
-    _, _, st_cnt = gidx.enumerate_device(d_seqs.data_ptr(), n_cnt, L, d_pams.data_ptr(), P, mismatches=m,
-                                         count_requests=True)
-    req = gidx.last_counters()
-    # the same pass once more tallying 128-byte blocks: what the memory system serves as ONE random request (a 128-byte
-    # block read by one instruction costs what a 64-byte one does: tools/gather_bench, profiles/r04_gather_calibration_groups.txt)
-    gidx.set_option("GS_COUNT_SHIFT", "7")
-    try:
-        gidx.enumerate_device(d_seqs.data_ptr(), n_cnt, L, d_pams.data_ptr(), P, mismatches=m, count_requests=True)
-        req128 = gidx.last_counters()
-    finally:
-        gidx.set_option("GS_COUNT_SHIFT", None)
-    n_req128 = sum(req128[k] for k in ("table_lines", "ctx16_lines", "ctx_words", "sa_isa_gathers", "occ_lines"))
+    if args.full:
+        # N_ext is a property of the input under the REFERENCE's traversal
+        # rules.  The timed path skips the input-independent top of the tree through the prefix
+        # table, so it is measured here, untimed, with the reference-order walk on a sample (sized so
+        # that the walk stays around a second: it is ~10^5 extensions per guide at m = 3, 3.5e7 at m = 6).
+        ns = min(batch, args.stream or batch, {0: 20000, 1: 20000, 2: 20000, 3: 20000, 4: 4000}.get(m, 0))
+        if ns:
+            _, _, st_ref = gidx.enumerate_device(d_seqs.data_ptr(), ns, L, d_pams.data_ptr(), P, mismatches=m,
+                                                 faithful=True)
+            n_ext_ref_per_guide = st_ref["n_ext"] / ns
+        else:
+            # m >= 5: one item of the walk is 10^7 extensions on ONE wavefront (16 s at m = 6 whatever the
+            # sample); SURVEY App. C's closed form, within 7 % of the measured walk at three genome sizes
+            from math import comb
+            n_rows = float(text.shape[0])
+            n_ext_ref_per_guide = 2.0 * sum(min(1.0, n_rows / 4.0 ** d) * sum(comb(d, k) * 3 ** k for k in range(min(m, d) + 1))
+                                            for d in range(L + 1))
+        # The bytes THIS algorithm asks the memory system for: one untimed pass of the first batch
+        # through the counting instantiation of k_search (same code, plus a tally of the distinct
+        # 64-byte lines every load instruction requests; include/guidescan_amd.h GS_FLAG_COUNT_REQUESTS)
+        _, _, st_cnt = gidx.enumerate_device(d_seqs.data_ptr(), n_cnt, L, d_pams.data_ptr(), P, mismatches=m,
+                                             count_requests=True)
+        req = gidx.last_counters()
+        # the same pass once more tallying 128-byte blocks: what the memory system serves as ONE random request (a 128-byte
+        # block read by one instruction costs what a 64-byte one does: tools/gather_bench, profiles/r04_gather_calibration_groups.txt)
+        gidx.set_option("GS_COUNT_SHIFT", "7")
+        try:
+            gidx.enumerate_device(d_seqs.data_ptr(), n_cnt, L, d_pams.data_ptr(), P, mismatches=m, count_requests=True)
+            req128 = gidx.last_counters()
+        finally:
+            gidx.set_option("GS_COUNT_SHIFT", None)
+        n_req128 = sum(req128[k] for k in ("table_lines", "ctx16_lines", "ctx_words", "sa_isa_gathers", "occ_lines"))
+    else:
+        # one untimed call on the first launch's guides, as the counting passes above: the handle's one-off work (derived
+        # tables, workspace, slot sizes learnt from a batch) is done before the warm-up, whatever --warmup says
+        gidx.enumerate_device(d_seqs.data_ptr(), n_cnt, L, d_pams.data_ptr(), P, mismatches=m)
 
     for i in range(args.warmup):
         step(i)
@@ -284,6 +334,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:   # before anything else calls the library: its buffers hold the last step's results
+        dump_outputs(args.dump_outputs, last_call, rank)
 
     mem = {"rank": rank, "index_build_s": round(t_index, 1), "free_after_index_bytes": free_after_index,
            "index_bytes_after_steps": int(gidx.device_bytes), "free_after_steps_bytes": int(torch.cuda.mem_get_info()[0]),
@@ -309,19 +361,67 @@ def main():
     # `traffic` is what the memory side actually moved (FETCH_SIZE + WRITE_SIZE from separate
     # rocprofv3 --pmc passes of this command, profiles/traffic.json) - only when that file was
     # recorded with these kernel sources; more than B means re-reads, less means cache hits.
-    lines = {k: req[k] for k in ("table_lines", "ctx16_lines", "ctx_words", "sa_isa_gathers", "occ_lines", "recipe_lines")}
-    # the recipe lists (a few KB, the same for every item) stay in the L2: their lines are reported, not priced
-    n_lines = sum(v for k, v in lines.items() if k != "recipe_lines")
-    alg_bytes_per_launch = 64.0 * n_lines + 16.0 * st_cnt["n_matches"]
-    search_s = (ms_search / (K * launches_per_step)) / 1e3   # one launch
-    achieved = alg_bytes_per_launch / search_s / 1e9 if search_s > 0 else 0.0
-    traffic, traffic_src, issue = recorded_traffic(args.workload, n_cnt, m)
-    if issue:
-        # what binds the kernel when the bytes do not: VALU wave-instructions of the same dispatch (SQ_INSTS_VALU
-        # of a separate --pmc pass) against the SIMDs' issue slots - 4 cycles per wave64 instruction, 1024 SIMDs, 2.4 GHz
-        issue = dict(issue, valu_frac_of_issue_cycles=issue["valu_wave_instructions"] * 4.0 /
-                     (1024 * 2.4e9 * issue["duration_ms"] * 1e-3), source=traffic_src.replace("fetch_size", "sq_wave_cycles").split(" + ")[0])
-    ref_bytes = 128.0 * n_ext_ref_per_guide * n_cnt
+    if args.full:
+        lines = {k: req[k] for k in ("table_lines", "ctx16_lines", "ctx_words", "sa_isa_gathers", "occ_lines", "recipe_lines")}
+        # the recipe lists (a few KB, the same for every item) stay in the L2: their lines are reported, not priced
+        n_lines = sum(v for k, v in lines.items() if k != "recipe_lines")
+        alg_bytes_per_launch = 64.0 * n_lines + 16.0 * st_cnt["n_matches"]
+        search_s = (ms_search / (K * launches_per_step)) / 1e3   # one launch
+        achieved = alg_bytes_per_launch / search_s / 1e9 if search_s > 0 else 0.0
+        traffic, traffic_src, issue = recorded_traffic(args.workload, n_cnt, m)
+        if issue:
+            # what binds the kernel when the bytes do not: VALU wave-instructions of the same dispatch (SQ_INSTS_VALU
+            # of a separate --pmc pass) against the SIMDs' issue slots - 4 cycles per wave64 instruction, 1024 SIMDs, 2.4 GHz
+            issue = dict(issue, valu_frac_of_issue_cycles=issue["valu_wave_instructions"] * 4.0 /
+                         (1024 * 2.4e9 * issue["duration_ms"] * 1e-3), source=traffic_src.replace("fetch_size", "sq_wave_cycles").split(" + ")[0])
+        ref_bytes = 128.0 * n_ext_ref_per_guide * n_cnt
+        roofline = {"bound": "hbm", "kernel": search_kernel_name(gidx), "achieved": achieved, "peak": HBM_PEAK_GBS,
+                    # achieved / frac price the lines each load instruction asks for; on a repeat-rich batch
+                    # neighbouring hits share lines that L2 serves, so the figure can pass the HBM peak -
+                    # `traffic` (PMC) is then the measure of what HBM delivered
+                    "frac_note": ("counted lines exceed what HBM delivered: many are served by L2 (see traffic)"
+                                  if achieved > HBM_PEAK_GBS * 0.8 else None),
+                    "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                    # PMC counters cannot be read from inside the process that is being timed: `traffic` is
+                    # the recorded figure of a separate rocprofv3 --pmc pass of this command with these
+                    # kernel sources (hash checked), or null
+                    "traffic_measured_in_this_run": False,
+                    "traffic_source": traffic_src, "instruction_issue": issue,
+                    # `traffic` is FETCH_SIZE + WRITE_SIZE, and FETCH_SIZE tallies every read request as 64 bytes: the
+                    # requests themselves, and the bytes they brought (a PAM-pair block is one request of 128)
+                    **memory_side_fields(recorded_memory_side(args.workload, n_cnt, m), ms_search / (K * launches_per_step)),
+                    "request_rate_calibration": REQUEST_CALIBRATION,
+                    "alg_bytes_per_launch": alg_bytes_per_launch,
+                    "avg_launch_ms": ms_search / (K * launches_per_step),
+                    "guides_per_launch": n_cnt,
+                    "requests_per_guide": {k: v / n_cnt for k, v in lines.items()},
+                    "random_requests": {
+                        # requests as the memory system counts them: distinct 128-byte aligned blocks per load
+                        # instruction (a PAM-pair block of sixteen 8-byte entries is ONE, not two lines)
+                        "per_guide": n_req128 / n_cnt, "unit": "128-byte aligned blocks per load instruction",
+                        "achieved_per_s": n_req128 / search_s if search_s > 0 else None,
+                        # (counted blocks incl. what the L2s serve; the calibration rates are for independent L2-MISSING blocks:
+                        # no fraction of them is a roofline - round 5's run at k = 13 passed the HBM figure)
+                        "calibration_per_s": [4.8e10, 5.7e10],
+                        # the same from the memory side (blocks the L2 serves are not in it): HBM lines of the recorded
+                        # PMC pass against the 64-byte lines per second a pure 128-byte-block gather reaches (9.6e10)
+                        "hbm_side": ({"lines_per_s": traffic / 64.0 / search_s} if traffic and search_s > 0 else None),
+                        "lines_64_per_guide": n_lines / n_cnt,
+                        "by_kind_per_guide": {k: req128[k] / n_cnt for k in ("table_lines", "ctx16_lines", "ctx_words",
+                                                                              "sa_isa_gathers", "occ_lines")},
+                        "note": "independent random blocks that miss the L2 are served at ~4.8e10 per second from HBM and 5.7e10 "
+                                "from the Infinity Cache whether they are 16, 64 or 128 bytes (tools/gather_calib): a calibration "
+                                "point, not a roof - a kernel's own rate depends on the chains its waves wait in and on the mix"},
+                    # SURVEY 8d's figure, kept for comparison: the bytes the REFERENCE'S traversal
+                    # (128 B per extended node, N_ext from the reference-order walk on a sample) would
+                    # need for this batch.  Not what this kernel does: table, context mask, context
+                    # arrays and two-sided seeding skip that work.
+                    "reference_traversal": {"alg_bytes_per_launch": ref_bytes,
+                                            "n_ext_per_guide": n_ext_ref_per_guide,
+                                            "n_ext_source": f"reference-order walk on {ns} guides" if ns
+                                            else "closed form of SURVEY App. C",
+                                            "bytes_vs_this_algorithm": ref_bytes / alg_bytes_per_launch
+                                            if alg_bytes_per_launch else None}}
     out = {
         "metric": f"guides/sec off-target enum, <={m} mismatches",
         "value": value,
@@ -350,63 +450,18 @@ def main():
                                + (", CFD + specificity in the step" if args.score else ""),
                    "guides_per_step_per_gpu": batch, "guides_per_step": batch_all, "mismatches": m,
                    "parallelism": f"replicated index, guide batch sharded x{world}"},
-        "roofline": {"bound": "hbm", "kernel": search_kernel_name(gidx), "achieved": achieved, "peak": HBM_PEAK_GBS,
-                     # achieved / frac price the lines each load instruction asks for; on a repeat-rich batch
-                     # neighbouring hits share lines that L2 serves, so the figure can pass the HBM peak -
-                     # `traffic` (PMC) is then the measure of what HBM delivered
-                     "frac_note": ("counted lines exceed what HBM delivered: many are served by L2 (see traffic)"
-                                   if achieved > HBM_PEAK_GBS * 0.8 else None),
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     # PMC counters cannot be read from inside the process that is being timed: `traffic` is
-                     # the recorded figure of a separate rocprofv3 --pmc pass of this command with these
-                     # kernel sources (hash checked), or null
-                     "traffic_measured_in_this_run": False,
-                     "traffic_source": traffic_src, "instruction_issue": issue,
-                     # `traffic` is FETCH_SIZE + WRITE_SIZE, and FETCH_SIZE tallies every read request as 64 bytes: the
-                     # requests themselves, and the bytes they brought (a PAM-pair block is one request of 128)
-                     **memory_side_fields(recorded_memory_side(args.workload, n_cnt, m), ms_search / (K * launches_per_step)),
-                     "request_rate_calibration": REQUEST_CALIBRATION,
-                     "alg_bytes_per_launch": alg_bytes_per_launch,
-                     "avg_launch_ms": ms_search / (K * launches_per_step),
-                     "guides_per_launch": n_cnt,
-                     "requests_per_guide": {k: v / n_cnt for k, v in lines.items()},
-                     "random_requests": {
-                         # requests as the memory system counts them: distinct 128-byte aligned blocks per load
-                         # instruction (a PAM-pair block of sixteen 8-byte entries is ONE, not two lines)
-                         "per_guide": n_req128 / n_cnt, "unit": "128-byte aligned blocks per load instruction",
-                         "achieved_per_s": n_req128 / search_s if search_s > 0 else None,
-                         # (counted blocks incl. what the L2s serve; the calibration rates are for independent L2-MISSING blocks:
-                         # no fraction of them is a roofline - round 5's run at k = 13 passed the HBM figure)
-                         "calibration_per_s": [4.8e10, 5.7e10],
-                         # the same from the memory side (blocks the L2 serves are not in it): HBM lines of the recorded
-                         # PMC pass against the 64-byte lines per second a pure 128-byte-block gather reaches (9.6e10)
-                         "hbm_side": ({"lines_per_s": traffic / 64.0 / search_s} if traffic and search_s > 0 else None),
-                         "lines_64_per_guide": n_lines / n_cnt,
-                         "by_kind_per_guide": {k: req128[k] / n_cnt for k in ("table_lines", "ctx16_lines", "ctx_words",
-                                                                               "sa_isa_gathers", "occ_lines")},
-                         "note": "independent random blocks that miss the L2 are served at ~4.8e10 per second from HBM and 5.7e10 "
-                                 "from the Infinity Cache whether they are 16, 64 or 128 bytes (tools/gather_calib): a calibration "
-                                 "point, not a roof - a kernel's own rate depends on the chains its waves wait in and on the mix"},
-                     # SURVEY 8d's figure, kept for comparison: the bytes the REFERENCE'S traversal
-                     # (128 B per extended node, N_ext from the reference-order walk on a sample) would
-                     # need for this batch.  Not what this kernel does: table, context mask, context
-                     # arrays and two-sided seeding skip that work.
-                     "reference_traversal": {"alg_bytes_per_launch": ref_bytes,
-                                             "n_ext_per_guide": n_ext_ref_per_guide,
-                                             "n_ext_source": f"reference-order walk on {ns} guides" if ns
-                                             else "closed form of SURVEY App. C",
-                                             "bytes_vs_this_algorithm": ref_bytes / alg_bytes_per_launch
-                                             if alg_bytes_per_launch else None}},
+        **({"roofline": roofline} if args.full else {}),
         "detail": {"executed_ext_per_guide": n_ext / (batch * K), "hits_per_guide": n_hits / (batch * K),
                    "prefix_table_k": os.environ.get("GS_PREFIX_K", "auto"),
                    "k_search_ms_per_step": per_step_ms,
                    "k_search_ms_min_median_max": spread(per_step_ms),
                    "clocks": gpu_clocks(),
                    "device_ms_total_per_step": ms_total / K, "index_build_s": t_index,
-                   "genome_gen_s": t_gen, "index_bytes": gidx.device_bytes,
-                   "items_two_sided": req["items_two_sided"], "items_one_sided": req["items_one_sided"],
-                   "overflow_items_first_pass": req["overflow_items"], "guides_redone": last_ctr["guides_redone"],
-                   "slots_per_item": req["slots_per_item"], "matches_max_per_item": req["matches_max_per_item"],
+                   "genome_gen_s": t_gen, "index_bytes": gidx.device_bytes, "guide_sets": n_sets,
+                   **({"items_two_sided": req["items_two_sided"], "items_one_sided": req["items_one_sided"],
+                       "overflow_items_first_pass": req["overflow_items"], "slots_per_item": req["slots_per_item"],
+                       "matches_max_per_item": req["matches_max_per_item"]} if args.full else {}),
+                   "guides_redone": last_ctr["guides_redone"],
                    "ordered_device_wide": last_ctr["ordered_device_wide"],
                    "redo_ordered_device_wide": last_ctr["redo_ordered_device_wide"],
                    "overflow_from_arena": last_ctr["overflow_from_arena"],
@@ -416,16 +471,17 @@ def main():
                    "tile_ordering_gave_up": last_ctr["tile_ordering_gave_up"], "per_rank_memory": per_rank},
     }
 
-    if rank == 0:
+    last_set = (nb - 1) % n_sets   # the guide set of the last step
+    if rank == 0 and args.full:
         # the device steps either side of the path (untimed side figures, never part of `value`):
         # CFD/specificity of the last batch's hits and the candidate-guide scan of chromosome 1
         try:
-            out["detail"]["next_rows"] = side_steps(torch, api, gidx, d_seqs, d_pams, batch, nb - 1, L, P, m,
+            out["detail"]["next_rows"] = side_steps(torch, api, gidx, d_seqs, d_pams, batch, last_set, L, P, m,
                                                     text, names, lengths)
         except Exception as e:
             print(f"[bench] side steps failed: {e!r}", file=sys.stderr)
     if args.verify:
-        out["verify"] = verify_last_batch(torch, gidx, d_seqs, d_pams, batch, nb - 1, L, P, m, text, seqs)
+        out["verify"] = verify_last_batch(torch, gidx, d_seqs, d_pams, batch, last_set, L, P, m, text, seqs)
     if rank == 0 and world == 1 and args.cpu_sample != 0:
         kind = args.cpu_kind
         if kind == "auto":
@@ -444,8 +500,8 @@ def main():
                 kind = "port"
         if kind == "port":
             out["cpu_baseline"] = cpu_baseline(text, gidx, seqs, pams, m, args.cpu_sample)
-    want_rows = args.extra_rows in ("on", "e2e") or (args.extra_rows == "auto" and args.workload == "hg38" and m == 3 and world == 1
-                                            and not args.batch and not args.stream and args.cpu_sample != 0)
+    want_rows = args.extra_rows in ("on", "e2e") or (args.extra_rows == "auto" and args.full and args.workload == "hg38" and m == 3
+                                                     and world == 1 and not args.batch and not args.stream and args.cpu_sample != 0)
     if rank == 0 and world == 1 and want_rows:
         # the rows the headline does not show, under the same clock: the deep budget on this genome and the
         # repeat-rich genome (24 k hits per guide: what real hg38's repeat half looks like) - never part of `value`
@@ -460,6 +516,72 @@ def main():
         gidx.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, last, rank=0):
+    """--dump-outputs: what the last timed call handed its caller (CSR offsets + hits in HBM; CFD + specificity with --score),
+    copied back and written as float64/float32 .npy files of at most DUMP_BYTES in all:
+      hit_counts.npy  float64[g]     hits per guide, of every guide (its hits, when written, are the rows of hits.npy
+                                     whose column 0 is its index)
+      hits.npy        float64[h, 4]  guide, position, key >> 32, key & 0xFFFFFFFF (exact: every value is below 2^53)
+      cfd.npy         float32[h]     --score: CFD of each row of hits.npy
+      specificity.npy float32[g]     --score: specificity per guide
+      guides.npy      float64[g]     only when the guides are too many: the fixed, seeded sample of guides written
+    Rows are every hit of the guides, in the library's order; when they would pass the budget, whole guides are taken in a
+    fixed seeded order until it is spent and written in guide order.  Rank r > 0 suffixes its names with _rank<r>."""
+    import ctypes as C
+    n, n_hits = int(last["n"]), int(last["n_hits"])
+    off = np.empty(n + 1, dtype=np.uint64)
+    hits = np.empty(n_hits, dtype=[("pos", "<i8"), ("key", "<u8")])
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    if hip.hipMemcpy(off.ctypes.data, last["d_off"], off.nbytes, 2) != 0 or \
+            (n_hits and hip.hipMemcpy(hits.ctypes.data, last["d_hits"], hits.nbytes, 2) != 0):
+        raise RuntimeError("--dump-outputs: hipMemcpy of the last step's results failed")
+    if int(off[0]) != 0 or int(off[-1]) != n_hits:
+        raise RuntimeError(f"--dump-outputs: offsets end at {int(off[-1])}, the call reported {n_hits} hits")
+    scored = last.get("cfd") is not None
+    files = output_arrays(off, hits, last["cfd"][:n_hits].cpu().numpy() if scored else None,
+                          last["spec"][:n].cpu().numpy() if scored else None)
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, arr in files.items():
+        np.save(d / (f"{name}.npy" if rank == 0 else f"{name}_rank{rank}.npy"), arr)
+
+
+def output_arrays(off, hits, cfd=None, spec=None, budget=DUMP_BYTES):
+    """the arrays of dump_outputs from host copies of the results: off uint64[n+1], hits [("pos", i8), ("key", u8)]"""
+    n = off.shape[0] - 1
+    scored = cfd is not None
+    per_guide = 8 + (4 if scored else 0)
+    guides = np.arange(n)
+    sampled = n * per_guide > budget // 2
+    if sampled:   # a fixed, seeded sample of the guides (the same for every build at this batch size)
+        per_guide += 8
+        guides = np.sort(np.random.Generator(np.random.PCG64(20251016)).choice(n, budget // 2 // per_guide, replace=False))
+    counts = (off[guides + 1] - off[guides]).astype(np.int64)
+    per_row = 32 + (4 if scored else 0)
+    room = (budget - 4096 - guides.size * per_guide) // per_row   # (4 KB: the files' headers)
+    take = guides
+    if counts.sum() > room:   # whole guides in a fixed seeded order until the budget is spent
+        order = np.random.Generator(np.random.PCG64(20251017)).permutation(guides.size)
+        fits = np.cumsum(counts[order]) <= room
+        take = guides[np.sort(order[fits])]
+    starts, ends = off[take].astype(np.int64), off[take + 1].astype(np.int64)
+    lens = ends - starts
+    rows = np.repeat(starts - np.concatenate([[0], np.cumsum(lens)[:-1]]), lens) + np.arange(int(lens.sum()))
+    sel = hits[rows]
+    table = np.empty((rows.size, 4), dtype=np.float64)
+    table[:, 0] = np.repeat(take, lens)
+    table[:, 1] = sel["pos"]
+    table[:, 2] = sel["key"] >> np.uint64(32)
+    table[:, 3] = sel["key"] & np.uint64(0xFFFFFFFF)
+    files = {"hit_counts": counts.astype(np.float64), "hits": table}
+    if scored:
+        files.update(cfd=cfd[rows].astype(np.float32), specificity=spec[guides].astype(np.float32))
+    if sampled:
+        files["guides"] = guides.astype(np.float64)
+    return files
 
 
 def search_kernel_name(gidx):

@@ -93,8 +93,10 @@ def ref():
     if _ref is None:
         so = ORACLE_DIR / "_ref" / "libgs_ref.so"
         if not so.exists():
-            if Path("/root/reference/sdsl/include").is_dir():
+            try:   # oracle/Makefile builds oracle/_ref where it can read the reference tree, and says so where it cannot
                 build_oracle()
+            except (OSError, subprocess.SubprocessError):
+                pass
             if not so.exists():
                 return None
         R = C.CDLL(str(so))

@@ -3,17 +3,20 @@ REFERENCE'S OWN enumerate pipeline compiled in place: oracle/_ref/gs_ref_enumera
 include/genomics/{index,process,printer}.hpp + src/genomics/*.cxx + sdsl csa_wt, built by
 oracle/Makefile from /root/reference with g++ only (oracle/ref_enumerate.cpp says how).
 
-Two kinds of test, CPU only, skipped when oracle/_ref was never built:
+Two kinds of test, CPU only:
  * the committed toy goldens (tests/golden/toy/ref_*) are reproduced byte for byte by this
    repository's own build of the reference (they were first written by the survey phase's cmake
-   build; from here on they are oracle/_ref outputs);
- * on fresh seeded genomes the oracle's whole output file equals the compiled reference's, over
+   build; from here on they are oracle/_ref outputs) - skipped when oracle/_ref was never built;
+ * on seeded genomes the oracle's whole output file equals the compiled reference's, over
    mismatch budgets 0..4, both formats and modes, alt PAMs, --start, --max-off-targets,
-   --threshold and RNA/DNA bulges.
+   --threshold and RNA/DNA bulges: against oracle/_ref where it was built, and always against the
+   size and sha256 of the reference's files recorded in tests/golden/reference/random_cases.json
+   (tools/make_ref_goldens.py).
 The index files the reference loads are written from the oracle's SA/BWT through the compiled
 reference containers (ref_write_index_file; byte-identical to the reference's own `index` output on
 the toy, test_oracle_vs_ref.py)."""
 import hashlib
+import json
 import subprocess
 import tempfile
 from importlib import import_module
@@ -30,8 +33,9 @@ seqio = import_module("guidescan-cli_amd.seqio")
 
 SHIM = ol.ORACLE_DIR / "_ref" / "gs_ref_enumerate"
 ref = ol.ref()
-pytestmark = pytest.mark.skipif(ref is None or not SHIM.exists(),
-                                reason="oracle/_ref not built (no reference tree)")
+needs_ref = pytest.mark.skipif(ref is None or not SHIM.exists(), reason="oracle/_ref not built (no reference tree)")
+RANDOM_SEEDS = [101, 102, 103, 104, 105, 106, 107, 108]
+REF_DIGESTS = ol.ROOT / "tests" / "golden" / "reference" / "random_cases.json"
 
 
 def run_shim(prefix, kmers_csv, out, m=3, fmt="csv", complete=True, alt=(), maxo=-1, thr=-1, start=False,
@@ -81,6 +85,7 @@ def toy_prefix(toy, tmp_path_factory):
     return d / "toy.idx"
 
 
+@needs_ref
 @pytest.mark.parametrize("name", sorted(RUNS))
 def test_compiled_reference_reproduces_committed_goldens(toy, toy_prefix, tmp_path, name):
     cfg = RUNS[name]
@@ -94,6 +99,7 @@ def test_compiled_reference_reproduces_committed_goldens(toy, toy_prefix, tmp_pa
         assert len(got) == int(size) and hashlib.sha256(got).hexdigest() == digest
 
 
+@needs_ref
 def test_compiled_reference_reproduces_config1_goldens(tmp_path):
     """BASELINE config 1 (sacCer3-sized genome regenerated from its seed, 1,000 guides): the
     committed reference files of tests/golden/config1 come out of this repository's own build of
@@ -162,8 +168,16 @@ OPTION_SETS = [
 ]
 
 
-@pytest.mark.parametrize("seed", [101, 102, 103, 104, 105, 106, 107, 108])
+def options_key(cfg):
+    """an option set as it is named in tests/golden/reference/random_cases.json"""
+    return ",".join(f"{k}={'+'.join(v) if isinstance(v, tuple) else v}" for k, v in sorted(cfg.items()))
+
+
+@pytest.mark.parametrize("seed", RANDOM_SEEDS)
 def test_oracle_equals_compiled_reference_on_random_genomes(seed, tmp_path):
+    live = ref is not None and SHIM.exists()
+    recorded = json.loads(REF_DIGESTS.read_text())[str(seed)]
+    assert [r["options"] for r in recorded] == [options_key(c) for c in OPTION_SETS]
     text, names, lengths, rows = random_case(seed)
     prefix = tmp_path / "g.idx"
     kcsv = tmp_path / "kmers.csv"
@@ -172,13 +186,16 @@ def test_oracle_equals_compiled_reference_on_random_genomes(seed, tmp_path):
     kmers = seqio.read_kmers(kcsv)
     oidx = ol.OracleIndex(text)
     try:
-        write_reference_index(oidx, text.shape[0] + 1, prefix, names, lengths)
-        for cfg in OPTION_SETS:
+        if live:
+            write_reference_index(oidx, text.shape[0] + 1, prefix, names, lengths)
+        for cfg, rec in zip(OPTION_SETS, recorded):
             fmt = cfg.get("fmt", "csv")
             complete = cfg.get("complete", True)
             kw = {k: v for k, v in cfg.items() if k not in ("fmt", "complete")}
-            want = run_shim(prefix, kcsv, tmp_path / "out", fmt=fmt, complete=complete, **kw)
             got = oracle_file(oidx, names, lengths, kmers, fmt=fmt, complete=complete, **kw)
-            assert got == want, (seed, cfg)
+            if live:
+                want = run_shim(prefix, kcsv, tmp_path / "out", fmt=fmt, complete=complete, **kw)
+                assert got == want, (seed, cfg)
+            assert (len(got), hashlib.sha256(got).hexdigest()) == (rec["bytes"], rec["sha256"]), (seed, cfg)
     finally:
         oidx.close()

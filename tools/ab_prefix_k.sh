@@ -2,7 +2,7 @@
 # bench.py with the strand tables built at another depth (GS_PREFIX_K: a build-time choice of the index builder)
 # usage: bash tools/ab_prefix_k.sh "<bench args>" k [k ...]
 mkdir -p gpurun_out
-ARGS=$1; shift
+ARGS="--full $1"; shift   # (the roofline's request counts: --full)
 for k in "$@"; do
   GS_PREFIX_K=$k timeout -k 10 300 python bench.py --cpu-sample 0 --steps 4 --warmup 1 --extra-rows off $ARGS > /tmp/abk.json 2> /tmp/abk.err || { echo "k=$k: failed"; tail -3 /tmp/abk.err; continue; }
   python3 - "$k" /tmp/abk.json "$ARGS" <<'PY'

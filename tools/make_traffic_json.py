@@ -6,7 +6,7 @@ FETCH_SIZE / WRITE_SIZE bytes of the timed k_search dispatch and a hash of the k
     tools/make_traffic_json.py TAG WORKLOAD BATCH M FETCH.json WRITE.json [SQ.json]
 
 FETCH.json / WRITE.json are tools/pmc_summary.py outputs of `rocprofv3 --pmc FETCH_SIZE` /
-`--pmc WRITE_SIZE` passes of `bench.py --steps 1 --warmup 0 --cpu-sample 0` (tools/profile_round.sh);
+`--pmc WRITE_SIZE` passes of `bench.py --full --steps 1 --warmup 0 --cpu-sample 0` (tools/profile_round.sh);
 the search dispatches there are: the reference-order walk sample (k_search_walk), the counting pass
 (k_search_count), the timed step, side steps - the first k_search_fast dispatch after the counting
 pass is the timed step.  Counters are in KB."""
@@ -79,7 +79,7 @@ def main():
            "issue": issue,
            "kernel_sha": bench.kernel_stamp(),
            "source": f"profiles/{tag}_pmc_fetch_size.json + {tag}_pmc_write_size.json: rocprofv3 --pmc FETCH_SIZE / "
-                     f"WRITE_SIZE (separate passes, tools/profile_round.sh) of `bench.py --cpu-sample 0`, {which}"}
+                     f"WRITE_SIZE (separate passes, tools/profile_round.sh) of `bench.py --full --cpu-sample 0`, {which}"}
     if ea:
         rd = ea.get("TCC_EA0_RDREQ_sum")
         r32, r64, r128 = ea.get("TCC_EA0_RDREQ_32B_sum"), ea.get("TCC_EA0_RDREQ_64B_sum"), ea.get("TCC_EA0_RDREQ_128B_sum")

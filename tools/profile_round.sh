@@ -17,7 +17,7 @@ SUM=gpurun_out/prof_summary
 rm -rf $OUT   # (a box may be one an earlier call ran on: summaries must not pick up its files)
 mkdir -p $OUT $SUM
 export TMPDIR=/tmp
-ARGS="--workload $WL --mismatches $M --batch $BATCH --cpu-sample 0 --extra-rows off"
+ARGS="--full --workload $WL --mismatches $M --batch $BATCH --cpu-sample 0 --extra-rows off"
 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats -- python3 bench.py $ARGS --steps $(( STEPS > 3 ? STEPS : 3 )) --warmup $(( WARM > 1 ? WARM : 1 )) > $SUM/${NAME}_bench_under_rocprof.json 2> $OUT/stats.err
 echo "stats rc=$?"
 f=$(find $OUT/stats -name '*kernel_stats.csv' | head -1)

@@ -8,7 +8,7 @@ OUT=/tmp/trace_$NAME
 SUM=gpurun_out/prof_summary
 mkdir -p $OUT $SUM
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -f csv -d $OUT -- python3 bench.py --workload $WL --mismatches $M --batch $BATCH --cpu-sample 0 "$@" \
+rocprofv3 --kernel-trace --stats -f csv -d $OUT -- python3 bench.py --full --workload $WL --mismatches $M --batch $BATCH --cpu-sample 0 "$@" \
   > $SUM/${NAME}_trace_bench.json 2> $OUT/err.log
 echo "rc=$? $(tail -c 300 $OUT/err.log)"
 f=$(find $OUT -name '*kernel_stats.csv' | head -1)
