@@ -199,7 +199,7 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_format_guide_ex", "gs_score_device", "gs_score", "gs_kmers_generate", "gs_kmers_get",
            "gs_kmers_free", "gs_format_guide_scored", "gs_index_verify_sa", "gs_index_last_counters", "gs_enumerate_general",
            "gs_index_last_guide_flags", "gs_enumerate_general_pams", "gs_index_save_sa", "gs_index_open_sa", "gs_format_guides_scored", "gs_result_ex_raw_hits",
-           "gs_debug_seed_recipes", "gs_debug_choose_thresholds", "gs_debug_tile_plan", "gs_debug_guide_descriptor", "gs_index_lock", "gs_index_unlock",
+           "gs_debug_seed_recipes", "gs_debug_choose_thresholds", "gs_debug_tile_plan", "gs_debug_search_form", "gs_debug_guide_descriptor", "gs_index_lock", "gs_index_unlock",
            "gs_index_last_sharing", "gs_index_set_option", "gs_index_get_option", "gs_index_prepare"]
 
 
@@ -260,6 +260,27 @@ def tile_plan(records):
     out = (C.c_uint32 * 5)()
     L_.gs_debug_tile_plan(records, out)
     return dict(buckets=out[0], slot=out[1], per=out[2], wave_tile=out[3], max_buckets=out[4])
+
+
+SEARCH_FORM_IN = ("items", "cus", "share_min", "backoff", "main", "walk", "one_chunk", "counting", "spec", "m", "est_heavy",
+                  "est_max", "last_hpass", "last_items", "heavy", "split_share", "split_from", "seed_form")
+
+
+def search_form(**kw):
+    """the search's form for a pass (gs_debug_search_form; host only): dict(estimate, thresh, heavy, split, seed_form, form).
+    Keyword arguments: SEARCH_FORM_IN; the switches default to -1 (not set), split_from to 2^19, the rest to 0."""
+    L_ = lib()
+    L_.gs_debug_search_form.restype = None
+    L_.gs_debug_search_form.argtypes = [C.c_void_p, C.c_void_p]
+    vals = dict(heavy=-1, split_share=-1, seed_form=-1, split_from=1 << 19)
+    vals.update(kw)
+    unknown = set(vals) - set(SEARCH_FORM_IN)
+    if unknown:
+        raise TypeError(f"unknown inputs {sorted(unknown)}")
+    inp = (C.c_int64 * len(SEARCH_FORM_IN))(*[int(vals.get(k, 0)) for k in SEARCH_FORM_IN])
+    out = (C.c_uint32 * 6)()
+    L_.gs_debug_search_form(inp, out)
+    return dict(zip(("estimate", "thresh", "heavy", "split", "seed_form", "form"), (int(x) for x in out)))
 
 
 def make_genome_structure(names, lengths):

@@ -1,8 +1,11 @@
 /*
  * gs_bigorder.hip -- the device-wide ordering of match records: what orders a batch the per-guide tile ordering
- * (gs_tileorder.hip) does not take.  Kernels only; the host side is big_order / big_locate in gs_enumerate.hip.
+ * (gs_tileorder.hip) does not take.  The kernels, then their host side (gs_bigorder_run / gs_bigorder_locate, called by
+ * the batch pipeline in gs_enumerate.hip).
  */
 #include "gs_kernels.h"
+
+#include <rocprim/rocprim.hpp>
 
 /* ---- guides with more matches than an LDS sort can hold: repeat-derived guides at any budget,
  * every guide at <= 6 mismatches on a genome of this size (~5,400 matches per item).  Their match
@@ -353,4 +356,302 @@ __global__ void k_fill_u32(uint32_t *p, uint32_t v, uint32_t n) {
 __global__ void k_mark_redo(const uint32_t *list, uint32_t n_o, uint32_t *redo_pos) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_o) redo_pos[list[i]] = i;
+}
+
+/* ---- host side: the set's records compacted, ordered by one 64-bit sort word, made unique, scanned ---- */
+/* n[a][r] = C(a, r) 3^r, the class bases of (mismatches, index) and the bits their count takes beyond four */
+static void big2_table(uint32_t L, uint32_t P, uint32_t m, gs_big2_tab &tab, unsigned long long &pam_mul, uint32_t &rbits) {
+  for (uint32_t a = 0; a < 32; a++)
+    for (uint32_t r = 0; r < 8; r++) {
+      unsigned long long v = 0;
+      if (r <= a) {
+        double c = 1;
+        for (uint32_t i = 0; i < r; i++) c = c * (double)(a - i) / (double)(i + 1);
+        v = (unsigned long long)(c + 0.5);
+        for (uint32_t i = 0; i < r; i++) v *= 3ull;
+      }
+      tab.n[a][r] = v;
+    }
+  pam_mul = 1;
+  for (uint32_t u = 0; u < P; u++) pam_mul *= 5ull;
+  /* (mismatches, index, rank) as one number below the guide: `4 + rbits` bits hold the count of all classes */
+  unsigned long long cum = 0;
+  for (uint32_t j = 0; j < 8; j++) {
+    const unsigned long long nj = j <= m && j <= L ? tab.n[L][j] * pam_mul : 0ull;
+    tab.base[2 * j] = cum;
+    tab.base[2 * j + 1] = cum + nj;
+    cum += 2ull * nj;
+  }
+  uint32_t cbits = 4;
+  while (cbits < 63 && ((cum - 1ull) >> cbits) != 0ull) cbits++;
+  rbits = cbits - 4;
+}
+static uint32_t guide_bits(uint32_t n_set) {
+  uint32_t gbits = 1;
+  while ((1ull << gbits) < n_set) gbits++;
+  return gbits;
+}
+bool gs_bigorder_fits(uint32_t L, uint32_t P, uint32_t m, uint32_t n_set) {
+  gs_big2_tab tab;
+  unsigned long long pam_mul;
+  uint32_t rbits;
+  big2_table(L, P, m, tab, pam_mul, rbits);
+  return guide_bits(n_set) + 4 + rbits <= 64;
+}
+gs_status gs_add_matches(gs_index *ix, unsigned long long add) {
+  unsigned long long *d = gs_misc_stats(ix->w_misc.p) + ST_MATCHES, cur = 0;
+  GS_HIP(hipMemcpy(&cur, d, 8, hipMemcpyDeviceToHost));
+  cur += add;
+  GS_HIP(hipMemcpy(d, &cur, 8, hipMemcpyHostToDevice));
+  return GS_OK;
+}
+
+/* compaction, sorts and flags of the T records: out.s2 holds them in final order, out.wfinal their sort words */
+static gs_status big2_sort(gs_index *ix, const gs_bigorder_in &in, hipStream_t st, gs_big2_compact_args &ca, uint64_t T,
+                           uint32_t wbits, gs_bigorder_out &out) {
+  gs_status r2;
+  unsigned long long *W = ca.W, *Wb = (unsigned long long *)ix->w_b_w0b.p;
+  uint32_t *idx = ca.idx, *idxb = (uint32_t *)ix->w_b_idxb.p;
+  uint32_t *rk = ca.rowkey, *rkb = (uint32_t *)ix->w_b_keeps.p;
+  uint4 *recs = ca.recs, *S2 = (uint4 *)out.s2;
+  uint32_t *d_scratch = gs_misc_work(ix->w_misc.p) + WK_BIG_SCRATCH;
+  /* Long runs of one sequence (a repeat-rich genome; the handle remembers having seen one): ONE sort by
+   * (word << b | low b bits of the first row), b = what 64 bits leave, instead of a sort by row and a
+   * stable one by word; the runs it leaves out of order (k_big2_wraps) are put right one by one
+   * (k_big2_fixruns).  b < 32 needs no run longer than 2^b (a run is no longer than the largest item):
+   * two rows of a run may then differ by a multiple of 2^b only through the high part.  0: not usable. */
+  auto composite_bits = [&]() -> uint32_t {
+    if (gs_opt(ix, "GS_BIG2_NO_COMPOSITE") || wbits >= 64) return 0u;
+    uint32_t rb = 64 - wbits > 32 ? 32u : 64u - wbits;
+    if (const char *e = gs_opt(ix, "GS_BIG2_ROWBITS")) return std::min<uint32_t>(rb, (uint32_t)std::max(1l, atol(e)));
+    /* the runs to put right afterwards multiply as the row bits shrink (hg38 size, 20 k repeat-rich guides:
+     * 243-548 per batch at 25 bits, 4.3 x 10^5 at 17 and 121 ms against the two sorts' 77): below 22 bits -
+     * sort words beyond 42 - the two sorts serve */
+    return rb >= 22 ? rb : 0u;
+  };
+  const bool two_from_start = ix->big_long_runs || gs_opt(ix, "GS_BIG2_TWO_SORTS");
+  uint32_t rowb = two_from_start ? composite_bits() : 0u;
+  ca.row_bits = rowb;
+  ca.row_off = gs_opt(ix, "GS_BIG2_ROWOFF") ? (uint32_t)atol(gs_opt(ix, "GS_BIG2_ROWOFF")) : 0u;
+  hipLaunchKernelGGL(k_big2_compact, dim3(ca.n_items + (in.from_arena ? in.n_used : 0u)), dim3(256), 0, st, ca);
+  size_t s1 = 0, s2 = 0, s3 = 0, tbs = 0;
+  GS_HIP(rocprim::radix_sort_pairs(nullptr, s1, rk, rkb, idx, idxb, (size_t)T, 0, 32, st));
+  GS_HIP(rocprim::radix_sort_pairs(nullptr, s2, Wb, W, idxb, idx, (size_t)T, 0, wbits, st));
+  GS_HIP(rocprim::radix_sort_pairs(nullptr, s3, Wb, W, idxb, idx, (size_t)T, 0, 64, st));
+  if ((r2 = gs_reserve(ix->w_h_tmp, std::max(std::max(s1, s2), s3) + 16)) != GS_OK) return r2;
+  const unsigned gT = (unsigned)((T + 255) / 256);
+  const unsigned long long *W_final = nullptr;
+  const uint32_t *idx_final = nullptr;
+  uint32_t wshift = 0;
+  bool comp_in_wb = false; /* the composite words were built from the plain ones, into Wb */
+  /* One sort by W and the rows put in order inside its (short, rare) runs - unless this handle has seen a
+   * batch with long runs of one sequence (a repeat-rich genome): then, and for the batch that shows the
+   * first such run, two stable sorts: by first row, then by W. */
+  uint32_t short_max = 32;
+  if (const char *e = gs_opt(ix, "GS_BIG2_SHORT")) short_max = (uint32_t)std::max(1l, atol(e));
+  if (!two_from_start) {
+    tbs = ix->w_h_tmp.cap;
+    GS_HIP(rocprim::radix_sort_pairs(ix->w_h_tmp.p, tbs, W, Wb, idx, idxb, (size_t)T, 0, wbits, st));
+    GS_HIP(hipMemsetAsync(d_scratch, 0, 4, st));
+    hipLaunchKernelGGL(k_big2_runs, dim3(gT), dim3(256), 0, st, (const unsigned long long *)Wb, (const uint32_t *)idxb,
+                       (const uint4 *)recs, T, short_max, idx, d_scratch);
+    uint32_t h_long = 0;
+    GS_HIP(hipMemcpyAsync(&h_long, d_scratch, 4, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    if (!h_long) {
+      W_final = Wb;
+      idx_final = idx;
+    } else {
+      ix->big_long_runs = true;
+      hipLaunchKernelGGL(k_iota_u32, dim3(gT), dim3(256), 0, st, idx, T);
+      rowb = composite_bits();
+      if (rowb) { /* the plain words and the rows are there: the composite words go where the failed order was */
+        hipLaunchKernelGGL(k_big2_comp, dim3(gT), dim3(256), 0, st, (const unsigned long long *)W, (const uint32_t *)rk, T, rowb,
+                           ca.row_off, Wb);
+        comp_in_wb = true;
+      }
+    }
+  }
+  if (!W_final && rowb) {
+    unsigned long long *src = comp_in_wb ? Wb : W, *dst = comp_in_wb ? W : Wb;
+    tbs = ix->w_h_tmp.cap;
+    GS_HIP(rocprim::radix_sort_pairs(ix->w_h_tmp.p, tbs, src, dst, idx, idxb, (size_t)T, 0, wbits + rowb, st));
+    W_final = dst;
+    idx_final = idxb;
+    wshift = rowb;
+    out.comp = true;
+  }
+  if (!W_final) {
+    tbs = ix->w_h_tmp.cap;
+    GS_HIP(rocprim::radix_sort_pairs(ix->w_h_tmp.p, tbs, rk, rkb, idx, idxb, (size_t)T, 0, 32, st));
+    hipLaunchKernelGGL(k_big2_gather_w, dim3(gT), dim3(256), 0, st, (const unsigned long long *)W, (const uint32_t *)idxb, T, Wb);
+    tbs = ix->w_h_tmp.cap;
+    GS_HIP(rocprim::radix_sort_pairs(ix->w_h_tmp.p, tbs, Wb, W, idxb, idx, (size_t)T, 0, wbits, st));
+    W_final = W;
+    idx_final = idx;
+  }
+  out.wfinal = W_final;
+  out.gshift = 4 + ca.rbits + wshift;
+  /* W_final = the sort words in final order, idx_final = where each record sits in recs */
+  hipLaunchKernelGGL(k_big2_gather, dim3(gT), dim3(256), 0, st, (const uint4 *)recs, idx_final, T, S2);
+  if (wshift && (wshift < 32 || ca.row_off != 0)) {
+    /* the descents go into the array the flags' row counts are written to afterwards, the claims into the
+     * flags' own; each run that shows one is put in order through the unordered records' array */
+    uint32_t h_n = 0, *list = (uint32_t *)ix->w_b_rows.p;
+    GS_HIP(hipMemsetAsync(d_scratch, 0, 4, st));
+    hipLaunchKernelGGL(k_big2_wraps, dim3(gT), dim3(256), 0, st, (const uint4 *)S2, W_final, T, wshift, list, d_scratch);
+    GS_HIP(hipMemcpyAsync(&h_n, d_scratch, 4, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    if (h_n) {
+      GS_HIP(hipMemsetAsync(ix->w_b_keep.p, 0, 4 * (size_t)(T + 1), st));
+      hipLaunchKernelGGL(k_big2_fixruns, dim3(std::min<uint32_t>(h_n, 8192u)), dim3(256), 0, st, S2, recs, W_final, T, wshift,
+                         ca.row_off, (const uint32_t *)list, h_n, (uint32_t *)ix->w_b_keep.p);
+    }
+    out.fixed += h_n;
+    if (gs_opt(ix, "GS_DEBUG"))
+      fprintf(stderr, "[gs] composite ordering: %llu records, word bits %u, row bits %u, %u descents inside runs\n",
+              (unsigned long long)T, wbits, wshift, h_n);
+  }
+  hipLaunchKernelGGL(k_big2_flags, dim3(gT), dim3(256), 0, st, (const uint4 *)S2, W_final, T,
+                     (uint32_t *)ix->w_b_keep.p, (unsigned long long *)ix->w_b_rows.p, wshift);
+  return GS_OK;
+}
+
+gs_status gs_bigorder_run(gs_index *ix, const gs_bigorder_in &in, hipStream_t st, gs_bigorder_out &out) {
+  gs_status r2;
+  const uint32_t n_it = 2 * in.n_set;
+  if ((r2 = gs_reserve(ix->w_b_src, sizeof(gs_big_src) * ((size_t)n_it + 1))) != GS_OK) return r2;
+  if ((r2 = gs_reserve(ix->w_b_cnt, 8 * ((size_t)n_it + 2))) != GS_OK) return r2;
+  if ((r2 = gs_reserve(ix->w_b_prefix, 8 * ((size_t)n_it + 2))) != GS_OK) return r2;
+  if (in.from_arena)
+    hipLaunchKernelGGL(k_big2_counts, dim3((n_it + 255) / 256), dim3(256), 0, st, (const uint32_t *)ix->w_counts.p, in.arena_list,
+                       n_it, (unsigned long long *)ix->w_b_cnt.p);
+  else
+    hipLaunchKernelGGL(k_big_sources, dim3((n_it + 255) / 256), dim3(256), 0, st, in.counts_main, in.redo_pos, in.slot_off2,
+                       in.counts2, n_it, in.cap_main, (gs_big_src *)ix->w_b_src.p, (unsigned long long *)ix->w_b_cnt.p);
+  GS_HIP(hipMemsetAsync((unsigned long long *)ix->w_b_cnt.p + n_it, 0, 8, st));
+  size_t tb = 0;
+  GS_HIP(rocprim::exclusive_scan(nullptr, tb, (unsigned long long *)ix->w_b_cnt.p,
+                                 (unsigned long long *)ix->w_b_prefix.p, 0ull, (size_t)n_it + 1,
+                                 rocprim::plus<unsigned long long>(), st));
+  if ((r2 = gs_reserve(ix->w_h_tmp, tb + 16)) != GS_OK) return r2;
+  size_t tbs = ix->w_h_tmp.cap;
+  GS_HIP(rocprim::exclusive_scan(ix->w_h_tmp.p, tbs, (unsigned long long *)ix->w_b_cnt.p,
+                                 (unsigned long long *)ix->w_b_prefix.p, 0ull, (size_t)n_it + 1,
+                                 rocprim::plus<unsigned long long>(), st));
+  unsigned long long T = 0;
+  GS_HIP(hipMemcpyAsync(&T, (unsigned long long *)ix->w_b_prefix.p + n_it, 8, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipStreamSynchronize(st));
+  if (T >= (1ull << 32) - 2) {
+    gs_set_error("more than 2^32 match records in one batch: use smaller batches at this mismatch budget");
+    return GS_ERR_UNSUPPORTED;
+  }
+  out.T = T;
+  gs_big2_tab tab;
+  unsigned long long pam_mul;
+  uint32_t rbits;
+  big2_table(in.L, in.P, in.m, tab, pam_mul, rbits);
+  const uint32_t gbits = guide_bits(in.n_set);
+  if (gbits + 4 + rbits > 64) {
+    gs_set_error("the device-wide ordering's sort word (guide, class, sequence rank) does not fit 64 bits: use smaller batches");
+    return GS_ERR_UNSUPPORTED;
+  }
+  if ((r2 = gs_reserve(ix->w_b_recs, 16 * (T + 1))) != GS_OK) return r2;
+  if ((r2 = gs_reserve(ix->w_b_w0, 8 * (T + 1))) != GS_OK) return r2;
+  if ((r2 = gs_reserve(ix->w_b_w0b, 8 * (T + 1))) != GS_OK) return r2;
+  if ((r2 = gs_reserve(ix->w_b_idx, 4 * (T + 1))) != GS_OK) return r2;
+  if ((r2 = gs_reserve(ix->w_b_idxb, 4 * (T + 1))) != GS_OK) return r2;
+  if ((r2 = gs_reserve(ix->w_b_keep, 4 * (T + 2))) != GS_OK) return r2;
+  if ((r2 = gs_reserve(ix->w_b_keeps, 4 * (T + 2))) != GS_OK) return r2;
+  if ((r2 = gs_reserve(ix->w_b_rows, 8 * (T + 2))) != GS_OK) return r2;
+  if ((r2 = gs_reserve(ix->w_b_rowss, 8 * (T + 2))) != GS_OK) return r2;
+  out.gshift = 4 + rbits;
+  if (T) {
+    /* the records in final order go where the arena's chunks were (read for the last time by the
+     * compaction) when they fit there: 16 bytes per record less next to a 220 GB index */
+    const bool s2_in_arena = in.from_arena && ix->w_arena.cap >= 16 * (T + 1);
+    if (!s2_in_arena && (r2 = gs_reserve(ix->w_b_s, 16 * (T + 1))) != GS_OK) return r2;
+    out.s2 = s2_in_arena ? ix->w_arena.p : ix->w_b_s.p;
+    if ((r2 = gs_reserve(ix->w_b_tab, sizeof(gs_big2_tab))) != GS_OK) return r2;
+    GS_HIP(hipMemcpy(ix->w_b_tab.p, &tab, sizeof(tab), hipMemcpyHostToDevice));
+    gs_big2_compact_args ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.slots_main = (const uint4 *)ix->w_slots.p;
+    ca.slots_alt = (const uint4 *)ix->w_slots2.p;
+    ca.src = (const gs_big_src *)ix->w_b_src.p;
+    if (in.from_arena) {
+      ca.from_arena = 1;
+      ca.arena = (const uint4 *)ix->w_arena.p;
+      ca.chunk_item = (const uint32_t *)ix->w_arena_meta.p;
+      ca.chunk_seq = ca.chunk_item + in.arena_chunks;
+      ca.counts = (const uint32_t *)ix->w_counts.p;
+      ca.list = in.arena_list;
+      ca.redo_pos = in.arena_redo_pos ? in.arena_redo_pos : (const uint32_t *)ix->w_b_redo_pos.p;
+      ca.cap = in.cap;
+      ca.n_used = in.n_used;
+    }
+    ca.prefix = (const unsigned long long *)ix->w_b_prefix.p;
+    ca.tab = (const gs_big2_tab *)ix->w_b_tab.p;
+    ca.recs = (uint4 *)ix->w_b_recs.p;
+    ca.W = (unsigned long long *)ix->w_b_w0.p;
+    ca.rowkey = (uint32_t *)ix->w_b_keep.p; /* free until the flags are written */
+    ca.idx = (uint32_t *)ix->w_b_idx.p;
+    ca.pam_mul = pam_mul;
+    ca.n_items = n_it;
+    ca.L = in.L;
+    ca.P = in.P;
+    ca.rbits = rbits;
+    if ((r2 = big2_sort(ix, in, st, ca, T, gbits + 4 + rbits, out)) != GS_OK) return r2;
+  }
+  GS_HIP(hipMemsetAsync((uint32_t *)ix->w_b_keep.p + T, 0, 4, st));
+  GS_HIP(hipMemsetAsync((unsigned long long *)ix->w_b_rows.p + T, 0, 8, st));
+  {
+    size_t s3 = 0, s4 = 0;
+    GS_HIP(rocprim::exclusive_scan(nullptr, s3, (uint32_t *)ix->w_b_keep.p, (uint32_t *)ix->w_b_keeps.p, 0u,
+                                   (size_t)T + 1, rocprim::plus<uint32_t>(), st));
+    GS_HIP(rocprim::exclusive_scan(nullptr, s4, (unsigned long long *)ix->w_b_rows.p,
+                                   (unsigned long long *)ix->w_b_rowss.p, 0ull, (size_t)T + 1,
+                                   rocprim::plus<unsigned long long>(), st));
+    if ((r2 = gs_reserve(ix->w_h_tmp, (s3 > s4 ? s3 : s4) + 16)) != GS_OK) return r2;
+    tbs = ix->w_h_tmp.cap;
+    GS_HIP(rocprim::exclusive_scan(ix->w_h_tmp.p, tbs, (uint32_t *)ix->w_b_keep.p, (uint32_t *)ix->w_b_keeps.p,
+                                   0u, (size_t)T + 1, rocprim::plus<uint32_t>(), st));
+    tbs = ix->w_h_tmp.cap;
+    GS_HIP(rocprim::exclusive_scan(ix->w_h_tmp.p, tbs, (unsigned long long *)ix->w_b_rows.p,
+                                   (unsigned long long *)ix->w_b_rowss.p, 0ull, (size_t)T + 1,
+                                   rocprim::plus<unsigned long long>(), st));
+  }
+  uint32_t *d_err = gs_misc_work(ix->w_misc.p) + WK_BIG_ERR;
+  hipLaunchKernelGGL(k_big_totals, dim3((in.n_set + 255) / 256), dim3(256), 0, st,
+                     (const unsigned long long *)ix->w_b_prefix.p, (const uint32_t *)ix->w_b_keeps.p,
+                     (const unsigned long long *)ix->w_b_rowss.p, in.n_set, in.nmatch, in.nhits, d_err);
+  uint32_t h_err = 0, h_uq = 0;
+  GS_HIP(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipMemcpyAsync(&h_uq, (uint32_t *)ix->w_b_keeps.p + T, 4, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipStreamSynchronize(st));
+  if (h_err) {
+    gs_set_error("more than 2^32 hits for one guide");
+    return GS_ERR_UNSUPPORTED;
+  }
+  return gs_add_matches(ix, h_uq); /* these guides were skipped by (or never went through) k_order */
+}
+
+void gs_bigorder_locate(gs_index *ix, const gs_bigorder_out &o, const uint32_t *gmap, uint32_t v_rem, hipStream_t st) {
+  if (!o.T) return;
+  gs_blocate3_args la;
+  la.sd[0] = ix->strand[0].d;
+  la.sd[1] = ix->strand[1].d;
+  la.S2 = (const uint4 *)o.s2;
+  la.W = o.wfinal;
+  la.keep = (const uint32_t *)ix->w_b_keep.p;
+  la.row_scan = (const unsigned long long *)ix->w_b_rowss.p;
+  la.prefix = (const unsigned long long *)ix->w_b_prefix.p;
+  la.gmap = gmap;
+  la.offsets = (const uint64_t *)ix->w_offsets.p;
+  la.hits = (gs_hit *)ix->w_hits.p;
+  la.genome_length = ix->genome_length;
+  la.T = o.T;
+  la.v_rem = v_rem;
+  la.gshift = o.gshift;
+  hipLaunchKernelGGL(k_big2_locate, dim3((unsigned)((o.T + 255) / 256)), dim3(256), 0, st, la);
 }

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <array>
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -186,13 +187,15 @@ struct gs_index {
   unsigned long long last_share[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* the last batch: shared items, packages reserved, queue capacity, tickets handed out; [4] guides beyond the tiles' reach, ordered device-wide alone */
   uint64_t shq_packages = 16384; /* packages the next batch's queue holds (1,152 bytes each): grown when a batch reserved more */
   uint64_t arena_chunks = 4096; /* chunks of 1,024 records the next batch's arena holds: grown when a batch needed more */
-  /* matches per item the last batch showed, per mismatch budget (slot sizing), and what it was measured on */
-  double seen_mean[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-  double seen_max[8] = {0};
-  uint64_t seen_hpass[8] = {0}, seen_items[8] = {0}; /* verification passes of share_min row groups or more in the last batch at this budget, and its items */
+  /* what the last batch showed, per mismatch budget, and the shape it was measured on (gs_enumerate.hip: shape_key) */
+  struct seen_t {
+    double mean = -1, max = 0;     /* matches per item (slot sizing) */
+    uint64_t hpass = 0, items = 0; /* verification passes of share_min row groups or more, and its items (the search's form) */
+    uint64_t key = 0;
+  };
+  std::array<seen_t, 8> seen;
   bool last_raw_valid = false;   /* w_raw holds the raw hit counts of the last batch (GS_FLAG_RAW_COUNTS) */
   uint64_t last_unsupported = 0; /* guides of the last batch flagged GS_GUIDE_NEEDS_GENERAL (w_flags) */
-  uint64_t seen_key[8] = {0};
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_tile = nullptr;  /* gs_tileorder_run: behind the copy of the slow-tile counts */
   hipStream_t st_help = nullptr; /* lowest priority: the launch that runs published packages next to the search launch (run_search) */
@@ -286,6 +289,8 @@ const char *gs_opt(const gs_index *ix, const char *key);
 void gs_opts_from_env(gs_index *ix);
 extern std::atomic<int> gs_debug_any; /* some handle has GS_DEBUG set: the allocator reports large growth */
 gs_status gs_reserve(gs_buffer &b, size_t bytes);
+/* frees the buffer (if any) and leaves it empty; returns the bytes it held */
+size_t gs_buffer_free(gs_buffer &b);
 
 /* GPU suffix array: d_text (n bytes incl. sentinel) -> d_sa (n uint32) */
 gs_status gs_device_suffix_array(const uint8_t *d_text, uint64_t n, uint32_t *d_sa, hipStream_t st);

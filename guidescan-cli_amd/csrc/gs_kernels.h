@@ -30,6 +30,33 @@
 #define META_PAM(m) ((uint32_t)(((m) >> 52) & 3))
 #define PATH_MASK ((1ull << 52) - 1)
 
+/* The handle's 512 bytes of counters (gs_index::w_misc), zeroed at the start of every batch: sixteen 64-bit stats words
+ * (k_search's counters, gs_index_last_counters), then 32-bit work words from byte 128, then k_prepare's PAM-pair
+ * histogram from byte 256.  Indices into the stats words (ST_*) and into the work words (WK_*). */
+enum : uint32_t {
+  ST_MATCHES = 2,       /* match records left after the orderings made them unique */
+  ST_ARENA_FAIL = 6,    /* items of the main pass the arena had no chunk left for */
+  ST_COUNT_SUM = 14,    /* k_count_stats: sum and maximum of the exact per-item counts ([14], [15]) */
+  WK_ITEMS = 0,         /* k_search's work counter */
+  WK_INVALID = 1,       /* guides k_prepare flagged for the general path */
+  WK_NLIST = 2,         /* k_collect_overflow's list length */
+  WK_BIG_ERR = 3,       /* k_big_totals: a guide with more than 2^32 hits */
+  WK_ARENA_NEXT = 4,    /* the arena's next free chunk */
+  WK_SEARCH_ERR = 5,    /* k_search: bit 1 a helping wave gave up waiting, else an item passed its iteration bound */
+  WK_BIG_SCRATCH = 6,   /* the device-wide ordering's long-run flag / descent count */
+  WK_HPASS = 8,         /* heavy verification passes of the main pass */
+  WK_HELPER_ITEMS = 9,  /* the launch without items: a work counter past the items from the start */
+  WK_SCRATCH2 = 10,     /* two words: the form estimate's result, k_need_chunks' count */
+  MISC_PAIR_HIST = 256, /* byte offset of the PAM-pair histogram (17 words) */
+};
+static inline unsigned long long *gs_misc_stats(void *misc) { return (unsigned long long *)misc; }
+static inline uint32_t *gs_misc_work(void *misc) { return (uint32_t *)((char *)misc + 128); }
+/* what one copy of the stats and the work words behind them brings back */
+struct gs_misc_readback {
+  unsigned long long stats[16];
+  uint32_t work[12];
+};
+
 
 struct gs_search_args {
   gs_strand_dev sd[2];
@@ -378,6 +405,37 @@ __global__ void k_big_sources(const uint32_t *counts_main, const uint32_t *redo_
                               unsigned long long *cnt64);
 __global__ void k_fill_u32(uint32_t *p, uint32_t v, uint32_t n);
 __global__ void k_mark_redo(const uint32_t *list, uint32_t n_o, uint32_t *redo_pos);
+
+/* host side (gs_bigorder.hip).  The set: the whole batch (counts_main != nullptr; records in the main slots, `cap_main`
+ * per item, or for guides with redo_pos in the exact-size array slot_off2 / counts2), a redo list alone (records in the
+ * exact-size array), or with from_arena a list of guides whose records are read where k_search left them. */
+struct gs_bigorder_in {
+  uint32_t n_set;
+  const uint32_t *counts_main, *redo_pos, *counts2;
+  uint32_t cap_main;
+  const uint64_t *slot_off2;
+  bool from_arena;
+  const uint32_t *arena_list, *arena_redo_pos; /* arena_redo_pos nullptr: ix->w_b_redo_pos */
+  uint32_t n_used, arena_chunks, cap;         /* chunks in use, the arena's size, the batch's slots per item */
+  uint32_t *nmatch, *nhits;                   /* per set guide */
+  uint32_t L, P, m;
+};
+/* what the last ordering left for gs_bigorder_locate, and what the batch reports (gs_index_last_counters [7]) */
+struct gs_bigorder_out {
+  uint64_t T = 0;                          /* records */
+  void *s2 = nullptr;                      /* the records in final order (one-word form) */
+  const unsigned long long *wfinal = nullptr; /* and their sort words */
+  uint32_t gshift = 0;
+  bool comp = false;  /* an ordering ran as one sort by (word, low bits of the row) */
+  uint32_t fixed = 0; /* descents found inside runs (k_big2_fixruns), over the batch's orderings */
+};
+/* does the sort word (guide of the set, class, sequence rank) of a set of n_set guides fit 64 bits? */
+bool gs_bigorder_fits(uint32_t L, uint32_t P, uint32_t m, uint32_t n_set);
+gs_status gs_bigorder_run(gs_index *ix, const gs_bigorder_in &in, hipStream_t st, gs_bigorder_out &out);
+/* the hits of the last ordering's set (gmap: set guide -> guide of the batch; nullptr: the whole batch) */
+void gs_bigorder_locate(gs_index *ix, const gs_bigorder_out &o, const uint32_t *gmap, uint32_t v_rem, hipStream_t st);
+/* the matches counter (ST_MATCHES) of guides that did not go through k_order */
+gs_status gs_add_matches(gs_index *ix, unsigned long long add);
 
 /* ---- gs_search.hip ---- */
 __global__ void k_search_walk(gs_search_args a);

@@ -280,6 +280,14 @@ gs_status gs_debug_guide_descriptor(uint64_t q, const uint32_t pam[4], uint32_t 
  * out = {buckets the item is dealt into (0: the item is one tile), records a bucket's slot holds, sample words per
  * splitter, records one wave orders, buckets an item may have at most (more: the batch is ordered device-wide)}. */
 void gs_debug_tile_plan(uint32_t records, uint32_t out[5]);
+/* The search's form for a pass, as data (host only; tests/test_search_form.py pins the table).  in = {items (2 x guides),
+ * CUs, share_min after the switches, the handle's back-off at the pass's start, main pass, walking kernel, one PAM chunk,
+ * counting requests, every item through PAM-pair + deep tables, mismatches, the form estimate's two words (guides with a
+ * heavy k-mer of their own, the largest such interval), heavy passes and items of the last batch of the same shape,
+ * GS_HEAVY, GS_SPLIT_SHARE, GS_SPLIT_FROM, GS_SEED_FORM (-1: not set)}.  out = {the estimate is wanted, its threshold in
+ * rows, heavy, split, seed form, the form gs_index_last_sharing reports: 0 plain, 1 heavy, 2 split, 3 two seeding
+ * launches}. */
+void gs_debug_search_form(const int64_t in[18], uint32_t out[6]);
 
 /* Self-check of a resident index from the genome text alone (no suffix-array builder involved):
  * the suffix array of `strand` is a permutation of [0, n) (all rows), n_samples evenly spread

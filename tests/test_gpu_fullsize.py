@@ -107,6 +107,7 @@ def three_paths_same_bytes(torch, gidx, d_seqs, d_pams, n, m, n_walk, on_host=Fa
     hip = _hip()
     if on_host:
         d_off, d_hits, st = gidx.enumerate_device(d_seqs.data_ptr(), n, 20, d_pams.data_ptr(), 3, mismatches=m)
+        st["form"] = gidx.last_sharing()["form"]
         off, hits = device_result_to_host(hip, d_off, d_hits, n, st["n_hits"])
         gidx.set_option("GS_NO_BIDIR", "1")
         try:
@@ -123,6 +124,7 @@ def three_paths_same_bytes(torch, gidx, d_seqs, d_pams, n, m, n_walk, on_host=Fa
         assert np.array_equal(o3, off[:n_walk + 1]) and h3.tobytes() == hits[:nh].tobytes(), "walk and fast path differ"
         return off, hits, st, st3
     d_off, d_hits, st = gidx.enumerate_device(d_seqs.data_ptr(), n, 20, d_pams.data_ptr(), 3, mismatches=m)
+    st["form"] = gidx.last_sharing()["form"]
     off, hits = device_result_to_torch(torch, hip, d_off, d_hits, n, st["n_hits"])
     gidx.set_option("GS_NO_BIDIR", "1")
     try:
@@ -377,6 +379,7 @@ def test_config3_hg38_sized_1M_guides_m3(hg38):
     seqs, pams, pos, strands = synth.sample_guides(hg38.text, n, seed=1000)
     d_seqs, d_pams = torch.from_numpy(seqs).cuda(), torch.from_numpy(pams).cuda()
     off, hits, st, st_walk = three_paths_same_bytes(torch, hg38.gidx, d_seqs, d_pams, n, 3, 20_000)
+    assert st["form"] == 3, st   # the timed call ran the two seeding launches, not a fall-back
     assert st["n_hits"] == off[-1] >= n
     checked = check_batch_properties(hg38.text, seqs, pos, strands, off, hits[:, 0], hits[:, 1].view(np.uint64))
     assert checked >= 10_000
