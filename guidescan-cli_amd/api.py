@@ -122,6 +122,8 @@ def lib():
     L.gs_index_copy_sa.argtypes = [vp, i32, vp]
     L.gs_index_last_counters.restype = i32
     L.gs_index_last_counters.argtypes = [vp, vp]
+    L.gs_index_last_launch.restype = i32
+    L.gs_index_last_launch.argtypes = [vp, vp]
     L.gs_index_last_sharing.restype = i32
     L.gs_index_last_sharing.argtypes = [vp, vp]
     L.gs_index_prepare.restype = i32
@@ -197,7 +199,7 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_format_guide", "gs_format_header", "gs_free", "gs_sdsl_extract_text",
            "gs_enumerate_bulges", "gs_result_ex_get", "gs_result_ex_free", "gs_decode_sequence_ex",
            "gs_format_guide_ex", "gs_score_device", "gs_score", "gs_kmers_generate", "gs_kmers_get",
-           "gs_kmers_free", "gs_format_guide_scored", "gs_index_verify_sa", "gs_index_last_counters", "gs_enumerate_general",
+           "gs_kmers_free", "gs_format_guide_scored", "gs_index_verify_sa", "gs_index_last_counters", "gs_index_last_launch", "gs_enumerate_general",
            "gs_index_last_guide_flags", "gs_enumerate_general_pams", "gs_index_save_sa", "gs_index_open_sa", "gs_format_guides_scored", "gs_result_ex_raw_hits",
            "gs_debug_seed_recipes", "gs_debug_choose_thresholds", "gs_debug_tile_plan", "gs_debug_search_form", "gs_debug_guide_descriptor", "gs_index_lock", "gs_index_unlock",
            "gs_index_last_sharing", "gs_index_set_option", "gs_index_get_option", "gs_index_prepare"]
@@ -673,6 +675,14 @@ class GenomeIndex:
                     items_pair_tables=v[7] >> 8, recipe_lines=v[3],
                     slots_per_item=v[13], matches_sum=v[14], matches_max_per_item=v[15],
                     table_lines=v[8], ctx16_lines=v[9], ctx_words=v[10], sa_isa_gathers=v[11], occ_lines=v[12])
+
+    def last_launch(self):
+        """what the main pass of the last enumerate_device call was launched with (gs_index_last_launch)"""
+        out = (C.c_uint64 * 8)()
+        _check(lib().gs_index_last_launch(self._h, out))
+        v = [int(x) for x in out]
+        return dict(walk=bool(v[0]), spec=bool(v[1]), deep=bool(v[2]), take=v[3], seed_take=v[4], pair_tables=v[5],
+                    x_len=v[6], rot_copies=v[7])
 
     def enumerate_device(self, d_guides_ptr, n, L, d_pams_ptr, P, mismatches=3, alt_pams=(),
                          start=False, stream=None, faithful=False, count_requests=False):

@@ -205,6 +205,9 @@ struct gs_index {
   uint32_t lock_depth = 0;
   uint32_t pt_k = 0; /* depth of the prefix interval tables (0: none) */
   unsigned long long last_counters[16] = {0}; /* k_search's stats array of the last gs_enumerate_device call */
+  /* the main pass's launch of the last batch (gs_index_last_launch): walking kernel, kernel without the strand tables' side,
+   * deep tables, items per visit, ... of the two seeding launches (0: not that form), PAM-pair tables, |X|, rotated copies per strand table */
+  unsigned long long last_launch[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   std::vector<gs_nrun> nruns_text; /* 'N' runs of the forward text */
   gs_buffer w_cand;                /* literal-N candidate windows (device): kept from batch to batch of one shape */
   uint64_t cand_key = ~0ull;       /* (L, P, bucketed or not) w_cand was made for; ~0: nothing kept */
@@ -221,6 +224,7 @@ struct gs_index {
   gs_pairtab_host pairtab[2];
   bool pairtab_off = false; /* a batch ran out of memory next to them: not built again on this handle */
   bool rot_off = false;     /* the same for the strand tables' rotated copies */
+  uint32_t dbg_nomem = 0;   /* GS_DBG_NOMEM (tests of those recoveries): passes of a batch that still end as if out of device memory */
   bool tile_order_off = false; /* a batch had interval records or one sequence at one row twice: the per-guide tile ordering is not tried again for that shape */
   uint64_t tile_order_off_key = 0;
   bool big_long_runs = false; /* a batch showed long runs of one sequence (repeat-rich genome): the device-wide ordering sorts by row, then by word (gs_search.hip) */

@@ -1058,6 +1058,12 @@ static gs_status run_search(batch &b, const search_pass &p, unsigned long long h
     if (k.seed_grid > need) k.seed_grid = need;
   }
   if (p.with_arena) ix->last_share[6] = sharing && d_shctl == nullptr ? 0u : k.f.form; /* (gs_index_last_sharing: the form of the main pass) */
+  if (p.with_arena) { /* (gs_index_last_launch: what the main pass is launched with) */
+    const bool seed_launches = k.f.seed_form != 0u && !k.walk && sa.shq == nullptr; /* (launch_search's branch) */
+    const unsigned long long ll[8] = {k.walk ? 1u : 0u, k.spec ? 1u : 0u, sa.bdeep, sa.take, seed_launches ? b.sw.seed_take : 0u, sa.n_pt, sa.x_len,
+                                      ix->strand[0].ptab_rot ? ix->strand[0].rot_plan_n : 0u};
+    memcpy(ix->last_launch, ll, sizeof(ll));
+  }
   GS_HIP(hipEventRecord(ix->ev[1], st));
   if ((rc = launch_search(b, p, sa, k)) != GS_OK) return rc;
   GS_HIP(hipEventRecord(ix->ev[2], st));
@@ -1673,6 +1679,11 @@ static gs_status enumerate_device_impl(gs_index *ix, const void *d_guides, uint6
   if (b.bidir && (rc = upload_windows(b)) != GS_OK) return rc;
   reserve_arena(b);
   if ((rc = main_pass(b)) != GS_OK) return rc;
+  if (ix->dbg_nomem != 0) { /* (tests: as if the workspace of the stages below had not fitted - tables placed, copies built, slots grown) */
+    ix->dbg_nomem--;
+    GS_HIP(hipStreamSynchronize(b.st));
+    return GS_ERR_NOMEM;
+  }
   if ((rc = order_items(b)) != GS_OK) return rc;
   if ((rc = overflow_redo(b)) != GS_OK) return rc;
   if ((rc = order_set(b)) != GS_OK) return rc;
@@ -1695,6 +1706,7 @@ static bool recover_share_timeout(gs_index *ix, gs_status rc) {
  * batch ordered device-wide leaves tens of bytes per record in a dozen arrays that a batch ordered in tiles never touches,
  * and the other way round (10^9 records: 70 GB either way) - and the batch is redone: every workspace buffer grows again
  * on demand.  Then the derived tables, one kind at a time: the strand tables' rotated copies, then the PAM-pair tables. */
+static const size_t RELEASE_REDO_MIN = (size_t)1 << 30; /* released bytes from which the same batch is worth another try */
 static bool recover_release_workspace(gs_index *ix, gs_status rc) {
   if (rc != GS_ERR_NOMEM) return false;
   (void)hipGetLastError();
@@ -1704,7 +1716,9 @@ static bool recover_release_workspace(gs_index *ix, gs_status rc) {
                        &ix->w_t_buckets, &ix->w_t_tiles, &ix->w_t_chunkof, &ix->w_t_big, &ix->w_hits, &ix->w_score_tmp, &ix->w_score_io,
                        &ix->w_arena, &ix->w_shq, &ix->w_slots})
     freed += gs_buffer_free(*b);
-  if (freed <= ((size_t)1 << 30)) return false;
+  size_t redo_min = RELEASE_REDO_MIN;
+  if (const char *e = gs_opt(ix, "GS_DBG_RELEASE_MIN")) redo_min = (size_t)strtoull(e, nullptr, 10); /* (tests: bytes) */
+  if (freed <= redo_min) return false;
   if (gs_opt(ix, "GS_DEBUG")) fprintf(stderr, "[gs] out of device memory: %.1f GB of workspace released, batch redone\n", 1e-9 * (double)freed);
   return true;
 }

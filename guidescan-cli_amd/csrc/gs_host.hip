@@ -20,6 +20,11 @@ const char *gs_opt(const gs_index *ix, const char *key) {
   const auto it = ix->opts.find(key);
   return it == ix->opts.end() ? nullptr : it->second.c_str();
 }
+/* GS_DBG_NOMEM=<n> arms a counter on the handle: the next n passes of a batch fail (enumerate_device_impl counts it down) */
+static void arm_dbg_nomem(gs_index *ix) {
+  const char *e = gs_opt(ix, "GS_DBG_NOMEM");
+  ix->dbg_nomem = e ? (uint32_t)std::max(0l, atol(e)) : 0u;
+}
 void gs_opts_from_env(gs_index *ix) {
   /* the one place that looks at the environment: when a handle is made */
   for (char **e = environ; e && *e; ++e) {
@@ -29,6 +34,7 @@ void gs_opts_from_env(gs_index *ix) {
     ix->opts[std::string(*e, (size_t)(eq - *e))] = std::string(eq + 1);
   }
   if (ix->opts.count("GS_DEBUG")) gs_debug_any.store(1);
+  arm_dbg_nomem(ix);
 }
 extern "C" gs_status gs_index_set_option(gs_index *ix, const char *key, const char *value) {
   GS_HANDLE_LOCK(ix);
@@ -42,6 +48,7 @@ extern "C" gs_status gs_index_set_option(gs_index *ix, const char *key, const ch
     return GS_ERR_NOMEM;
   }
   if (value && strcmp(key, "GS_DEBUG") == 0) gs_debug_any.store(1);
+  if (strcmp(key, "GS_DBG_NOMEM") == 0) arm_dbg_nomem(ix);
   return GS_OK;
 }
 extern "C" gs_status gs_index_get_option(const gs_index *ix, const char *key, char *out, uint64_t cap) {

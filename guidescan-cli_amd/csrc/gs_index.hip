@@ -623,6 +623,13 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
       hipFree(d_es);
     }
     s->bytes += 6 * s->n;
+  } else {
+    /* No context arrays: k_ctx_build, which computes the entries' context masks (z, w), does not run, and the table-seeded
+     * walk tests its seeds against them all the same.  Every pair set: no seed is dropped by a mask nobody computed.
+     * (x, y keep what k_ptab_build and k_ptab_finish wrote; 2^24 rows per call.) */
+    for (uint64_t e0 = 0; e0 < entries; e0 += 1ull << 24)
+      GS_HIP(hipMemset2DAsync((char *)(tab + e0) + 2 * sizeof(uint32_t), sizeof(uint4), 0xFF, 2 * sizeof(uint32_t),
+                              (size_t)std::min<uint64_t>(entries - e0, 1ull << 24), st));
   }
   /* optional structures, HBM capacity spent to cut random requests: the
    * rotated table copies (k-1 tables: 56 GB per strand at k = 14) and the inverse suffix array
@@ -682,6 +689,7 @@ gs_status gs_strand_rot_ensure(gs_index *ix, hipStream_t st) {
     GS_HIP(hipMemGetInfo(&free_b, &total_b));
     double reserve = 32e9; /* they are dropped first when a batch runs short, and written again in 50 ms */
     if (reserve > 0.125 * (double)total_b) reserve = 0.125 * (double)total_b;
+    if (const char *e = gs_opt(ix, "GS_ROT_RESERVE_GB")) reserve = atof(e) * 1e9; /* (tests: no rung by what other processes hold) */
     uint4 *rot = nullptr;
     if ((double)bytes + reserve > (double)free_b || hipMalloc(&rot, bytes) != hipSuccess) {
       (void)hipGetLastError();
@@ -1018,6 +1026,12 @@ extern "C" gs_status gs_index_last_counters(const gs_index *ix, uint64_t out[16]
   GS_HANDLE_LOCK(ix);
   if (!ix || !out) return GS_ERR_ARG;
   for (int i = 0; i < 16; i++) out[i] = ix->last_counters[i];
+  return GS_OK;
+}
+extern "C" gs_status gs_index_last_launch(const gs_index *ix, uint64_t out[8]) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !out) return GS_ERR_ARG;
+  for (int i = 0; i < 8; i++) out[i] = ix->last_launch[i];
   return GS_OK;
 }
 extern "C" uint64_t gs_index_genome_length(const gs_index *ix) { return ix ? ix->genome_length : 0; }

@@ -173,6 +173,11 @@ void gs_index_close(gs_index *ix);
  * [12] Occ block lines, [3] lines of the seed recipe lists.  (the bytes the
  * roofline is priced on.)  [7] >> 8: items whose seeds went through PAM-pair tables. */
 gs_status gs_index_last_counters(const gs_index *ix, uint64_t out[16]);
+/* what the main pass of the last gs_enumerate_device call was launched with: [0] 1 = the walking kernel, [1] 1 = the kernel
+ * without the strand tables' side of the seeding (every pattern on PAM-pair + deep tables), [2] 1 = deep tables on the other
+ * strand's side, [3] items a wave takes per visit to the work counter, [4] ... in the two seeding launches (0: another form
+ * ran), [5] PAM-pair tables in use, [6] |X|, [7] rotated copies per strand table in place */
+gs_status gs_index_last_launch(const gs_index *ix, uint64_t out[8]);
 /* The last batch's heavy items (DESIGN.md sections 5.1, 5.3): [0] items of which at least one verification pass was
  * handed to other waves, [1] packages reserved in the queue, [2] packages the queue holds, [3] tickets the helping waves
  * drew; [4] guides with an item of more than 2^20 match records, which the per-guide tile ordering leaves to the

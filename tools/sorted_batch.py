@@ -5,8 +5,8 @@ the PAM-pair table, the other strand's seeds without one in R (the last guide sy
 table.  Guides that share those symbols and run at the same time share the lines in the L2s.  The same 1 M guides,
 in the order drawn and sorted by either key: k_search time and hits (the hit set must not depend on the order).
 Usage (GPU box, repo root): python tools/sorted_batch.py [workload] [batch] [m]"""
+import ctypes as C
 import sys
-import zlib
 from importlib import import_module
 from pathlib import Path
 
@@ -24,6 +24,23 @@ def keys(seqs, lo, hi):
     for t in range(lo, hi):
         k = (k << np.uint64(2)) | code[seqs[:, t]]
     return k
+
+
+def copy_offsets(d_off, n):
+    """the n + 1 hit offsets of the last enumerate_device call, from the handle's device buffer"""
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    off = np.empty(n + 1, dtype=np.uint64)
+    if hip.hipMemcpy(off.ctypes.data, d_off, 8 * (n + 1), 2) != 0:
+        raise RuntimeError("hipMemcpy of the hit offsets failed")
+    return off
+
+
+def counts_as_drawn(off, order):
+    """hits per guide in the drawn order, from the offsets of a batch that ran in `order` (row j of it = guide order[j])"""
+    per = np.empty(order.shape[0], dtype=np.uint64)
+    per[order] = np.diff(off)
+    return per
 
 
 def main():
@@ -59,10 +76,10 @@ def main():
                 ms.append(round(st["ms_search"], 2))
             n_hits = int(st["n_hits"])
             # the hit set per guide must be the one the drawn order gives: compare per-guide counts through the permutation
-            off = api.copy_offsets(d_off, batch) if hasattr(api, "copy_offsets") else None
+            per = counts_as_drawn(copy_offsets(d_off, batch), o)
             print(f"{name:28s} k_search {ms} ms, {n_hits} hits", flush=True)
-            ref = n_hits if ref is None else ref
-            assert n_hits == ref, "the order of a batch changed its hits"
+            ref = per if ref is None else ref
+            assert n_hits == int(ref.sum()) and np.array_equal(per, ref), "the order of a batch changed its hits"
     finally:
         g.close()
 
