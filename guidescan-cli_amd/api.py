@@ -95,6 +95,12 @@ def lib():
     L.gs_sdsl_extract_text.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(u64)]
     L.gs_index_save_sa.restype = i32
     L.gs_index_save_sa.argtypes = [vp, vp, u64, C.c_char_p]
+    L.gs_index_save_sdsl.restype = i32
+    L.gs_index_save_sdsl.argtypes = [vp, vp, u64, C.c_char_p]
+    L.gs_debug_sdsl_sections.restype = i32
+    L.gs_debug_sdsl_sections.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
+    L.gs_debug_sdsl_export_scratch.restype = u64
+    L.gs_debug_sdsl_export_scratch.argtypes = []
     L.gs_index_open_sa.restype = i32
     L.gs_index_open_sa.argtypes = [vp, u64, C.c_char_p, i32, C.POINTER(vp)]
     L.gs_index_close.argtypes = [vp]
@@ -202,7 +208,8 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_kmers_free", "gs_format_guide_scored", "gs_index_verify_sa", "gs_index_last_counters", "gs_index_last_launch", "gs_enumerate_general",
            "gs_index_last_guide_flags", "gs_enumerate_general_pams", "gs_index_save_sa", "gs_index_open_sa", "gs_format_guides_scored", "gs_result_ex_raw_hits",
            "gs_debug_seed_recipes", "gs_debug_choose_thresholds", "gs_debug_tile_plan", "gs_debug_search_form", "gs_debug_guide_descriptor", "gs_index_lock", "gs_index_unlock",
-           "gs_index_last_sharing", "gs_index_set_option", "gs_index_get_option", "gs_index_prepare"]
+           "gs_index_last_sharing", "gs_index_set_option", "gs_index_get_option", "gs_index_prepare",
+           "gs_index_save_sdsl", "gs_debug_sdsl_sections", "gs_debug_sdsl_export_scratch"]
 
 
 def _check(rc):
@@ -407,6 +414,25 @@ def sdsl_extract_text(index_file) -> np.ndarray:
     return t
 
 
+def sdsl_sections(counts):
+    """(tree, alphabet): the serialised _byte_tree and byte_alphabet sections of a reference index file whose text,
+    sentinel included, has these 256 symbol counts (gs_debug_sdsl_sections; host only)"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    if counts.shape != (256,):
+        raise ValueError("counts: 256 entries, one per byte value")
+    t, tn, a, an = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+    _check(lib().gs_debug_sdsl_sections(counts.ctypes.data, C.byref(t), C.byref(tn), C.byref(a), C.byref(an)))
+    tree, alphabet = C.string_at(t, tn.value), C.string_at(a, an.value)
+    lib().gs_free(t)
+    lib().gs_free(a)
+    return tree, alphabet
+
+
+def sdsl_export_scratch() -> int:
+    """peak device scratch in bytes of this process's last GenomeIndex.save_sdsl"""
+    return int(lib().gs_debug_sdsl_export_scratch())
+
+
 def decode_sequence_ex(hit) -> str:
     """match.sequence of one HIT_EX_DTYPE record"""
     return bytes(hit["seq"])[:int(hit["seq_len"])].decode()
@@ -458,6 +484,12 @@ class GenomeIndex:
         """store both suffix arrays next to the text (gs_index_save_sa)"""
         text = np.ascontiguousarray(text, dtype=np.uint8)
         _check(lib().gs_index_save_sa(self._h, text.ctypes.data, text.shape[0], str(path).encode()))
+
+    def save_sdsl(self, text, prefix):
+        """write <prefix>.forward and <prefix>.reverse, the reference's own index files, byte for byte
+        (gs_index_save_sdsl); text as given to build"""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        _check(lib().gs_index_save_sdsl(self._h, text.ctypes.data, text.shape[0], str(prefix).encode()))
 
     @classmethod
     def open_sa(cls, text, path, device: int = 0):

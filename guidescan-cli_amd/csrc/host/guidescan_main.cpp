@@ -3,11 +3,14 @@
  * (src/guidescan.cxx:28-95, 316-358) and database output, and calls the MI355X path through the
  * C-ABI (include/guidescan_amd.h).  Control plane only: no search logic lives here.
  *
- *   guidescan index  [--index PREFIX] [--store-sa] GENOME.fa
+ *   guidescan index  [--index PREFIX] [--store-sa] [--sdsl] [--device D] GENOME.fa
  *       writes PREFIX.gs (chromosome names/lengths, src/genomics/seq_io.cxx:112-122) and
  *       PREFIX.dna (= the reference's <fasta>.forward.dna: upper-cased concatenated sequence,
  *       seq_io.cxx:57-63).  The FM-index itself is built on the GPU when `enumerate` starts
  *       (~25 s at hg38 size, about what the reference needs to load its index files).
+ *       --sdsl: builds the index on the GPU now and also writes PREFIX.forward / PREFIX.reverse, the reference's
+ *       own index files (src/guidescan.cxx:168-175), byte for byte what its `index` command writes: the
+ *       reference binary opens them, and so does `enumerate` here when PREFIX.dna is absent.
  *   guidescan enumerate PREFIX -f KMERS.csv -o OUT [-m 3] [-a PAM ...] [--format csv|sam|bam]
  *       [--mode succinct|complete] [--max-off-targets N] [--start] [--device D] [--gpus N] [--batch-size B]
  *       --gpus N: one index per device (devices D .. D+N-1), one host thread per device pulling batches
@@ -170,7 +173,7 @@ bool read_kmers(const std::string &path, std::vector<kmer_row> &rows, std::strin
 }
 
 int usage() {
-  std::cerr << "usage: guidescan index [--index PREFIX] [--store-sa [--device D]] GENOME.fa\n"
+  std::cerr << "usage: guidescan index [--index PREFIX] [--store-sa] [--sdsl] [--device D] GENOME.fa\n"
                "       guidescan enumerate PREFIX -f KMERS -o OUT [-m N] [-a PAM]... [--format csv|sam|bam]\n"
                "                 [--mode succinct|complete] [--max-off-targets N] [--start]\n"
                "                 [--rna-bulges N] [--dna-bulges N] [-t THRESHOLD] [-n FORMAT_THREADS]\n"
@@ -180,7 +183,7 @@ int usage() {
 
 int do_index(int argc, char **argv) {
   std::string fasta, prefix;
-  bool store_sa = false;
+  bool store_sa = false, sdsl = false;
   int device = 0;
   for (int i = 0; i < argc; i++) {
     const std::string a = argv[i];
@@ -188,6 +191,8 @@ int do_index(int argc, char **argv) {
       prefix = argv[++i];
     else if (a == "--store-sa")
       store_sa = true;
+    else if (a == "--sdsl")
+      sdsl = true;
     else if (a == "--device" && i + 1 < argc)
       device = atoi(argv[++i]);
     else if (!a.empty() && a[0] != '-')
@@ -215,18 +220,21 @@ int do_index(int argc, char **argv) {
   }
   std::cout << "Wrote " << prefix << ".gs and " << prefix << ".dna (" << text.size() << " bases, "
             << gs.names.size() << " sequences)\n";
-  if (store_sa) {
+  if (store_sa || sdsl) {
     /* the part of the index worth storing: both suffix arrays (built on the GPU now), so that
-     * `enumerate` skips the sort; 8 bytes per base on disk */
+     * `enumerate` skips the sort; 8 bytes per base on disk (--store-sa) - or the reference's own
+     * index files, about half a byte per base and strand (--sdsl) */
     gs_index *ix = nullptr;
     gs_status rc = gs_index_build((const uint8_t *)text.data(), text.size(), device, &ix);
-    if (rc == GS_OK) rc = gs_index_save_sa(ix, (const uint8_t *)text.data(), text.size(), (prefix + ".sa").c_str());
+    if (rc == GS_OK && store_sa) rc = gs_index_save_sa(ix, (const uint8_t *)text.data(), text.size(), (prefix + ".sa").c_str());
+    if (rc == GS_OK && sdsl) rc = gs_index_save_sdsl(ix, (const uint8_t *)text.data(), text.size(), prefix.c_str());
     if (ix) gs_index_close(ix);
     if (rc != GS_OK) {
       std::cerr << "error: " << gs_status_string(rc) << "\n";
       return 1;
     }
-    std::cout << "Wrote " << prefix << ".sa\n";
+    if (store_sa) std::cout << "Wrote " << prefix << ".sa\n";
+    if (sdsl) std::cout << "Wrote " << prefix << ".forward and " << prefix << ".reverse\n";
   }
   return 0;
 }

@@ -155,6 +155,21 @@ gs_status gs_sdsl_extract_text(const char *index_file, uint8_t **text, uint64_t 
  * layout here is derived data rebuilt from text + suffix arrays in seconds).  `text` as given to
  * gs_index_build.  gs_index_open_sa returns GS_ERR_FORMAT when the file belongs to another text. */
 gs_status gs_index_save_sa(gs_index *ix, const uint8_t *text, uint64_t len, const char *path);
+/* The reference's own index files from a handle, however it was made: <prefix>.forward and <prefix>.reverse, byte for
+ * byte what sdsl::csa_wt<wt_huff<>,64,8192>::serialize writes for the strand's text - the seam of the reference's `index`
+ * command (src/guidescan.cxx:168-175), layout in SURVEY.md App. A.  The reference binary and gs_index_open_sdsl open
+ * them.  BWT, wavelet-tree bits, rank blocks, select samples and SA / ISA samples are made on the device from the handle's
+ * suffix arrays, strand by strand (scratch: about 3.5 bytes per base; GS_ERR_NOMEM leaves the handle usable); each file
+ * is written under a temporary name and renamed.  `text` as given to gs_index_build; GS_ERR_ARG when len is not the
+ * handle's.  The handle is left as it was found. */
+gs_status gs_index_save_sdsl(gs_index *ix, const uint8_t *text, uint64_t len, const char *prefix);
+/* The two parts of such a file that are functions of the 256 symbol counts alone (host only; tests pin them): the
+ * serialised _byte_tree (Huffman shape, wt_huff.hpp:84-117; wt_helper.hpp:164-278) and the serialised byte_alphabet
+ * (sdsl/lib/csa_alphabet_strategy.cpp:25-55, 103-113).  Both malloc'ed: release with gs_free. */
+gs_status gs_debug_sdsl_sections(const uint64_t counts[256], uint8_t **tree, uint64_t *tree_len, uint8_t **alphabet,
+                                 uint64_t *alphabet_len);
+/* peak device scratch, in bytes, of the last gs_index_save_sdsl of this process */
+uint64_t gs_debug_sdsl_export_scratch(void);
 gs_status gs_index_open_sa(const uint8_t *text, uint64_t len, const char *path, int device, gs_index **out);
 
 void gs_index_close(gs_index *ix);
