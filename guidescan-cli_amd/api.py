@@ -185,6 +185,15 @@ def lib():
                                   vp, vp, vp]
     L.gs_score.restype = i32
     L.gs_score.argtypes = [vp, vp, u64, u32, u32, u32, C.c_int64, C.POINTER(GsGenomeStructure), vp, vp, vp, vp]
+    L.gs_format_device.restype = i32
+    L.gs_format_device.argtypes = [vp, C.POINTER(GsGenomeStructure), vp, u64, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, u32,
+                                   C.c_int64, vp, C.POINTER(vp), C.POINTER(u64)]
+    L.gs_enumerate_text.restype = i32
+    L.gs_enumerate_text.argtypes = [vp, vp, u64, u32, vp, u32, C.c_char_p, u32, u32, u32, C.c_int64,
+                                    C.POINTER(GsGenomeStructure), vp, vp, vp, vp, C.POINTER(vp), C.POINTER(u64),
+                                    C.POINTER(GsResultView)]
+    L.gs_index_last_text_offsets.restype = i32
+    L.gs_index_last_text_offsets.argtypes = [vp, vp, u64]
     L.gs_kmers_generate.restype = i32
     L.gs_kmers_generate.argtypes = [i32, vp, u64, i32, C.c_char_p, u32, u32, vp, C.POINTER(vp)]
     L.gs_kmers_get.restype = i32
@@ -209,7 +218,8 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_index_last_guide_flags", "gs_enumerate_general_pams", "gs_index_save_sa", "gs_index_open_sa", "gs_format_guides_scored", "gs_result_ex_raw_hits",
            "gs_debug_seed_recipes", "gs_debug_choose_thresholds", "gs_debug_tile_plan", "gs_debug_search_form", "gs_debug_guide_descriptor", "gs_index_lock", "gs_index_unlock",
            "gs_index_last_sharing", "gs_index_set_option", "gs_index_get_option", "gs_index_prepare",
-           "gs_index_save_sdsl", "gs_debug_sdsl_sections", "gs_debug_sdsl_export_scratch"]
+           "gs_index_save_sdsl", "gs_debug_sdsl_sections", "gs_debug_sdsl_export_scratch",
+           "gs_format_device", "gs_enumerate_text", "gs_index_last_text_offsets"]
 
 
 def _check(rc):
@@ -350,6 +360,24 @@ def format_guides(gs, ids, seqs, pams, senses_positive, offsets, hits, specifici
     s = C.string_at(out, ln.value)
     lib().gs_free(out)
     return s
+
+
+def _id_blob(ids):
+    """ids -> (bytes back to back, uint64 offsets[n+1]): the layout gs_format_device / gs_enumerate_text take"""
+    enc = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+    off = np.zeros(len(enc) + 1, dtype=np.uint64)
+    if enc:
+        off[1:] = np.cumsum([len(e) for e in enc], dtype=np.uint64)
+    return b"".join(enc), off
+
+
+def _bytes_or_none(x, n):
+    if x is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(x) != 0, dtype=np.uint8)
+    if a.shape != (n,):
+        raise ValueError("one entry per guide")
+    return a
 
 
 class DeviceKmers:
@@ -619,6 +647,62 @@ class GenomeIndex:
         flags = (GS_TEXT_SAM if sam else 0) | (GS_FLAG_PAM_AT_START if start else 0)
         _check(lib().gs_score_device(self._h, d_guides_ptr, n, L, P, flags, max_off_targets, C.byref(gs),
                                      d_offsets_ptr, d_hits_ptr, stream, d_cfd_ptr, d_spec_ptr))
+
+    def format_device(self, gs, d_guides_ptr, n, L, d_pams_ptr, P, ids, senses, skip, d_offsets_ptr, d_hits_ptr,
+                      d_spec_ptr, mismatches, sam=False, complete=True, start=False, max_off_targets=-1, stream=None):
+        """the database text of a fast-path batch encoded in HBM (gs_format_device): raw device addresses in (ids,
+        senses and skip are host sequences, the last two may be None), (d_text_ptr, length) out - device memory of
+        the handle, valid until the next call on it; the bytes are those of format_guides"""
+        blob, off = _id_blob(ids)
+        if len(ids) != n:
+            raise ValueError("one id per guide")
+        se, sk = _bytes_or_none(senses, n), _bytes_or_none(skip, n)
+        flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
+                 (GS_FLAG_PAM_AT_START if start else 0))
+        d_text, ln = C.c_void_p(), C.c_uint64()
+        keep = C.create_string_buffer(blob, len(blob) + 1)
+        _check(lib().gs_format_device(self._h, C.byref(gs), d_guides_ptr, n, L, d_pams_ptr, P, C.addressof(keep),
+                                      off.ctypes.data, se.ctypes.data if se is not None else None,
+                                      sk.ctypes.data if sk is not None else None, d_offsets_ptr, d_hits_ptr, d_spec_ptr,
+                                      mismatches, flags, max_off_targets, stream, C.byref(d_text), C.byref(ln)))
+        return d_text.value, int(ln.value)
+
+    def enumerate_text(self, seqs, pams, ids, senses, gs, mismatches=3, alt_pams=(), start=False, sam=False,
+                       complete=True, max_off_targets=-1, skip=None) -> bytes:
+        """guides in, database text out (gs_enumerate_text): search, scoring and encoding on the device.  Raises
+        GsError with status 3 (GS_ERR_UNSUPPORTED) when a guide of the batch needs the general path."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        n, L = seqs.shape
+        pams = np.ascontiguousarray(pams, dtype=np.uint8)
+        P = pams.shape[1] if pams.ndim == 2 else 0
+        pams = pams.reshape(n, P)
+        for p in alt_pams:
+            if len(p) != P:
+                raise ValueError("alt PAM length differs from the guides' PAM length")
+        alt = b"".join(p.encode() for p in alt_pams)
+        if len(ids) != n:
+            raise ValueError("one id per guide")
+        blob, off = _id_blob(ids)
+        se, sk = _bytes_or_none(senses, n), _bytes_or_none(skip, n)
+        flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
+                 (GS_FLAG_PAM_AT_START if start else 0))
+        keep = C.create_string_buffer(blob, len(blob) + 1)
+        out, ln = C.c_void_p(), C.c_uint64()
+        _check(lib().gs_enumerate_text(self._h, seqs.ctypes.data, n, L, pams.ctypes.data if P else None, P,
+                                       alt if alt_pams else None, len(alt_pams), mismatches, flags, max_off_targets,
+                                       C.byref(gs), C.addressof(keep), off.ctypes.data,
+                                       se.ctypes.data if se is not None else None,
+                                       sk.ctypes.data if sk is not None else None, C.byref(out), C.byref(ln), None))
+        s = C.string_at(out, ln.value)
+        lib().gs_free(out)
+        return s
+
+    def last_text_offsets(self, n):
+        """byte offset at which each guide's lines begin in the text of the last format_device / enumerate_text of n
+        guides on this handle, uint64[n+1] (gs_index_last_text_offsets)"""
+        out = np.empty(n + 1, dtype=np.uint64)
+        _check(lib().gs_index_last_text_offsets(self._h, out.ctypes.data, n))
+        return out
 
     def enumerate_general(self, seqs, pams, mismatches=3, rna_bulges=0, dna_bulges=0, alt_pams=(),
                           start=False):

@@ -180,7 +180,9 @@ struct gs_index {
       /* per-guide ordering in LDS tiles (gs_tileorder.hip): k_search's per-class counts, the plan's scans, tile
        * descriptors, bucket space, chunk index, partitioned items, class starts, rank tables + flags */
       w_cls, w_desc, w_sched, /* gs_seed.hip: descriptors per guide; work counters, histograms, the two schedules */
-      w_t_plan, w_t_tiles, w_t_buckets, w_t_chunkof, w_t_big, w_t_rel, w_t_tab, w_t_excl, w_t_spill, w_b_redo_pos2;
+      w_t_plan, w_t_tiles, w_t_buckets, w_t_chunkof, w_t_big, w_t_rel, w_t_tab, w_t_excl, w_t_spill, w_b_redo_pos2,
+      /* gs_textdev.hip: what gs_format_device uploads, its scratch, the of:H: fields, the text it returns; gs_enumerate_text's specificities */
+      w_text_in, w_text_tmp, w_text_hex, w_text, w_text_spec, w_text_goff /* per-guide text offsets */;
   uint32_t share_backoff = 0; /* batches this handle still runs without sharing after a sharing launch was not resident as a whole */
   bool share_timed_out = false; /* a helping wave gave up waiting for a package (k_search_body): the call fails, gs_enumerate_device redoes the batch without sharing */
   uint32_t opt_share_min = 512, opt_share_max = 2048; /* groups of eight rows: a verification pass of share_min or more is handed out, in packages of at most share_max (0: items are never shared) */
@@ -227,6 +229,7 @@ struct gs_index {
   uint32_t dbg_nomem = 0;   /* GS_DBG_NOMEM (tests of those recoveries): passes of a batch that still end as if out of device memory */
   bool tile_order_off = false; /* a batch had interval records or one sequence at one row twice: the per-guide tile ordering is not tried again for that shape */
   uint64_t tile_order_off_key = 0;
+  uint64_t tx_n = 0; /* gs_textdev.hip: guides of the last gs_format_device, whose per-guide text offsets w_text_goff holds (0: none) */
   bool big_long_runs = false; /* a batch showed long runs of one sequence (repeat-rich genome): the device-wide ordering sorts by row, then by word (gs_search.hip) */
 };
 

@@ -1661,6 +1661,7 @@ static gs_status enumerate_device_impl(gs_index *ix, const void *d_guides, uint6
   b.count_req = (flags & GS_FLAG_COUNT_REQUESTS) != 0;
   GS_HIP(hipSetDevice(ix->device));
   ix->last_unsupported = 0;
+  ix->tx_n = 0; /* the last text and its per-guide offsets do not outlive the next batch */
   for (int i = 0; i < 4; i++)
     if (!ix->ev[i]) GS_HIP(hipEventCreate(&ix->ev[i]));
   gs_status rc;
@@ -1714,7 +1715,7 @@ static bool recover_release_workspace(gs_index *ix, gs_status rc) {
   for (gs_buffer *b : {&ix->w_b_src, &ix->w_b_cnt, &ix->w_b_prefix, &ix->w_b_recs, &ix->w_b_w0, &ix->w_b_w0b, &ix->w_b_idx,
                        &ix->w_b_idxb, &ix->w_b_keep, &ix->w_b_keeps, &ix->w_b_rows, &ix->w_b_rowss, &ix->w_b_s, &ix->w_slots2, &ix->w_h_tmp,
                        &ix->w_t_buckets, &ix->w_t_tiles, &ix->w_t_chunkof, &ix->w_t_big, &ix->w_hits, &ix->w_score_tmp, &ix->w_score_io,
-                       &ix->w_arena, &ix->w_shq, &ix->w_slots})
+                       &ix->w_arena, &ix->w_shq, &ix->w_slots, &ix->w_text_tmp, &ix->w_text_hex, &ix->w_text})
     freed += gs_buffer_free(*b);
   size_t redo_min = RELEASE_REDO_MIN;
   if (const char *e = gs_opt(ix, "GS_DBG_RELEASE_MIN")) redo_min = (size_t)strtoull(e, nullptr, 10); /* (tests: bytes) */

@@ -5,7 +5,9 @@
 #include "gs_common.h"
 #include "cfd_table.h"
 
+#include <algorithm>
 #include <cctype>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 
@@ -84,7 +86,7 @@ extern "C" const char *gs_status_string(gs_status s) {
   }
   return "unknown";
 }
-extern "C" const char *gs_version(void) { return "guidescan-amd 0.2 (gfx950)"; }
+extern "C" const char *gs_version(void) { return "guidescan-amd 0.3 (gfx950)"; }
 
 /* Page-locked host buffers for the results of the host-pointer entry point, kept in a small
  * process-wide pool: a 1 M-guide batch returns ~215 MB of hits, and a fresh pageable buffer costs
@@ -201,6 +203,99 @@ extern "C" gs_status gs_enumerate(gs_index *ix, const char *guides, uint64_t n, 
   GS_HANDLE_LOCK(ix);
   try { /* nothing may throw across the C boundary */
     return enumerate_host(ix, guides, n, L, guide_pams, P, alt_pams, n_alt, mismatches, flags, out);
+  } catch (const std::bad_alloc &) {
+    return GS_ERR_NOMEM;
+  }
+}
+
+/* search -> score -> encode on the device (gs_textdev.hip), then the text back to the host: two page-locked staging
+ * buffers, the copy out of one overlapping the transfer into the other */
+static gs_status enumerate_text(gs_index *ix, const char *guides, uint64_t n, uint32_t L, const char *guide_pams, uint32_t P,
+                                const char *alt_pams, uint32_t n_alt, uint32_t mismatches, uint32_t flags,
+                                int64_t max_off_targets, const gs_genome_structure *gs, const char *ids,
+                                const uint64_t *id_offsets, const uint8_t *senses, const uint8_t *skip, char **text,
+                                uint64_t *len, gs_result_view *stats) {
+  GS_HIP(hipSetDevice(ix->device));
+  gs_status rc = gs_reserve(ix->w_guides, n * (size_t)(L + P) + 16);
+  if (rc != GS_OK) return rc;
+  if ((rc = gs_reserve(ix->w_text_spec, 4 * n + 16)) != GS_OK) return rc;
+  char *d_g = (char *)ix->w_guides.p;
+  char *d_p = d_g + n * (size_t)L;
+  if (n) {
+    GS_HIP(hipMemcpy(d_g, guides, n * (size_t)L, hipMemcpyHostToDevice));
+    if (P) GS_HIP(hipMemcpy(d_p, guide_pams, n * (size_t)P, hipMemcpyHostToDevice));
+  }
+  const void *d_off = nullptr, *d_hits = nullptr, *d_text = nullptr;
+  gs_result_view v;
+  memset(&v, 0, sizeof v);
+  const uint32_t tflags = flags & (GS_TEXT_SAM | GS_TEXT_COMPLETE), sflags = flags & ~(GS_TEXT_SAM | GS_TEXT_COMPLETE);
+  rc = gs_enumerate_device(ix, d_g, n, L, d_p, P, alt_pams, n_alt, mismatches, sflags, nullptr, &d_off, &d_hits, &v);
+  if (rc != GS_OK) return rc;
+  if (stats) *stats = v;
+  if (ix->last_unsupported) {
+    gs_set_error("a guide of the batch needs the general path");
+    return GS_ERR_UNSUPPORTED;
+  }
+  uint64_t tl = 0;
+  if (n) {
+    rc = gs_score_device(ix, d_g, n, L, P, tflags | (sflags & GS_FLAG_PAM_AT_START), max_off_targets, gs, d_off, d_hits, nullptr,
+                         nullptr, ix->w_text_spec.p);
+    if (rc != GS_OK) return rc;
+    rc = gs_format_device(ix, gs, d_g, n, L, d_p, P, ids, id_offsets, senses, skip, d_off, d_hits, ix->w_text_spec.p, mismatches,
+                          tflags | (sflags & GS_FLAG_PAM_AT_START), max_off_targets, nullptr, &d_text, &tl);
+    if (rc != GS_OK) return rc;
+  }
+  char *out = (char *)malloc(tl + 1);
+  if (!out) return GS_ERR_NOMEM;
+  const size_t CH = (size_t)32 << 20;
+  gs_pinned pin[2] = {pin_acquire(std::min<size_t>(CH, tl)), tl > CH ? pin_acquire(std::min<size_t>(CH, tl - CH)) : gs_pinned()};
+  hipError_t e = hipSuccess;
+  if (tl && (!pin[0].p || (tl > CH && !pin[1].p))) { /* no page-locked memory: the runtime stages the copy */
+    e = hipMemcpy(out, d_text, tl, hipMemcpyDeviceToHost);
+  } else if (tl) {
+    const size_t nch = (tl + CH - 1) / CH;
+    auto bytes = [&](size_t c) { return std::min<size_t>(CH, tl - c * CH); };
+    e = hipMemcpyAsync(pin[0].p, d_text, bytes(0), hipMemcpyDeviceToHost, nullptr);
+    for (size_t c = 0; c < nch && e == hipSuccess; c++) {
+      e = hipStreamSynchronize(nullptr);
+      if (e == hipSuccess && c + 1 < nch)
+        e = hipMemcpyAsync(pin[(c + 1) & 1].p, (const char *)d_text + (c + 1) * CH, bytes(c + 1), hipMemcpyDeviceToHost, nullptr);
+      if (e == hipSuccess) memcpy(out + c * CH, pin[c & 1].p, bytes(c));
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(nullptr);
+  }
+  pin_release(pin[0]);
+  pin_release(pin[1]);
+  if (e != hipSuccess) {
+    free(out);
+    gs_set_error(std::string("copy of the text: ") + hipGetErrorString(e));
+    return GS_ERR_DEVICE;
+  }
+  out[tl] = 0;
+  *text = out;
+  *len = tl;
+  return GS_OK;
+}
+extern "C" gs_status gs_enumerate_text(gs_index *ix, const char *guides, uint64_t n, uint32_t L, const char *guide_pams,
+                                       uint32_t P, const char *alt_pams, uint32_t n_alt, uint32_t mismatches, uint32_t flags,
+                                       int64_t max_off_targets, const gs_genome_structure *gs, const char *ids,
+                                       const uint64_t *id_offsets, const uint8_t *senses, const uint8_t *skip, char **text,
+                                       uint64_t *len, gs_result_view *stats) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !gs || !text || !len) return GS_ERR_ARG;
+  if (n && (!guides || !ids || !id_offsets || (P && !guide_pams))) return GS_ERR_ARG;
+  if ((n_alt && !alt_pams) || (gs->n_chr && (!gs->chr_names || !gs->chr_lengths))) return GS_ERR_ARG;
+  if (n >= (1ull << 31) || max_off_targets < -1 || mismatches > 7 || n_alt > 31) return GS_ERR_ARG;
+  if (L < 1 || L > 31 || P > 8 || 2 * L + 3 * P > 59) return GS_ERR_ARG;
+  for (uint64_t g = 0; g < n; g++)
+    if (id_offsets[g + 1] < id_offsets[g]) return GS_ERR_ARG;
+  for (uint32_t c = 0; c < gs->n_chr; c++)
+    if (!gs->chr_names[c]) return GS_ERR_ARG;
+  *text = nullptr;
+  *len = 0;
+  try { /* nothing may throw across the C boundary */
+    return enumerate_text(ix, guides, n, L, guide_pams, P, alt_pams, n_alt, mismatches, flags, max_off_targets, gs, ids, id_offsets,
+                          senses, skip, text, len, stats);
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;
   }

@@ -1,0 +1,754 @@
+/*
+ * gs_textdev.hip -- the database text on the device ("at scale"): the bytes
+ * gs_format_guides_scored writes (gs_text.hip: get_csv_lines / get_sam_lines, include/genomics/printer.hpp:115-360,
+ * resolve_absolute, src/genomics/structures.cxx:7-52), produced from the CSR hit lists, the guides and the per-guide
+ * specificities where they already are: in HBM.  Integer arithmetic only - the specificity's "%f" included.
+ *
+ * Rows are the unit of work, not guides.  Every guide owns one guide slot (its `NA` row, the checks made once per
+ * guide) followed by one slot per hit: slot of guide g = (offsets[g] - offsets[0]) + g.  A tile is 64 consecutive slots,
+ * one wavefront:
+ *   k_tx_len    the byte length of every slot's row (0: no row), the tile's sum;
+ *   (rocPRIM)   64-bit exclusive scan of the tile sums: a batch of 4 M guides is more than 4 GB of text;
+ *   k_tx_write  every lane composes its row into the wave's LDS slice at its offset inside the tile, then the wave
+ *               streams the tile's contiguous span out with 16-byte stores (LDS and HBM addresses are congruent mod 16;
+ *               only the span's ragged head and tail are byte stores).  A tile whose span outgrows the slice (very long
+ *               ids or chromosome names, long of:H: fields) is composed in HBM directly.
+ * Both kernels run ONE row routine over two sinks, a counting one and a writing one: the lengths cannot disagree.
+ * SAM needs three per-guide facts first (k_tx_sam_ok, k_tx_sam_guide): the unfiltered count per distance, the hits kept
+ * per distance (the cap counts kept hits, after the boundary drop: printer.hpp:129 - the CSV cap counts raw indices,
+ * :259), and the of:H: field, which is composed once per guide into a scratch span (k_tx_sam_hex) and copied into each
+ * of the guide's lines by the whole wave.
+ */
+#include "gs_device.h"
+
+#include <rocprim/rocprim.hpp>
+
+#include <algorithm>
+
+#define TX_WAVES 4
+#define TX_LDS 12288u            /* bytes of a wave's slice */
+#define TX_MAX_ROW (1u << 25)    /* a row of this many bytes or more is refused: 64 of them stay below 2^31 */
+#define TX_ERR_ARG 1u
+#define TX_ERR_BIG 2u
+
+struct tx_args {
+  const uint8_t *guides, *pams;   /* n*L, n*P ASCII */
+  const uint8_t *ids;             /* the ids back to back */
+  const uint64_t *id_off;         /* n+1, from 0 */
+  const uint8_t *senses, *skip;   /* n bytes each, or nullptr */
+  const uint64_t *offsets;        /* n+1 positions into hits */
+  const gs_hit *hits;
+  const float *spec;
+  const uint64_t *chr_cum;        /* n_chr+1 prefix sums of the chromosome lengths */
+  const uint8_t *chr_names;
+  const uint32_t *chr_name_off;   /* n_chr+1 */
+  uint32_t *lens;                 /* per slot */
+  uint64_t *tile_sum, *tile_off;  /* per tile (+1) */
+  char *text;
+  uint32_t *err;
+  /* SAM: boundary flags and their prefix sums per hit; per guide and distance the unfiltered count, the prefix sum at
+   * the distance's first hit, the 16-character units of the of:H: field before the distance's positions */
+  uint32_t *okf, *S, *cnt, *sbase, *kbase;
+  uint64_t *hex_units, *hex_off;
+  char *hex;
+  uint64_t slots, off0, n_hits;
+  long long max_off, delim;
+  uint32_t n, L, P, n_chr, m, start, sam, complete;
+};
+
+/* ---- small pieces -------------------------------------------------------------------------------------------- */
+__device__ __forceinline__ uint32_t tx_comp(uint32_t c) { /* src/genomics/sequences.cxx:14-26 */
+  switch (c) {
+    case 'A': return 'T';
+    case 'T': return 'A';
+    case 'C': return 'G';
+    case 'G': return 'C';
+    case 'a': return 't';
+    case 't': return 'a';
+    case 'c': return 'g';
+    case 'g': return 'c';
+    default: return c;
+  }
+}
+__device__ __forceinline__ uint32_t tx_digits(uint64_t v) {
+  uint32_t k = 1;
+  if (v < (1ull << 32)) {
+    uint32_t w = (uint32_t)v;
+    while (w >= 10u) {
+      w /= 10u;
+      k++;
+    }
+    return k;
+  }
+  while (v >= 10ull) {
+    v /= 10ull;
+    k++;
+  }
+  return k;
+}
+
+/* "%f" of a float in [0, 1] as round(f * 10^6) under round-half-even on the exact value (what glibc prints):
+ * f = m * 2^e with m < 2^24, so m * 10^6 < 2^44; shifted right by -e with the exact remainder deciding. */
+__device__ __forceinline__ bool tx_spec_ok(uint32_t bits) { return bits <= 0x3F800000u; } /* +0 .. 1.0; no sign, NaN, inf */
+__device__ __forceinline__ uint32_t tx_spec_q(uint32_t bits) {
+  const uint32_t ex = bits >> 23, mant = bits & 0x7FFFFFu;
+  const uint64_t m = ex ? (uint64_t)(mant | 0x800000u) : (uint64_t)mant;
+  const uint32_t sh = ex ? 150u - ex : 149u; /* f = m * 2^-sh, sh >= 23 for f <= 1 */
+  const uint64_t x = m * 1000000ull;
+  if (sh >= 64u) return 0u; /* x < 2^44 <= half an ulp of the last digit */
+  uint64_t q = x >> sh;
+  const uint64_t rem = x & ((1ull << sh) - 1ull), half = 1ull << (sh - 1u);
+  if (rem > half || (rem == half && (q & 1ull))) q++;
+  return (uint32_t)q;
+}
+
+struct tx_loc {
+  int c; /* chromosome, -1: dropped at a boundary */
+  long long s;
+  char st;
+};
+/* src/genomics/structures.cxx:7-52 by binary search over the prefix sums (as format_csv_fast restates it) */
+__device__ __forceinline__ tx_loc tx_resolve(const tx_args &a, long long pos) {
+  tx_loc r;
+  r.c = -1;
+  r.s = 0;
+  r.st = '+';
+  unsigned long long ab = (unsigned long long)pos;
+  if (pos < 0) {
+    ab = 0ull - ab;
+    r.st = '-';
+  }
+  if (a.n_chr == 0u || ab >= a.chr_cum[a.n_chr]) return r;
+  uint32_t lo = 0, hi = a.n_chr; /* first chromosome whose end exceeds ab */
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (ab < a.chr_cum[mid + 1u])
+      hi = mid;
+    else
+      lo = mid + 1u;
+  }
+  if (lo >= a.n_chr) return r;
+  const long long in_chr = (long long)(ab - a.chr_cum[lo]), len = (long long)(a.chr_cum[lo + 1u] - a.chr_cum[lo]);
+  long long s, e;
+  if (r.st == '+') {
+    e = in_chr + 1;
+    s = e - (long long)a.L - (long long)a.P + 1;
+  } else {
+    s = in_chr + 1;
+    e = s + (long long)a.L + (long long)a.P - 1;
+  }
+  if (s < 0 || e > len) return r; /* :46-48, s < 0 not s < 1 */
+  r.c = (int)lo;
+  r.s = s;
+  return r;
+}
+
+/* slots: guide g's own slot, then its hits */
+__device__ __forceinline__ uint64_t tx_slot_of(const tx_args &a, uint32_t g) { return a.offsets[g] - a.off0 + g; }
+/* the guide of a tile's first slot (wave-uniform), then each lane walks to its own */
+__device__ __forceinline__ uint32_t tx_guide_of(const tx_args &a, uint64_t s0, uint64_t s) {
+  uint32_t lo = 0, hi = a.n; /* last g with slot_of(g) <= s0 */
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (tx_slot_of(a, mid) <= s0)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  uint32_t g = lo;
+  while (g + 1u < a.n && tx_slot_of(a, g + 1u) <= s) g++;
+  return g;
+}
+/* first hit of [b, e) at distance d or more (hits are in canonical order: distance ascending) */
+__device__ __forceinline__ uint64_t tx_first_at(const gs_hit *hits, uint64_t b, uint64_t e, uint32_t d) {
+  while (b < e) {
+    const uint64_t mid = (b + e) >> 1;
+    if ((uint32_t)(hits[mid].key >> 61) < d)
+      b = mid + 1u;
+    else
+      e = mid;
+  }
+  return b;
+}
+
+/* ---- the two sinks ------------------------------------------------------------------------------------------- */
+struct tx_count {
+  uint64_t n = 0;
+  __device__ __forceinline__ void ch(uint32_t) { n++; }
+  __device__ __forceinline__ void put(const uint8_t *, uint32_t k) { n += k; }
+  __device__ __forceinline__ void lit(const char *, uint32_t k) { n += k; }
+  __device__ __forceinline__ void u64(uint64_t v) { n += tx_digits(v); }
+  __device__ __forceinline__ void span(const char *, uint64_t k) { n += k; }
+};
+struct tx_write {
+  char *p;
+  /* the of:H: field of a SAM line is copied by the whole wave afterwards */
+  char *sp_dst = nullptr;
+  const char *sp_src = nullptr;
+  uint64_t sp_n = 0;
+  __device__ __forceinline__ void ch(uint32_t c) { *p++ = (char)c; }
+  __device__ __forceinline__ void put(const uint8_t *s, uint32_t k) {
+    for (uint32_t i = 0; i < k; i++) p[i] = (char)s[i];
+    p += k;
+  }
+  __device__ __forceinline__ void lit(const char *s, uint32_t k) {
+    for (uint32_t i = 0; i < k; i++) p[i] = s[i];
+    p += k;
+  }
+  __device__ __forceinline__ void u64(uint64_t v) {
+    const uint32_t k = tx_digits(v);
+    char *q = p + k;
+    if (v < (1ull << 32)) {
+      uint32_t w = (uint32_t)v;
+      do {
+        *--q = (char)('0' + w % 10u);
+        w /= 10u;
+      } while (w);
+    } else {
+      do {
+        *--q = (char)('0' + (uint32_t)(v % 10ull));
+        v /= 10ull;
+      } while (v);
+    }
+    p += k;
+  }
+  __device__ __forceinline__ void span(const char *s, uint64_t k) {
+    sp_dst = p;
+    sp_src = s;
+    sp_n = k;
+    p += k;
+  }
+};
+#define TX_LIT(o, s) (o).lit(s, (uint32_t)sizeof(s) - 1u)
+
+/* ---- the rows ------------------------------------------------------------------------------------------------ */
+template <class S>
+__device__ __forceinline__ void tx_id(S &o, const tx_args &a, uint32_t g) {
+  const uint64_t b = a.id_off[g];
+  o.put(a.ids + b, (uint32_t)(a.id_off[g + 1u] - b));
+}
+template <class S>
+__device__ __forceinline__ void tx_sequence(S &o, const tx_args &a, uint32_t g) { /* sequence + pam, or pam + sequence under --start */
+  const uint8_t *gd = a.guides + (size_t)g * a.L, *pm = a.pams + (size_t)g * a.P;
+  if (a.start) o.put(pm, a.P);
+  o.put(gd, a.L);
+  if (!a.start) o.put(pm, a.P);
+}
+template <class S>
+__device__ __forceinline__ void tx_specificity(S &o, uint32_t q) { /* std::to_string(float): d.dddddd */
+  o.ch('0' + q / 1000000u);
+  o.ch('.');
+  uint32_t r = q % 1000000u, div = 100000u;
+  for (int i = 0; i < 6; i++) {
+    o.ch('0' + r / div);
+    r %= div;
+    div /= 10u;
+  }
+}
+template <class S>
+__device__ __forceinline__ void tx_chr_name(S &o, const tx_args &a, int c) {
+  const uint32_t b = a.chr_name_off[c];
+  o.put(a.chr_names + b, a.chr_name_off[c + 1] - b);
+}
+
+/* the guide's own slot: its NA row (printer.hpp:189-199), and the checks made once per guide */
+template <class S>
+__device__ __forceinline__ void tx_guide_row(S &o, const tx_args &a, uint32_t g, uint32_t &err) {
+  if (a.skip && a.skip[g]) return;
+  const uint64_t nh = a.offsets[g + 1u] - a.offsets[g];
+  if (nh) {
+    if (!tx_spec_ok(__float_as_uint(a.spec[g]))) err |= TX_ERR_ARG;
+    if ((uint32_t)(a.hits[a.offsets[g + 1u] - 1u].key >> 61) > a.m) err |= TX_ERR_ARG; /* the last hit has the largest distance */
+    return;
+  }
+  if (a.sam) return;
+  tx_id(o, a, g);
+  o.ch(',');
+  tx_sequence(o, a, g);
+  TX_LIT(o, ",NA,NA,NA,0");
+  if (a.complete) TX_LIT(o, ",NA,NA,NA");
+  TX_LIT(o, ",1.0\n");
+}
+
+/* one CSV row (printer.hpp:245-300 as format_csv_fast restates it) */
+template <class S>
+__device__ __forceinline__ void tx_csv_row(S &o, const tx_args &a, uint32_t g, uint64_t h, uint32_t &err) {
+  if (a.skip && a.skip[g]) return;
+  const gs_hit hit = a.hits[h];
+  const uint32_t d = (uint32_t)(hit.key >> 61);
+  if (d > a.m) {
+    err |= TX_ERR_ARG;
+    return;
+  }
+  if (a.max_off != -1) { /* the raw index within the distance, :259 */
+    const uint64_t first = tx_first_at(a.hits, a.offsets[g], h, d);
+    if ((long long)(h - first) >= a.max_off) return;
+  }
+  const tx_loc loc = tx_resolve(a, (long long)hit.pos);
+  if (loc.c < 0) return; /* boundary hit: no row (:280-283) */
+  tx_id(o, a, g);
+  o.ch(',');
+  tx_sequence(o, a, g);
+  o.ch(',');
+  tx_chr_name(o, a, loc.c);
+  o.ch(',');
+  o.u64((uint64_t)loc.s);
+  o.ch(',');
+  o.ch(loc.st);
+  o.ch(',');
+  o.ch('0' + d);
+  if (a.complete) {
+    o.ch(',');
+    /* complement(match.sequence) from key bits 59:1 (gs_decode_sequence + printer.hpp:232,264) */
+    const uint8_t *gd = a.guides + (size_t)g * a.L;
+    const uint64_t path = (hit.key >> 1) & ((1ull << 59) - 1ull);
+    for (uint32_t t = 0; t < a.L; t++) {
+      const uint32_t gq = a.start ? gd[a.L - 1u - t] : gd[t];
+      const uint32_t qc = a.start ? gq : tx_comp(gq); /* the query symbol of this step (index.hpp:218) */
+      const uint32_t code = (uint32_t)(path >> (57u - 2u * t)) & 3u;
+      if (code == 0u) {
+        o.ch(tx_comp(qc));
+      } else {
+        const int q = qc == 'A' ? 0 : qc == 'C' ? 1 : qc == 'G' ? 2 : qc == 'T' ? 3 : -1;
+        if (q < 0) {
+          err |= TX_ERR_ARG;
+          return;
+        }
+        int b = (int)code - 1;
+        if (b >= q) b++;
+        o.ch(b == 0 ? 't' : b == 1 ? 'g' : b == 2 ? 'c' : 'a'); /* complement, lower case: the mismatch (index.hpp:243) */
+      }
+    }
+    for (uint32_t u = 0; u < a.P; u++) {
+      const uint32_t code = (uint32_t)(path >> (56u - 2u * a.L - 3u * u)) & 7u;
+      if (code > 4u) {
+        err |= TX_ERR_ARG;
+        return;
+      }
+      o.ch(code == 0u ? 'T' : code == 1u ? 'G' : code == 2u ? 'C' : code == 3u ? 'N' : 'A'); /* complement of A,C,G,N,T */
+    }
+    TX_LIT(o, ",0,0"); /* rna_bulges, dna_bulges */
+  }
+  o.ch(',');
+  tx_specificity(o, tx_spec_q(__float_as_uint(a.spec[g])));
+  o.ch('\n');
+}
+
+/* one SAM line: a distance-0 hit (printer.hpp:314-357) */
+template <class S>
+__device__ __forceinline__ void tx_sam_row(S &o, const tx_args &a, uint32_t g, uint64_t h) {
+  if (a.skip && a.skip[g]) return;
+  const gs_hit hit = a.hits[h];
+  if ((uint32_t)(hit.key >> 61) != 0u) return;
+  const bool pos_sense = a.senses ? a.senses[g] != 0 : true;
+  const tx_loc loc = tx_resolve(a, (long long)hit.pos);
+  tx_id(o, a, g);
+  o.ch('\t');
+  if (pos_sense)
+    o.ch('0');
+  else
+    TX_LIT(o, "16");
+  o.ch('\t');
+  if (loc.c >= 0) tx_chr_name(o, a, loc.c); /* no sentinel check in the reference: empty RNAME */
+  o.ch('\t');
+  o.u64(loc.c >= 0 ? (uint64_t)loc.s : 0ull);
+  TX_LIT(o, "\t100\t");
+  o.u64((uint64_t)a.L + a.P);
+  TX_LIT(o, "M\t*\t0\t0\t");
+  if (pos_sense) {
+    tx_sequence(o, a, g);
+  } else { /* reverse_complement(sequence) */
+    const uint8_t *gd = a.guides + (size_t)g * a.L, *pm = a.pams + (size_t)g * a.P;
+    const uint32_t lp = a.L + a.P;
+    for (uint32_t i = 0; i < lp; i++) {
+      const uint32_t j = lp - 1u - i; /* sequence[j] */
+      const uint32_t c = a.start ? (j < a.P ? pm[j] : gd[j - a.P]) : (j < a.L ? gd[j] : pm[j - a.L]);
+      o.ch(tx_comp(c));
+    }
+  }
+  TX_LIT(o, "\t*");
+  for (uint32_t d = 0; d <= a.m; d++) {
+    TX_LIT(o, "\tk");
+    o.ch('0' + d);
+    TX_LIT(o, ":i:");
+    o.u64(a.cnt[(size_t)g * 8u + d]); /* unfiltered */
+  }
+  if (a.complete) {
+    TX_LIT(o, "\tof:H:");
+    o.span(a.hex + 16u * a.hex_off[g], 16u * (a.hex_off[g + 1u] - a.hex_off[g]));
+  }
+  TX_LIT(o, "\tsp:f:");
+  tx_specificity(o, tx_spec_q(__float_as_uint(a.spec[g])));
+  o.ch('\n');
+}
+
+template <class S>
+__device__ __forceinline__ void tx_slot_row(S &o, const tx_args &a, uint64_t s0, uint64_t s, uint32_t &err) {
+  const uint32_t g = tx_guide_of(a, s0, s);
+  const uint64_t gs0 = tx_slot_of(a, g);
+  if (s == gs0)
+    tx_guide_row(o, a, g, err);
+  else if (a.sam)
+    tx_sam_row(o, a, g, a.offsets[g] + (s - gs0 - 1u));
+  else
+    tx_csv_row(o, a, g, a.offsets[g] + (s - gs0 - 1u), err);
+}
+
+/* ---- kernels ------------------------------------------------------------------------------------------------- */
+__global__ __launch_bounds__(WAVE *TX_WAVES) void k_tx_len(tx_args a, uint32_t n_tiles) {
+  const uint32_t lane = threadIdx.x & (WAVE - 1u);
+  const uint32_t wave0 = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE, n_waves = gridDim.x * blockDim.x / WAVE;
+  for (uint32_t tile = wave0; tile < n_tiles; tile += n_waves) {
+    const uint64_t s0 = (uint64_t)tile * WAVE, s = s0 + lane;
+    uint32_t len = 0, err = 0;
+    if (s < a.slots) {
+      tx_count o;
+      tx_slot_row(o, a, s0, s, err);
+      if (o.n >= TX_MAX_ROW) {
+        err |= TX_ERR_BIG;
+        o.n = 0;
+      }
+      len = err ? 0u : (uint32_t)o.n;
+      a.lens[s] = len;
+    }
+    if (err) atomicOr(a.err, err);
+    const uint32_t incl = wave_incl_sum(len);
+    if (lane == WAVE - 1u) a.tile_sum[tile] = incl;
+  }
+}
+
+__global__ __launch_bounds__(WAVE *TX_WAVES) void k_tx_write(tx_args a, uint32_t n_tiles) {
+  __shared__ __attribute__((aligned(16))) char s_buf[TX_WAVES][TX_LDS];
+  const uint32_t lane = threadIdx.x & (WAVE - 1u);
+  char *buf = s_buf[threadIdx.x / WAVE];
+  const uint32_t wave0 = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE, n_waves = gridDim.x * blockDim.x / WAVE;
+  for (uint32_t tile = wave0; tile < n_tiles; tile += n_waves) {
+    const uint64_t s0 = (uint64_t)tile * WAVE, s = s0 + lane;
+    const uint32_t len = s < a.slots ? a.lens[s] : 0u;
+    const uint32_t incl = wave_incl_sum(len);
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
+    if (total == 0u) continue;
+    const uint64_t base = a.tile_off[tile];
+    const uint32_t a0 = (uint32_t)(base & 15u); /* the slice holds the span at the same address mod 16 as HBM does */
+    const bool in_lds = a0 + total <= TX_LDS;
+    uint32_t err = 0;
+    tx_write o;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); /* (the tile before has been read out of the slice) */
+    if (in_lds) {
+      o.p = buf + a0 + (incl - len);
+      if (len) tx_slot_row(o, a, s0, s, err);
+    } else {
+      o.p = a.text + base + (incl - len);
+      if (len) tx_slot_row(o, a, s0, s, err);
+    }
+    /* the of:H: fields: one line after the other, 64 bytes per step */
+    uint64_t todo = __ballot(o.sp_n != 0ull);
+    while (todo) {
+      const int l = __ffsll((long long)todo) - 1;
+      todo &= todo - 1ull;
+      char *dst = (char *)(((uint64_t)(uint32_t)__shfl((int)((uint64_t)o.sp_dst >> 32), l) << 32) |
+                           (uint32_t)__shfl((int)(uint32_t)(uint64_t)o.sp_dst, l));
+      const char *src = (const char *)(((uint64_t)(uint32_t)__shfl((int)((uint64_t)o.sp_src >> 32), l) << 32) |
+                                       (uint32_t)__shfl((int)(uint32_t)(uint64_t)o.sp_src, l));
+      const uint64_t k = ((uint64_t)(uint32_t)__shfl((int)(o.sp_n >> 32), l) << 32) | (uint32_t)__shfl((int)(uint32_t)o.sp_n, l);
+      for (uint64_t i = lane; i < k; i += WAVE) dst[i] = src[i];
+    }
+    if (!in_lds) continue;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    char *out = a.text + (base - a0); /* 16-byte aligned */
+    const uint32_t end = a0 + total, c_first = (a0 + 15u) >> 4, c_last = end >> 4; /* whole 16-byte chunks [c_first, c_last) */
+    if (c_first >= c_last) {
+      for (uint32_t i = a0 + lane; i < end; i += WAVE) out[i] = buf[i];
+    } else {
+      for (uint32_t i = a0 + lane; i < c_first * 16u; i += WAVE) out[i] = buf[i];
+      for (uint32_t c = c_first + lane; c < c_last; c += WAVE) ((uint4 *)out)[c] = ((const uint4 *)buf)[c];
+      for (uint32_t i = c_last * 16u + lane; i < end; i += WAVE) out[i] = buf[i];
+    }
+  }
+}
+
+/* SAM: 1 = the hit survives resolve_absolute */
+__global__ __launch_bounds__(256) void k_tx_sam_ok(tx_args a) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= a.n_hits; i += (uint64_t)gridDim.x * blockDim.x)
+    a.okf[i] = i < a.n_hits && tx_resolve(a, (long long)a.hits[a.off0 + i].pos).c >= 0 ? 1u : 0u;
+}
+/* SAM: per guide and distance the unfiltered count (k{d}:i:), and where its kept positions stand in the of:H: field
+ * (off_target_fields, printer.hpp:115-170: the cap counts hits that passed the boundary check) */
+__global__ __launch_bounds__(256) void k_tx_sam_guide(tx_args a) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g > a.n) return;
+  if (g == a.n) {
+    a.hex_units[g] = 0;
+    return;
+  }
+  const uint64_t b = a.offsets[g], e = a.offsets[g + 1u];
+  uint64_t lo = b;
+  uint32_t units = 0;
+  bool lines = false;
+  for (uint32_t d = 0; d <= a.m; d++) {
+    const uint64_t hi = tx_first_at(a.hits, lo, e, d + 1u);
+    const uint32_t okc = a.S[hi - a.off0] - a.S[lo - a.off0];
+    const uint32_t kept = a.max_off == -1 ? okc : (uint32_t)((long long)okc < a.max_off ? (long long)okc : a.max_off);
+    a.cnt[(size_t)g * 8u + d] = (uint32_t)(hi - lo);
+    a.sbase[(size_t)g * 8u + d] = a.S[lo - a.off0];
+    a.kbase[(size_t)g * 8u + d] = units;
+    units += kept + 2u; /* the positions, the distance, the delimiter */
+    if (d == 0u) lines = hi > lo && !(a.skip && a.skip[g]); /* a line per distance-0 hit: none, no field */
+    lo = hi;
+  }
+  a.hex_units[g] = (a.complete && lines) ? units : 0u;
+}
+__device__ __forceinline__ uint4 tx_hex_le(uint64_t v) { /* printer.hpp:18-79: the bytes low to high, two digits each */
+  uint32_t w[4];
+  for (int j = 0; j < 4; j++) {
+    uint32_t x = 0;
+    for (int k = 0; k < 2; k++) {
+      const uint32_t byte = (uint32_t)(v >> (16 * j + 8 * k)) & 0xFFu;
+      const uint32_t hi = byte >> 4, lo = byte & 15u;
+      const uint32_t ch = (hi < 10u ? '0' + hi : 'a' + hi - 10u), cl = (lo < 10u ? '0' + lo : 'a' + lo - 10u);
+      x |= (ch | (cl << 8)) << (16 * k);
+    }
+    w[j] = x;
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+/* SAM: the of:H: field of every guide that has lines, once, in the scratch span hex[16 * hex_off[g] ...) */
+__global__ __launch_bounds__(WAVE *TX_WAVES) void k_tx_sam_hex(tx_args a, uint32_t n_tiles) {
+  const uint32_t lane = threadIdx.x & (WAVE - 1u);
+  const uint32_t wave0 = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE, n_waves = gridDim.x * blockDim.x / WAVE;
+  uint4 *hex = (uint4 *)a.hex;
+  for (uint32_t tile = wave0; tile < n_tiles; tile += n_waves) {
+    const uint64_t s0 = (uint64_t)tile * WAVE, s = s0 + lane;
+    if (s >= a.slots) continue;
+    const uint32_t g = tx_guide_of(a, s0, s);
+    const uint64_t units = a.hex_off[g + 1u] - a.hex_off[g], u0 = a.hex_off[g];
+    if (units == 0u) continue;
+    const uint64_t gs0 = tx_slot_of(a, g);
+    const uint32_t *kb = a.kbase + (size_t)g * 8u;
+    if (s == gs0) {
+      for (uint32_t d = 0; d <= a.m; d++) {
+        const uint64_t at = u0 + (d < a.m ? kb[d + 1u] : (uint32_t)units) - 2u;
+        hex[at] = tx_hex_le(d);
+        hex[at + 1u] = tx_hex_le((uint64_t)a.delim);
+      }
+      continue;
+    }
+    const uint64_t h = a.offsets[g] + (s - gs0 - 1u), i = h - a.off0;
+    const gs_hit hit = a.hits[h];
+    const uint32_t d = (uint32_t)(hit.key >> 61);
+    if (d > a.m || a.S[i + 1u] == a.S[i]) continue; /* dropped at a boundary */
+    const uint32_t before = a.S[i] - a.sbase[(size_t)g * 8u + d];
+    if (a.max_off != -1 && (long long)before >= a.max_off) continue;
+    hex[u0 + kb[d] + before] = tx_hex_le((uint64_t)hit.pos);
+  }
+}
+
+/* where each guide's lines begin in the text: the tile's offset plus the lengths of the slots before the guide's own */
+__global__ __launch_bounds__(256) void k_tx_guide_off(const uint64_t *offsets, uint64_t off0, uint32_t n, const uint32_t *lens,
+                                                      const uint64_t *tile_off, uint64_t *out) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g > n) return;
+  const uint64_t s = offsets[g] - off0 + g, s0 = s & ~(uint64_t)(WAVE - 1u); /* g == n: one past the last slot */
+  uint64_t at = tile_off[s / WAVE];
+  for (uint64_t i = s0; i < s; i++) at += lens[i];
+  out[g] = at;
+}
+
+/* ---- host ---------------------------------------------------------------------------------------------------- */
+namespace {
+struct bump { /* one buffer, parts behind each other on 256-byte boundaries */
+  size_t at = 0;
+  size_t take(size_t bytes) {
+    const size_t r = at;
+    at += (bytes + 255) & ~(size_t)255;
+    return r;
+  }
+};
+}  // namespace
+
+extern "C" gs_status gs_format_device(gs_index *ix, const gs_genome_structure *gs, const void *d_guides, uint64_t n, uint32_t L,
+                                      const void *d_guide_pams, uint32_t P, const char *ids, const uint64_t *id_offsets,
+                                      const uint8_t *senses, const uint8_t *skip, const void *d_offsets, const void *d_hits,
+                                      const void *d_specificity, uint32_t mismatches, uint32_t flags, int64_t max_off_targets,
+                                      void *stream, const void **d_text, uint64_t *text_len) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !gs || !d_text || !text_len) return GS_ERR_ARG;
+  if (n && (!d_guides || !ids || !id_offsets || !d_offsets || !d_specificity || (P && !d_guide_pams))) return GS_ERR_ARG;
+  if (gs->n_chr && (!gs->chr_names || !gs->chr_lengths)) return GS_ERR_ARG;
+  if (n >= (1ull << 31) || max_off_targets < -1 || mismatches > 7) return GS_ERR_ARG;
+  if (L < 1 || L > 31 || P > 8 || 2 * L + 3 * P > 59) return GS_ERR_ARG;
+  for (uint64_t g = 0; g < n; g++)
+    if (id_offsets[g + 1] < id_offsets[g]) return GS_ERR_ARG;
+  for (uint32_t c = 0; c < gs->n_chr; c++)
+    if (!gs->chr_names[c]) return GS_ERR_ARG;
+  *d_text = nullptr;
+  *text_len = 0;
+  ix->tx_n = 0;
+  if (n == 0) return GS_OK;
+  try {
+    hipStream_t st = (hipStream_t)stream;
+    GS_HIP(hipSetDevice(ix->device));
+    gs_status rc;
+    /* what the call uploads: id offsets and bytes, chromosome prefix sums and names, senses, skip */
+    const uint64_t id0 = id_offsets[0], id_bytes = id_offsets[n] - id0;
+    std::vector<uint32_t> name_off(gs->n_chr + 1, 0);
+    for (uint32_t c = 0; c < gs->n_chr; c++) name_off[c + 1] = name_off[c] + (uint32_t)strlen(gs->chr_names[c]);
+    bump in;
+    const size_t i_idoff = in.take(8 * (n + 1)), i_cum = in.take(8 * ((size_t)gs->n_chr + 1)), i_noff = in.take(4 * ((size_t)gs->n_chr + 1)),
+                 i_ids = in.take(id_bytes), i_names = in.take(name_off[gs->n_chr]), i_sense = in.take(senses ? n : 0),
+                 i_skip = in.take(skip ? n : 0);
+    std::vector<uint8_t> host(in.at + 16);
+    {
+      uint64_t *po = (uint64_t *)(host.data() + i_idoff);
+      for (uint64_t g = 0; g <= n; g++) po[g] = id_offsets[g] - id0;
+      uint64_t *pc = (uint64_t *)(host.data() + i_cum);
+      pc[0] = 0;
+      for (uint32_t c = 0; c < gs->n_chr; c++) pc[c + 1] = pc[c] + gs->chr_lengths[c];
+      memcpy(host.data() + i_noff, name_off.data(), 4 * name_off.size());
+      if (id_bytes) memcpy(host.data() + i_ids, ids + id0, id_bytes);
+      for (uint32_t c = 0; c < gs->n_chr; c++) memcpy(host.data() + i_names + name_off[c], gs->chr_names[c], name_off[c + 1] - name_off[c]);
+      if (senses) memcpy(host.data() + i_sense, senses, n);
+      if (skip) memcpy(host.data() + i_skip, skip, n);
+    }
+    uint64_t genome = 0;
+    for (uint32_t c = 0; c < gs->n_chr; c++) genome += gs->chr_lengths[c];
+    if ((rc = gs_reserve(ix->w_text_in, in.at + 16)) != GS_OK) return rc;
+    const uint8_t *din = (const uint8_t *)ix->w_text_in.p;
+    GS_HIP(hipMemcpyAsync(ix->w_text_in.p, host.data(), in.at, hipMemcpyHostToDevice, st));
+    uint64_t ends[2] = {0, 0};
+    GS_HIP(hipMemcpyAsync(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipMemcpyAsync(&ends[1], (const uint64_t *)d_offsets + n, 8, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st)); /* `host` and `ends` are locals */
+    if (ends[1] < ends[0]) return GS_ERR_ARG;
+    const uint64_t nh = ends[1] - ends[0];
+    if (nh && !d_hits) return GS_ERR_ARG;
+    ix->tx_n = 0;
+    if (nh >= (1ull << 32) && (flags & GS_TEXT_SAM)) { /* the SAM side tables count hits in 32 bits */
+      gs_set_error("gs_format_device: SAM text of 2^32 hits or more in one batch");
+      return GS_ERR_UNSUPPORTED;
+    }
+    const uint64_t slots = nh + n;
+    if ((slots + WAVE - 1) / WAVE >= (1ull << 31)) return GS_ERR_UNSUPPORTED;
+    const uint32_t n_tiles = (uint32_t)((slots + WAVE - 1) / WAVE);
+    const bool sam = (flags & GS_TEXT_SAM) != 0, complete = (flags & GS_TEXT_COMPLETE) != 0;
+
+    /* scratch: lengths, tile sums and offsets, the scans' temporary storage, the SAM tables */
+    size_t tb_tiles = 0, tb_hits = 0, tb_guides = 0;
+    GS_HIP(rocprim::exclusive_scan(nullptr, tb_tiles, (uint64_t *)nullptr, (uint64_t *)nullptr, 0ull, (size_t)n_tiles + 1,
+                                   rocprim::plus<uint64_t>(), st));
+    if (sam) {
+      GS_HIP(rocprim::exclusive_scan(nullptr, tb_hits, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)nh + 1,
+                                     rocprim::plus<uint32_t>(), st));
+      GS_HIP(rocprim::exclusive_scan(nullptr, tb_guides, (uint64_t *)nullptr, (uint64_t *)nullptr, 0ull, (size_t)n + 1,
+                                     rocprim::plus<uint64_t>(), st));
+    }
+    bump tm;
+    const size_t t_err = tm.take(16), t_lens = tm.take(4 * slots), t_tsum = tm.take(8 * ((size_t)n_tiles + 1)),
+                 t_toff = tm.take(8 * ((size_t)n_tiles + 1)), t_scan = tm.take(std::max(tb_tiles, std::max(tb_hits, tb_guides))),
+                 t_okf = tm.take(sam ? 4 * (nh + 1) : 0), t_S = tm.take(sam ? 4 * (nh + 1) : 0), t_cnt = tm.take(sam ? 32 * n : 0),
+                 t_sbase = tm.take(sam ? 32 * n : 0), t_kbase = tm.take(sam ? 32 * n : 0), t_hu = tm.take(sam ? 8 * (n + 1) : 0),
+                 t_ho = tm.take(sam ? 8 * (n + 1) : 0);
+    if ((rc = gs_reserve(ix->w_text_tmp, tm.at + 16)) != GS_OK) return rc;
+    char *tmp = (char *)ix->w_text_tmp.p;
+
+    tx_args a;
+    memset(&a, 0, sizeof a);
+    a.guides = (const uint8_t *)d_guides;
+    a.pams = (const uint8_t *)d_guide_pams;
+    a.ids = din + i_ids;
+    a.id_off = (const uint64_t *)(din + i_idoff);
+    a.senses = senses ? din + i_sense : nullptr;
+    a.skip = skip ? din + i_skip : nullptr;
+    a.offsets = (const uint64_t *)d_offsets;
+    a.hits = (const gs_hit *)d_hits;
+    a.spec = (const float *)d_specificity;
+    a.chr_cum = (const uint64_t *)(din + i_cum);
+    a.chr_names = din + i_names;
+    a.chr_name_off = (const uint32_t *)(din + i_noff);
+    a.lens = (uint32_t *)(tmp + t_lens);
+    a.tile_sum = (uint64_t *)(tmp + t_tsum);
+    a.tile_off = (uint64_t *)(tmp + t_toff);
+    a.err = (uint32_t *)(tmp + t_err);
+    a.okf = (uint32_t *)(tmp + t_okf);
+    a.S = (uint32_t *)(tmp + t_S);
+    a.cnt = (uint32_t *)(tmp + t_cnt);
+    a.sbase = (uint32_t *)(tmp + t_sbase);
+    a.kbase = (uint32_t *)(tmp + t_kbase);
+    a.hex_units = (uint64_t *)(tmp + t_hu);
+    a.hex_off = (uint64_t *)(tmp + t_ho);
+    a.slots = slots;
+    a.off0 = ends[0];
+    a.n_hits = nh;
+    a.max_off = (long long)max_off_targets;
+    a.delim = -((long long)genome + 1);
+    a.n = (uint32_t)n;
+    a.L = L;
+    a.P = P;
+    a.n_chr = gs->n_chr;
+    a.m = mismatches;
+    a.start = (flags & GS_FLAG_PAM_AT_START) ? 1u : 0u;
+    a.sam = sam ? 1u : 0u;
+    a.complete = complete ? 1u : 0u;
+
+    const uint32_t cus = (uint32_t)gs_num_cus(ix->device);
+    const uint32_t grid = std::max(1u, std::min((n_tiles + TX_WAVES - 1) / TX_WAVES, cus * 32u));
+    GS_HIP(hipMemsetAsync(tmp + t_err, 0, 16, st));
+    GS_HIP(hipMemsetAsync(a.tile_sum + n_tiles, 0, 8, st));
+    if (sam) {
+      const uint32_t gh = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nh + 256) / 256, (uint64_t)cus * 32u));
+      hipLaunchKernelGGL(k_tx_sam_ok, dim3(gh), dim3(256), 0, st, a);
+      GS_HIP(rocprim::exclusive_scan(tmp + t_scan, tb_hits, a.okf, a.S, 0u, (size_t)nh + 1, rocprim::plus<uint32_t>(), st));
+      hipLaunchKernelGGL(k_tx_sam_guide, dim3((uint32_t)((n + 256) / 256)), dim3(256), 0, st, a);
+      GS_HIP(rocprim::exclusive_scan(tmp + t_scan, tb_guides, a.hex_units, a.hex_off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+      uint64_t units = 0;
+      GS_HIP(hipMemcpyAsync(&units, a.hex_off + n, 8, hipMemcpyDeviceToHost, st));
+      GS_HIP(hipStreamSynchronize(st));
+      if (units) {
+        if ((rc = gs_reserve(ix->w_text_hex, 16 * units + 16)) != GS_OK) return rc;
+        a.hex = (char *)ix->w_text_hex.p;
+        hipLaunchKernelGGL(k_tx_sam_hex, dim3(grid), dim3(WAVE * TX_WAVES), 0, st, a, n_tiles);
+      }
+    }
+    hipLaunchKernelGGL(k_tx_len, dim3(grid), dim3(WAVE * TX_WAVES), 0, st, a, n_tiles);
+    GS_HIP(rocprim::exclusive_scan(tmp + t_scan, tb_tiles, a.tile_sum, a.tile_off, 0ull, (size_t)n_tiles + 1, rocprim::plus<uint64_t>(), st));
+    /* the length and the device's verdict come back together */
+    uint64_t total = 0;
+    uint32_t err = 0;
+    GS_HIP(hipMemcpyAsync(&total, a.tile_off + n_tiles, 8, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipMemcpyAsync(&err, a.err, 4, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    GS_HIP(hipGetLastError());
+    if (err & TX_ERR_ARG) {
+      gs_set_error("gs_format_device: a specificity outside [0, 1], a distance beyond `mismatches` or a key that does not decode");
+      return GS_ERR_ARG;
+    }
+    if (err & TX_ERR_BIG) {
+      gs_set_error("gs_format_device: a line of 32 MB or more");
+      return GS_ERR_UNSUPPORTED;
+    }
+    if ((rc = gs_reserve(ix->w_text, total + 16)) != GS_OK) return rc;
+    a.text = (char *)ix->w_text.p;
+    if ((rc = gs_reserve(ix->w_text_goff, 8 * (n + 1) + 16)) != GS_OK) return rc;
+    if (total) hipLaunchKernelGGL(k_tx_write, dim3(grid), dim3(WAVE * TX_WAVES), 0, st, a, n_tiles);
+    /* where each guide's lines begin (gs_index_last_text_offsets): 8 bytes per guide, kept beside the text */
+    hipLaunchKernelGGL(k_tx_guide_off, dim3((uint32_t)((n + 256) / 256)), dim3(256), 0, st, a.offsets, a.off0, a.n, (const uint32_t *)a.lens,
+                       (const uint64_t *)a.tile_off, (uint64_t *)ix->w_text_goff.p);
+    GS_HIP(hipStreamSynchronize(st));
+    GS_HIP(hipGetLastError());
+    *d_text = ix->w_text.p;
+    *text_len = total;
+    ix->tx_n = n;
+    return GS_OK;
+  } catch (const std::bad_alloc &) {
+    return GS_ERR_NOMEM;
+  }
+}
+
+extern "C" gs_status gs_index_last_text_offsets(gs_index *ix, uint64_t *out, uint64_t n) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !out || ix->tx_n == 0 || n != ix->tx_n) return GS_ERR_ARG;
+  GS_HIP(hipSetDevice(ix->device));
+  GS_HIP(hipMemcpy(out, ix->w_text_goff.p, 8 * (n + 1), hipMemcpyDeviceToHost));
+  return GS_OK;
+}

@@ -177,7 +177,7 @@ int usage() {
                "       guidescan enumerate PREFIX -f KMERS -o OUT [-m N] [-a PAM]... [--format csv|sam|bam]\n"
                "                 [--mode succinct|complete] [--max-off-targets N] [--start]\n"
                "                 [--rna-bulges N] [--dna-bulges N] [-t THRESHOLD] [-n FORMAT_THREADS]\n"
-               "                 [--device D] [--gpus N] [--batch-size B]\n";
+               "                 [--device D] [--gpus N] [--batch-size B] [--encoder host|gpu]\n";
   return 2;
 }
 
@@ -256,6 +256,10 @@ struct batch {
   std::vector<uint32_t> gen_of;       /* guide -> its position in resx, or ~0u */
   std::vector<float> spec;
   std::vector<char> skip;
+  char *text = nullptr; /* --encoder gpu: the batch's lines as the device wrote them (gs_enumerate_text) */
+  uint64_t text_len = 0;
+  bool text_done = false;
+  std::vector<uint64_t> text_goff; /* --format bam: where each guide begins in it, n + 1 entries */
   std::string error;
   bool handed = false; /* a device thread took it (set under enumerate_job::mtx) */
   bool ready = false;
@@ -283,6 +287,10 @@ struct enumerate_job {
    * threads (bam_writer.hpp; the reference leaves that step to `samtools view -b`, manual/manual.tex:581-582) */
   bool bam = false;
   std::map<std::string, int32_t> refid;
+  /* --encoder gpu: a batch that is all fast path leaves the device as text (gs_enumerate_text: search, scoring and the
+   * CSV / SAM encoder in HBM), any other batch - and one that answers GS_ERR_UNSUPPORTED - takes the host encoders */
+  bool encoder_gpu = false;
+  size_t enc_device = 0; /* batches the device encoded (under mtx); every other batch went to the host encoders */
 };
 
 /* a part's SAM text -> BGZF-compressed BAM records (in place: the text is released) */
@@ -301,6 +309,37 @@ static bool part_to_bam(const enumerate_job &job, text_part &part) {
 /* text of one batch from its hit lists: contiguous guide ranges formatted in parallel */
 static void format_batch(enumerate_job &job, batch &b) {
   const size_t n = b.hi - b.lo;
+  if (b.text_done) {
+    /* the text is there.  CSV / SAM: it goes to the writer as it is.  BAM: split at the line ends where the host
+     * path's guide ranges end - BGZF blocks start anew with every part, so the parts must be the same ones - and turned
+     * into records by the formatting threads. */
+    unsigned nt = job.bam ? job.fmt_threads : 1;
+    if (nt < 1) nt = 1;
+    if (nt > n) nt = (unsigned)n;
+    b.parts.assign(nt, text_part());
+    if (!job.bam) {
+      b.parts[0].p = b.text;
+      b.parts[0].n = (size_t)b.text_len;
+      b.text = nullptr;
+      return;
+    }
+    /* part t begins where guide n t / nt begins (gs_index_last_text_offsets, taken when the text was) */
+    std::vector<size_t> cut(nt + 1, (size_t)b.text_len);
+    for (unsigned t = 0; t <= nt; t++) cut[t] = (size_t)b.text_goff[n * t / nt];
+    std::vector<char> okp(nt, 1);
+    std::vector<std::thread> pool;
+    for (unsigned t = 0; t < nt; t++)
+      pool.emplace_back([&, t]() {
+        std::string raw;
+        okp[t] = bam::records(b.text + cut[t], cut[t + 1] - cut[t], job.refid, raw) && bam::bgzf_append(raw, b.parts[t].s);
+      });
+    for (auto &th : pool) th.join();
+    for (unsigned t = 0; t < nt; t++)
+      if (!okp[t] && b.error.empty()) b.error = gs_status_string(GS_ERR_FORMAT);
+    gs_free(b.text);
+    b.text = nullptr;
+    return;
+  }
   gs_result_view v;
   memset(&v, 0, sizeof v);
   if (b.res) gs_result_get(b.res, &v);
@@ -452,6 +491,35 @@ static std::string search_batch_as(enumerate_job &job, gs_index *ix, batch &b, b
     for (size_t g = 0; g < n; g++) b.gen_of[g] = (uint32_t)g;
     return "";
   }
+  if (job.encoder_gpu && job.mismatches <= 7) {
+    std::string ids;
+    std::vector<uint64_t> id_off(n + 1, 0);
+    std::vector<uint8_t> senses(n);
+    for (size_t g = 0; g < n; g++) {
+      const kmer_row &k = job.kmers[b.lo + g];
+      ids += k.id;
+      id_off[g + 1] = ids.size();
+      senses[g] = k.sense == "+" ? 1 : 0;
+    }
+    rc = gs_enumerate_text(ix, b.seqs.data(), n, L, b.pams.data(), P, job.alts.data(), n_alt, job.mismatches,
+                           job.sflags | job.tflags, job.max_off, &job.cgs, ids.data(), id_off.data(), senses.data(),
+                           b.skip.empty() ? nullptr : (const uint8_t *)b.skip.data(), &b.text, &b.text_len, nullptr);
+    {
+      std::lock_guard<std::mutex> lk(job.mtx);
+      if (rc == GS_OK) job.enc_device++;
+    }
+    if (rc == GS_OK && job.bam) { /* this thread alone uses the handle: the last text is still this one */
+      b.text_goff.resize(n + 1);
+      rc = gs_index_last_text_offsets(ix, b.text_goff.data(), n);
+      if (rc != GS_OK) return gs_status_string(rc);
+    }
+    if (rc == GS_OK) {
+      b.text_done = true;
+      return "";
+    }
+    if (rc != GS_ERR_UNSUPPORTED) return gs_status_string(rc);
+    /* a guide of the batch needs the general path: the batch is redone the usual way */
+  }
   rc = gs_enumerate(ix, b.seqs.data(), n, L, b.pams.data(), P, job.alts.data(), n_alt, job.mismatches, job.sflags,
                     &b.res);
   if (rc != GS_OK) return gs_status_string(rc);
@@ -484,6 +552,8 @@ static std::string search_batch_as(enumerate_job &job, gs_index *ix, batch &b, b
 
 int do_enumerate(int argc, char **argv) {
   std::string prefix, kmers_file, output, format = "csv", mode = "complete";
+  /* GS_ENCODER: the default of --encoder (the end-to-end rows of a benchmark run either way with one command line) */
+  std::string encoder = getenv("GS_ENCODER") ? getenv("GS_ENCODER") : "host";
   std::vector<std::string> alt_pams;
   long long mismatches = 3, max_off = -1, threshold = -1, rna = 0, dna = 0;
   int device = 0, gpus = 1;
@@ -514,13 +584,16 @@ int do_enumerate(int argc, char **argv) {
     else if (a == "--device") device = atoi(need("--device"));
     else if (a == "--gpus") gpus = atoi(need("--gpus"));
     else if (a == "--batch-size") batch_size = (size_t)atoll(need("--batch-size"));
+    else if (a == "--encoder") encoder = need("--encoder");
     else if (!a.empty() && a[0] != '-' && prefix.empty()) prefix = a;
     else return usage();
   }
   if (prefix.empty() || kmers_file.empty() || output.empty()) return usage();
   if ((format != "csv" && format != "sam" && format != "bam") || (mode != "succinct" && mode != "complete")) return usage();
   if (gpus < 1 || mismatches < 0 || rna < 0 || dna < 0) return usage();
+  if (encoder != "host" && encoder != "gpu") return usage();
   enumerate_job job;
+  job.encoder_gpu = encoder == "gpu";
   std::string err;
   if (!read_gs(prefix + ".gs", job.gs, err)) {
     std::cerr << "error: " << err << "\n";
@@ -764,6 +837,9 @@ int do_enumerate(int argc, char **argv) {
   std::cout << "Processed " << job.kmers.size() << " kmers in " << secs << " seconds.\n";
   std::cout << "Stages (overlapping): device " << job.s_device << " s, text formatting " << job.s_format
             << " s, file writes " << job.s_write << " s\n";
+  if (job.encoder_gpu)
+    std::cout << "Encoder: gpu (" << job.enc_device << " batch(es) encoded on the device, " << job.batches.size() - job.enc_device
+              << " by the host encoders)\n";
   for (gs_index *p : ix) gs_index_close(p);
   /* only a regular file is ever removed: -o /dev/stdout, a FIFO or a device node stays (written through pwrite they
    * fail with ESPIPE, and unlinking them would delete the node itself) */

@@ -456,6 +456,47 @@ gs_status gs_score(gs_index *ix, const char *guides, uint64_t n, uint32_t L, uin
                    int64_t max_off_targets, const gs_genome_structure *gs, const uint64_t *offsets,
                    const gs_hit *hits, float *cfd, float *specificity);
 
+/* ---- the database text on the device (at scale) ----------------------- */
+
+/* The lines of guides [0, n) of a fast-path batch, encoded in HBM: the same bytes as gs_format_guides_scored, i.e.
+ * get_csv_lines / get_sam_lines (include/genomics/printer.hpp:181-300, 115-170 and 302-360) with resolve_absolute
+ * (src/genomics/structures.cxx:7-52), the `NA` row of a guide without hits (:189-199), --max-off-targets as each
+ * printer applies it (:259 raw index, :129 kept hits) and the specificity printed as std::to_string(float).
+ *   d_guides, d_guide_pams : n*L and n*P ASCII bytes in HBM, as passed to gs_enumerate_device
+ *   ids, id_offsets        : host; the guides' ids back to back and n+1 offsets into them
+ *   senses, skip           : host, n bytes each, either may be NULL: senses[g] != 0 = the kmers file's sense "+"
+ *                            (NULL: all "+"); skip[g] != 0 leaves the guide's lines out (NULL: none)
+ *   d_offsets, d_hits      : what gs_enumerate_device returned, or any CSR hit list in that layout (d_offsets[0] need
+ *                            not be 0: hits are indexed by the offsets' values)
+ *   d_specificity          : float[n] of gs_score_device for the same flags and max_off_targets
+ *   flags                  : GS_FLAG_PAM_AT_START | GS_TEXT_SAM | GS_TEXT_COMPLETE
+ * *d_text (device memory owned by the handle, valid until the next call on it) holds *text_len bytes, no terminator.
+ * GS_ERR_ARG, reported by the device together with the length: a specificity outside [0, 1] (gs_score_device never
+ * produces one), a hit whose distance exceeds `mismatches`, a key that does not decode. */
+gs_status gs_format_device(gs_index *ix, const gs_genome_structure *gs, const void *d_guides, uint64_t n, uint32_t L,
+                           const void *d_guide_pams, uint32_t P, const char *ids, const uint64_t *id_offsets,
+                           const uint8_t *senses, const uint8_t *skip, const void *d_offsets, const void *d_hits,
+                           const void *d_specificity, uint32_t mismatches, uint32_t flags, int64_t max_off_targets,
+                           void *stream, const void **d_text, uint64_t *text_len);
+/* Where each guide's lines begin in the text of the last gs_format_device / gs_enumerate_text on this handle: out[g] for
+ * g in [0, n], out[n] = the text's length; n as passed to that call (else GS_ERR_ARG, as after any other call on the handle
+ * that runs a batch).  Made on the device from the row lengths, with the text.  Stands where the reference's writer has
+ * the lines guide by guide anyway (include/genomics/process.hpp:117-158): a host that cuts the text at guide boundaries -
+ * `guidescan enumerate --format bam` compresses ranges of guides in parallel - needs no parsing. */
+gs_status gs_index_last_text_offsets(gs_index *ix, uint64_t *out, uint64_t n);
+/* Guides in, database text out: gs_enumerate_device -> gs_score_device -> gs_format_device inside the library, the text
+ * copied back through page-locked staging.  Replaces, for a batch, the per-guide pipeline from the search to the
+ * output lines (include/genomics/process.hpp:35-158 with printer.hpp:115-360).  Host pointers in; *text is malloc'ed
+ * (NUL terminated, *len bytes before the terminator): release with gs_free.  flags: those of gs_enumerate plus
+ * GS_TEXT_SAM / GS_TEXT_COMPLETE.  GS_ERR_UNSUPPORTED and no text when a guide of the batch carries
+ * GS_GUIDE_NEEDS_GENERAL: the caller takes gs_enumerate + gs_enumerate_general + the host encoders for that batch.
+ * stats (or NULL): the search's counters and timings; its pointers are NULL. */
+gs_status gs_enumerate_text(gs_index *ix, const char *guides, uint64_t n, uint32_t L, const char *guide_pams, uint32_t P,
+                            const char *alt_pams, uint32_t n_alt, uint32_t mismatches, uint32_t flags,
+                            int64_t max_off_targets, const gs_genome_structure *gs, const char *ids,
+                            const uint64_t *id_offsets, const uint8_t *senses, const uint8_t *skip, char **text,
+                            uint64_t *len, gs_result_view *stats);
+
 /* ---- candidate-guide generation on the device ------------------- */
 
 typedef struct gs_kmers gs_kmers;
