@@ -200,6 +200,20 @@ def lib():
     L.gs_kmers_get.argtypes = [vp, i32, C.POINTER(u64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                C.POINTER(vp)]
     L.gs_kmers_free.argtypes = [vp]
+    L.gs_format_device_ids.restype = i32
+    L.gs_format_device_ids.argtypes = L.gs_format_device.argtypes
+    L.gs_enumerate_text_device.restype = i32
+    L.gs_enumerate_text_device.argtypes = [vp, vp, u64, u32, vp, u32, C.c_char_p, u32, u32, u32, C.c_int64,
+                                           C.POINTER(GsGenomeStructure), vp, vp, vp, vp, C.POINTER(vp), C.POINTER(u64),
+                                           C.POINTER(GsResultView), vp]
+    L.gs_kmers_encode_ids.restype = i32
+    L.gs_kmers_encode_ids.argtypes = [vp, C.c_char_p, C.c_char_p, vp]
+    L.gs_kmers_get_ids.restype = i32
+    L.gs_kmers_get_ids.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.gs_kmers_csv.restype = i32
+    L.gs_kmers_csv.argtypes = [vp, C.c_char_p, C.c_char_p, C.POINTER(vp), C.POINTER(u64)]
+    L.gs_kmers_concat.restype = i32
+    L.gs_kmers_concat.argtypes = [vp, u32, C.POINTER(vp)]
     L.gs_status_string.restype = C.c_char_p
     L.gs_status_string.argtypes = [i32]
     L.gs_version.restype = C.c_char_p
@@ -219,7 +233,9 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_debug_seed_recipes", "gs_debug_choose_thresholds", "gs_debug_tile_plan", "gs_debug_search_form", "gs_debug_guide_descriptor", "gs_index_lock", "gs_index_unlock",
            "gs_index_last_sharing", "gs_index_set_option", "gs_index_get_option", "gs_index_prepare",
            "gs_index_save_sdsl", "gs_debug_sdsl_sections", "gs_debug_sdsl_export_scratch",
-           "gs_format_device", "gs_enumerate_text", "gs_index_last_text_offsets"]
+           "gs_format_device", "gs_enumerate_text", "gs_index_last_text_offsets",
+           "gs_format_device_ids", "gs_enumerate_text_device", "gs_kmers_encode_ids", "gs_kmers_get_ids", "gs_kmers_csv",
+           "gs_kmers_concat"]
 
 
 def _check(rc):
@@ -405,6 +421,31 @@ class DeviceKmers:
         sense = np.frombuffer(C.string_at(d, m), dtype=np.uint8).copy()
         return seqs, pams, pos, sense
 
+    def encode_ids(self, prefix, chr_name):
+        """the ids "{prefix}{chr_name}:{position}:{sense}" encoded in HBM (gs_kmers_encode_ids); sets ids_ptr,
+        id_offsets_ptr (n + 1 uint64) and sense_positive_ptr (n bytes, 1 = "+"): raw device addresses"""
+        _check(lib().gs_kmers_encode_ids(self._h, prefix.encode(), chr_name.encode(), None))
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().gs_kmers_get_ids(self._h, 1, C.byref(a), C.byref(b), C.byref(c)))
+        self.ids_ptr, self.id_offsets_ptr, self.sense_positive_ptr = a.value, b.value, c.value
+
+    def ids_to_host(self):
+        """-> (ids bytes back to back, offsets uint64[n+1], sense_positive uint8[n]) of the last encode_ids"""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().gs_kmers_get_ids(self._h, 0, C.byref(a), C.byref(b), C.byref(c)))
+        off = np.frombuffer(C.string_at(b, 8 * (self.n + 1)), dtype=np.uint64).copy()
+        ids = C.string_at(a, int(off[-1])) if off[-1] else b""
+        sp = np.frombuffer(C.string_at(c, self.n), dtype=np.uint8).copy() if self.n else np.empty(0, np.uint8)
+        return ids, off, sp
+
+    def csv(self, prefix, chr_name) -> bytes:
+        """the records as rows of the kmers file, no header (gs_kmers_csv)"""
+        out, ln = C.c_void_p(), C.c_uint64()
+        _check(lib().gs_kmers_csv(self._h, prefix.encode(), chr_name.encode(), C.byref(out), C.byref(ln)))
+        s = C.string_at(out, ln.value)
+        lib().gs_free(out)
+        return s
+
     def close(self):
         if self._h:
             lib().gs_kmers_free(self._h)
@@ -431,6 +472,19 @@ def generate_kmers(chrm, pam="NGG", k=20, start=False, device=0, chrm_device_ptr
         _check(lib().gs_kmers_generate(device, arr.ctypes.data if arr.size else None, arr.shape[0], 0,
                                        pam.encode(), k, flags, None, C.byref(h)))
     return DeviceKmers(h, k, len(pam))
+
+
+def concat_kmers(parts):
+    """the records of several DeviceKmers in one, in HBM, ids included when every part has them (gs_kmers_concat)"""
+    arr = (C.c_void_p * max(1, len(parts)))(*[p._h for p in parts])
+    h = C.c_void_p()
+    _check(lib().gs_kmers_concat(arr, len(parts), C.byref(h)))
+    km = DeviceKmers(h, parts[0].k if parts else 0, parts[0].P if parts else 0)
+    if parts and all(hasattr(p, "ids_ptr") for p in parts):
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().gs_kmers_get_ids(h, 1, C.byref(a), C.byref(b), C.byref(c)))
+        km.ids_ptr, km.id_offsets_ptr, km.sense_positive_ptr = a.value, b.value, c.value
+    return km
 
 
 def sdsl_extract_text(index_file) -> np.ndarray:
@@ -696,6 +750,50 @@ class GenomeIndex:
         s = C.string_at(out, ln.value)
         lib().gs_free(out)
         return s
+
+    def format_device_ids(self, gs, d_guides_ptr, n, L, d_pams_ptr, P, d_ids_ptr, d_id_offsets_ptr, d_senses_ptr, skip,
+                          d_offsets_ptr, d_hits_ptr, d_spec_ptr, mismatches, sam=False, complete=True, start=False,
+                          max_off_targets=-1, stream=None):
+        """format_device with ids, id offsets and senses that are in HBM already (gs_format_device_ids): raw device
+        addresses; `skip` stays a host sequence or None"""
+        sk = _bytes_or_none(skip, n)
+        flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
+                 (GS_FLAG_PAM_AT_START if start else 0))
+        d_text, ln = C.c_void_p(), C.c_uint64()
+        _check(lib().gs_format_device_ids(self._h, C.byref(gs), d_guides_ptr, n, L, d_pams_ptr, P, d_ids_ptr,
+                                          d_id_offsets_ptr, d_senses_ptr, sk.ctypes.data if sk is not None else None,
+                                          d_offsets_ptr, d_hits_ptr, d_spec_ptr, mismatches, flags, max_off_targets, stream,
+                                          C.byref(d_text), C.byref(ln)))
+        return d_text.value, int(ln.value)
+
+    def enumerate_text_device(self, d_guides_ptr, n, L, d_pams_ptr, P, d_ids_ptr, d_id_offsets_ptr, d_senses_ptr, gs,
+                              mismatches=3, alt_pams=(), start=False, sam=False, complete=True, max_off_targets=-1,
+                              skip=None) -> bytes:
+        """enumerate_text over guides, ids and senses in HBM (gs_enumerate_text_device): only the text comes back.
+        Raises GsError with status 3 when a guide needs the general path or 2L + 3P > 59."""
+        alt = b"".join(p.encode() for p in alt_pams)
+        sk = _bytes_or_none(skip, n)
+        flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
+                 (GS_FLAG_PAM_AT_START if start else 0))
+        out, ln = C.c_void_p(), C.c_uint64()
+        _check(lib().gs_enumerate_text_device(self._h, d_guides_ptr, n, L, d_pams_ptr, P, alt if alt_pams else None,
+                                              len(alt_pams), mismatches, flags, max_off_targets, C.byref(gs), d_ids_ptr,
+                                              d_id_offsets_ptr, d_senses_ptr, sk.ctypes.data if sk is not None else None,
+                                              C.byref(out), C.byref(ln), None, None))
+        s = C.string_at(out, ln.value)
+        lib().gs_free(out)
+        return s
+
+    def raw_counts_device(self, d_guides_ptr, n, L, d_pams_ptr, P, gs, mismatches, alt_pams=(), start=False):
+        """the counting pass of --threshold over guides in HBM (gs_enumerate_text_device with GS_FLAG_RAW_COUNTS):
+        hits per guide before duplicate sequences collapse, uint32[n]"""
+        alt = b"".join(p.encode() for p in alt_pams)
+        raw = np.zeros(n, dtype=np.uint32)
+        flags = GS_FLAG_RAW_COUNTS | (GS_FLAG_PAM_AT_START if start else 0)
+        _check(lib().gs_enumerate_text_device(self._h, d_guides_ptr, n, L, d_pams_ptr, P, alt if alt_pams else None,
+                                              len(alt_pams), mismatches, flags, -1, C.byref(gs), None, None, None, None,
+                                              None, None, None, raw.ctypes.data))
+        return raw
 
     def last_text_offsets(self, n):
         """byte offset at which each guide's lines begin in the text of the last format_device / enumerate_text of n

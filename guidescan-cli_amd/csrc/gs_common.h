@@ -296,6 +296,8 @@ const char *gs_opt(const gs_index *ix, const char *key);
 void gs_opts_from_env(gs_index *ix);
 extern std::atomic<int> gs_debug_any; /* some handle has GS_DEBUG set: the allocator reports large growth */
 gs_status gs_reserve(gs_buffer &b, size_t bytes);
+/* gs_host.hip: tl bytes of text in HBM -> *text, malloc'ed and NUL terminated, through page-locked staging */
+gs_status gs_text_to_host(const void *d_text, uint64_t tl, char **text);
 /* frees the buffer (if any) and leaves it empty; returns the bytes it held */
 size_t gs_buffer_free(gs_buffer &b);
 

@@ -208,43 +208,9 @@ extern "C" gs_status gs_enumerate(gs_index *ix, const char *guides, uint64_t n, 
   }
 }
 
-/* search -> score -> encode on the device (gs_textdev.hip), then the text back to the host: two page-locked staging
- * buffers, the copy out of one overlapping the transfer into the other */
-static gs_status enumerate_text(gs_index *ix, const char *guides, uint64_t n, uint32_t L, const char *guide_pams, uint32_t P,
-                                const char *alt_pams, uint32_t n_alt, uint32_t mismatches, uint32_t flags,
-                                int64_t max_off_targets, const gs_genome_structure *gs, const char *ids,
-                                const uint64_t *id_offsets, const uint8_t *senses, const uint8_t *skip, char **text,
-                                uint64_t *len, gs_result_view *stats) {
-  GS_HIP(hipSetDevice(ix->device));
-  gs_status rc = gs_reserve(ix->w_guides, n * (size_t)(L + P) + 16);
-  if (rc != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_text_spec, 4 * n + 16)) != GS_OK) return rc;
-  char *d_g = (char *)ix->w_guides.p;
-  char *d_p = d_g + n * (size_t)L;
-  if (n) {
-    GS_HIP(hipMemcpy(d_g, guides, n * (size_t)L, hipMemcpyHostToDevice));
-    if (P) GS_HIP(hipMemcpy(d_p, guide_pams, n * (size_t)P, hipMemcpyHostToDevice));
-  }
-  const void *d_off = nullptr, *d_hits = nullptr, *d_text = nullptr;
-  gs_result_view v;
-  memset(&v, 0, sizeof v);
-  const uint32_t tflags = flags & (GS_TEXT_SAM | GS_TEXT_COMPLETE), sflags = flags & ~(GS_TEXT_SAM | GS_TEXT_COMPLETE);
-  rc = gs_enumerate_device(ix, d_g, n, L, d_p, P, alt_pams, n_alt, mismatches, sflags, nullptr, &d_off, &d_hits, &v);
-  if (rc != GS_OK) return rc;
-  if (stats) *stats = v;
-  if (ix->last_unsupported) {
-    gs_set_error("a guide of the batch needs the general path");
-    return GS_ERR_UNSUPPORTED;
-  }
-  uint64_t tl = 0;
-  if (n) {
-    rc = gs_score_device(ix, d_g, n, L, P, tflags | (sflags & GS_FLAG_PAM_AT_START), max_off_targets, gs, d_off, d_hits, nullptr,
-                         nullptr, ix->w_text_spec.p);
-    if (rc != GS_OK) return rc;
-    rc = gs_format_device(ix, gs, d_g, n, L, d_p, P, ids, id_offsets, senses, skip, d_off, d_hits, ix->w_text_spec.p, mismatches,
-                          tflags | (sflags & GS_FLAG_PAM_AT_START), max_off_targets, nullptr, &d_text, &tl);
-    if (rc != GS_OK) return rc;
-  }
+/* a text in HBM -> a malloc'ed, NUL-terminated copy: two page-locked staging buffers, the copy out of one overlapping
+ * the transfer into the other */
+gs_status gs_text_to_host(const void *d_text, uint64_t tl, char **text) {
   char *out = (char *)malloc(tl + 1);
   if (!out) return GS_ERR_NOMEM;
   const size_t CH = (size_t)32 << 20;
@@ -273,6 +239,65 @@ static gs_status enumerate_text(gs_index *ix, const char *guides, uint64_t n, ui
   }
   out[tl] = 0;
   *text = out;
+  return GS_OK;
+}
+
+/* search -> score -> encode on the device (gs_textdev.hip), then the text back to the host.  The guides come from the
+ * host (guides / guide_pams, uploaded here) or are in HBM already (d_guides / d_guide_pams); ids, id_offsets and senses
+ * are host arrays in the first case and device arrays in the second. */
+static gs_status enumerate_text(gs_index *ix, bool on_device, const void *guides, uint64_t n, uint32_t L, const void *guide_pams,
+                                uint32_t P, const char *alt_pams, uint32_t n_alt, uint32_t mismatches, uint32_t flags,
+                                int64_t max_off_targets, const gs_genome_structure *gs, const void *ids, const void *id_offsets,
+                                const void *senses, const uint8_t *skip, char **text, uint64_t *len, gs_result_view *stats,
+                                uint32_t *raw_hits) {
+  GS_HIP(hipSetDevice(ix->device));
+  gs_status rc;
+  if ((rc = gs_reserve(ix->w_text_spec, 4 * n + 16)) != GS_OK) return rc;
+  const char *d_g = (const char *)guides, *d_p = (const char *)guide_pams;
+  if (!on_device) {
+    if ((rc = gs_reserve(ix->w_guides, n * (size_t)(L + P) + 16)) != GS_OK) return rc;
+    char *up = (char *)ix->w_guides.p;
+    if (n) {
+      GS_HIP(hipMemcpy(up, guides, n * (size_t)L, hipMemcpyHostToDevice));
+      if (P) GS_HIP(hipMemcpy(up + n * (size_t)L, guide_pams, n * (size_t)P, hipMemcpyHostToDevice));
+    }
+    d_g = up;
+    d_p = up + n * (size_t)L;
+  }
+  const void *d_off = nullptr, *d_hits = nullptr, *d_text = nullptr;
+  gs_result_view v;
+  memset(&v, 0, sizeof v);
+  const uint32_t tflags = flags & (GS_TEXT_SAM | GS_TEXT_COMPLETE), sflags = flags & ~(GS_TEXT_SAM | GS_TEXT_COMPLETE);
+  rc = gs_enumerate_device(ix, d_g, n, L, d_p, P, alt_pams, n_alt, mismatches, sflags, nullptr, &d_off, &d_hits, &v);
+  if (rc != GS_OK) return rc;
+  if (stats) *stats = v;
+  if (ix->last_unsupported) {
+    gs_set_error("a guide of the batch needs the general path");
+    return GS_ERR_UNSUPPORTED;
+  }
+  if (raw_hits) { /* the counting pass of --threshold: the counts, no text */
+    if (n && !ix->last_raw_valid) {
+      gs_set_error("the search kept no raw counts");
+      return GS_ERR_UNSUPPORTED;
+    }
+    if (n) GS_HIP(hipMemcpy(raw_hits, ix->w_raw.p, 4 * n, hipMemcpyDeviceToHost));
+    return GS_OK;
+  }
+  uint64_t tl = 0;
+  if (n) {
+    rc = gs_score_device(ix, d_g, n, L, P, tflags | (sflags & GS_FLAG_PAM_AT_START), max_off_targets, gs, d_off, d_hits, nullptr,
+                         nullptr, ix->w_text_spec.p);
+    if (rc != GS_OK) return rc;
+    const uint32_t fflags = tflags | (sflags & GS_FLAG_PAM_AT_START);
+    if (on_device)
+      rc = gs_format_device_ids(ix, gs, d_g, n, L, d_p, P, ids, id_offsets, senses, skip, d_off, d_hits, ix->w_text_spec.p,
+                                mismatches, fflags, max_off_targets, nullptr, &d_text, &tl);
+    else
+      rc = gs_format_device(ix, gs, d_g, n, L, d_p, P, (const char *)ids, (const uint64_t *)id_offsets, (const uint8_t *)senses,
+                            skip, d_off, d_hits, ix->w_text_spec.p, mismatches, fflags, max_off_targets, nullptr, &d_text, &tl);
+    if (rc != GS_OK) return rc;
+  }
+  if ((rc = gs_text_to_host(d_text, tl, text)) != GS_OK) return rc;
   *len = tl;
   return GS_OK;
 }
@@ -294,8 +319,36 @@ extern "C" gs_status gs_enumerate_text(gs_index *ix, const char *guides, uint64_
   *text = nullptr;
   *len = 0;
   try { /* nothing may throw across the C boundary */
-    return enumerate_text(ix, guides, n, L, guide_pams, P, alt_pams, n_alt, mismatches, flags, max_off_targets, gs, ids, id_offsets,
-                          senses, skip, text, len, stats);
+    return enumerate_text(ix, false, guides, n, L, guide_pams, P, alt_pams, n_alt, mismatches, flags, max_off_targets, gs, ids,
+                          id_offsets, senses, skip, text, len, stats, nullptr);
+  } catch (const std::bad_alloc &) {
+    return GS_ERR_NOMEM;
+  }
+}
+extern "C" gs_status gs_enumerate_text_device(gs_index *ix, const void *d_guides, uint64_t n, uint32_t L, const void *d_guide_pams,
+                                              uint32_t P, const char *alt_pams, uint32_t n_alt, uint32_t mismatches, uint32_t flags,
+                                              int64_t max_off_targets, const gs_genome_structure *gs, const void *d_ids,
+                                              const void *d_id_offsets, const void *d_senses, const uint8_t *skip, char **text,
+                                              uint64_t *len, gs_result_view *stats, uint32_t *raw_hits) {
+  GS_HANDLE_LOCK(ix);
+  const bool counting = (flags & GS_FLAG_RAW_COUNTS) != 0;
+  if (!ix || !gs) return GS_ERR_ARG;
+  if (counting ? !raw_hits : (!text || !len || raw_hits)) return GS_ERR_ARG;
+  if (n && (!d_guides || (P && !d_guide_pams))) return GS_ERR_ARG;
+  if (n && !counting && (!d_ids || !d_id_offsets)) return GS_ERR_ARG;
+  if ((n_alt && !alt_pams) || (gs->n_chr && (!gs->chr_names || !gs->chr_lengths))) return GS_ERR_ARG;
+  if (n >= (1ull << 31) || max_off_targets < -1 || mismatches > 7 || n_alt > 31) return GS_ERR_ARG;
+  for (uint32_t c = 0; c < gs->n_chr; c++)
+    if (!gs->chr_names[c]) return GS_ERR_ARG;
+  if (text) *text = nullptr;
+  if (len) *len = 0;
+  if (L < 1 || L > 31 || P > 8 || 2 * L + 3 * P > 59) { /* as for a guide that needs the general path: the caller takes the host route for the batch */
+    gs_set_error("gs_enumerate_text_device: 2L + 3P > 59 or L, P outside the fast path's key");
+    return GS_ERR_UNSUPPORTED;
+  }
+  try { /* nothing may throw across the C boundary */
+    return enumerate_text(ix, true, d_guides, n, L, d_guide_pams, P, alt_pams, n_alt, mismatches, flags, max_off_targets, gs, d_ids,
+                          d_id_offsets, d_senses, skip, text, len, stats, raw_hits);
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;
   }

@@ -14,6 +14,15 @@
  *   k_km_emit    one thread per site: protospacer (reverse-complemented on the - strand),
  *                position, sense, PAM pattern.
  * The output arrays stay in HBM in exactly the layout gs_enumerate_device takes.
+ *
+ * The records as text, also in HBM (the shape of gs_textdev.hip: a length per record, an exclusive scan, a write):
+ *   k_km_text_len    bytes of every record's id "{prefix}{chromosome}:{position}:{sense}" or of its kmers-file row
+ *                    "id,sequence,pam,chromosome,position,sense\n" (scripts/generate_kmers.py:120-125)   (4 B read, 8 B written)
+ *   (rocprim 64-bit exclusive scan of the n + 1 lengths: the offsets)
+ *   k_km_text_write  one thread per record composes its bytes at its offset (a row: 4 + 8 + k + 1 B read, ~2k + 2P + 40 B
+ *                    written; an id: 4 + 8 + 1 B read, ~20 B written, plus the sense as 0/1 for the SAM encoder)
+ * gs_kmers_concat joins the records of several chromosomes into one stream, ids included (k_km_rebase shifts the id
+ * offsets), so that a batch can hold the tail of one chromosome and the heads of the next ones.
  */
 #include "gs_common.h"
 
@@ -29,6 +38,12 @@ struct gs_kmers {
   std::vector<uint8_t> h_seqs, h_pams, h_sense;
   std::vector<uint32_t> h_pos;
   bool have_host = false;
+  /* gs_kmers_encode_ids: the ids back to back, n + 1 offsets, the senses as 0 / 1 ("+") */
+  void *d_ids = nullptr, *d_id_off = nullptr, *d_sense01 = nullptr;
+  uint64_t id_bytes = 0;
+  bool have_ids = false, have_host_ids = false;
+  std::vector<uint8_t> h_ids, h_sense01;
+  std::vector<uint64_t> h_id_off;
 };
 
 struct gs_km_args {
@@ -145,8 +160,10 @@ __global__ __launch_bounds__(KM_BLOCK) void k_km_emit(gs_km_emit_args a) {
 
 static void km_release(gs_kmers *km) {
   if (!km) return;
-  hipSetDevice(km->device);
-  for (void *p : {km->d_seqs, km->d_pams, km->d_pos, km->d_sense})
+  bool any = false; /* an empty object never touched a device */
+  for (void *p : {km->d_seqs, km->d_pams, km->d_pos, km->d_sense, km->d_ids, km->d_id_off, km->d_sense01}) any = any || p;
+  if (any) hipSetDevice(km->device);
+  for (void *p : {km->d_seqs, km->d_pams, km->d_pos, km->d_sense, km->d_ids, km->d_id_off, km->d_sense01})
     if (p) hipFree(p);
   delete km;
 }
@@ -323,6 +340,295 @@ extern "C" gs_status gs_kmers_get(gs_kmers *km, int on_device, uint64_t *n, cons
   if (pams) *pams = km->h_pams.data();
   if (positions) *positions = km->h_pos.data();
   if (senses) *senses = km->h_sense.data();
+  return GS_OK;
+}
+
+/* ---- the records as text ------------------------------------------------------------------------------------- */
+struct gs_km_text_args {
+  const uint8_t *seqs, *pams, *sense;
+  const uint32_t *pos;
+  const uint8_t *names; /* prefix, then the chromosome name */
+  uint64_t *lens;       /* n + 1 */
+  const uint64_t *off;  /* n + 1 */
+  uint8_t *text, *sense01;
+  uint64_t n;
+  uint32_t k, P, prefix_len, name_len, rows;
+};
+__device__ __forceinline__ uint32_t km_digits(uint32_t v) { /* 1 .. 10: 4,294,967,295 has ten */
+  uint32_t d = 1;
+  while (v >= 10u) {
+    v /= 10u;
+    d++;
+  }
+  return d;
+}
+__global__ __launch_bounds__(KM_BLOCK) void k_km_text_len(gs_km_text_args a) {
+  const uint64_t j = (uint64_t)blockIdx.x * KM_BLOCK + threadIdx.x;
+  if (j > a.n) return;
+  if (j == a.n) {
+    a.lens[j] = 0;
+    return;
+  }
+  const uint32_t id = a.prefix_len + a.name_len + 1u + km_digits(a.pos[j]) + 2u;
+  /* id , sequence , pam , chromosome , position , sense \n */
+  a.lens[j] = a.rows ? (uint64_t)id + 1u + a.k + 1u + a.P + 1u + a.name_len + 1u + km_digits(a.pos[j]) + 3u : (uint64_t)id;
+}
+__device__ __forceinline__ uint8_t *km_put(uint8_t *o, const uint8_t *s, uint32_t n) {
+  for (uint32_t i = 0; i < n; i++) o[i] = s[i];
+  return o + n;
+}
+__device__ __forceinline__ uint8_t *km_put_u32(uint8_t *o, uint32_t v) {
+  const uint32_t d = km_digits(v);
+  uint8_t *q = o + d;
+  do {
+    *--q = (uint8_t)('0' + v % 10u);
+    v /= 10u;
+  } while (v);
+  return o + d;
+}
+__global__ __launch_bounds__(KM_BLOCK) void k_km_text_write(gs_km_text_args a) {
+  const uint64_t j = (uint64_t)blockIdx.x * KM_BLOCK + threadIdx.x;
+  if (j >= a.n) return;
+  const uint32_t pos = a.pos[j];
+  const uint8_t sense = a.sense[j];
+  uint8_t *o = a.text + a.off[j];
+  o = km_put(o, a.names, a.prefix_len + a.name_len);
+  *o++ = ':';
+  o = km_put_u32(o, pos);
+  *o++ = ':';
+  *o++ = sense;
+  if (!a.rows) {
+    a.sense01[j] = sense == '+' ? 1 : 0;
+    return;
+  }
+  *o++ = ',';
+  o = km_put(o, a.seqs + j * a.k, a.k);
+  *o++ = ',';
+  o = km_put(o, a.pams + j * a.P, a.P);
+  *o++ = ',';
+  o = km_put(o, a.names + a.prefix_len, a.name_len);
+  *o++ = ',';
+  o = km_put_u32(o, pos);
+  *o++ = ',';
+  *o++ = sense;
+  *o++ = '\n';
+}
+__global__ __launch_bounds__(KM_BLOCK) void k_km_rebase(const uint64_t *in, uint64_t n, uint64_t base, uint64_t *out) {
+  const uint64_t j = (uint64_t)blockIdx.x * KM_BLOCK + threadIdx.x;
+  if (j < n) out[j] = in[j] + base;
+}
+
+/* ids (rows == 0, kept in the object) or kmers-file rows (*d_text: the caller frees it) of all records */
+static gs_status km_encode(gs_kmers *km, const char *prefix, const char *chr_name, bool rows, hipStream_t st, void **d_text,
+                           void **d_off, uint64_t *bytes) {
+  const size_t pl = strlen(prefix), nl = strlen(chr_name);
+  if (pl >= (1u << 20) || nl >= (1u << 20)) return GS_ERR_ARG;
+  GS_HIP(hipSetDevice(km->device));
+  const uint64_t n = km->n;
+  void *d_names = nullptr, *d_lens = nullptr, *d_tmp = nullptr, *off = nullptr, *text = nullptr, *s01 = nullptr;
+  auto cleanup = [&](bool all) {
+    for (void *p : {d_names, d_lens, d_tmp})
+      if (p) hipFree(p);
+    if (all)
+      for (void *p : {off, text, s01})
+        if (p) hipFree(p);
+  };
+#define KM_HIP(expr)                                                    \
+  do {                                                                  \
+    hipError_t e__ = (expr);                                            \
+    if (e__ != hipSuccess) {                                            \
+      gs_set_error(std::string(#expr) + ": " + hipGetErrorString(e__)); \
+      cleanup(true);                                                    \
+      return GS_ERR_DEVICE;                                             \
+    }                                                                   \
+  } while (0)
+  std::string names = std::string(prefix) + chr_name;
+  KM_HIP(hipMalloc(&d_names, names.size() + 16));
+  KM_HIP(hipMemcpyAsync(d_names, names.data(), names.size(), hipMemcpyHostToDevice, st));
+  KM_HIP(hipMalloc(&d_lens, 8 * (n + 1)));
+  KM_HIP(hipMalloc(&off, 8 * (n + 1)));
+  gs_km_text_args a;
+  memset(&a, 0, sizeof a);
+  a.seqs = (const uint8_t *)km->d_seqs;
+  a.pams = (const uint8_t *)km->d_pams;
+  a.sense = (const uint8_t *)km->d_sense;
+  a.pos = (const uint32_t *)km->d_pos;
+  a.names = (const uint8_t *)d_names;
+  a.lens = (uint64_t *)d_lens;
+  a.off = (const uint64_t *)off;
+  a.n = n;
+  a.k = km->k;
+  a.P = km->P;
+  a.prefix_len = (uint32_t)pl;
+  a.name_len = (uint32_t)nl;
+  a.rows = rows ? 1u : 0u;
+  const unsigned grid = (unsigned)((n + 1 + KM_BLOCK - 1) / KM_BLOCK);
+  hipLaunchKernelGGL(k_km_text_len, dim3(grid), dim3(KM_BLOCK), 0, st, a);
+  size_t tb = 0;
+  KM_HIP(rocprim::exclusive_scan(nullptr, tb, (uint64_t *)d_lens, (uint64_t *)off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+  KM_HIP(hipMalloc(&d_tmp, tb + 16));
+  KM_HIP(rocprim::exclusive_scan(d_tmp, tb, (uint64_t *)d_lens, (uint64_t *)off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+  uint64_t total = 0;
+  KM_HIP(hipMemcpyAsync(&total, (uint64_t *)off + n, 8, hipMemcpyDeviceToHost, st));
+  KM_HIP(hipStreamSynchronize(st));
+  KM_HIP(hipMalloc(&text, total + 16));
+  if (!rows) KM_HIP(hipMalloc(&s01, n + 16));
+  a.text = (uint8_t *)text;
+  a.sense01 = (uint8_t *)s01;
+  if (n) hipLaunchKernelGGL(k_km_text_write, dim3((unsigned)((n + KM_BLOCK - 1) / KM_BLOCK)), dim3(KM_BLOCK), 0, st, a);
+  KM_HIP(hipStreamSynchronize(st));
+  KM_HIP(hipGetLastError());
+#undef KM_HIP
+  cleanup(false);
+  if (rows) {
+    hipFree(off);
+    *d_text = text;
+  } else {
+    for (void *p : {km->d_ids, km->d_id_off, km->d_sense01})
+      if (p) hipFree(p);
+    km->d_ids = text;
+    km->d_id_off = off;
+    km->d_sense01 = s01;
+    km->id_bytes = total;
+    km->have_ids = true;
+    km->have_host_ids = false;
+  }
+  if (d_off) *d_off = off;
+  *bytes = total;
+  return GS_OK;
+}
+
+extern "C" gs_status gs_kmers_encode_ids(gs_kmers *km, const char *prefix, const char *chr_name, void *stream) {
+  if (!km || !prefix || !chr_name) return GS_ERR_ARG;
+  uint64_t bytes = 0;
+  try {
+    return km_encode(km, prefix, chr_name, false, (hipStream_t)stream, nullptr, nullptr, &bytes);
+  } catch (const std::bad_alloc &) {
+    return GS_ERR_NOMEM;
+  }
+}
+
+extern "C" gs_status gs_kmers_get_ids(gs_kmers *km, int on_device, const void **ids, const void **id_offsets,
+                                      const void **sense_positive) {
+  if (!km) return GS_ERR_ARG;
+  if (!km->have_ids) {
+    gs_set_error("gs_kmers_get_ids before gs_kmers_encode_ids");
+    return GS_ERR_ARG;
+  }
+  if (on_device) {
+    if (ids) *ids = km->d_ids;
+    if (id_offsets) *id_offsets = km->d_id_off;
+    if (sense_positive) *sense_positive = km->d_sense01;
+    return GS_OK;
+  }
+  try {
+    if (!km->have_host_ids) {
+      GS_HIP(hipSetDevice(km->device));
+      km->h_ids.resize((size_t)km->id_bytes);
+      km->h_id_off.resize((size_t)km->n + 1);
+      km->h_sense01.resize((size_t)km->n);
+      if (km->id_bytes) GS_HIP(hipMemcpy(km->h_ids.data(), km->d_ids, km->h_ids.size(), hipMemcpyDeviceToHost));
+      GS_HIP(hipMemcpy(km->h_id_off.data(), km->d_id_off, 8 * km->h_id_off.size(), hipMemcpyDeviceToHost));
+      if (km->n) GS_HIP(hipMemcpy(km->h_sense01.data(), km->d_sense01, km->h_sense01.size(), hipMemcpyDeviceToHost));
+      km->have_host_ids = true;
+    }
+  } catch (const std::bad_alloc &) {
+    return GS_ERR_NOMEM;
+  }
+  if (ids) *ids = km->h_ids.data();
+  if (id_offsets) *id_offsets = km->h_id_off.data();
+  if (sense_positive) *sense_positive = km->h_sense01.data();
+  return GS_OK;
+}
+
+extern "C" gs_status gs_kmers_csv(gs_kmers *km, const char *prefix, const char *chr_name, char **text, uint64_t *len) {
+  if (!km || !prefix || !chr_name || !text || !len) return GS_ERR_ARG;
+  *text = nullptr;
+  *len = 0;
+  void *d_text = nullptr;
+  uint64_t bytes = 0;
+  gs_status rc;
+  try {
+    rc = km_encode(km, prefix, chr_name, true, nullptr, &d_text, nullptr, &bytes);
+  } catch (const std::bad_alloc &) {
+    return GS_ERR_NOMEM;
+  }
+  if (rc != GS_OK) return rc;
+  rc = gs_text_to_host(d_text, bytes, text);
+  hipFree(d_text);
+  if (rc == GS_OK) *len = bytes;
+  return rc;
+}
+
+extern "C" gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, gs_kmers **out) {
+  if (!out || (n_parts && !parts)) return GS_ERR_ARG;
+  for (uint32_t i = 0; i < n_parts; i++)
+    if (!parts[i]) return GS_ERR_ARG;
+  for (uint32_t i = 0; i < n_parts; i++)
+    if (parts[i]->device != parts[0]->device || parts[i]->k != parts[0]->k || parts[i]->P != parts[0]->P ||
+        parts[i]->have_ids != parts[0]->have_ids) {
+      gs_set_error("gs_kmers_concat: parts of different devices, kmer or PAM lengths, or ids on some of them only");
+      return GS_ERR_ARG;
+    }
+  gs_kmers *km = new (std::nothrow) gs_kmers();
+  if (!km) return GS_ERR_NOMEM;
+  if (n_parts == 0) {
+    *out = km;
+    return GS_OK;
+  }
+  km->device = parts[0]->device;
+  km->k = parts[0]->k;
+  km->P = parts[0]->P;
+  km->have_ids = parts[0]->have_ids;
+  for (uint32_t i = 0; i < n_parts; i++) {
+    km->n += parts[i]->n;
+    km->id_bytes += parts[i]->id_bytes;
+  }
+  const uint32_t k = km->k, P = km->P;
+#define KM_HIP(expr)                                                    \
+  do {                                                                  \
+    hipError_t e__ = (expr);                                            \
+    if (e__ != hipSuccess) {                                            \
+      gs_set_error(std::string(#expr) + ": " + hipGetErrorString(e__)); \
+      km_release(km);                                                   \
+      return GS_ERR_DEVICE;                                             \
+    }                                                                   \
+  } while (0)
+  KM_HIP(hipSetDevice(km->device));
+  KM_HIP(hipMalloc(&km->d_seqs, (size_t)km->n * k + 16));
+  KM_HIP(hipMalloc(&km->d_pams, (size_t)km->n * P + 16));
+  KM_HIP(hipMalloc(&km->d_pos, 4 * (size_t)km->n + 16));
+  KM_HIP(hipMalloc(&km->d_sense, (size_t)km->n + 16));
+  if (km->have_ids) {
+    KM_HIP(hipMalloc(&km->d_ids, (size_t)km->id_bytes + 16));
+    KM_HIP(hipMalloc(&km->d_id_off, 8 * ((size_t)km->n + 1)));
+    KM_HIP(hipMalloc(&km->d_sense01, (size_t)km->n + 16));
+  }
+  uint64_t at = 0, id_at = 0;
+  for (uint32_t i = 0; i < n_parts; i++) {
+    const gs_kmers *p = parts[i];
+    const bool last = i + 1 == n_parts;
+    if (p->n) {
+      KM_HIP(hipMemcpyAsync((char *)km->d_seqs + at * k, p->d_seqs, (size_t)p->n * k, hipMemcpyDeviceToDevice, nullptr));
+      KM_HIP(hipMemcpyAsync((char *)km->d_pams + at * P, p->d_pams, (size_t)p->n * P, hipMemcpyDeviceToDevice, nullptr));
+      KM_HIP(hipMemcpyAsync((char *)km->d_pos + at * 4, p->d_pos, (size_t)p->n * 4, hipMemcpyDeviceToDevice, nullptr));
+      KM_HIP(hipMemcpyAsync((char *)km->d_sense + at, p->d_sense, (size_t)p->n, hipMemcpyDeviceToDevice, nullptr));
+    }
+    if (km->have_ids) {
+      if (p->n) KM_HIP(hipMemcpyAsync((char *)km->d_sense01 + at, p->d_sense01, (size_t)p->n, hipMemcpyDeviceToDevice, nullptr));
+      if (p->id_bytes) KM_HIP(hipMemcpyAsync((char *)km->d_ids + id_at, p->d_ids, (size_t)p->id_bytes, hipMemcpyDeviceToDevice, nullptr));
+      const uint64_t cnt = p->n + (last ? 1u : 0u); /* the last part's closing offset closes the stream */
+      if (cnt)
+        hipLaunchKernelGGL(k_km_rebase, dim3((unsigned)((cnt + KM_BLOCK - 1) / KM_BLOCK)), dim3(KM_BLOCK), 0, nullptr,
+                           (const uint64_t *)p->d_id_off, cnt, id_at, (uint64_t *)km->d_id_off + at);
+    }
+    at += p->n;
+    id_at += p->id_bytes;
+  }
+  KM_HIP(hipStreamSynchronize(nullptr));
+  KM_HIP(hipGetLastError());
+#undef KM_HIP
+  *out = km;
   return GS_OK;
 }
 

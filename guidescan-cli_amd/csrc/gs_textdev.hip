@@ -224,8 +224,8 @@ struct tx_write {
 /* ---- the rows ------------------------------------------------------------------------------------------------ */
 template <class S>
 __device__ __forceinline__ void tx_id(S &o, const tx_args &a, uint32_t g) {
-  const uint64_t b = a.id_off[g];
-  o.put(a.ids + b, (uint32_t)(a.id_off[g + 1u] - b));
+  const uint64_t b = a.id_off[g], e = a.id_off[g + 1u];
+  o.put(a.ids + b, e >= b ? (uint32_t)(e - b) : 0u); /* e < b: GS_ERR_ARG from the guide's own slot */
 }
 template <class S>
 __device__ __forceinline__ void tx_sequence(S &o, const tx_args &a, uint32_t g) { /* sequence + pam, or pam + sequence under --start */
@@ -254,6 +254,7 @@ __device__ __forceinline__ void tx_chr_name(S &o, const tx_args &a, int c) {
 /* the guide's own slot: its NA row (printer.hpp:189-199), and the checks made once per guide */
 template <class S>
 __device__ __forceinline__ void tx_guide_row(S &o, const tx_args &a, uint32_t g, uint32_t &err) {
+  if (a.id_off[g + 1u] < a.id_off[g]) err |= TX_ERR_ARG; /* offsets that came from the device: not checked on the host */
   if (a.skip && a.skip[g]) return;
   const uint64_t nh = a.offsets[g + 1u] - a.offsets[g];
   if (nh) {
@@ -567,21 +568,15 @@ struct bump { /* one buffer, parts behind each other on 256-byte boundaries */
 };
 }  // namespace
 
-extern "C" gs_status gs_format_device(gs_index *ix, const gs_genome_structure *gs, const void *d_guides, uint64_t n, uint32_t L,
-                                      const void *d_guide_pams, uint32_t P, const char *ids, const uint64_t *id_offsets,
-                                      const uint8_t *senses, const uint8_t *skip, const void *d_offsets, const void *d_hits,
-                                      const void *d_specificity, uint32_t mismatches, uint32_t flags, int64_t max_off_targets,
-                                      void *stream, const void **d_text, uint64_t *text_len) {
-  GS_HANDLE_LOCK(ix);
-  if (!ix || !gs || !d_text || !text_len) return GS_ERR_ARG;
-  if (n && (!d_guides || !ids || !id_offsets || !d_offsets || !d_specificity || (P && !d_guide_pams))) return GS_ERR_ARG;
-  if (gs->n_chr && (!gs->chr_names || !gs->chr_lengths)) return GS_ERR_ARG;
-  if (n >= (1ull << 31) || max_off_targets < -1 || mismatches > 7) return GS_ERR_ARG;
-  if (L < 1 || L > 31 || P > 8 || 2 * L + 3 * P > 59) return GS_ERR_ARG;
-  for (uint64_t g = 0; g < n; g++)
-    if (id_offsets[g + 1] < id_offsets[g]) return GS_ERR_ARG;
-  for (uint32_t c = 0; c < gs->n_chr; c++)
-    if (!gs->chr_names[c]) return GS_ERR_ARG;
+/* the body of both entry points: ids / id_offsets / senses are host arrays that this call uploads, or d_ids /
+ * d_id_offsets / d_senses are in HBM already (the offsets index d_ids as they stand) */
+static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, const void *d_guides, uint64_t n, uint32_t L,
+                               const void *d_guide_pams, uint32_t P, const char *ids, const uint64_t *id_offsets,
+                               const uint8_t *senses, const void *d_ids, const void *d_id_offsets, const void *d_senses,
+                               const uint8_t *skip, const void *d_offsets, const void *d_hits, const void *d_specificity,
+                               uint32_t mismatches, uint32_t flags, int64_t max_off_targets, void *stream, const void **d_text,
+                               uint64_t *text_len) {
+  const bool up = d_ids == nullptr; /* the ids come from the host */
   *d_text = nullptr;
   *text_len = 0;
   ix->tx_n = 0;
@@ -591,17 +586,17 @@ extern "C" gs_status gs_format_device(gs_index *ix, const gs_genome_structure *g
     GS_HIP(hipSetDevice(ix->device));
     gs_status rc;
     /* what the call uploads: id offsets and bytes, chromosome prefix sums and names, senses, skip */
-    const uint64_t id0 = id_offsets[0], id_bytes = id_offsets[n] - id0;
+    const uint64_t id0 = up ? id_offsets[0] : 0, id_bytes = up ? id_offsets[n] - id0 : 0;
     std::vector<uint32_t> name_off(gs->n_chr + 1, 0);
     for (uint32_t c = 0; c < gs->n_chr; c++) name_off[c + 1] = name_off[c] + (uint32_t)strlen(gs->chr_names[c]);
     bump in;
-    const size_t i_idoff = in.take(8 * (n + 1)), i_cum = in.take(8 * ((size_t)gs->n_chr + 1)), i_noff = in.take(4 * ((size_t)gs->n_chr + 1)),
+    const size_t i_idoff = in.take(up ? 8 * (n + 1) : 0), i_cum = in.take(8 * ((size_t)gs->n_chr + 1)), i_noff = in.take(4 * ((size_t)gs->n_chr + 1)),
                  i_ids = in.take(id_bytes), i_names = in.take(name_off[gs->n_chr]), i_sense = in.take(senses ? n : 0),
                  i_skip = in.take(skip ? n : 0);
     std::vector<uint8_t> host(in.at + 16);
     {
       uint64_t *po = (uint64_t *)(host.data() + i_idoff);
-      for (uint64_t g = 0; g <= n; g++) po[g] = id_offsets[g] - id0;
+      for (uint64_t g = 0; up && g <= n; g++) po[g] = id_offsets[g] - id0;
       uint64_t *pc = (uint64_t *)(host.data() + i_cum);
       pc[0] = 0;
       for (uint32_t c = 0; c < gs->n_chr; c++) pc[c + 1] = pc[c] + gs->chr_lengths[c];
@@ -656,9 +651,9 @@ extern "C" gs_status gs_format_device(gs_index *ix, const gs_genome_structure *g
     memset(&a, 0, sizeof a);
     a.guides = (const uint8_t *)d_guides;
     a.pams = (const uint8_t *)d_guide_pams;
-    a.ids = din + i_ids;
-    a.id_off = (const uint64_t *)(din + i_idoff);
-    a.senses = senses ? din + i_sense : nullptr;
+    a.ids = up ? din + i_ids : (const uint8_t *)d_ids;
+    a.id_off = up ? (const uint64_t *)(din + i_idoff) : (const uint64_t *)d_id_offsets;
+    a.senses = senses ? din + i_sense : (const uint8_t *)d_senses;
     a.skip = skip ? din + i_skip : nullptr;
     a.offsets = (const uint64_t *)d_offsets;
     a.hits = (const gs_hit *)d_hits;
@@ -720,7 +715,7 @@ extern "C" gs_status gs_format_device(gs_index *ix, const gs_genome_structure *g
     GS_HIP(hipStreamSynchronize(st));
     GS_HIP(hipGetLastError());
     if (err & TX_ERR_ARG) {
-      gs_set_error("gs_format_device: a specificity outside [0, 1], a distance beyond `mismatches` or a key that does not decode");
+      gs_set_error("gs_format_device: a specificity outside [0, 1], a distance beyond `mismatches`, a key that does not decode or id offsets that descend");
       return GS_ERR_ARG;
     }
     if (err & TX_ERR_BIG) {
@@ -743,6 +738,42 @@ extern "C" gs_status gs_format_device(gs_index *ix, const gs_genome_structure *g
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;
   }
+}
+
+extern "C" gs_status gs_format_device(gs_index *ix, const gs_genome_structure *gs, const void *d_guides, uint64_t n, uint32_t L,
+                                      const void *d_guide_pams, uint32_t P, const char *ids, const uint64_t *id_offsets,
+                                      const uint8_t *senses, const uint8_t *skip, const void *d_offsets, const void *d_hits,
+                                      const void *d_specificity, uint32_t mismatches, uint32_t flags, int64_t max_off_targets,
+                                      void *stream, const void **d_text, uint64_t *text_len) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !gs || !d_text || !text_len) return GS_ERR_ARG;
+  if (n && (!d_guides || !ids || !id_offsets || !d_offsets || !d_specificity || (P && !d_guide_pams))) return GS_ERR_ARG;
+  if (gs->n_chr && (!gs->chr_names || !gs->chr_lengths)) return GS_ERR_ARG;
+  if (n >= (1ull << 31) || max_off_targets < -1 || mismatches > 7) return GS_ERR_ARG;
+  if (L < 1 || L > 31 || P > 8 || 2 * L + 3 * P > 59) return GS_ERR_ARG;
+  for (uint64_t g = 0; g < n; g++)
+    if (id_offsets[g + 1] < id_offsets[g]) return GS_ERR_ARG;
+  for (uint32_t c = 0; c < gs->n_chr; c++)
+    if (!gs->chr_names[c]) return GS_ERR_ARG;
+  return format_device(ix, gs, d_guides, n, L, d_guide_pams, P, ids, id_offsets, senses, nullptr, nullptr, nullptr, skip, d_offsets,
+                       d_hits, d_specificity, mismatches, flags, max_off_targets, stream, d_text, text_len);
+}
+
+extern "C" gs_status gs_format_device_ids(gs_index *ix, const gs_genome_structure *gs, const void *d_guides, uint64_t n, uint32_t L,
+                                          const void *d_guide_pams, uint32_t P, const void *d_ids, const void *d_id_offsets,
+                                          const void *d_senses, const uint8_t *skip, const void *d_offsets, const void *d_hits,
+                                          const void *d_specificity, uint32_t mismatches, uint32_t flags, int64_t max_off_targets,
+                                          void *stream, const void **d_text, uint64_t *text_len) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !gs || !d_text || !text_len) return GS_ERR_ARG;
+  if (n && (!d_guides || !d_ids || !d_id_offsets || !d_offsets || !d_specificity || (P && !d_guide_pams))) return GS_ERR_ARG;
+  if (gs->n_chr && (!gs->chr_names || !gs->chr_lengths)) return GS_ERR_ARG;
+  if (n >= (1ull << 31) || max_off_targets < -1 || mismatches > 7) return GS_ERR_ARG;
+  if (L < 1 || L > 31 || P > 8 || 2 * L + 3 * P > 59) return GS_ERR_ARG;
+  for (uint32_t c = 0; c < gs->n_chr; c++)
+    if (!gs->chr_names[c]) return GS_ERR_ARG;
+  return format_device(ix, gs, d_guides, n, L, d_guide_pams, P, nullptr, nullptr, nullptr, d_ids, d_id_offsets, d_senses, skip,
+                       d_offsets, d_hits, d_specificity, mismatches, flags, max_off_targets, stream, d_text, text_len);
 }
 
 extern "C" gs_status gs_index_last_text_offsets(gs_index *ix, uint64_t *out, uint64_t n) {

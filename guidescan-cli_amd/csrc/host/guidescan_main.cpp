@@ -11,8 +11,18 @@
  *       --sdsl: builds the index on the GPU now and also writes PREFIX.forward / PREFIX.reverse, the reference's
  *       own index files (src/guidescan.cxx:168-175), byte for byte what its `index` command writes: the
  *       reference binary opens them, and so does `enumerate` here when PREFIX.dna is absent.
- *   guidescan enumerate PREFIX -f KMERS.csv -o OUT [-m 3] [-a PAM ...] [--format csv|sam|bam]
+ *   guidescan kmers PREFIX -o KMERS.csv [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S] [--start]
+ *       [--chromosomes a,b,...] [--device D]
+ *       the kmers file of every candidate guide of the indexed genome, byte for byte what the reference's
+ *       scripts/generate_kmers.py prints for the FASTA: PREFIX.gs cuts PREFIX.dna into chromosomes, each is scanned
+ *       and its rows are encoded on the device (gs_kmers_generate, gs_kmers_csv).  --chromosomes: these only.
+ *   guidescan enumerate PREFIX (-f KMERS.csv | --all-candidates) -o OUT [-m 3] [-a PAM ...] [--format csv|sam|bam]
  *       [--mode succinct|complete] [--max-off-targets N] [--start] [--device D] [--gpus N] [--batch-size B]
+ *       --all-candidates [--pam ...] [--kmer-length ...] [--min-chr-length ...] [--prefix ...] [--chromosomes ...]:
+ *       the guides are the candidates `guidescan kmers` would write with the same options, and OUT is the file
+ *       `enumerate -f` writes for that kmers file.  With --encoder gpu on one device the candidates, their ids and
+ *       senses stay in HBM from the scan to the text (gs_enumerate_text_device); any other batch is copied to the
+ *       host and takes the route of a kmers file's batch.
  *       --gpus N: one index per device (devices D .. D+N-1), one host thread per device pulling batches
  *       from a shared queue, output written in input order (src/guidescan.cxx:226-251 is the
  *       reference's fan-out over threads).  On every device the search of batch i+1 overlaps the text
@@ -100,6 +110,75 @@ bool read_gs(const std::string &path, genome_structure &gs, std::string &err) { 
   return true;
 }
 
+/* what the candidate scan takes (scripts/generate_kmers.py:14-47) */
+struct candidate_opts {
+  std::string pam = "NGG", prefix;
+  long long k = 20, min_chr = 0;
+  bool start = false, have_chromosomes = false;
+  std::vector<std::string> chromosomes;
+};
+std::vector<std::string> split_commas(const std::string &v) {
+  std::vector<std::string> out;
+  std::stringstream ss(v);
+  std::string f;
+  while (std::getline(ss, f, ',')) out.push_back(f);
+  return out;
+}
+bool read_file(const std::string &path, std::string &text) {
+  std::ifstream in(path, std::ios::binary | std::ios::ate);
+  if (!in) return false;
+  text.resize((size_t)in.tellg());
+  in.seekg(0);
+  in.read(&text[0], (std::streamsize)text.size());
+  return (bool)in;
+}
+/* the chromosomes a candidate scan takes, in .gs order, and where each begins in the .dna text */
+bool select_chromosomes(const std::string &prefix, const genome_structure &gs, uint64_t dna_size, const candidate_opts &co,
+                        std::vector<size_t> &sel, std::vector<uint64_t> &begin, std::string &err) {
+  begin.assign(gs.lengths.size() + 1, 0);
+  for (size_t c = 0; c < gs.lengths.size(); c++) begin[c + 1] = begin[c] + gs.lengths[c];
+  if (begin.back() != dna_size) {
+    /* the reference counts untrimmed line lengths (seq_io.cxx:103): blanks at line ends make the two disagree */
+    err = "the chromosome lengths in " + prefix + ".gs sum to " + std::to_string(begin.back()) + " but " + prefix + ".dna holds " +
+          std::to_string(dna_size) + " bases: the chromosomes cannot be cut from it";
+    return false;
+  }
+  for (const std::string &want : co.chromosomes) {
+    bool found = false;
+    for (const std::string &n : gs.names) found = found || n == want;
+    if (!found) {
+      err = "--chromosomes: no chromosome named '" + want + "' in " + prefix + ".gs";
+      return false;
+    }
+  }
+  for (size_t c = 0; c < gs.names.size(); c++) {
+    if ((long long)gs.lengths[c] < co.min_chr) continue; /* scripts/generate_kmers.py:132 */
+    if (co.have_chromosomes && std::find(co.chromosomes.begin(), co.chromosomes.end(), gs.names[c]) == co.chromosomes.end()) continue;
+    sel.push_back(c);
+  }
+  return true;
+}
+/* one of the candidate options? (i advances over its value) */
+bool candidate_option(const std::string &a, int &i, int argc, char **argv, candidate_opts &co, bool &bad) {
+  auto val = [&]() -> const char * {
+    if (i + 1 >= argc) {
+      std::cerr << "error: " << a << " needs a value\n";
+      bad = true;
+      return "";
+    }
+    return argv[++i];
+  };
+  if (a == "--pam") co.pam = val();
+  else if (a == "--kmer-length") co.k = atoll(val());
+  else if (a == "--min-chr-length") co.min_chr = atoll(val());
+  else if (a == "--prefix") co.prefix = val();
+  else if (a == "--chromosomes") {
+    co.have_chromosomes = true;
+    for (auto &n : split_commas(val())) co.chromosomes.push_back(n);
+  } else return false;
+  return true;
+}
+
 struct kmer_row {
   std::string id, sequence, pam, chromosome, sense;
   long long position;
@@ -174,10 +253,14 @@ bool read_kmers(const std::string &path, std::vector<kmer_row> &rows, std::strin
 
 int usage() {
   std::cerr << "usage: guidescan index [--index PREFIX] [--store-sa] [--sdsl] [--device D] GENOME.fa\n"
-               "       guidescan enumerate PREFIX -f KMERS -o OUT [-m N] [-a PAM]... [--format csv|sam|bam]\n"
+               "       guidescan kmers PREFIX -o KMERS [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S]\n"
+               "                 [--start] [--chromosomes a,b,...] [--device D]\n"
+               "       guidescan enumerate PREFIX (-f KMERS | --all-candidates) -o OUT [-m N] [-a PAM]... [--format csv|sam|bam]\n"
                "                 [--mode succinct|complete] [--max-off-targets N] [--start]\n"
                "                 [--rna-bulges N] [--dna-bulges N] [-t THRESHOLD] [-n FORMAT_THREADS]\n"
-               "                 [--device D] [--gpus N] [--batch-size B] [--encoder host|gpu]\n";
+               "                 [--device D] [--gpus N] [--batch-size B] [--encoder host|gpu]\n"
+               "                 with --all-candidates: [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S]\n"
+               "                 [--chromosomes a,b,...]\n";
   return 2;
 }
 
@@ -239,6 +322,96 @@ int do_index(int argc, char **argv) {
   return 0;
 }
 
+int do_kmers(int argc, char **argv) {
+  std::string prefix, output;
+  candidate_opts co;
+  int device = 0;
+  for (int i = 0; i < argc; i++) {
+    const std::string a = argv[i];
+    bool bad = false;
+    if (candidate_option(a, i, argc, argv, co, bad)) {
+      if (bad) return 2;
+    } else if ((a == "-o" || a == "--output") && i + 1 < argc)
+      output = argv[++i];
+    else if (a == "--start")
+      co.start = true;
+    else if (a == "--device" && i + 1 < argc)
+      device = atoi(argv[++i]);
+    else if (!a.empty() && a[0] != '-' && prefix.empty())
+      prefix = a;
+    else
+      return usage();
+  }
+  if (prefix.empty() || output.empty() || co.k < 1) return usage();
+  genome_structure gs;
+  std::string err, text;
+  if (!read_gs(prefix + ".gs", gs, err)) {
+    std::cerr << "error: " << err << "\n";
+    return 1;
+  }
+  if (!read_file(prefix + ".dna", text)) {
+    std::cerr << "error: cannot read " << prefix << ".dna (the genome text `guidescan index` writes)\n";
+    return 1;
+  }
+  std::vector<size_t> sel;
+  std::vector<uint64_t> begin;
+  if (!select_chromosomes(prefix, gs, text.size(), co, sel, begin, err)) {
+    std::cerr << "error: " << err << "\n";
+    return 1;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  const std::string tmp = output + ".tmp";
+  FILE *out = fopen(tmp.c_str(), "wb");
+  if (!out) {
+    std::cerr << "error: cannot write " << tmp << "\n";
+    return 1;
+  }
+  static const char header[] = "id,sequence,pam,chromosome,position,sense\n";
+  bool ok = fwrite(header, 1, sizeof(header) - 1, out) == sizeof(header) - 1;
+  uint64_t total = 0;
+  double s_scan = 0, s_rows = 0, s_write = 0;
+  gs_status rc = GS_OK;
+  for (size_t c : sel) {
+    auto t1 = std::chrono::steady_clock::now();
+    gs_kmers *km = nullptr;
+    rc = gs_kmers_generate(device, (const uint8_t *)text.data() + begin[c], gs.lengths[c], 0, co.pam.c_str(), (uint32_t)co.k,
+                           co.start ? GS_FLAG_PAM_AT_START : 0u, nullptr, &km);
+    if (rc != GS_OK) break;
+    auto t2 = std::chrono::steady_clock::now();
+    s_scan += std::chrono::duration<double>(t2 - t1).count();
+    uint64_t n = 0, len = 0;
+    char *rows = nullptr;
+    gs_kmers_get(km, 1, &n, nullptr, nullptr, nullptr, nullptr);
+    rc = gs_kmers_csv(km, co.prefix.c_str(), gs.names[c].c_str(), &rows, &len);
+    gs_kmers_free(km);
+    if (rc != GS_OK) break;
+    auto t3 = std::chrono::steady_clock::now();
+    s_rows += std::chrono::duration<double>(t3 - t2).count();
+    ok = ok && fwrite(rows, 1, len, out) == len;
+    gs_free(rows);
+    s_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - t3).count();
+    total += n;
+  }
+  ok = (fclose(out) == 0) && ok;
+  if (rc != GS_OK || !ok) {
+    if (rc != GS_OK)
+      std::cerr << "error: candidate scan (--pam " << co.pam << ", --kmer-length " << co.k << "): " << gs_status_string(rc) << "\n";
+    else
+      std::cerr << "error: short write to " << tmp << "\n";
+    unlink(tmp.c_str());
+    return 1;
+  }
+  if (rename(tmp.c_str(), output.c_str()) != 0) {
+    std::cerr << "error: cannot rename " << tmp << " to " << output << "\n";
+    unlink(tmp.c_str());
+    return 1;
+  }
+  std::cout << "Wrote " << total << " candidate(s) of " << sel.size() << " chromosome(s) to " << output << " in "
+            << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s\n";
+  std::cout << "Stages: scan " << s_scan << " s, rows " << s_rows << " s, file writes " << s_write << " s\n";
+  return 0;
+}
+
 /* One batch of kmers with equal (L, P), as it moves through the pipeline: a device thread searches
  * and scores it, a formatting task turns the hit lists into text, the main thread writes the text
  * in input order. */
@@ -249,6 +422,9 @@ struct text_part { /* the lines of one contiguous range of a batch */
 };
 struct batch {
   size_t lo = 0, hi = 0;
+  uint32_t L = 0, P = 0;
+  const kmer_row *rows = nullptr; /* hi - lo rows: the kmers file's, or `own` */
+  std::vector<kmer_row> own;      /* --all-candidates: the batch's candidates, once they had to come to the host */
   std::vector<text_part> parts;
   std::string seqs, pams;
   gs_result *res = nullptr;
@@ -265,8 +441,27 @@ struct batch {
   bool ready = false;
 };
 
+/* --all-candidates: every candidate of the selected chromosomes in one stream in HBM (gs_kmers_concat), ids included;
+ * host copies only when a batch takes the host route */
+struct candidate_set {
+  gs_kmers *all = nullptr;
+  uint64_t n = 0;
+  size_t n_chr = 0;
+  uint32_t L = 0, P = 0;
+  const char *d_seqs = nullptr, *d_pams = nullptr, *d_ids = nullptr, *d_sense = nullptr;
+  const uint64_t *d_id_off = nullptr;
+  std::mutex mtx;
+  bool on_host = false;
+  std::string host_error;
+  const char *h_seqs = nullptr, *h_pams = nullptr, *h_ids = nullptr;
+  const uint8_t *h_sense = nullptr;
+  const uint64_t *h_id_off = nullptr;
+};
+
 struct enumerate_job {
   std::vector<kmer_row> kmers;
+  candidate_set *cand = nullptr;
+  bool cand_device = false; /* batches go to gs_enumerate_text_device first */
   std::vector<batch> batches;
   genome_structure gs;
   gs_genome_structure cgs{};
@@ -360,7 +555,7 @@ static void format_batch(enumerate_job &job, batch &b) {
         /* the whole range in one buffer, rows written in place (no per-hit strings) */
         std::vector<gs_kmer> ck(hi - lo);
         for (size_t g = lo; g < hi; g++) {
-          const kmer_row &k = job.kmers[b.lo + g];
+          const kmer_row &k = b.rows[g];
           ck[g - lo] = gs_kmer{k.id.c_str(), k.sequence.c_str(), k.pam.c_str(), k.sense == "+" ? 1 : 0};
         }
         prc[t] = gs_format_guides_scored(&job.cgs, ck.data(), hi - lo, v.guide_offsets + lo, v.hits, b.spec.data() + lo,
@@ -373,7 +568,7 @@ static void format_batch(enumerate_job &job, batch &b) {
       size_t tl = 0;
       for (size_t g = lo; g < hi; g++) {
         if (!b.skip.empty() && b.skip[g]) continue;
-        const kmer_row &k = job.kmers[b.lo + g];
+        const kmer_row &k = b.rows[g];
         gs_kmer ck{k.id.c_str(), k.sequence.c_str(), k.pam.c_str(), k.sense == "+" ? 1 : 0};
         gs_status r;
         const uint32_t gx = b.gen_of.empty() ? ~0u : b.gen_of[g];
@@ -409,8 +604,99 @@ static void format_batch(enumerate_job &job, batch &b) {
 /* the device side of one batch: threshold filter, search (fast path; general path for the guides it
  * flags, or for all of them with bulges), scoring */
 static std::string search_batch_as(enumerate_job &job, gs_index *ix, batch &b, bool all_general, gs_status &rc);
+/* --all-candidates: the batch's candidates as rows on the host, for the route a kmers file's batch takes */
+static std::string candidates_to_host(enumerate_job &job, batch &b) {
+  candidate_set &cs = *job.cand;
+  {
+    std::lock_guard<std::mutex> lk(cs.mtx);
+    if (!cs.on_host && cs.host_error.empty()) {
+      const void *a = nullptr, *p = nullptr, *i = nullptr, *o = nullptr, *s = nullptr;
+      gs_status rc = gs_kmers_get(cs.all, 0, nullptr, &a, &p, nullptr, nullptr);
+      if (rc == GS_OK) rc = gs_kmers_get_ids(cs.all, 0, &i, &o, &s);
+      if (rc != GS_OK) {
+        cs.host_error = gs_status_string(rc);
+      } else {
+        cs.h_seqs = (const char *)a;
+        cs.h_pams = (const char *)p;
+        cs.h_ids = (const char *)i;
+        cs.h_id_off = (const uint64_t *)o;
+        cs.h_sense = (const uint8_t *)s;
+        cs.on_host = true;
+      }
+    }
+    if (!cs.host_error.empty()) return cs.host_error;
+  }
+  const size_t n = b.hi - b.lo;
+  b.own.resize(n);
+  b.seqs.assign(cs.h_seqs + b.lo * cs.L, n * cs.L);
+  b.pams.assign(cs.h_pams + b.lo * cs.P, n * cs.P);
+  for (size_t g = 0; g < n; g++) {
+    kmer_row &r = b.own[g];
+    const size_t at = b.lo + g;
+    r.id.assign(cs.h_ids + cs.h_id_off[at], (size_t)(cs.h_id_off[at + 1] - cs.h_id_off[at]));
+    r.sequence.assign(cs.h_seqs + at * cs.L, cs.L);
+    r.pam.assign(cs.h_pams + at * cs.P, cs.P);
+    r.sense = cs.h_sense[at] ? "+" : "-";
+    r.position = 0;
+  }
+  b.rows = b.own.data();
+  return "";
+}
+/* --all-candidates with --encoder gpu: the batch from HBM to text (gs_enumerate_text_device).  true: done, or failed
+ * (err); false: the batch takes the host route */
+static bool search_batch_device(enumerate_job &job, gs_index *ix, batch &b, std::string &err) {
+  const candidate_set &cs = *job.cand;
+  const size_t n = b.hi - b.lo;
+  const uint32_t n_alt = cs.P ? job.n_alt : 0;
+  for (uint32_t j = 0; j < n_alt; j++)
+    if (job.alt_lens[j] != cs.P) return false;
+  if (job.rna > 0 || job.dna > 0 || job.mismatches > 7) return false;
+  const char *d_g = cs.d_seqs + b.lo * cs.L, *d_p = cs.d_pams + b.lo * cs.P;
+  gs_status rc;
+  if (job.threshold > 0) { /* process.hpp:66-76, as search_batch_as does it: the raw counts of a search at t mismatches */
+    if (job.threshold > 7) return false;
+    std::vector<uint32_t> raw(n);
+    rc = gs_enumerate_text_device(ix, d_g, n, cs.L, d_p, cs.P, job.alts.data(), n_alt, (uint32_t)job.threshold,
+                                  job.sflags | GS_FLAG_RAW_COUNTS, -1, &job.cgs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, raw.data());
+    if (rc == GS_ERR_UNSUPPORTED) return false;
+    if (rc != GS_OK) {
+      err = gs_status_string(rc);
+      return true;
+    }
+    b.skip.assign(n, 0);
+    for (size_t g = 0; g < n; g++) b.skip[g] = raw[g] > 1;
+  }
+  rc = gs_enumerate_text_device(ix, d_g, n, cs.L, d_p, cs.P, job.alts.data(), n_alt, job.mismatches, job.sflags | job.tflags,
+                                job.max_off, &job.cgs, cs.d_ids, cs.d_id_off + b.lo, cs.d_sense + b.lo,
+                                b.skip.empty() ? nullptr : (const uint8_t *)b.skip.data(), &b.text, &b.text_len, nullptr, nullptr);
+  if (rc == GS_ERR_UNSUPPORTED) {
+    b.skip.clear();
+    return false;
+  }
+  if (rc == GS_OK && job.bam) { /* this thread alone uses the handle: the last text is still this one */
+    b.text_goff.resize(n + 1);
+    rc = gs_index_last_text_offsets(ix, b.text_goff.data(), n);
+  }
+  if (rc != GS_OK) {
+    err = gs_status_string(rc);
+    return true;
+  }
+  {
+    std::lock_guard<std::mutex> lk(job.mtx);
+    job.enc_device++;
+  }
+  b.text_done = true;
+  return true;
+}
 static std::string search_batch(enumerate_job &job, gs_index *ix, batch &b) {
-  const uint32_t L = (uint32_t)job.kmers[b.lo].sequence.size(), P = (uint32_t)job.kmers[b.lo].pam.size();
+  if (job.cand) {
+    std::string err;
+    if (job.cand_device && search_batch_device(job, ix, b, err)) return err;
+    err = candidates_to_host(job, b);
+    if (!err.empty()) return err;
+  }
+  const uint32_t L = b.L, P = b.P;
   /* Match sequences beyond the fast path's key: up to 59 bits (23-mers with a four-symbol PAM: 58) the table-seeded
    * kernels carry them; the reference-order walk (small genomes whose table is too shallow for the context arrays)
    * stops at 52 and says GS_ERR_UNSUPPORTED - then, and beyond 59 bits, the general path carries sequences as bytes */
@@ -427,7 +713,7 @@ static std::string search_batch(enumerate_job &job, gs_index *ix, batch &b) {
 }
 static std::string search_batch_as(enumerate_job &job, gs_index *ix, batch &b, bool all_general, gs_status &rc) {
   const size_t n = b.hi - b.lo;
-  const uint32_t L = (uint32_t)job.kmers[b.lo].sequence.size(), P = (uint32_t)job.kmers[b.lo].pam.size();
+  const uint32_t L = b.L, P = b.P;
   const uint32_t n_alt = P ? job.n_alt : 0;
   const bool bulges = job.rna > 0 || job.dna > 0;
   /* an alt PAM shorter or longer than the batch's PAM: the fixed-width fast path does not take it; the
@@ -496,7 +782,7 @@ static std::string search_batch_as(enumerate_job &job, gs_index *ix, batch &b, b
     std::vector<uint64_t> id_off(n + 1, 0);
     std::vector<uint8_t> senses(n);
     for (size_t g = 0; g < n; g++) {
-      const kmer_row &k = job.kmers[b.lo + g];
+      const kmer_row &k = b.rows[g];
       ids += k.id;
       id_off[g + 1] = ids.size();
       senses[g] = k.sense == "+" ? 1 : 0;
@@ -559,9 +845,16 @@ int do_enumerate(int argc, char **argv) {
   int device = 0, gpus = 1;
   size_t batch_size = 0;
   unsigned fmt_threads = 0;
-  bool start = false;
+  bool start = false, all_candidates = false, candidate_opts_given = false;
+  candidate_opts co;
   for (int i = 0; i < argc; i++) {
     const std::string a = argv[i];
+    bool bad = false;
+    if (candidate_option(a, i, argc, argv, co, bad)) {
+      if (bad) return 2;
+      candidate_opts_given = true;
+      continue;
+    }
     auto need = [&](const char *what) -> const char * {
       if (i + 1 >= argc) {
         std::cerr << "error: " << what << " needs a value\n";
@@ -581,6 +874,7 @@ int do_enumerate(int argc, char **argv) {
     else if (a == "--format") format = need("--format");
     else if (a == "--mode") mode = need("--mode");
     else if (a == "--start") start = true;
+    else if (a == "--all-candidates") all_candidates = true;
     else if (a == "--device") device = atoi(need("--device"));
     else if (a == "--gpus") gpus = atoi(need("--gpus"));
     else if (a == "--batch-size") batch_size = (size_t)atoll(need("--batch-size"));
@@ -588,7 +882,18 @@ int do_enumerate(int argc, char **argv) {
     else if (!a.empty() && a[0] != '-' && prefix.empty()) prefix = a;
     else return usage();
   }
-  if (prefix.empty() || kmers_file.empty() || output.empty()) return usage();
+  if (!prefix.empty() && !output.empty() && kmers_file.empty() == !all_candidates) {
+    std::cerr << (all_candidates ? "error: -f KMERS and --all-candidates exclude each other: the guides come from the file or from the scan\n"
+                                 : "error: no guides: give -f KMERS or --all-candidates\n");
+    return usage();
+  }
+  if (prefix.empty() || output.empty()) return usage();
+  if (all_candidates && co.k < 1) return usage();
+  if (!all_candidates && candidate_opts_given) {
+    std::cerr << "error: --pam, --kmer-length, --min-chr-length, --prefix and --chromosomes describe the scan of --all-candidates; with -f the kmers file says what the guides are\n";
+    return usage();
+  }
+  co.start = start;
   if ((format != "csv" && format != "sam" && format != "bam") || (mode != "succinct" && mode != "complete")) return usage();
   if (gpus < 1 || mismatches < 0 || rna < 0 || dna < 0) return usage();
   if (encoder != "host" && encoder != "gpu") return usage();
@@ -609,17 +914,83 @@ int do_enumerate(int argc, char **argv) {
       dna_in.seekg(0);
       dna_in.read(&text[0], (std::streamsize)text.size());
     } else if (std::ifstream(prefix + ".forward")) {
+      if (all_candidates) {
+        std::cerr << "error: --all-candidates needs " << prefix << ".dna, the genome text the candidates are cut from: " << prefix
+                  << " has only the .forward / .reverse index files\n";
+        return 1;
+      }
       from_sdsl = true;
     } else {
       std::cerr << "error: neither " << prefix << ".dna nor " << prefix << ".forward exists\n";
       return 1;
     }
   }
-  if (!read_kmers(kmers_file, job.kmers, err)) {
-    std::cerr << "error: " << err << "\n";
-    return 1;
+  candidate_set cand;
+  struct cand_guard {
+    candidate_set &c;
+    ~cand_guard() {
+      if (c.all) gs_kmers_free(c.all);
+    }
+  } cand_guard_{cand};
+  if (all_candidates) {
+    /* scan first, search afterwards: the table rule below needs the true candidate count.  Every selected chromosome
+     * is scanned and its ids are encoded on `device`; one concatenation makes the stream the batches are cut from */
+    const auto ts = std::chrono::steady_clock::now();
+    std::vector<size_t> sel;
+    std::vector<uint64_t> begin;
+    if (!select_chromosomes(prefix, job.gs, text.size(), co, sel, begin, err)) {
+      std::cerr << "error: " << err << "\n";
+      return 1;
+    }
+    std::vector<gs_kmers *> parts;
+    gs_status rc = GS_OK;
+    for (size_t c : sel) {
+      gs_kmers *km = nullptr;
+      rc = gs_kmers_generate(device, (const uint8_t *)text.data() + begin[c], job.gs.lengths[c], 0, co.pam.c_str(), (uint32_t)co.k,
+                             start ? GS_FLAG_PAM_AT_START : 0u, nullptr, &km);
+      if (rc != GS_OK) break;
+      parts.push_back(km);
+      rc = gs_kmers_encode_ids(km, co.prefix.c_str(), job.gs.names[c].c_str(), nullptr);
+      if (rc != GS_OK) break;
+    }
+    if (rc == GS_OK && parts.empty()) { /* no chromosome selected: an empty set with ids */
+      gs_kmers *km = nullptr;
+      rc = gs_kmers_generate(device, nullptr, 0, 0, co.pam.c_str(), (uint32_t)co.k, 0u, nullptr, &km);
+      if (rc == GS_OK) {
+        parts.push_back(km);
+        rc = gs_kmers_encode_ids(km, "", "", nullptr);
+      }
+    }
+    if (rc == GS_OK) rc = gs_kmers_concat(parts.data(), (uint32_t)parts.size(), &cand.all);
+    for (gs_kmers *km : parts) gs_kmers_free(km);
+    const void *a = nullptr, *p = nullptr, *i = nullptr, *o = nullptr, *s = nullptr;
+    if (rc == GS_OK) rc = gs_kmers_get(cand.all, 1, &cand.n, &a, &p, nullptr, nullptr);
+    if (rc == GS_OK) rc = gs_kmers_get_ids(cand.all, 1, &i, &o, &s);
+    if (rc != GS_OK) {
+      std::cerr << "error: candidate scan (--pam " << co.pam << ", --kmer-length " << co.k << "): " << gs_status_string(rc) << "\n";
+      return 1;
+    }
+    cand.d_seqs = (const char *)a;
+    cand.d_pams = (const char *)p;
+    cand.d_ids = (const char *)i;
+    cand.d_id_off = (const uint64_t *)o;
+    cand.d_sense = (const char *)s;
+    cand.n_chr = sel.size();
+    cand.L = (uint32_t)co.k;
+    cand.P = (uint32_t)co.pam.size();
+    job.cand = &cand;
+    /* 2L + 3P > 59: no batch fits the fast path's key, every one takes the host route */
+    job.cand_device = job.encoder_gpu && gpus == 1 && cand.L <= 31 && 2 * cand.L + 3 * cand.P <= 59;
+    std::cout << "Scanned " << cand.n << " candidate(s) of " << sel.size() << " chromosome(s) in "
+              << std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count() << " s\n";
+  } else {
+    if (!read_kmers(kmers_file, job.kmers, err)) {
+      std::cerr << "error: " << err << "\n";
+      return 1;
+    }
+    std::cout << "Read in " << job.kmers.size() << " kmer(s).\n";
   }
-  std::cout << "Read in " << job.kmers.size() << " kmer(s).\n";
+  const size_t n_guides = all_candidates ? (size_t)cand.n : job.kmers.size();
 
   /* one index per device, built side by side (src/guidescan.cxx:226-251 fans the guides out over
    * threads that share one index; here every GPU holds its own copy in HBM) */
@@ -691,7 +1062,7 @@ int do_enumerate(int argc, char **argv) {
      * round 6 the saving was 15 ms per million and the bar stood at 15 M guides.) */
     uint64_t glen = 0;
     for (uint64_t l : job.gs.lengths) glen += l;
-    if ((double)job.kmers.size() / (double)gpus < 6e-4 * (double)glen) job.sflags |= GS_FLAG_NO_NEW_TABLES;
+    if ((double)n_guides / (double)gpus < 6e-4 * (double)glen) job.sflags |= GS_FLAG_NO_NEW_TABLES;
   }
   job.mismatches = (uint32_t)mismatches;
   job.rna = (uint32_t)rna;
@@ -724,14 +1095,23 @@ int do_enumerate(int argc, char **argv) {
   /* searched, being formatted, being written: three batches in flight per device where a batch's hit lists and text are
    * small (m <= 4: ~0.2 GB), two where they are gigabytes */
   if (mismatches <= 4) job.max_in_flight = 3 * (size_t)gpus;
-  for (size_t done = 0; done < job.kmers.size();) {
-    const size_t L = job.kmers[done].sequence.size(), P = job.kmers[done].pam.size();
+  for (size_t done = 0; done < n_guides;) {
     batch b;
     b.lo = done;
     size_t end = done;
-    while (end < job.kmers.size() && end - done < batch_size && job.kmers[end].sequence.size() == L &&
-           job.kmers[end].pam.size() == P)
-      end++;
+    if (all_candidates) { /* the concatenated stream, whatever chromosome a candidate is of */
+      b.L = cand.L;
+      b.P = cand.P;
+      end = std::min(n_guides, done + batch_size);
+    } else {
+      const size_t L = job.kmers[done].sequence.size(), P = job.kmers[done].pam.size();
+      b.L = (uint32_t)L;
+      b.P = (uint32_t)P;
+      b.rows = &job.kmers[done];
+      while (end < job.kmers.size() && end - done < batch_size && job.kmers[end].sequence.size() == L &&
+             job.kmers[end].pam.size() == P)
+        end++;
+    }
     b.hi = end;
     job.batches.push_back(std::move(b));
     done = end;
@@ -765,7 +1145,7 @@ int do_enumerate(int argc, char **argv) {
           job.in_flight++;
         }
         batch &b = job.batches[bi];
-        for (size_t g = b.lo; g < b.hi; g++) {
+        for (size_t g = b.lo; g < b.hi && !job.cand; g++) {
           b.seqs += job.kmers[g].sequence;
           b.pams += job.kmers[g].pam;
         }
@@ -819,6 +1199,7 @@ int do_enumerate(int argc, char **argv) {
     b.parts = std::vector<text_part>();
     b.seqs = std::string();
     b.pams = std::string();
+    b.own = std::vector<kmer_row>();
     {
       std::lock_guard<std::mutex> lk(job.mtx);
       job.in_flight--;
@@ -834,9 +1215,11 @@ int do_enumerate(int argc, char **argv) {
     file_off += eof.size();
   }
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  std::cout << "Processed " << job.kmers.size() << " kmers in " << secs << " seconds.\n";
+  std::cout << "Processed " << n_guides << " kmers in " << secs << " seconds.\n";
   std::cout << "Stages (overlapping): device " << job.s_device << " s, text formatting " << job.s_format
             << " s, file writes " << job.s_write << " s\n";
+  if (job.cand)
+    std::cout << "Candidates: " << cand.n << " guide(s) from " << cand.n_chr << " chromosome(s) in " << job.batches.size() << " batch(es)\n";
   if (job.encoder_gpu)
     std::cout << "Encoder: gpu (" << job.enc_device << " batch(es) encoded on the device, " << job.batches.size() - job.enc_device
               << " by the host encoders)\n";
@@ -913,6 +1296,7 @@ int main(int argc, char **argv) {
   if (argc < 2) return usage();
   if (!strcmp(argv[1], "sam2bam")) return do_sam2bam(argc - 2, argv + 2);
   if (!strcmp(argv[1], "index")) return do_index(argc - 2, argv + 2);
+  if (!strcmp(argv[1], "kmers")) return do_kmers(argc - 2, argv + 2);
   if (!strcmp(argv[1], "enumerate")) return do_enumerate(argc - 2, argv + 2);
   return usage();
 }

@@ -102,14 +102,23 @@ def find_all_kmers_device(chrm, pam="NGG", k=20, start=False, device=0):
 
 def write_kmers_csv(fh, records, pam="NGG", k=20, start=False, prefix="", min_chr_length=0, device=None):
     """records: iterable of (name, sequence bytes).  Writes the kmers CSV (header included).
-    device: GPU ordinal to scan on (None = the numpy restatement)."""
+    device: GPU ordinal to scan on (None = the numpy restatement); the rows are then encoded on the device too
+    (gs_kmers_csv, csrc/gs_kmers.hip) and reach the host as text."""
     fh.write("id,sequence,pam,chromosome,position,sense\n")
     n = 0
     for name, seq in records:
         if len(seq) < min_chr_length:
             continue
-        found = find_all_kmers(seq, pam, k, start) if device is None else \
-            find_all_kmers_device(seq, pam, k, start, device)
+        if device is not None:
+            from importlib import import_module
+            km = import_module("guidescan-cli_amd.api").generate_kmers(seq, pam, k, start, device)
+            try:
+                fh.write(km.csv(prefix, name).decode())
+                n += km.n
+            finally:
+                km.close()
+            continue
+        found = find_all_kmers(seq, pam, k, start)
         for kmer, pos, sense in found:
             fh.write(f"{prefix}{name}:{pos}:{sense},{kmer},{pam},{name},{pos},{sense}\n")
             n += 1

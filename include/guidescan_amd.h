@@ -478,6 +478,15 @@ gs_status gs_format_device(gs_index *ix, const gs_genome_structure *gs, const vo
                            const uint8_t *senses, const uint8_t *skip, const void *d_offsets, const void *d_hits,
                            const void *d_specificity, uint32_t mismatches, uint32_t flags, int64_t max_off_targets,
                            void *stream, const void **d_text, uint64_t *text_len);
+/* gs_format_device with ids that are in HBM already (gs_kmers_get_ids): d_ids, d_id_offsets (n + 1 uint64 that index d_ids
+ * as they stand: d_id_offsets[0] need not be 0) and d_senses (n bytes, != 0 = "+", or NULL) are device pointers; `skip`
+ * stays a host array.  The same bytes as gs_format_device on the same inputs; offsets that descend are reported by the
+ * device as GS_ERR_ARG. */
+gs_status gs_format_device_ids(gs_index *ix, const gs_genome_structure *gs, const void *d_guides, uint64_t n, uint32_t L,
+                               const void *d_guide_pams, uint32_t P, const void *d_ids, const void *d_id_offsets,
+                               const void *d_senses, const uint8_t *skip, const void *d_offsets, const void *d_hits,
+                               const void *d_specificity, uint32_t mismatches, uint32_t flags, int64_t max_off_targets,
+                               void *stream, const void **d_text, uint64_t *text_len);
 /* Where each guide's lines begin in the text of the last gs_format_device / gs_enumerate_text on this handle: out[g] for
  * g in [0, n], out[n] = the text's length; n as passed to that call (else GS_ERR_ARG, as after any other call on the handle
  * that runs a batch).  Made on the device from the row lengths, with the text.  Stands where the reference's writer has
@@ -497,6 +506,19 @@ gs_status gs_enumerate_text(gs_index *ix, const char *guides, uint64_t n, uint32
                             const uint64_t *id_offsets, const uint8_t *senses, const uint8_t *skip, char **text,
                             uint64_t *len, gs_result_view *stats);
 
+/* gs_enumerate_text over guides, ids and senses that are in HBM already (a gs_kmers object's arrays, or a range of them):
+ * gs_enumerate_device -> gs_score_device -> gs_format_device_ids; only the text - and `skip`, a host array or NULL -
+ * crosses the bus.  GS_ERR_UNSUPPORTED and no text when a guide carries GS_GUIDE_NEEDS_GENERAL or the shape is outside
+ * the fast path's key (2L + 3P > 59).
+ * With GS_FLAG_RAW_COUNTS in flags the call is the counting pass of --threshold (process.hpp:66-76) instead: the search
+ * alone at `mismatches`, its raw hit counts copied to raw_hits (host, n entries, required); no text is made, `text`,
+ * `len`, the ids and senses may be NULL.  Without the flag raw_hits must be NULL. */
+gs_status gs_enumerate_text_device(gs_index *ix, const void *d_guides, uint64_t n, uint32_t L, const void *d_guide_pams,
+                                   uint32_t P, const char *alt_pams, uint32_t n_alt, uint32_t mismatches, uint32_t flags,
+                                   int64_t max_off_targets, const gs_genome_structure *gs, const void *d_ids,
+                                   const void *d_id_offsets, const void *d_senses, const uint8_t *skip, char **text,
+                                   uint64_t *len, gs_result_view *stats, uint32_t *raw_hits);
+
 /* ---- candidate-guide generation on the device ------------------- */
 
 typedef struct gs_kmers gs_kmers;
@@ -514,6 +536,20 @@ gs_status gs_kmers_generate(int device, const uint8_t *chr, uint64_t chr_len, in
  * the layout gs_enumerate_device takes; else host copies owned by the object. */
 gs_status gs_kmers_get(gs_kmers *km, int on_device, uint64_t *n, const void **seqs, const void **pams,
                        const void **positions, const void **senses);
+/* The records' ids "{prefix}{chr_name}:{position}:{sense}" (scripts/generate_kmers.py:120-125) encoded in HBM and kept
+ * in the object: the bytes back to back, n + 1 uint64 offsets from 0, and the senses as 0 / 1 (1 = "+"), the three
+ * arrays gs_format_device_ids / gs_enumerate_text_device take.  A second call replaces them. */
+gs_status gs_kmers_encode_ids(gs_kmers *km, const char *prefix, const char *chr_name, void *stream);
+/* on_device as in gs_kmers_get; GS_ERR_ARG before gs_kmers_encode_ids */
+gs_status gs_kmers_get_ids(gs_kmers *km, int on_device, const void **ids, const void **id_offsets,
+                           const void **sense_positive);
+/* The records as rows of the kmers file, `id,sequence,pam,chromosome,position,sense\n` (the same lines of the script,
+ * `pam` = the pattern): rows only, no header, encoded in HBM and copied back through page-locked staging.  *text is
+ * malloc'ed (NUL terminated, *len bytes before the terminator): release with gs_free. */
+gs_status gs_kmers_csv(gs_kmers *km, const char *prefix, const char *chr_name, char **text, uint64_t *len);
+/* One object holding the records of parts[0], parts[1], ... in that order (same device, k and P), in HBM; ids too when
+ * every part has them.  The parts stay valid and are still the caller's to free. */
+gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, gs_kmers **out);
 void gs_kmers_free(gs_kmers *km);
 
 const char *gs_status_string(gs_status s);
