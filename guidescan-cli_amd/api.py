@@ -67,6 +67,13 @@ class GsKmer(C.Structure):
 
 GS_TEXT_SAM = 0x100
 GS_TEXT_COMPLETE = 0x200
+GS_DECODE_NO_HEADER = 0x400
+
+
+class GsDecodeBatch(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("ids", C.c_void_p), ("id_off", C.c_void_p), ("seqs", C.c_void_p),
+                ("seq_off", C.c_void_p), ("reverse", C.c_void_p), ("chr", C.c_void_p), ("pos0", C.c_void_p),
+                ("hex", C.c_void_p), ("hex_off", C.c_void_p)]
 
 
 def build_library():
@@ -214,6 +221,19 @@ def lib():
     L.gs_kmers_csv.argtypes = [vp, C.c_char_p, C.c_char_p, C.POINTER(vp), C.POINTER(u64)]
     L.gs_kmers_concat.restype = i32
     L.gs_kmers_concat.argtypes = [vp, u32, C.POINTER(vp)]
+    L.gs_decoder_open.restype = i32
+    L.gs_decoder_open.argtypes = [i32, vp, u64, C.POINTER(GsGenomeStructure), vp, vp, C.POINTER(vp)]
+    L.gs_decoder_close.argtypes = [vp]
+    L.gs_decode_records.restype = i32
+    L.gs_decode_records.argtypes = [vp, C.POINTER(GsDecodeBatch), u32, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    L.gs_decode_records_device.restype = i32
+    L.gs_decode_records_device.argtypes = L.gs_decode_records.argtypes
+    L.gs_decode_sam.restype = i32
+    L.gs_decode_sam.argtypes = [vp, vp, u64, u32, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    L.gs_debug_repr_doubles.restype = i32
+    L.gs_debug_repr_doubles.argtypes = [vp, u64, vp]
+    L.gs_debug_decode_tables.restype = i32
+    L.gs_debug_decode_tables.argtypes = [vp, vp]
     L.gs_status_string.restype = C.c_char_p
     L.gs_status_string.argtypes = [i32]
     L.gs_version.restype = C.c_char_p
@@ -235,7 +255,8 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_index_save_sdsl", "gs_debug_sdsl_sections", "gs_debug_sdsl_export_scratch",
            "gs_format_device", "gs_enumerate_text", "gs_index_last_text_offsets",
            "gs_format_device_ids", "gs_enumerate_text_device", "gs_kmers_encode_ids", "gs_kmers_get_ids", "gs_kmers_csv",
-           "gs_kmers_concat"]
+           "gs_kmers_concat", "gs_decoder_open", "gs_decoder_close", "gs_decode_records", "gs_decode_records_device",
+           "gs_decode_sam", "gs_debug_repr_doubles", "gs_debug_decode_tables"]
 
 
 def _check(rc):
@@ -485,6 +506,114 @@ def concat_kmers(parts):
         _check(lib().gs_kmers_get_ids(h, 1, C.byref(a), C.byref(b), C.byref(c)))
         km.ids_ptr, km.id_offsets_ptr, km.sense_positive_ptr = a.value, b.value, c.value
     return km
+
+
+def repr_doubles(values) -> list:
+    """Python's repr() of each double as the decoder's kernels print it (gs_debug_repr_doubles; host only)"""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    out = np.zeros((v.shape[0], 32), np.uint8)
+    _check(lib().gs_debug_repr_doubles(v.ctypes.data if v.size else None, v.shape[0], out.ctypes.data if v.size else None))
+    return [r.tobytes().rstrip(b"\0").decode() for r in out]
+
+
+def decode_tables():
+    """the CFD tables the decoder uploads, keyed as the reference's score tables are -> (mm {key: float}, pam {pair: float})"""
+    mm, pam = np.zeros(320), np.zeros(16)
+    _check(lib().gs_debug_decode_tables(mm.ctypes.data, pam.ctypes.data))
+    keys = {f"r{r}:d{d},{i + 1}": float(mm[(ri * 4 + di) * 20 + i]) for ri, r in enumerate("ACGU")
+            for di, d in enumerate("ACGT") for i in range(20) if "TGCA"[ri] != d}
+    return keys, {a + b: float(pam[ai * 4 + bi]) for ai, a in enumerate("ACGT") for bi, b in enumerate("ACGT")}
+
+
+class Decoder:
+    """A SAM/BAM database's decoder on one GPU (gs_decoder_open): sq = [(name, LN)] of the @SQ lines, fasta =
+    {name: symbols} of the genome's FASTA records (decode.parse_fasta_records).  decode_records() takes
+    decode.Record objects and returns the rows scripts/decode_database.py prints, without the header line."""
+
+    def __init__(self, sq, fasta, device=0):
+        names = [n for n, _ in sq]
+        parts, off, ln, at = [], [], [], 0
+        for n in names:
+            if n in fasta:
+                b = fasta[n].encode("latin-1")
+                parts.append(b)
+                off.append(at)
+                ln.append(len(b))
+                at += len(b)
+            else:
+                off.append(0)
+                ln.append(2**64 - 1)
+        text = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        self.names = names
+        gs = self._gs = make_genome_structure(names, [n for _, n in sq])
+        off, ln = np.array(off, dtype=np.uint64), np.array(ln, dtype=np.uint64)
+        h = C.c_void_p()
+        _check(lib().gs_decoder_open(device, text.ctypes.data if text.size else None, text.shape[0], C.byref(gs),
+                                     off.ctypes.data if len(names) else None, ln.ctypes.data if len(names) else None, C.byref(h)))
+        self._h = h
+
+    def _batch(self, records):
+        index = {}
+        for i, n in enumerate(self.names):
+            index.setdefault(n, i)
+
+        def blob(items):
+            items = [x.encode("latin-1") for x in items]
+            return (np.frombuffer(b"".join(items) + b"\0", dtype=np.uint8),
+                    np.cumsum([0] + [len(x) for x in items], dtype=np.uint64))
+
+        ids, id_off = blob([r.id for r in records])
+        seqs, seq_off = blob([r.seq for r in records])
+        hexs, hex_off = blob([r.hex or "" for r in records])
+        rev = np.array([1 if r.reverse else 0 for r in records], dtype=np.uint8)
+        chrm = np.array([index.get(r.rname, -1) for r in records], dtype=np.int32)
+        pos0 = np.array([r.pos0 for r in records], dtype=np.int64)
+        keep = (ids, id_off, seqs, seq_off, hexs, hex_off, rev, chrm, pos0)
+        b = GsDecodeBatch(len(records), ids.ctypes.data, id_off.ctypes.data, seqs.ctypes.data, seq_off.ctypes.data,
+                          rev.ctypes.data, chrm.ctypes.data, pos0.ctypes.data, hexs.ctypes.data, hex_off.ctypes.data)
+        return b, keep
+
+    def decode_records(self, records, complete=False, first_record=0, on_device=False) -> str:
+        """on_device: through gs_decode_records_device, the text copied back from HBM here"""
+        if not records:
+            return ""
+        b, keep = self._batch(records)
+        flags = GS_TEXT_COMPLETE if complete else 0
+        out, ln, rows = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        fn = lib().gs_decode_records_device if on_device else lib().gs_decode_records
+        _check(fn(self._h, C.byref(b), flags, first_record, C.byref(out), C.byref(ln), C.byref(rows)))
+        self.last_rows = rows.value
+        if on_device:
+            if ln.value == 0:
+                return ""
+            hip = C.CDLL("libamdhip64.so")
+            hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+            host = np.empty(ln.value, dtype=np.uint8)
+            if hip.hipMemcpy(host.ctypes.data, out, ln.value, 2) != 0:
+                raise GsError(2, "copy of the decoded text")
+            return host.tobytes().decode("latin-1")
+        s = C.string_at(out, ln.value).decode("latin-1")
+        lib().gs_free(out)
+        return s
+
+    def decode_sam(self, sam: bytes, complete=False, header=True, first_record=0) -> str:
+        flags = (GS_TEXT_COMPLETE if complete else 0) | (0 if header else GS_DECODE_NO_HEADER)
+        out, ln, n = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _check(lib().gs_decode_sam(self._h, sam, len(sam), flags, first_record, C.byref(out), C.byref(ln), C.byref(n)))
+        s = C.string_at(out, ln.value).decode("latin-1")
+        lib().gs_free(out)
+        return s
+
+    def close(self):
+        if self._h:
+            lib().gs_decoder_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def sdsl_extract_text(index_file) -> np.ndarray:

@@ -1,0 +1,520 @@
+/*
+ * decode_cmd.hpp -- `guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--verbose]
+ * DATABASE GENOME.fa`: the CSV
+ * that the reference's scripts/decode_database.py prints for a SAM/BAM off-target database (manual, "Off-Target
+ * Databases"), through the device decoder (gs_decoder_open / gs_decode_sam / gs_decode_records).  Control plane only:
+ * the FASTA records are read and handed over once (SeqIO.to_dict, :223), the database is read in batches of whole
+ * records, so a database larger than host memory streams; the output does not depend on where the batches are cut.
+ * DATABASE is SAM text, or BAM when it begins with the gzip magic: the BGZF blocks are inflated with zlib and the
+ * records read per SAMv1 section 4 (@SQ from the text header, else from the binary reference list).
+ * On a failure the exit status is 1, the message names the record, and an OUT file is removed.  Without -o the table
+ * streams to stdout, so the header line and the rows of earlier batches have already gone out when a later batch
+ * fails (usage() says so): only -o gives all or nothing.  --batch-size: records per batch (2^20; a batch also ends at 256 MB of
+ * lines or hex digits).  --verbose: one line on stderr with the seconds of each stage.
+ */
+#ifndef GS_DECODE_CMD_HPP
+#define GS_DECODE_CMD_HPP
+
+#include <time.h>
+#include <zlib.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "guidescan_amd.h"
+
+namespace decode_cmd {
+
+struct fasta_records { /* name (first word of the title) -> its symbols as they stand, blanks removed */
+  std::string text;
+  std::map<std::string, std::pair<uint64_t, uint64_t>> where;
+};
+/* the file is read whole and compacted where it is: title lines and blanks drop out, the symbols move up */
+inline bool read_fasta(const std::string &path, fasta_records &fa, std::string &err) {
+  {
+    std::ifstream in(path, std::ios::binary | std::ios::ate);
+    if (!in) {
+      err = "cannot read " + path;
+      return false;
+    }
+    fa.text.resize((size_t)in.tellg());
+    in.seekg(0);
+    in.read(&fa.text[0], (std::streamsize)fa.text.size());
+    if (!in) {
+      err = "cannot read " + path;
+      return false;
+    }
+  }
+  std::string &t = fa.text, name;
+  const size_t size = t.size();
+  bool have = false;
+  size_t w = 0, begin = 0;
+  auto close_record = [&]() {
+    if (have) fa.where[name] = {begin, w - begin};
+  };
+  for (size_t r = 0; r < size;) {
+    const char *nl = (const char *)memchr(t.data() + r, '\n', size - r);
+    const size_t end = nl ? (size_t)(nl - t.data()) : size;
+    if (t[r] == '>') {
+      close_record();
+      size_t b = r + 1, e;
+      while (b < end && isspace((unsigned char)t[b])) b++;
+      e = b;
+      while (e < end && !isspace((unsigned char)t[e])) e++;
+      name = t.substr(b, e - b);
+      if (fa.where.count(name)) {
+        err = "FASTA record '" + name + "' occurs twice in " + path;
+        return false;
+      }
+      have = true;
+      begin = w;
+    } else if (have) {
+      size_t e = end;
+      while (e > r && isspace((unsigned char)t[e - 1])) e--;
+      bool blanks = false;
+      for (const char c : {' ', '\t', '\r', '\v', '\f'}) blanks = blanks || memchr(t.data() + r, c, e - r) != nullptr;
+      if (!blanks) {
+        memmove(&t[w], &t[r], e - r);
+        w += e - r;
+      } else {
+        for (size_t i = r; i < e; i++)
+          if (!isspace((unsigned char)t[i])) t[w++] = t[i];
+      }
+    }
+    r = end + 1;
+  }
+  close_record();
+  t.resize(w);
+  return true;
+}
+
+struct sq_list {
+  std::vector<std::string> names;
+  std::vector<uint64_t> lengths;
+};
+/* the @SQ lines of a SAM header text */
+inline void read_sq(const std::string &head, sq_list &sq) {
+  size_t at = 0;
+  while (at < head.size()) {
+    size_t e = head.find('\n', at);
+    if (e == std::string::npos) e = head.size();
+    if (head.compare(at, 4, "@SQ\t") == 0) {
+      std::string sn;
+      uint64_t ln = 0;
+      size_t f = at;
+      while (f < e) {
+        size_t t = head.find('\t', f);
+        if (t == std::string::npos || t > e) t = e;
+        size_t fe = t;
+        while (fe > f && head[fe - 1] == '\r') fe--;
+        if (head.compare(f, 3, "SN:") == 0) sn = head.substr(f + 3, fe - f - 3);
+        if (head.compare(f, 3, "LN:") == 0) ln = strtoull(head.c_str() + f + 3, nullptr, 10);
+        f = t + 1;
+      }
+      sq.names.push_back(sn);
+      sq.lengths.push_back(ln);
+    }
+    at = e + 1;
+  }
+}
+
+/* the inflated bytes of a BGZF file (a series of gzip members), pulled in pieces */
+struct bgzf_reader {
+  std::ifstream in;
+  z_stream zs;
+  std::vector<unsigned char> ibuf;
+  bool open_ok = false, eof = false, bad = false;
+  explicit bgzf_reader(const std::string &path) : in(path, std::ios::binary), ibuf(1 << 20) {
+    memset(&zs, 0, sizeof zs);
+    open_ok = (bool)in && inflateInit2(&zs, 15 + 32) == Z_OK;
+  }
+  ~bgzf_reader() {
+    if (open_ok) inflateEnd(&zs);
+  }
+  /* n bytes, or false at the end of the data (*got: what there was) */
+  bool read(void *dst, size_t n, size_t *got = nullptr) {
+    zs.next_out = (Bytef *)dst;
+    zs.avail_out = (uInt)n;
+    while (zs.avail_out && !bad) {
+      if (zs.avail_in == 0) {
+        if (eof) break;
+        in.read((char *)ibuf.data(), (std::streamsize)ibuf.size());
+        zs.next_in = ibuf.data();
+        zs.avail_in = (uInt)in.gcount();
+        if (zs.avail_in == 0) {
+          eof = true;
+          break;
+        }
+      }
+      const int rc = inflate(&zs, Z_NO_FLUSH);
+      if (rc == Z_STREAM_END)
+        inflateReset(&zs); /* the next member */
+      else if (rc != Z_OK && rc != Z_BUF_ERROR)
+        bad = true;
+    }
+    if (got) *got = n - zs.avail_out;
+    return zs.avail_out == 0 && !bad;
+  }
+};
+
+/* does the file end with the empty BGZF block that marks its end (SAMv1 section 4.1.2)? */
+inline bool ends_with_bgzf_eof(const std::string &path) {
+  static const unsigned char eof_block[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43,
+                                              0x02, 0,    0x1b, 0,    3, 0, 0, 0, 0, 0,    0,    0, 0,    0};
+  std::ifstream in(path, std::ios::binary | std::ios::ate);
+  if (!in || in.tellg() < 28) return false;
+  unsigned char tail[28];
+  in.seekg(-28, std::ios::end);
+  in.read((char *)tail, 28);
+  return (bool)in && !memcmp(tail, eof_block, 28);
+}
+
+struct record_batch {
+  std::string ids, seqs, hex;
+  std::vector<uint64_t> id_off{0}, seq_off{0}, hex_off{0};
+  std::vector<uint8_t> reverse;
+  std::vector<int32_t> chr;
+  std::vector<int64_t> pos0;
+  void clear() {
+    ids.clear(), seqs.clear(), hex.clear();
+    id_off.assign(1, 0), seq_off.assign(1, 0), hex_off.assign(1, 0);
+    reverse.clear(), chr.clear(), pos0.clear();
+  }
+  size_t size() const { return chr.size(); }
+};
+
+inline double now_s() {
+  timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
+struct job {
+  double t_decode = 0, t_write = 0; /* seconds in the library's calls, in the output's writes */
+  gs_decoder *dec = nullptr;
+  uint32_t flags = 0;
+  uint64_t done = 0; /* records decoded so far */
+  FILE *out = nullptr;
+  std::string err;
+  bool write(const char *p, size_t n) {
+    const double t0 = now_s();
+    const bool ok = !n || fwrite(p, 1, n, out) == n;
+    t_write += now_s() - t0;
+    if (!ok) err = "cannot write the output";
+    return ok;
+  }
+  /* the header line is the library's (gs_decode_sam of no lines): the command keeps no copy of it */
+  bool write_header() {
+    char *text = nullptr;
+    uint64_t len = 0;
+    const gs_status rc = gs_decode_sam(dec, "", 0, flags, 0, &text, &len, nullptr);
+    if (rc != GS_OK) {
+      err = gs_status_string(rc);
+      return false;
+    }
+    const bool ok = write(text, len);
+    gs_free(text);
+    return ok;
+  }
+  bool flush_sam(std::string &lines) {
+    if (lines.empty()) return true;
+    char *text = nullptr;
+    uint64_t len = 0, n = 0;
+    const double t0 = now_s();
+    const gs_status rc = gs_decode_sam(dec, lines.data(), lines.size(), flags | GS_DECODE_NO_HEADER, done, &text, &len, &n);
+    t_decode += now_s() - t0;
+    if (rc != GS_OK) {
+      err = gs_status_string(rc);
+      return false;
+    }
+    const bool ok = write(text, len);
+    gs_free(text);
+    done += n;
+    lines.clear();
+    return ok;
+  }
+  bool flush_records(record_batch &b) {
+    if (!b.size()) return true;
+    gs_decode_batch gb;
+    memset(&gb, 0, sizeof gb);
+    gb.n = b.size();
+    gb.ids = b.ids.data();
+    gb.id_off = b.id_off.data();
+    gb.seqs = b.seqs.data();
+    gb.seq_off = b.seq_off.data();
+    gb.reverse = b.reverse.data();
+    gb.chr = b.chr.data();
+    gb.pos0 = b.pos0.data();
+    gb.hex = b.hex.data();
+    gb.hex_off = b.hex_off.data();
+    char *text = nullptr;
+    uint64_t len = 0;
+    const double t0 = now_s();
+    const gs_status rc = gs_decode_records(dec, &gb, flags, done, &text, &len, nullptr);
+    t_decode += now_s() - t0;
+    if (rc != GS_OK) {
+      err = gs_status_string(rc);
+      return false;
+    }
+    const bool ok = write(text, len);
+    gs_free(text);
+    done += b.size();
+    b.clear();
+    return ok;
+  }
+};
+
+inline bool open_decoder(job &j, int device, const sq_list &sq, const fasta_records &fa) {
+  std::vector<const char *> names;
+  std::vector<uint64_t> off, len;
+  for (const std::string &n : sq.names) {
+    names.push_back(n.c_str());
+    auto it = fa.where.find(n);
+    off.push_back(it == fa.where.end() ? 0 : it->second.first);
+    len.push_back(it == fa.where.end() ? ~0ull : it->second.second); /* fails only when an off-target lies on it */
+  }
+  gs_genome_structure gs;
+  gs.chr_names = names.data();
+  gs.chr_lengths = sq.lengths.data();
+  gs.n_chr = (uint32_t)names.size();
+  const gs_status rc = gs_decoder_open(device, (const uint8_t *)fa.text.data(), fa.text.size(), &gs, off.data(), len.data(), &j.dec);
+  if (rc != GS_OK) {
+    j.err = gs_status_string(rc);
+    return false;
+  }
+  return j.write_header();
+}
+
+inline bool decode_sam_file(job &j, const std::string &path, int device, const fasta_records &fa, uint64_t batch_records, size_t batch_bytes) {
+  std::ifstream in(path, std::ios::binary);
+  if (!in) {
+    j.err = "cannot read " + path;
+    return false;
+  }
+  std::string line, head, lines;
+  uint64_t n_lines = 0;
+  bool opened = false;
+  auto ensure_open = [&]() {
+    if (opened) return true;
+    sq_list sq;
+    read_sq(head, sq);
+    opened = open_decoder(j, device, sq, fa);
+    return opened;
+  };
+  while (std::getline(in, line)) {
+    if (!opened && !line.empty() && line[0] == '@') {
+      head += line;
+      head += '\n';
+      continue;
+    }
+    if (line.empty() || line[0] == '@') continue;
+    if (!ensure_open()) return false;
+    lines += line;
+    lines += '\n';
+    if (++n_lines >= batch_records || lines.size() >= batch_bytes) {
+      if (!j.flush_sam(lines)) return false;
+      n_lines = 0;
+    }
+  }
+  if (!ensure_open()) return false;
+  return j.flush_sam(lines);
+}
+
+inline bool decode_bam_file(job &j, const std::string &path, int device, const fasta_records &fa, uint64_t batch_records, size_t batch_bytes) {
+  bgzf_reader rd(path);
+  if (!rd.open_ok) {
+    j.err = "cannot read " + path;
+    return false;
+  }
+  auto malformed = [&](const char *what) {
+    j.err = "malformed BAM file " + path + ": " + what;
+    return false;
+  };
+  char magic[4];
+  int32_t l_text = 0, n_ref = 0;
+  if (!rd.read(magic, 4) || memcmp(magic, "BAM\1", 4) || !rd.read(&l_text, 4) || l_text < 0) return malformed("no BAM header");
+  std::string head((size_t)l_text, '\0');
+  if (l_text && !rd.read(&head[0], (size_t)l_text)) return malformed("the header text is cut");
+  head.resize(strlen(head.c_str()));
+  if (!rd.read(&n_ref, 4) || n_ref < 0) return malformed("no reference list");
+  sq_list refs, sq;
+  for (int32_t i = 0; i < n_ref; i++) {
+    int32_t l_name = 0, l_ref = 0;
+    if (!rd.read(&l_name, 4) || l_name < 1) return malformed("a reference name");
+    std::string name((size_t)l_name, '\0');
+    if (!rd.read(&name[0], (size_t)l_name) || !rd.read(&l_ref, 4)) return malformed("a reference");
+    name.resize(strlen(name.c_str()));
+    refs.names.push_back(name);
+    refs.lengths.push_back((uint64_t)(uint32_t)l_ref);
+  }
+  read_sq(head, sq);
+  /* refID indexes the binary list; the decoder's chromosomes are the @SQ lines when the text header has them */
+  const bool from_text = !sq.names.empty();
+  std::vector<int32_t> ref_to_sq((size_t)n_ref, -2);
+  if (from_text) {
+    std::map<std::string, int32_t> first;
+    for (size_t c = 0; c < sq.names.size(); c++) first.emplace(sq.names[c], (int32_t)c);
+    for (int32_t i = 0; i < n_ref; i++) {
+      auto it = first.find(refs.names[(size_t)i]);
+      if (it != first.end()) ref_to_sq[(size_t)i] = it->second;
+    }
+  } else {
+    for (int32_t i = 0; i < n_ref; i++) ref_to_sq[(size_t)i] = i;
+  }
+  if (!open_decoder(j, device, from_text ? sq : refs, fa)) return false;
+  record_batch b;
+  std::vector<unsigned char> rec;
+  static const char nt16[] = "=ACMGRSVTWYHKDBN";
+  for (;;) {
+    int32_t block = 0;
+    size_t got = 0;
+    if (!rd.read(&block, 4, &got)) {
+      if (got == 0 && !rd.bad) break;
+      return malformed("a record's size");
+    }
+    if (block < 32) return malformed("a record shorter than its fixed part");
+    rec.resize((size_t)block);
+    if (!rd.read(rec.data(), rec.size())) return malformed("a record is cut");
+    int32_t ref_id, pos, l_seq;
+    uint16_t n_cigar, flag;
+    memcpy(&ref_id, &rec[0], 4);
+    memcpy(&pos, &rec[4], 4);
+    const uint32_t l_name = rec[8];
+    memcpy(&n_cigar, &rec[12], 2);
+    memcpy(&flag, &rec[14], 2);
+    memcpy(&l_seq, &rec[16], 4);
+    size_t p = 32;
+    if (l_name < 1 || l_seq < 0 || p + l_name + 4ull * n_cigar + ((size_t)l_seq + 1) / 2 + (size_t)l_seq > rec.size())
+      return malformed("a record's fields outrun it");
+    if (ref_id >= n_ref) return malformed("a record's reference is beyond the list");
+    b.ids.append((const char *)&rec[p], l_name - 1);
+    b.id_off.push_back(b.ids.size());
+    p += l_name + 4ull * n_cigar;
+    for (int32_t i = 0; i < l_seq; i++) b.seqs.push_back(nt16[(rec[p + (size_t)(i >> 1)] >> ((i & 1) ? 0 : 4)) & 15]);
+    b.seq_off.push_back(b.seqs.size());
+    p += ((size_t)l_seq + 1) / 2 + (size_t)l_seq;
+    b.reverse.push_back((flag & 16) ? 1 : 0);
+    b.chr.push_back(ref_id < 0 || ref_to_sq[(size_t)ref_id] < 0 ? -1 : ref_to_sq[(size_t)ref_id]); /* no @SQ line: unmapped */
+    b.pos0.push_back(pos);
+    size_t hb = 0, hl = 0;
+    while (p + 3 <= rec.size()) { /* the tags: the last of:H: */
+      const unsigned char t0 = rec[p], t1 = rec[p + 1], ty = rec[p + 2];
+      p += 3;
+      size_t sz = 0;
+      if (ty == 'Z' || ty == 'H') {
+        const void *z = memchr(&rec[p], 0, rec.size() - p);
+        if (!z) return malformed("a text tag without its end");
+        sz = (size_t)((const unsigned char *)z - &rec[p]);
+        if (t0 == 'o' && t1 == 'f' && ty == 'H') hb = p, hl = sz;
+        sz += 1;
+      } else if (ty == 'B') {
+        if (p + 5 > rec.size()) return malformed("an array tag");
+        const unsigned char sub = rec[p];
+        int32_t cnt;
+        memcpy(&cnt, &rec[p + 1], 4);
+        const size_t w = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+        sz = 5 + w * (size_t)(cnt < 0 ? 0 : cnt);
+      } else {
+        sz = (ty == 'A' || ty == 'c' || ty == 'C') ? 1 : (ty == 's' || ty == 'S') ? 2 : (ty == 'i' || ty == 'I' || ty == 'f') ? 4 : 0;
+        if (!sz) return malformed("a tag of unknown type");
+      }
+      if (p + sz > rec.size()) return malformed("a tag outruns its record");
+      p += sz;
+    }
+    b.hex.append((const char *)&rec[hb], hl);
+    b.hex_off.push_back(b.hex.size());
+    if (b.size() >= batch_records || b.hex.size() >= batch_bytes)
+      if (!j.flush_records(b)) return false;
+  }
+  if (rd.bad) return malformed("a BGZF block does not inflate");
+  if (!ends_with_bgzf_eof(path)) /* the records ended on a block boundary: nothing shows whether more were written (htslib warns too) */
+    std::cerr << "warning: " << path << " has no BGZF end-of-file block and may be cut short\n";
+  return j.flush_records(b);
+}
+
+/* -> exit status; 2 = usage */
+inline int run(int argc, char **argv) {
+  std::string mode = "succinct", output, database, fasta;
+  int device = 0;
+  bool verbose = false;
+  long long batch_records = 1 << 20;
+  std::vector<std::string> positional;
+  for (int i = 0; i < argc; i++) {
+    const std::string a = argv[i];
+    char *end = nullptr;
+    if (a == "--mode" && i + 1 < argc) {
+      mode = argv[++i];
+    } else if (a == "--device" && i + 1 < argc) {
+      device = (int)strtol(argv[++i], &end, 10);
+      if (*end || end == argv[i]) return 2;
+    } else if (a == "--batch-size" && i + 1 < argc) {
+      batch_records = strtoll(argv[++i], &end, 10);
+      if (*end || end == argv[i] || batch_records < 1) return 2;
+    } else if (a == "--verbose") {
+      verbose = true;
+    } else if (a == "-o" && i + 1 < argc) {
+      output = argv[++i];
+    } else if (!a.empty() && a[0] != '-') {
+      positional.push_back(a);
+    } else {
+      return 2;
+    }
+  }
+  if (positional.size() != 2 || (mode != "succinct" && mode != "complete")) return 2;
+  database = positional[0];
+  fasta = positional[1];
+  job j;
+  j.flags = mode == "complete" ? GS_TEXT_COMPLETE : 0u;
+  unsigned char magic[2] = {0, 0};
+  {
+    std::ifstream in(database, std::ios::binary);
+    if (!in) {
+      std::cerr << "error: cannot read " << database << "\n";
+      return 1;
+    }
+    in.read((char *)magic, 2);
+  }
+  const double t_start = now_s();
+  fasta_records fa;
+  if (!read_fasta(fasta, fa, j.err)) {
+    std::cerr << "error: " << j.err << "\n";
+    return 1;
+  }
+  const double t_fasta = now_s() - t_start;
+  j.out = output.empty() ? stdout : fopen(output.c_str(), "wb");
+  if (!j.out) {
+    std::cerr << "error: cannot write " << output << "\n";
+    return 1;
+  }
+  const size_t batch_bytes = (size_t)256 << 20;
+  bool ok = (magic[0] == 0x1f && magic[1] == 0x8b) ? decode_bam_file(j, database, device, fa, (uint64_t)batch_records, batch_bytes)
+                                                   : decode_sam_file(j, database, device, fa, (uint64_t)batch_records, batch_bytes);
+  if (j.dec) gs_decoder_close(j.dec);
+  if (ok && fflush(j.out) != 0) {
+    ok = false;
+    j.err = "cannot write the output";
+  }
+  if (!output.empty()) fclose(j.out);
+  if (!ok) {
+    std::cerr << "error: " << j.err << "\n";
+    if (!output.empty()) remove(output.c_str());
+    return 1;
+  }
+  if (verbose) { /* stderr: stdout may be the table */
+    const double all = now_s() - t_start;
+    fprintf(stderr, "Decoded %llu records in %.3f s: FASTA read %.3f s, library calls (decoder's batches, text back) %.3f s, output writes %.3f s, "
+                    "database read and decoder set-up %.3f s\n",
+            (unsigned long long)j.done, all, t_fasta, j.t_decode, j.t_write, all - t_fasta - j.t_decode - j.t_write);
+  }
+  return 0;
+}
+
+}  // namespace decode_cmd
+
+#endif

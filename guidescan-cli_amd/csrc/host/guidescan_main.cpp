@@ -27,6 +27,10 @@
  *       from a shared queue, output written in input order (src/guidescan.cxx:226-251 is the
  *       reference's fan-out over threads).  On every device the search of batch i+1 overlaps the text
  *       formatting of batch i.
+ *   guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] DATABASE GENOME.fa
+ *       the CSV scripts/decode_database.py prints for a SAM/BAM database, decoded on the device (decode_cmd.hpp);
+ *       stdout unless -o.  SEQ of at most 32 symbols.  The table streams, so only -o is all or nothing: stdout has
+ *       the header and the earlier batches' rows when a later record fails.
  */
 #include <chrono>
 #include <cstdio>
@@ -49,6 +53,7 @@
 
 #include "guidescan_amd.h"
 #include "bam_writer.hpp"
+#include "decode_cmd.hpp"
 
 namespace {
 
@@ -260,7 +265,12 @@ int usage() {
                "                 [--rna-bulges N] [--dna-bulges N] [-t THRESHOLD] [-n FORMAT_THREADS]\n"
                "                 [--device D] [--gpus N] [--batch-size B] [--encoder host|gpu]\n"
                "                 with --all-candidates: [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S]\n"
-               "                 [--chromosomes a,b,...]\n";
+               "                 [--chromosomes a,b,...]\n"
+               "       guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--verbose]\n"
+               "                 DATABASE GENOME.fa\n"
+               "                 a stored guide (SEQ) may have at most 32 symbols.  The table streams: without -o the header\n"
+               "                 and the rows of earlier batches are on stdout already when a later record fails (exit\n"
+               "                 status 1); with -o a failure leaves no file.\n";
   return 2;
 }
 
@@ -1298,5 +1308,9 @@ int main(int argc, char **argv) {
   if (!strcmp(argv[1], "index")) return do_index(argc - 2, argv + 2);
   if (!strcmp(argv[1], "kmers")) return do_kmers(argc - 2, argv + 2);
   if (!strcmp(argv[1], "enumerate")) return do_enumerate(argc - 2, argv + 2);
+  if (!strcmp(argv[1], "decode")) {
+    const int rc = decode_cmd::run(argc - 2, argv + 2);
+    return rc == 2 ? usage() : rc;
+  }
   return usage();
 }

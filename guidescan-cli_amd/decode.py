@@ -1,0 +1,311 @@
+"""Off-target databases back to readable CSV: what the reference's scripts/decode_database.py prints for a SAM/BAM
+database and the genome's FASTA (manual section "Off-Target Databases"), restated in plain Python/numpy.
+
+This module is the model the device decoder (csrc/gs_decode.hip) is tested against, and the `device=None` path of
+decode_database().  Rules, with the script's lines:
+
+  records   one output unit per SAM record; sgrna = SEQ as stored, reverse-complemented under FLAG 16 (:117-119);
+            revcom maps A,C,G,T,U,N and leaves every other symbol alone (:93-97)
+  of:H:     16 hex digits per little-endian int64 (:26-27); delim = -(sum LN + 1) (:17-21); for every delim at index e
+            with the delim before it at s (or -1): positions words[s+1 : e-1], distance words[e-1] (:29-36); a list that
+            BEGINS with a delim makes the script slice words[0:-1] and fail on the delim itself, so such a list of two
+            words or more is an error here and a list of that one word is empty
+  place     strand '+' iff word > 0; x = |word| walked down the @SQ lengths (:38-50); printed 0-based, unshifted
+  sequence  the chromosome's own FASTA record, Python slice [x+1-n, x+1) for '+', [x, x+n) for '-', upper-cased, and
+            reverse-complemented for '-' (:52-59, :124, :135)
+  cfd       only for slices of 23 symbols (:123-127): product over i < 20 of mm[r sg[i] : d comp(seq[i]), i+1] where the
+            symbols differ after T->U, a missing key skipped (:67-83), times pam[seq[21:23]]; 0.0 prints empty (:153)
+  succinct  counters for distances 0..3, the CFDs' left fold when every off-target has one, minus the first distance-0
+            off-target's; specificity 1/(1+sum) unless the sum is absent or 0.0 (:156-187)
+Where the script would raise, DecodeError names the record and the reason; no partial output is produced.  One limit
+is this project's own: a record whose stored SEQ has more than 32 symbols is refused (ERR_LONG), with or without
+off-targets, because the device decoder refuses it - the script has no such limit.
+"""
+from __future__ import annotations
+
+import bisect
+import gzip
+import json
+import struct
+from pathlib import Path
+
+import numpy as np
+
+SUCCINCT_HEADER = ("id,sequence,chromosome,position,sense,distance_0_matches,distance_1_matches,"
+                   "distance_2_matches,distance_3_matches,specificity")
+COMPLETE_HEADER = "id,match_number,sequence,chromosome,position,sense,distance,cfd"
+
+REASONS = {1: "hex digits that are no multiple of 16, or a symbol that is no hex digit",
+           2: "an off-target word beyond the genome (|word| >= sum of @SQ LN), or a list that begins with the delimiter",
+           3: "a PAM pair outside A,C,G,T in a 23-symbol off-target",
+           4: "a distance outside 0..3 in succinct mode",
+           5: "an off-target on a chromosome that the FASTA does not hold",
+           6: "a stored sequence longer than 32 symbols",
+           7: "a line or field that is no SAM record"}
+ERR_HEX, ERR_WORD, ERR_PAM, ERR_DISTANCE, ERR_CHROMOSOME, ERR_LONG, ERR_RECORD = 1, 2, 3, 4, 5, 6, 7
+MAX_SEQ = 32   # the device gathers an off-target into 32 symbols (DC_MAX_SEQ); a longer stored SEQ is refused here too
+
+
+class DecodeError(ValueError):
+    def __init__(self, record, reason):
+        super().__init__(f"record {record}: {REASONS[reason]}")
+        self.record = record
+        self.reason = reason
+
+
+_COMP = {"A": "T", "C": "G", "G": "C", "T": "A", "U": "A", "N": "N"}
+
+
+def revcom(s: str) -> str:
+    return "".join(_COMP.get(c, c) for c in reversed(s))
+
+
+def cfd_tables(path=None):
+    """-> (mm {key: float}, pam {pair: float}): the 240 + 16 values of the reference's score tables, keyed as it keys
+    them.  From a JSON file of them (tests/golden/decode/cfd_tables.json), or - path=None - the library's own copy."""
+    if path is None:
+        from importlib import import_module
+        return import_module("guidescan-cli_amd.api").decode_tables()
+    d = json.loads(Path(path).read_text())
+    return d["mm"], d["pam"]
+
+
+def parse_fasta_records(path) -> dict:
+    """name (first word of the title) -> the record's symbols as they stand, blanks removed"""
+    recs, name, parts = {}, None, []
+    with open(path, "rb") as f:
+        for raw in f:
+            line = raw.decode("latin-1")
+            if line.startswith(">"):
+                if name is not None:
+                    recs[name] = "".join(parts)
+                words = line[1:].split()
+                name, parts = (words[0] if words else ""), []
+                if name in recs:
+                    raise ValueError(f"FASTA record '{name}' occurs twice")
+            elif name is not None:
+                parts.append("".join(line.split()))
+    if name is not None:
+        recs[name] = "".join(parts)
+    return recs
+
+
+class Record:
+    __slots__ = ("id", "seq", "reverse", "rname", "pos0", "hex")
+
+    def __init__(self, id, seq, reverse, rname, pos0, hex):
+        self.id, self.seq, self.reverse, self.rname, self.pos0, self.hex = id, seq, reverse, rname, pos0, hex
+
+
+def parse_sam(text: str):
+    """-> (sq [(name, LN)], [Record]); hex is None without an of:H: field"""
+    sq, recs = [], []
+    for i, line in enumerate(text.split("\n")):
+        if line.endswith("\r"):
+            line = line[:-1]
+        if not line:
+            continue
+        if line.startswith("@"):
+            f = line.split("\t")
+            if f[0] == "@SQ":
+                tags = dict(x.split(":", 1) for x in f[1:] if ":" in x)
+                sq.append((tags["SN"], int(tags["LN"])))
+            continue
+        f = line.split("\t")
+        if len(f) < 11:
+            raise DecodeError(len(recs), ERR_RECORD)
+        try:
+            flag, pos = int(f[1]), int(f[3])
+        except ValueError:
+            raise DecodeError(len(recs), ERR_RECORD) from None
+        hexs = None
+        for t in f[11:]:
+            if t.startswith("of:H:"):
+                hexs = t[5:]
+        # an RNAME that no @SQ line names is unmapped, like '*' (htslib), and prints as pysam's None
+        rname = f[2] if any(f[2] == n for n, _ in sq) else None
+        recs.append(Record(f[0], f[9], bool(flag & 16), rname, pos - 1, hexs))
+    return sq, recs
+
+
+def read_bam(path):
+    """-> (sq, [Record]) of a BAM file (SAMv1 section 4): BGZF is a series of gzip members"""
+    with gzip.open(path, "rb") as f:
+        data = f.read()
+    if data[:4] != b"BAM\1":
+        raise ValueError("not a BAM file")
+    (l_text,) = struct.unpack_from("<i", data, 4)
+    header = data[8:8 + l_text].split(b"\0")[0].decode()
+    at = 8 + l_text
+    (n_ref,) = struct.unpack_from("<i", data, at)
+    at += 4
+    refs = []
+    for _ in range(n_ref):
+        (l_name,) = struct.unpack_from("<i", data, at)
+        name = data[at + 4:at + 4 + l_name - 1].decode()
+        (l_ref,) = struct.unpack_from("<i", data, at + 4 + l_name)
+        refs.append((name, l_ref))
+        at += 8 + l_name
+    sq, _ = parse_sam(header)
+    if not sq:
+        sq = refs
+    named = {n for n, _ in sq}   # refID counts the binary list; a reference that no @SQ line names is unmapped, as in SAM
+    recs = []
+    while at < len(data):
+        (block,) = struct.unpack_from("<i", data, at)
+        b = data[at + 4:at + 4 + block]
+        at += 4 + block
+        ref_id, pos, l_read_name, _mapq, _bin, n_cigar, flag, l_seq = struct.unpack_from("<iiBBHHHi", b, 0)
+        p = 32
+        name = b[p:p + l_read_name - 1].decode()
+        p += l_read_name + 4 * n_cigar
+        packed = b[p:p + (l_seq + 1) // 2]
+        seq = "".join("=ACMGRSVTWYHKDBN"[(packed[i >> 1] >> (0 if i & 1 else 4)) & 15] for i in range(l_seq))
+        p += (l_seq + 1) // 2 + l_seq
+        hexs = None
+        while p < len(b):
+            tag, typ = b[p:p + 2], chr(b[p + 2])
+            p += 3
+            if typ in "HZ":
+                e = b.index(b"\0", p)
+                if tag == b"of" and typ == "H":
+                    hexs = b[p:e].decode()
+                p = e + 1
+            elif typ == "B":
+                sub, cnt = chr(b[p]), struct.unpack_from("<i", b, p + 1)[0]
+                p += 5 + cnt * {"c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4}[sub]
+            else:
+                p += {"A": 1, "c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4}[typ]
+        recs.append(Record(name, seq, bool(flag & 16), refs[ref_id][0] if ref_id >= 0 and refs[ref_id][0] in named else None, pos,
+                           hexs))
+    return sq, recs
+
+
+def off_target_words(hexs, delim, record):
+    """-> [(distance, word)] in list order"""
+    if hexs is None:
+        return []
+    if len(hexs) % 16 or any(c not in "0123456789abcdefABCDEF" for c in hexs):
+        raise DecodeError(record, ERR_HEX)
+    words = np.frombuffer(bytes.fromhex(hexs), dtype="<i8")
+    where = np.flatnonzero(words == delim)
+    if len(where) and where[0] == 0 and len(words) > 1:
+        raise DecodeError(record, ERR_WORD)
+    out, start = [], -1
+    for end in where:
+        if end - 1 > start:
+            d = int(words[end - 1])
+            out.extend((d, int(w)) for w in words[start + 1:end - 1])
+        start = end
+    return out
+
+
+class Decoder:
+    """the model: Decoder(sq, fasta_records).rows(records, complete) -> [str]"""
+
+    def __init__(self, sq, fasta, tables=None):
+        self.sq = list(sq)
+        self.total = sum(ln for _, ln in self.sq)
+        self.delim = -(self.total + 1)
+        self.cum = [0]
+        for _, ln in self.sq:
+            self.cum.append(self.cum[-1] + ln)
+        self.fasta = fasta
+        self.mm, self.pam = tables or cfd_tables()
+
+    def place(self, word, record):
+        x = abs(word)
+        if x >= self.total:
+            raise DecodeError(record, ERR_WORD)
+        c = bisect.bisect_right(self.cum, x) - 1
+        return c, x - self.cum[c], "+" if word > 0 else "-"
+
+    def cfd(self, sg, seq, record):
+        score = 1
+        for i in range(20):
+            a, b = sg[i].replace("T", "U"), seq[i].replace("T", "U")
+            if a != b:
+                key = "r" + a + ":d" + revcom(b) + "," + str(i + 1)
+                if key in self.mm:
+                    score *= self.mm[key]
+        if seq[21:23] not in self.pam:
+            raise DecodeError(record, ERR_PAM)
+        return score * self.pam[seq[21:23]]
+
+    def off_targets(self, rec, record):
+        """-> [(distance, chromosome name, x, strand, printed sequence, cfd or None)]"""
+        sg = revcom(rec.seq) if rec.reverse else rec.seq
+        n, out = len(sg), []
+        for d, w in off_target_words(rec.hex, self.delim, record):
+            c, x, strand = self.place(w, record)
+            name = self.sq[c][0]
+            if name not in self.fasta:
+                raise DecodeError(record, ERR_CHROMOSOME)
+            chrom = self.fasta[name]
+            s = chrom[x + 1 - n:x + 1] if strand == "+" else chrom[x:x + n]
+            s = s.upper()
+            if strand == "-":
+                s = revcom(s)
+            out.append((d, name, x, strand, s, self.cfd(sg, s, record) if len(s) == 23 else None))
+        return out
+
+    def rows(self, records, complete, first_record=0):
+        out = []
+        for k, rec in enumerate(records):
+            k += first_record
+            if len(rec.seq) > MAX_SEQ:
+                raise DecodeError(k, ERR_LONG)
+            ots = self.off_targets(rec, k)
+            if complete:
+                for i, (d, name, x, strand, s, cfd) in enumerate(ots):
+                    out.append(f"{rec.id},{i},{s},{name},{x},{strand},{d},{repr(cfd) if cfd else ''}")
+                continue
+            counts, total = [0, 0, 0, 0], None
+            if ots and all(o[5] is not None for o in ots):
+                total = 0
+                for o in ots:
+                    total = total + o[5]
+            seen = False
+            for d, _, _, _, _, cfd in ots:
+                if not 0 <= d <= 3:
+                    raise DecodeError(k, ERR_DISTANCE)
+                counts[d] += 1
+                if d == 0 and not seen and total is not None:
+                    total -= cfd
+                    seen = True
+            spec = repr(1 / (1 + total)) if total else ""
+            out.append(f"{rec.id},{rec.seq},{rec.rname},{rec.pos0},{'-' if rec.reverse else '+'},"
+                       f"{counts[0]},{counts[1]},{counts[2]},{counts[3]},{spec}")
+        return out
+
+
+def read_database(db_path):
+    """SAM text or BAM (gzip magic) -> (sq, records)"""
+    with open(db_path, "rb") as f:
+        magic = f.read(2)
+    if magic == b"\x1f\x8b":
+        return read_bam(db_path)
+    return parse_sam(Path(db_path).read_text(encoding="latin-1"))
+
+
+def decode_text(sq, records, fasta, mode="succinct", tables=None) -> str:
+    complete = mode == "complete"
+    rows = Decoder(sq, fasta, tables).rows(records, complete)
+    return "\n".join([COMPLETE_HEADER if complete else SUCCINCT_HEADER] + rows) + "\n"
+
+
+def decode_database(db_path, fasta_path, mode="succinct", device=None, tables=None) -> str:
+    """the text `decode_database.py DB FASTA --mode MODE` prints.  device=None: this module; an int: that GPU
+    (api.Decoder over gs_decode_records; the records are read here and handed over as arrays).  tables: cfd_tables()
+    of another source than the library's, for the model."""
+    if mode not in ("succinct", "complete"):
+        raise ValueError("mode is succinct or complete")
+    sq, records = read_database(db_path)
+    fasta = parse_fasta_records(fasta_path)
+    if device is None:
+        return decode_text(sq, records, fasta, mode, tables)
+    from importlib import import_module
+    api = import_module("guidescan-cli_amd.api")
+    with api.Decoder(sq, fasta, device=device) as dec:
+        body = dec.decode_records(records, complete=mode == "complete")
+    return (COMPLETE_HEADER if mode == "complete" else SUCCINCT_HEADER) + "\n" + body

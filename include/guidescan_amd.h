@@ -552,6 +552,59 @@ gs_status gs_kmers_csv(gs_kmers *km, const char *prefix, const char *chr_name, c
 gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, gs_kmers **out);
 void gs_kmers_free(gs_kmers *km);
 
+/* ---- SAM/BAM databases back to CSV on the device (scripts/decode_database.py) --------------------------------- */
+
+typedef struct gs_decoder gs_decoder;
+
+/* What the script loads once (load_guide_db, :142-146, and SeqIO.to_dict, :223): the @SQ names and LN in header order
+ * (sq), and the FASTA records' symbols back to back in `text` (any case; folded to upper case on upload, :59).
+ * Chromosome c of sq is the record text[chr_text_off[c], + chr_text_len[c]) - its own length, which may differ from
+ * LN; chr_text_len[c] = UINT64_MAX: the FASTA has no record of that name (an off-target on it fails, as fasta_dict[chr]
+ * does).  The text, the tables of the CFD (calc_cfd_e, :67-83) and of the double printer stay in HBM until
+ * gs_decoder_close.  No index is needed. */
+gs_status gs_decoder_open(int device, const uint8_t *text, uint64_t len, const gs_genome_structure *sq,
+                          const uint64_t *chr_text_off, const uint64_t *chr_text_len, gs_decoder **out);
+void gs_decoder_close(gs_decoder *dec);
+
+/* the fields the script reads of n records (pysam's query_name, query_sequence, is_reverse, reference_name,
+ * reference_start, get_tag('of')), each variable-length one as bytes back to back with n + 1 offsets */
+typedef struct {
+  uint64_t n;
+  const char *ids;
+  const uint64_t *id_off;
+  const char *seqs; /* SEQ as stored, at most 32 symbols each */
+  const uint64_t *seq_off;
+  const uint8_t *reverse; /* FLAG & 16 */
+  const int32_t *chr;     /* index into sq, -1: RNAME is '*' or a name that no @SQ line has (printed as None) */
+  const int64_t *pos0;    /* POS - 1 */
+  const char *hex;        /* the of:H: digits; an empty span: no field */
+  const uint64_t *hex_off;
+} gs_decode_batch;
+
+#define GS_DECODE_NO_HEADER 0x400u /* gs_decode_sam: rows only */
+
+/* The rows the script prints for these records, no header line: output_succinct (:156-187; flags 0) or output_complete
+ * (:148-154; GS_TEXT_COMPLETE) over decode_off_targets (:106-140), byte for byte, floats as Python's repr.  *n_rows
+ * (may be NULL): rows written.  Where the script would raise - hex digits that are no multiple of 16 or no hex digits,
+ * |word| >= sum of LN, a PAM pair outside the 16 keys, in succinct mode a distance outside 0..3 (negative ones too),
+ * a chromosome the FASTA lacks - GS_ERR_FORMAT, no text, and gs_status_string(GS_ERR_FORMAT) names record `first_record` + its index
+ * in the batch, its id and the reason; the first such record of the batch.  The result does not depend on how the
+ * records are cut into batches.  *text is malloc'ed (NUL terminated, *len bytes before the terminator): gs_free. */
+gs_status gs_decode_records(gs_decoder *dec, const gs_decode_batch *batch, uint32_t flags, uint64_t first_record, char **text,
+                            uint64_t *len, uint64_t *n_rows);
+/* the same with the text left in HBM: *d_text belongs to the decoder and is valid until its next call */
+gs_status gs_decode_records_device(gs_decoder *dec, const gs_decode_batch *batch, uint32_t flags, uint64_t first_record,
+                                   const void **d_text, uint64_t *len, uint64_t *n_rows);
+/* SAM text (whole lines; header lines are skipped: the @SQ lines went into gs_decoder_open) split into records on the
+ * host, then gs_decode_records; the script's header line first (:213-217) unless GS_DECODE_NO_HEADER.  A line with
+ * fewer than eleven fields or a FLAG or POS that is no number: GS_ERR_FORMAT. */
+gs_status gs_decode_sam(gs_decoder *dec, const char *sam, uint64_t sam_len, uint32_t flags, uint64_t first_record, char **text,
+                        uint64_t *len, uint64_t *n_records);
+/* Host only: Python's repr() of n doubles, 32 bytes each, NUL padded - the routine the decoder's kernels print with. */
+gs_status gs_debug_repr_doubles(const double *v, uint64_t n, char *out);
+/* Host only: the CFD tables the decoder uploads: mm[(r * 4 + d) * 20 + i] for the key r{ACGU}:d{ACGT},i+1 (320), pam[16] */
+gs_status gs_debug_decode_tables(double *mm, double *pam);
+
 const char *gs_status_string(gs_status s);
 const char *gs_version(void);
 
