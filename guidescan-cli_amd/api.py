@@ -182,6 +182,8 @@ def lib():
     L.gs_enumerate_general_pams.restype = i32
     L.gs_enumerate_general_pams.argtypes = [vp, vp, u64, u32, vp, u32, C.c_char_p, vp, u32, u32, u32, u32, u32,
                                             C.POINTER(vp)]
+    L.gs_debug_general_last.restype = i32
+    L.gs_debug_general_last.argtypes = [vp, C.POINTER(u64)]
     L.gs_index_last_guide_flags.restype = i32
     L.gs_index_last_guide_flags.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.gs_format_guide_ex.restype = i32
@@ -250,7 +252,7 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_format_guide_ex", "gs_score_device", "gs_score", "gs_kmers_generate", "gs_kmers_get",
            "gs_kmers_free", "gs_format_guide_scored", "gs_index_verify_sa", "gs_index_last_counters", "gs_index_last_launch", "gs_enumerate_general",
            "gs_index_last_guide_flags", "gs_enumerate_general_pams", "gs_index_save_sa", "gs_index_open_sa", "gs_format_guides_scored", "gs_result_ex_raw_hits",
-           "gs_debug_seed_recipes", "gs_debug_choose_thresholds", "gs_debug_tile_plan", "gs_debug_search_form", "gs_debug_guide_descriptor", "gs_index_lock", "gs_index_unlock",
+           "gs_debug_seed_recipes", "gs_debug_choose_thresholds", "gs_debug_tile_plan", "gs_debug_search_form", "gs_debug_guide_descriptor", "gs_debug_general_last", "gs_index_lock", "gs_index_unlock",
            "gs_index_last_sharing", "gs_index_set_option", "gs_index_get_option", "gs_index_prepare",
            "gs_index_save_sdsl", "gs_debug_sdsl_sections", "gs_debug_sdsl_export_scratch",
            "gs_format_device", "gs_enumerate_text", "gs_index_last_text_offsets",
@@ -932,23 +934,33 @@ class GenomeIndex:
         return out
 
     def enumerate_general(self, seqs, pams, mismatches=3, rna_bulges=0, dna_bulges=0, alt_pams=(),
-                          start=False):
+                          start=False, force_pams=False, raw=False):
         """the general path (any symbol, any number of PAMs, bulges) -> (offsets uint64[n+1], hits HIT_EX_DTYPE[])"""
-        return self.enumerate_bulges(seqs, pams, mismatches, rna_bulges, dna_bulges, alt_pams, start)
+        return self.enumerate_bulges(seqs, pams, mismatches, rna_bulges, dna_bulges, alt_pams, start, force_pams, raw)
 
     def enumerate_bulges(self, seqs, pams, mismatches=3, rna_bulges=0, dna_bulges=0, alt_pams=(),
-                         start=False):
-        """bulge-aware search (index.hpp:250-375) -> (offsets uint64[n+1], hits HIT_EX_DTYPE[])"""
+                         start=False, force_pams=False, raw=False):
+        """bulge-aware search (index.hpp:250-375) -> (offsets uint64[n+1], hits HIT_EX_DTYPE[]).  Alt PAMs whose lengths
+        differ from one another or from the guides' PAM go through gs_enumerate_general_pams with a length per pattern;
+        force_pams=True takes that entry point for equal lengths too.  raw=True: a third value, uint32[n], the hits of
+        each guide before duplicate sequences are dropped (gs_result_ex_raw_hits)."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
         n, L = seqs.shape
         pams = np.ascontiguousarray(pams, dtype=np.uint8)
         P = pams.shape[1] if pams.ndim == 2 else 0
         pams = pams.reshape(n, P)
         alt = b"".join(p.encode() for p in alt_pams)
+        flags = GS_FLAG_PAM_AT_START if start else 0
         r = C.c_void_p()
-        _check(lib().gs_enumerate_bulges(self._h, seqs.ctypes.data, n, L, pams.ctypes.data if P else None, P,
-                                         alt if alt_pams else None, len(alt_pams), mismatches, rna_bulges,
-                                         dna_bulges, GS_FLAG_PAM_AT_START if start else 0, C.byref(r)))
+        if force_pams or any(len(p) != P for p in alt_pams):
+            lens = np.array([len(p) for p in alt_pams], dtype=np.uint32)
+            _check(lib().gs_enumerate_general_pams(self._h, seqs.ctypes.data, n, L, pams.ctypes.data if P else None, P,
+                                                   alt if alt_pams else None, lens.ctypes.data if alt_pams else None,
+                                                   len(alt_pams), mismatches, rna_bulges, dna_bulges, flags, C.byref(r)))
+        else:
+            _check(lib().gs_enumerate_bulges(self._h, seqs.ctypes.data, n, L, pams.ctypes.data if P else None, P,
+                                             alt if alt_pams else None, len(alt_pams), mismatches, rna_bulges,
+                                             dna_bulges, flags, C.byref(r)))
         try:
             ng, po, ph = C.c_uint64(), C.c_void_p(), C.c_void_p()
             _check(lib().gs_result_ex_get(r, C.byref(ng), C.byref(po), C.byref(ph)))
@@ -956,9 +968,21 @@ class GenomeIndex:
             nh = int(offsets[-1])
             hits = (np.frombuffer(C.string_at(ph, 48 * nh), dtype=HIT_EX_DTYPE).copy() if nh
                     else np.empty(0, dtype=HIT_EX_DTYPE))
+            if raw:
+                pr = C.c_void_p()
+                _check(lib().gs_result_ex_raw_hits(r, C.byref(pr)))
+                raw_hits = (np.frombuffer(C.string_at(pr, 4 * n), dtype=np.uint32).copy() if n
+                            else np.empty(0, dtype=np.uint32))
         finally:
             lib().gs_result_ex_free(r)
-        return offsets, hits
+        return (offsets, hits, raw_hits) if raw else (offsets, hits)
+
+    def general_last(self):
+        """the last general-path call on this handle (gs_debug_general_last): [items, workgroups, the first pass's pool,
+        match records T, search passes, largest stack of any item, steps the room rule cut, steps without room]"""
+        out = (C.c_uint64 * 8)()
+        _check(lib().gs_debug_general_last(self._h, out))
+        return [int(x) for x in out]
 
     def locked(self):
         """context manager: hold the handle across several device-pointer calls (gs_index_lock / gs_index_unlock);

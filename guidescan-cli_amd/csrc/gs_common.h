@@ -210,6 +210,9 @@ struct gs_index {
   /* the main pass's launch of the last batch (gs_index_last_launch): walking kernel, kernel without the strand tables' side,
    * deep tables, items per visit, ... of the two seeding launches (0: not that form), PAM-pair tables, |X|, rotated copies per strand table */
   unsigned long long last_launch[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  /* the last call of the general path (gs_debug_general_last): items, workgroups, the first pass's pool, records, search passes,
+   * then k_search_general's three counters of the last pass: largest stack, steps the room rule cut, steps with no room at all */
+  unsigned long long last_general[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   std::vector<gs_nrun> nruns_text; /* 'N' runs of the forward text */
   gs_buffer w_cand;                /* literal-N candidate windows (device): kept from batch to batch of one shape */
   uint64_t cand_key = ~0ull;       /* (L, P, bucketed or not) w_cand was made for; ~0: nothing kept */

@@ -76,13 +76,15 @@ struct gs_gsearch_args {
   unsigned long long *pool_next;
   unsigned long long pool_cap;
   uint32_t *counts;
-  uint32_t *work;   /* [0] work-queue head, [1] error flag (iteration bound hit) */
+  uint32_t *work;   /* [0] work-queue head, [1] error flag (iteration bound hit), [4..5] pool_next, [8] the largest stack of any
+                       item, [9] steps the room rule cut, [10] steps without room for one lane's children (gs_debug_general_last) */
   uint8_t alt[32][8]; /* alt PAM patterns in consumption order */
   uint8_t plen[40];   /* symbols of pattern j (alt PAMs, then the guides' own at n_alt): the reference searches
                          alt PAMs of any length next to the guides' PAM (process.hpp:51-56) */
   uint32_t p_max;     /* the longest of them */
   uint32_t n_items, L, P, m, n_alt, max_rna, max_dna;
   uint32_t max_iter; /* per-item iteration bound */
+  uint32_t stack_cap; /* GS_GENERAL_STACK: `limit` is at most this many nodes (it can only lower the stack's use) */
 };
 
 __device__ __forceinline__ void gseq_append(uint32_t (&s)[8], uint32_t slen, uint32_t byte) {
@@ -97,7 +99,8 @@ __global__ __launch_bounds__(WAVE) void k_search_general(gs_gsearch_args a) {
   const uint32_t L = a.L, P = a.P, m = a.m;
   const uint32_t npams = P ? a.n_alt + 1u : 1u;
   const uint32_t reserve = (GFAN - 1) * (L + a.p_max + a.max_dna + npams + 4u);
-  const uint32_t limit = GSTACK > reserve ? GSTACK - reserve : 1u;
+  const uint32_t limit_own = GSTACK > reserve ? GSTACK - reserve : 1u;
+  const uint32_t limit = limit_own < a.stack_cap ? limit_own : a.stack_cap;
   const uint32_t BASES[4] = {'A', 'C', 'G', 'T'};
   for (;;) {
     uint32_t item = 0;
@@ -164,13 +167,18 @@ __global__ __launch_bounds__(WAVE) void k_search_general(gs_gsearch_args a) {
      * instead of spinning.  The exit and the tail below are free of lane-conditional blocks
      * (compiler pitfall). */
     uint32_t guard = 0;
+    /* the item's counters (gs_debug_general_last) share one vector register - the kernel has no scalar register to
+     * spare -: lane 0 holds the stack's high-water mark, lane 1 the steps the room rule cut, lane 2 those with fit == 0 */
+    uint32_t tally = lane == 0u ? 1u : 0u;
     bool bail = false;
     while (size > 0 && !bail) {
       bail = ++guard > a.max_iter;
       uint32_t w = size < WAVE ? size : WAVE;
       const uint32_t room = size < limit ? limit - size : 0u;
       const uint32_t fit = room / (GFAN - 1);
+      const uint32_t w_all = w;
       if (w > fit) w = fit ? fit : 1u;
+      tally += lane == 1u ? (w < w_all ? 1u : 0u) : lane == 2u ? (fit == 0u ? 1u : 0u) : 0u;
       const bool active = lane < w;
       uint4 n0 = make_uint4(0, 0, 0, 0), n1 = n0, n2 = n0;
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -277,10 +285,16 @@ __global__ __launch_bounds__(WAVE) void k_search_general(gs_gsearch_args a) {
         gseq_append(s2, slen, '.');
         route(rna_ok, false, sp, ep, s2, gm_make(t + 1u, mm, dna, r_rna, 2u, 1u, slen + 1u, 0u, 0u, 0u));
       }
+      tally = lane == 0u && size > tally ? size : tally;
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     }
     a.counts[slot] = n_match; /* same address, same value from every lane */
     if (bail) atomicOr(&a.work[1], 1u);
+    /* the item's three counters: one lane's value counts, the other lanes bring the operation's identity - a select,
+     * not an `if (lane == ...)` block, which this tail must stay free of */
+    atomicMax(&a.work[8], lane == 0u ? tally : 0u);
+    atomicAdd(&a.work[9], lane == 1u ? tally : 0u);
+    atomicAdd(&a.work[10], lane == 2u ? tally : 0u);
   }
 }
 
@@ -385,7 +399,8 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
                                    gs_result_ex **out, const uint32_t *alt_lens = nullptr) {
   if (!ix || !out || (n && !guides) || (n && P && !guide_pams) || (n_alt && !alt_pams)) return GS_ERR_ARG;
   uint32_t p_max = P;
-  for (uint32_t j = 0; alt_lens && j < n_alt && j < 32; j++) {
+  /* (an empty guide PAM drops the alt PAMs, process.hpp:52-53: their lengths then bound nothing) */
+  for (uint32_t j = 0; alt_lens && P && j < n_alt && j < 32; j++) {
     if (alt_lens[j] < 1 || alt_lens[j] > 8) {
       gs_set_error("alt PAMs of 1 to 8 symbols");
       return GS_ERR_UNSUPPORTED;
@@ -415,6 +430,7 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
   res->offsets.assign(n + 1, 0);
   res->raw.assign(n, 0);
   if (n == 0) {
+    memset(ix->last_general, 0, sizeof(ix->last_general));
     guard.p = nullptr;
     *out = res;
     return GS_OK;
@@ -473,6 +489,8 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
   sa.max_rna = rna_bulges;
   sa.max_dna = dna_bulges;
   sa.max_iter = gs_opt(ix, "GS_BULGE_MAX_ITER") ? (uint32_t)atol(gs_opt(ix, "GS_BULGE_MAX_ITER")) : (1u << 26);
+  sa.stack_cap = 0xFFFFFFFFu;
+  if (const char *e = gs_opt(ix, "GS_GENERAL_STACK")) sa.stack_cap = (uint32_t)std::min(std::max(1ll, atoll(e)), (long long)GSTACK);
   const uint32_t grid_max = (uint32_t)gs_num_cus(ix->device) * 3u; /* 48 KB of LDS per single-wave workgroup */
   uint32_t grid = 2 * n32;
   if (grid > grid_max) grid = grid_max;
@@ -492,6 +510,7 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
       (void)hipGetLastError();
     }
   }
+  const uint64_t cap_first = cap;
   for (int attempt = 0; attempt < 2; attempt++) {
     if (d_a.p) {
       hipFree(d_a.p);
@@ -508,8 +527,13 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
     sa.pool_next = (unsigned long long *)((char *)d_misc.p + 16);
     sa.pool_cap = cap;
     hipLaunchKernelGGL(k_search_general, dim3(grid), dim3(WAVE), 0, st, sa);
-    uint32_t h_misc[8] = {0};
-    GS_HIP(hipMemcpy(h_misc, d_misc.p, 32, hipMemcpyDeviceToHost));
+    uint32_t h_misc[16] = {0};
+    GS_HIP(hipMemcpy(h_misc, d_misc.p, 64, hipMemcpyDeviceToHost));
+    {
+      const unsigned long long lg[8] = {sa.n_items, grid, cap_first, ((unsigned long long)h_misc[5] << 32) | h_misc[4],
+                                        (unsigned long long)attempt + 1u, h_misc[8], h_misc[9], h_misc[10]};
+      memcpy(ix->last_general, lg, sizeof(lg));
+    }
     if (h_misc[1]) {
       gs_set_error("internal: general search exceeded its iteration bound");
       return GS_ERR_DEVICE;
@@ -651,6 +675,12 @@ extern "C" gs_status gs_enumerate_bulges(gs_index *ix, const char *guides, uint6
                                          uint32_t dna_bulges, uint32_t flags, gs_result_ex **out) {
   return gs_enumerate_general(ix, guides, n, L, guide_pams, P, alt_pams, n_alt, mismatches, rna_bulges, dna_bulges,
                               flags, out);
+}
+extern "C" gs_status gs_debug_general_last(const gs_index *ix, uint64_t out[8]) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !out) return GS_ERR_ARG;
+  for (int i = 0; i < 8; i++) out[i] = ix->last_general[i];
+  return GS_OK;
 }
 extern "C" gs_status gs_result_ex_get(const gs_result_ex *r, uint64_t *n_guides, const uint64_t **offsets,
                                       const gs_hit_ex **hits) {

@@ -308,6 +308,13 @@ void gs_debug_tile_plan(uint32_t records, uint32_t out[5]);
  * rows, heavy, split, seed form, the form gs_index_last_sharing reports: 0 plain, 1 heavy, 2 split, 3 two seeding
  * launches}. */
 void gs_debug_search_form(const int64_t in[18], uint32_t out[6]);
+/* The last gs_enumerate_general* / gs_enumerate_bulges call on the handle, as data (tests pin what the general path's
+ * kernel met): out = {items (2 x guides), workgroups launched, records the first pass's pool held, match records T,
+ * search passes run (1, or 2 when the pool was outgrown), then from the kernel, for the last pass: the largest number
+ * of nodes any item's stack held after the pushes of a step, steps whose pop the room rule cut below min(nodes, 64)
+ * lanes, steps that found no room for one lane's children (the pop is then one node)}.  A call that was refused
+ * before its launch leaves the words as they were. */
+gs_status gs_debug_general_last(const gs_index *ix, uint64_t out[8]);
 
 /* Self-check of a resident index from the genome text alone (no suffix-array builder involved):
  * the suffix array of `strand` is a permutation of [0, n) (all rows), n_samples evenly spread

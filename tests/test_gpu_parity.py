@@ -128,8 +128,11 @@ def test_toy_hit_sets_bit_exact(toy_gpu, cfg):
 
 
 def general_hits_as_records(offsets, hits, i):
-    return [(int(x["pos"]), int(x["mismatches"]), int(x["index"]), api.decode_sequence_ex(x), int(x["dna_bulges"]),
-             int(x["rna_bulges"])) for x in hits[offsets[i]:offsets[i + 1]]]
+    """guide i's hits as the oracle's tuples; column by column, for a guide can have several 100,000 hits"""
+    x = hits[int(offsets[i]):int(offsets[i + 1])]
+    seqs = [s[:n].decode() for s, n in zip(x["seq"].tolist(), x["seq_len"].tolist())]   # api.decode_sequence_ex per row
+    return list(zip(x["pos"].tolist(), x["mismatches"].tolist(), x["index"].tolist(), seqs, x["dna_bulges"].tolist(),
+                    x["rna_bulges"].tolist()))
 
 
 def oracle_general_records(oidx, seq, pam, opts):
