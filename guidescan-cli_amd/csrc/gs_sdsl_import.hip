@@ -652,12 +652,18 @@ static gs_status open_sdsl_on_device(const char *prefix, int device, gs_index **
   f.text = nullptr;
   rc = gs_build_from_device_sa(text.data(), len, f.sa, r.sa, device, out);
   if (rc != GS_OK) return rc;
-  /* the arrays came from the file's samples, not from a sort of this text: neighbouring rows are compared by their
-   * suffixes in the text at 2^16 places per strand (a damaged sample moves a whole walk of 64 rows: a permutation still,
-   * in the wrong order) */
+  /* the arrays came from the file's samples, not from a sort of this text.  A damaged sample value moves its whole walk
+   * (64 rows on average) to another place of the text.  Where the symbols there differ, the two files' texts no longer
+   * agree (refused above); where they are the same - two copies of a repeat - the text stays and only the order of some
+   * hundred rows is wrong.  So every row is checked (GS_VERIFY_ALL_ROWS: detects every wrong order) where the strand has
+   * its inverse suffix array; where it has none (GS_NO_ISA, GS_NO_BIDIR, a memory budget that left it out) neighbouring
+   * rows are compared by their suffixes at 2^16 places per strand, which from some 2^22 rows on MISSES most such damage */
   for (int strand = 0; strand < 2; strand++) {
     gs_sa_report rep;
-    rc = gs_index_verify_sa(*out, strand, text.data(), len, 65536, 0x5D51ull + (uint64_t)strand, &rep);
+    if ((*out)->strand[strand].isa)
+      rc = gs_index_verify_sa(*out, strand, text.data(), len, GS_VERIFY_ALL_ROWS, 0, &rep);
+    else
+      rc = gs_index_verify_sa(*out, strand, text.data(), len, 65536, 0x5D51ull + (uint64_t)strand, &rep);
     if (rc == GS_OK && (rep.not_permutation || rep.out_of_order || rep.bwt_mismatch)) {
       gs_set_error("the index file's suffix array samples do not order its text");
       rc = GS_ERR_FORMAT;

@@ -142,8 +142,13 @@ gs_status gs_index_build_with_sa(const uint8_t *text, uint64_t len, const uint32
  * Replaces sdsl::load_from_file (src/guidescan.cxx:198-208).  Both files are turned into text AND suffix array on the
  * device - BWT by wavelet-tree access, LF walks from the SA samples, every step writing text[q - 1] and SA[row] - so no
  * suffix sort runs; .reverse must be the index of reverse_complement(.forward's text) (src/guidescan.cxx:146-157),
- * else GS_ERR_FORMAT.  Without a .reverse file (or with more than 16 distinct symbols) .forward's text is recovered on
- * the host and both strands are built from it. */
+ * else GS_ERR_FORMAT.  The arrays come from the files' samples, not from a sort, so they are then checked against the
+ * text (gs_index_verify_sa; GS_ERR_FORMAT): every row (GS_VERIFY_ALL_ROWS) where the strand has its inverse suffix array -
+ * a damaged file whose arrays are in any wrong order is DETECTED; where it has none (GS_NO_ISA, GS_NO_BIDIR, a memory
+ * budget that left it out) 65,536 sampled pairs per strand - values out of range or repeated and damage that changes
+ * the text are detected, but sample values exchanged between copies of a repeat (the text stays, a few hundred rows
+ * name the other copy) are mostly NOT detected from some 2^22 rows on.  Without a .reverse file (or with more than 16
+ * distinct symbols) .forward's text is recovered on the host and both strands are built from it. */
 gs_status gs_index_open_sdsl(const char *prefix, int device, gs_index **out);
 /* The genome text stored in one reference index file (BWT inverted on the host: the importer's host path).
  * *text is malloc'ed: release with gs_free. */
@@ -321,7 +326,13 @@ gs_status gs_debug_general_last(const gs_index *ix, uint64_t out[8]);
  * adjacent row pairs are in suffix order by direct comparison of the text, and the BWT symbol
  * each sampled row's Occ block holds is text[SA[row]-1].  `text` = the forward genome text as given
  * to gs_index_build.  Stands where the reference relies on sdsl::construct being right
- * (sdsl/include/sdsl/construct.hpp:121-166); used by the parity tests at n > 2^31. */
+ * (sdsl/include/sdsl/construct.hpp:121-166); used by the parity tests at n > 2^31.
+ * What sampled mode leaves out: sample i looks at the pair (r, r+1) and at row r's BWT symbol for one r in
+ * [i*stride, (i+1)*stride), stride = (n-1) / n_samples rounded down - so the BWT symbol of row n-1 is never
+ * looked at, and with n_samples < n-1 neither are the trailing (n-1) mod n_samples pairs, which lie beyond the
+ * last sample's stride.  n_samples >= n-1 compares every pair once (row n-1's symbol still left out); only
+ * GS_VERIFY_ALL_ROWS below looks at every row.  The runs of 'N' that the comparison skips are those of the
+ * text the index was built from.  tests/sa_model.py restates both modes in numpy; the reports are held equal to it. */
 typedef struct {
   uint64_t rows;            /* n = text length + 1 */
   uint64_t not_permutation; /* rows whose value is out of range or was seen before */
