@@ -258,7 +258,8 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_format_device", "gs_enumerate_text", "gs_index_last_text_offsets",
            "gs_format_device_ids", "gs_enumerate_text_device", "gs_kmers_encode_ids", "gs_kmers_get_ids", "gs_kmers_csv",
            "gs_kmers_concat", "gs_decoder_open", "gs_decoder_close", "gs_decode_records", "gs_decode_records_device",
-           "gs_decode_sam", "gs_debug_repr_doubles", "gs_debug_decode_tables"]
+           "gs_decode_sam", "gs_debug_repr_doubles", "gs_debug_decode_tables",
+           "gs_index_last_spaced", "gs_debug_seed_recipes_a8", "gs_debug_spaced_rows"]
 
 
 def _check(rc):
@@ -282,6 +283,20 @@ def seed_recipes(k, L, P, m, n_x, astar=None, deep=False):
     _check(L_.gs_debug_seed_recipes(k, L, P, m, n_x, a, 1 if deep else 0, out.ctypes.data, n, counts))
     c0, c1 = int(counts[0]), int(counts[1])
     return out[:c0], out[c0:c0 + c1], out[c0 + c1:]
+
+
+def seed_recipes_a8(k, m, n_x, astar, trimmed=False):
+    """this strand's share as read through PAM-pair tables (gs_debug_seed_recipes_a8; host only): the whole list, or the one
+    without the spaced tables' class (no substitution in X, all m in O)"""
+    L_ = lib()
+    L_.gs_debug_seed_recipes_a8.restype = C.c_int
+    L_.gs_debug_seed_recipes_a8.argtypes = [C.c_uint32] * 3 + [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    a = (C.c_uint32 * 8)(*(list(astar) + [15] * 8)[:8])
+    n = C.c_uint64()
+    _check(L_.gs_debug_seed_recipes_a8(k, m, n_x, a, 1 if trimmed else 0, None, 0, C.byref(n)))
+    out = np.zeros(int(n.value), dtype=np.uint64)
+    _check(L_.gs_debug_seed_recipes_a8(k, m, n_x, a, 1 if trimmed else 0, out.ctypes.data, out.shape[0], C.byref(n)))
+    return out
 
 
 def guide_descriptor(q: int, pams, L: int, P: int, k: int, x_len: int, codes=(0, 0xFFFFFFFF), n_pt: int = 1, valid: bool = True):
@@ -1034,7 +1049,14 @@ class GenomeIndex:
         out = (C.c_uint64 * 16)()
         _check(lib().gs_index_last_counters(self._h, out))
         v = list(out)
-        return dict(n_ext=v[0], overflow_items=v[1], n_matches=v[2], items_two_sided=v[4], items_one_sided=v[5],
+        sp = (C.c_uint64 * 6)()
+        L_ = lib()
+        L_.gs_index_last_spaced.restype = C.c_int
+        L_.gs_index_last_spaced.argtypes = [C.c_void_p, C.c_void_p]
+        _check(L_.gs_index_last_spaced(self._h, sp))
+        return dict(spaced_items=int(sp[0]), spaced_rows=int(sp[1]), spaced_rows_max=int(sp[2]), spaced_matches=int(sp[3]),
+                    spaced_bytes=int(sp[4]), spaced_build_us=int(sp[5]),
+                    n_ext=v[0], overflow_items=v[1], n_matches=v[2], items_two_sided=v[4], items_one_sided=v[5],
                     guides_redone=v[6], ordered_device_wide=bool(v[7] & 1), redo_ordered_device_wide=bool(v[7] & 2),
                     overflow_from_arena=bool(v[7] & 4),
                     ordered_by_one_composite_sort=bool(v[7] & 8), runs_turned_round=bool(v[7] & 16),
@@ -1042,6 +1064,18 @@ class GenomeIndex:
                     items_pair_tables=v[7] >> 8, recipe_lines=v[3],
                     slots_per_item=v[13], matches_sum=v[14], matches_max_per_item=v[15],
                     table_lines=v[8], ctx16_lines=v[9], ctx_words=v[10], sa_isa_gathers=v[11], occ_lines=v[12])
+
+    def spaced_rows(self, slot, strand, key, cap=4096):
+        """the rows under `key` in a slot's spaced table (gs_debug_spaced_rows) -> (rows uint32[n, 4], n under the key, info)"""
+        L_ = lib()
+        L_.gs_debug_spaced_rows.restype = C.c_int
+        L_.gs_debug_spaced_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        out = np.zeros((cap, 4), dtype=np.uint32)
+        n = C.c_uint64()
+        info = (C.c_uint32 * 8)()
+        _check(L_.gs_debug_spaced_rows(self._h, slot, strand, int(key), out.ctypes.data, cap, C.byref(n), info))
+        names = ("built", "code", "v_rem", "x_len", "r_len", "k", "key_bits_in_row", "rows")
+        return out[:min(cap, int(n.value))], int(n.value), dict(zip(names, (int(x) for x in info)))
 
     def last_launch(self):
         """what the main pass of the last enumerate_device call was launched with (gs_index_last_launch)"""

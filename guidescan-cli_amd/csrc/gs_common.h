@@ -49,6 +49,12 @@ struct gs_pairtab_dev {
   uint32_t code;
   /* the deep table of the strand seen from the other strand's items (gs_pairtab.hip), or nullptr */
   const uint4 *deep;
+  /* the spaced table (gs_pairtab.hip), or nullptr: the table's rows sorted by key = (X symbols of the row's k-mer, its R
+   * symbols) - what a site that spent the whole budget inside O shares with its guide.  sp_off: 2^d + 1 offsets into
+   * sp_rows over the key's top d bits; sp_rows: {row in the row arrays, O symbols << sp_rem | the key's low sp_rem bits} */
+  const uint32_t *sp_off;
+  const uint2 *sp_rows;
+  uint32_t sp_rem;
 };
 struct gs_strand_dev {
   const uint4 *blocks;       /* (n >> 7) + 1 blocks of 4 x uint4 */
@@ -141,6 +147,11 @@ struct gs_pairtab_host {
   void *mem[2][8] = {{nullptr}, {nullptr}};
   bool deep = false;               /* both strands' deep tables exist (PAM length deep_P) */
   uint32_t deep_P = 0, deep_kb = 0;
+  bool spaced = false;             /* both strands' spaced tables exist, keyed by the first sp_x and the last sp_g guide symbols */
+  uint32_t sp_x = 0, sp_g = 0;
+  uint64_t sp_bytes = 0, sp_rows[2] = {0, 0};
+  uint64_t n_slots[2] = {0, 0};    /* slots of each strand's row arrays (rows + the big entries' header slots) */
+  double sp_build_ms = 0;
   uint64_t bytes = 0, used = 0;
 };
 
@@ -149,6 +160,7 @@ struct gs_recipe_set {
   uint64_t key[2] = {0, 0};
   bool valid = false;
   uint32_t n_full = 0, n_a = 0, n_b = 0, n_a8 = 0; /* full | a | b | a as read through PAM-pair tables */
+  uint32_t n_a8s = 0; /* | the same without the class (no substitution in X, the whole budget in O): the spaced tables' share */
   uint32_t a_rot_first = 31; /* lowest consumption step whose rotated copy the PAM-pair list reads (31: none) */
 };
 
@@ -228,6 +240,8 @@ struct gs_index {
   /* PAM-pair tables (gs_pairtab.hip), built on first use for the pairs a batch's patterns end in */
   gs_pairtab_host pairtab[2];
   bool pairtab_off = false; /* a batch ran out of memory next to them: not built again on this handle */
+  bool spaced_off = false;  /* the same for the spaced tables */
+  unsigned long long last_spaced[4] = {0, 0, 0, 0}; /* the last batch (gs_index_last_spaced): items looked up, rows read, most rows under one key, rows that matched */
   bool rot_off = false;     /* the same for the strand tables' rotated copies */
   uint32_t dbg_nomem = 0;   /* GS_DBG_NOMEM (tests of those recoveries): passes of a batch that still end as if out of device memory */
   bool tile_order_off = false; /* a batch had interval records or one sequence at one row twice: the per-guide tile ordering is not tried again for that shape */
@@ -244,6 +258,11 @@ gs_status gs_pairtab_ensure(gs_index *ix, uint32_t slot, uint32_t v_rem, uint32_
 /* add the deep tables (the other strand's side, PAM of three symbols) to a valid slot; p.deep stays false when they do not fit */
 gs_status gs_pairtab_ensure_deep(gs_index *ix, uint32_t slot, uint32_t P, uint32_t kb, hipStream_t st);
 void gs_pairtab_free(gs_index *ix, uint32_t slot);
+/* add the spaced tables to a valid slot (keys: the first x_len and the last g guide symbols); p.spaced stays false when they
+ * do not fit or the key does not fit the layout */
+gs_status gs_pairtab_ensure_spaced(gs_index *ix, uint32_t slot, uint32_t x_len, uint32_t g, hipStream_t st);
+/* false: the slot had none */
+bool gs_pairtab_free_spaced(gs_index *ix, uint32_t slot);
 /* gs_index.hip: the strand tables' rotated copies, built by the first batch that reads them */
 gs_status gs_strand_rot_ensure(gs_index *ix, hipStream_t st);
 bool gs_strand_rot_release(gs_index *ix);

@@ -39,6 +39,8 @@ struct switches {
   uint64_t search_take, share_queue;  /* 0: not set */
   uint32_t max_iter, v_max, dbg_skip, cnt_shift, split_from, seed_sort_from, seed_opt, seed_take, wide_from;
   int heavy, split_share, seed_form;  /* -1: not set */
+  bool seed_spaced;                   /* GS_SEED_SPACED: the seeding launches read the spaced tables (0: off) */
+  uint32_t spaced_from;               /* GS_SPACED_FROM: recipes of the class from which a spaced table is worth its memory */
 };
 static switches read_switches(const gs_index *ix) {
   auto has = [&](const char *k) { return gs_opt(ix, k) != nullptr; };
@@ -91,6 +93,8 @@ static switches read_switches(const gs_index *ix) {
   w.heavy = has("GS_HEAVY") ? (num("GS_HEAVY", 0) != 0 ? 1 : 0) : -1;
   w.split_share = has("GS_SPLIT_SHARE") ? (int)std::min(3l, std::max(0l, num("GS_SPLIT_SHARE", 0))) : -1;
   w.seed_form = has("GS_SEED_FORM") ? (int)std::min(2l, std::max(0l, num("GS_SEED_FORM", 0))) : -1;
+  w.seed_spaced = num("GS_SEED_SPACED", 1) != 0;
+  w.spaced_from = has("GS_SPACED_FROM") ? (uint32_t)std::max(1l, num("GS_SPACED_FROM", 0)) : 256u;
   return w;
 }
 
@@ -266,6 +270,7 @@ struct batch {
   /* the seeding plan */
   uint32_t v_rem = 0, x_len = 0, deep_kb = 0, n_codes = 0;
   bool bidir = false, deep = false;
+  bool spaced_wanted = false; /* the batch's shape allows the spaced lookup: every pattern on pair + deep tables, budget <= 4, the class this strand's and large enough */
   uint32_t astar[8] = {15, 15, 15, 15, 15, 15, 15, 15}, astar_packed = 0xFFFFFFFFu;
   uint32_t n_pt = 0, pt_slot[2] = {0, 0};
   uint32_t n_cand[2] = {0, 0};
@@ -546,6 +551,19 @@ static gs_status seeding_plan(batch &b) {
     for (uint32_t i = 0; i < b.n_pt; i++) all_deep = all_deep && ix->pairtab[b.pt_slot[i]].deep;
     if (all_deep) break;
     try_deep = false; /* not every pattern has its deep table: plan again with the strand tables on that side */
+  }
+  /* the spaced tables (gs_pairtab.hip): the class "no substitution in X, all m in O" of this strand's seeds as one lookup per
+   * item - for a batch the seeding launches can serve (every pattern on its pair + deep tables, budget <= 4), when the class
+   * is this strand's under the thresholds and large enough to be worth a table (540 recipes at k = 14, 108 at k = 13).  Whether
+   * the batch may read them is decided here; they are built where the form is known (run_search): a batch that runs the heavy,
+   * the split or the one-launch form builds and holds none */
+  b.spaced_wanted = false;
+  {
+    const uint32_t k = ix->pt_k, nO = k > b.x_len ? k - b.x_len : 0u, m = b.m;
+    double cls = m <= nO ? 1.0 : 0.0; /* C(|O|, m) 3^m */
+    for (uint32_t i = 0; i < m && cls > 0; i++) cls = cls * (nO - i) / (i + 1) * 3.0;
+    b.spaced_wanted = b.sw.seed_spaced && b.bidir && b.deep && b.n_pt != 0 && b.n_pt == b.n_codes && b.h_pairs[16] == 0 && m >= 1 &&
+                      m <= 4 && b.astar[m] > 0 && b.x_len + 2 <= k && cls >= (double)b.sw.spaced_from;
   }
   /* the strand tables' rotated copies: read by this strand's seeds of items without PAM-pair tables, by the
    * other strand's seeds unless the deep tables take them, by one-sided items - built now if any of that
@@ -1063,6 +1081,24 @@ static gs_status run_search(batch &b, const search_pass &p, unsigned long long h
     const unsigned long long ll[8] = {k.walk ? 1u : 0u, k.spec ? 1u : 0u, sa.bdeep, sa.take, seed_launches ? b.sw.seed_take : 0u, sa.n_pt, sa.x_len,
                                       ix->strand[0].ptab_rot ? ix->strand[0].rot_plan_n : 0u};
     memcpy(ix->last_launch, ll, sizeof(ll));
+  }
+  bool spaced = b.spaced_wanted && k.f.seed_form != 0u && !k.walk && sa.shq == nullptr; /* (launch_search's branch: the two seeding launches) */
+  if (spaced) { /* the tables of this |X|, |R| on every PAM-pair table of the batch: built here, by the first batch that reads them */
+    const bool frozen = (b.flags & GS_FLAG_NO_NEW_TABLES) != 0;
+    for (uint32_t i = 0; i < b.n_pt; i++) {
+      if (!frozen && !ix->spaced_off && (rc = gs_pairtab_ensure_spaced(ix, b.pt_slot[i], b.x_len, b.L - ix->pt_k, st)) != GS_OK) return rc;
+      const gs_pairtab_host &pt = ix->pairtab[b.pt_slot[i]];
+      spaced = spaced && pt.spaced && pt.sp_x == b.x_len && pt.sp_g == b.L - ix->pt_k;
+      sa.pt[i][0] = pt.d[0];
+      sa.pt[i][1] = pt.d[1];
+    }
+  }
+  if (spaced) {
+    const gs_recipe_set &R = ix->rec[ix->rec_cur];
+    sa.spaced = 1u;
+    sa.spaced_ctr = b.d_work + WK_SPACED;
+    sa.rec_a8 = sa.rec_a8 + R.n_a8; /* the list without the class the lookup finds */
+    sa.n_rec_a8 = (sa.dbg_skip & 4u) ? 0u : R.n_a8s;
   }
   GS_HIP(hipEventRecord(ix->ev[1], st));
   if ((rc = launch_search(b, p, sa, k)) != GS_OK) return rc;
@@ -1593,9 +1629,12 @@ static gs_status order_set(batch &b) {
 static gs_status finish(batch &b, const void **d_offsets, const void **d_hits, gs_result_view *stats) {
   gs_index *ix = b.ix;
   GS_HIP(hipEventRecord(ix->ev[3], b.st));
-  unsigned long long h_stats3[16] = {0};
-  GS_HIP(hipMemcpyAsync(h_stats3, b.d_stats, sizeof(h_stats3), hipMemcpyDeviceToHost, b.st));
+  gs_misc_readback rb; /* the stats and, behind them, the work words: one copy */
+  memset(&rb, 0, sizeof(rb));
+  unsigned long long *const h_stats3 = rb.stats;
+  GS_HIP(hipMemcpyAsync(&rb, b.d_stats, sizeof(rb), hipMemcpyDeviceToHost, b.st));
   GS_HIP(hipStreamSynchronize(b.st));
+  for (int i = 0; i < 4; i++) ix->last_spaced[i] = rb.work[WK_SPACED + i];
   if (b.bidir && b.sw.debug)
     fprintf(stderr, "[gs] items: seeded from both strands %llu, one-sided (PAM with more than two N) %llu; slots %u per item, "
             "%u guides redone%s%s\n", h_stats3[4], h_stats3[5], b.cap, b.n_o, b.big_batch ? " (whole batch through the wide ordering)" : "",
@@ -1610,7 +1649,7 @@ static gs_status finish(batch &b, const void **d_offsets, const void **d_hits, g
                 (b.n_o && b.arena_chunks != 0 && b.arena_fail == 0 ? 4u : 0u) | (b.big.comp ? 8u : 0u) | (b.big.fixed ? 16u : 0u) |
                 (b.tile_used ? 32u : 0u) | (b.tile_fell_back ? 64u : 0u);
   h_stats3[13] = b.cap;
-  memcpy(ix->last_counters, h_stats3, sizeof(h_stats3));
+  memcpy(ix->last_counters, h_stats3, sizeof(rb.stats));
   /* matches per item seen at this budget: sizes the slots of the next batch */
   if (b.m < 8 && b.n32) {
     ix->seen[b.m].mean = (double)h_stats3[14] / (2.0 * b.n32);
@@ -1723,6 +1762,16 @@ static bool recover_release_workspace(gs_index *ix, gs_status rc) {
   if (gs_opt(ix, "GS_DEBUG")) fprintf(stderr, "[gs] out of device memory: %.1f GB of workspace released, batch redone\n", 1e-9 * (double)freed);
   return true;
 }
+/* the spaced tables go first: without them a batch of the headline's shape takes 17.0 instead of 15.7 ms, without any other table far more */
+static bool recover_drop_spaced(gs_index *ix, gs_status rc) {
+  if (rc != GS_ERR_NOMEM) return false;
+  const bool a = gs_pairtab_free_spaced(ix, 0), b = gs_pairtab_free_spaced(ix, 1);
+  if (!a && !b) return false;
+  (void)hipGetLastError();
+  ix->spaced_off = true;
+  if (gs_opt(ix, "GS_DEBUG")) fprintf(stderr, "[gs] out of device memory: spaced tables dropped, batch redone without them\n");
+  return true;
+}
 static bool recover_drop_rotated(gs_index *ix, gs_status rc) {
   if (rc != GS_ERR_NOMEM || !gs_strand_rot_release(ix)) return false;
   (void)hipGetLastError();
@@ -1750,7 +1799,7 @@ extern "C" gs_status gs_enumerate_device(gs_index *ix, const void *d_guides, uin
     gs_status rc = enumerate_device_impl(ix, d_guides, n, L, d_guide_pams, P, alt_pams, n_alt, mismatches, flags, stream,
                                          d_offsets, d_hits, stats);
     if (ix)
-      for (auto recover : {recover_share_timeout, recover_release_workspace, recover_drop_rotated, recover_drop_pairtabs})
+      for (auto recover : {recover_share_timeout, recover_drop_spaced, recover_release_workspace, recover_drop_rotated, recover_drop_pairtabs})
         if (recover(ix, rc))
           rc = enumerate_device_impl(ix, d_guides, n, L, d_guide_pams, P, alt_pams, n_alt, mismatches, flags, stream, d_offsets,
                                      d_hits, stats);

@@ -1035,6 +1035,14 @@ extern "C" gs_status gs_index_last_launch(const gs_index *ix, uint64_t out[8]) {
   for (int i = 0; i < 8; i++) out[i] = ix->last_launch[i];
   return GS_OK;
 }
+extern "C" gs_status gs_index_last_spaced(const gs_index *ix, uint64_t out[6]) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !out) return GS_ERR_ARG;
+  for (int i = 0; i < 4; i++) out[i] = ix->last_spaced[i];
+  out[4] = ix->pairtab[0].sp_bytes + ix->pairtab[1].sp_bytes;
+  out[5] = (uint64_t)(1e3 * (ix->pairtab[0].sp_build_ms + ix->pairtab[1].sp_build_ms));
+  return GS_OK;
+}
 extern "C" uint64_t gs_index_genome_length(const gs_index *ix) { return ix ? ix->genome_length : 0; }
 extern "C" uint64_t gs_index_device_bytes(const gs_index *ix) {
   return ix ? ix->strand[0].bytes + ix->strand[1].bytes + ix->pairtab[0].bytes + ix->pairtab[1].bytes : 0;

@@ -47,6 +47,7 @@ enum : uint32_t {
   WK_HPASS = 8,         /* heavy verification passes of the main pass */
   WK_HELPER_ITEMS = 9,  /* the launch without items: a work counter past the items from the start */
   WK_SCRATCH2 = 10,     /* two words: the form estimate's result, k_need_chunks' count */
+  WK_SPACED = 12,       /* four words (k_seed_a's spaced lookups): items, rows read, most rows under one key, rows that matched */
   MISC_PAIR_HIST = 256, /* byte offset of the PAM-pair histogram (17 words) */
 };
 static inline unsigned long long *gs_misc_stats(void *misc) { return (unsigned long long *)misc; }
@@ -54,7 +55,7 @@ static inline uint32_t *gs_misc_work(void *misc) { return (uint32_t *)((char *)m
 /* what one copy of the stats and the work words behind them brings back */
 struct gs_misc_readback {
   unsigned long long stats[16];
-  uint32_t work[12];
+  uint32_t work[16];
 };
 
 
@@ -174,6 +175,10 @@ struct gs_search_args {
   const struct gs_guide_desc *desc_a, *desc_b;
   uint32_t *xwork;
   uint32_t seed_opt; /* bit 0: single-use reads non-temporal; bit 1: seeds without a substitution in X read the plain table */
+  /* k_seed_a: the sites without a substitution in X and with all m in O come from one lookup per item and table in the spaced
+   * tables (gs_pairtab_dev::sp_*), and rec_a8 is the list without that class; spaced_ctr: the WK_SPACED words */
+  uint32_t spaced;
+  uint32_t *spaced_ctr;
 };
 /* what an item of the table-seeded search derives from its guide alone (strand independent): 64 bytes, one scalar load */
 struct gs_guide_desc {

@@ -15,6 +15,10 @@
  * the nearest v_rem are left out: k_search reports those sites from the literal-N window list.
  * Derived data, built on the device from the strand's table and ctx[] on first use (~0.1 s at hg38
  * size), 4.3 GB per table copy + 10 bytes per selected row.
+ *
+ * The spaced table of a pair table (gs_seed.hip reads it): the same rows sorted by what a site that spent its whole
+ * budget inside O - the k-mer's symbols behind X - still shares with its guide: X and R.  One lookup keyed on (X, R)
+ * answers what C(|O|, m) 3^m seeds of the class (no substitution in X, m in O) ask one table entry each.
  */
 #include "gs_device.h"
 
@@ -173,6 +177,8 @@ void gs_pairtab_free(gs_index *ix, uint32_t slot) {
     }
   p.valid = false;
   p.deep = false;
+  p.spaced = false;
+  p.sp_bytes = 0;
   p.d[0] = gs_pairtab_dev{};
   p.d[1] = gs_pairtab_dev{};
   p.bytes = 0;
@@ -250,6 +256,7 @@ static gs_status build_one(gs_index *ix, gs_pairtab_host &p, int s, uint32_t k, 
   d.rot_first = nrot ? rot_from : 31u;
   d.code = p.code;
   p.bytes += sizeof(uint2) * entries * (1 + nrot) + 10 * rows;
+  p.n_slots[s] = rows;
   if (gs_opt(ix, "GS_DEBUG"))
     fprintf(stderr, "[gs] PAM-pair table: strand %d, pair %u at context depth %u: %llu of %llu rows, %u rotated copies, %.2f GB\n",
             s, p.code, p.v_rem, (unsigned long long)rows, (unsigned long long)S.n, nrot,
@@ -367,5 +374,275 @@ gs_status gs_pairtab_ensure_deep(gs_index *ix, uint32_t slot, uint32_t P, uint32
   p.deep = true;
   p.deep_P = P;
   p.deep_kb = kb;
+  return GS_OK;
+}
+
+/* ---- the spaced table: the pair table's rows by (X symbols of the k-mer, R symbols of the context) -------------------
+ * key = X << 2g | ctx & mask(g), X = the index's highest 2 x_len bits (consumption steps 0 .. x_len-1), g = L - k; payload =
+ * {row in the row arrays, O symbols (the index's other bits) << rem | the key's low rem bits}.  Sorted by key; the offsets
+ * array is direct-addressed by the key's top d bits, d from the number of rows (2^d >= rows), so the layout serves keys of
+ * any width up to 32 bits: the `rem` bits below are stored with the row and compared by the reader. */
+struct sp_args {
+  const uint2 *tab;
+  const uint32_t *ctx, *rowid;
+  uint32_t k, x_len, g, rem;
+  uint64_t entries;
+  uint32_t *count;
+  const uint32_t *start;
+  uint32_t *keys;
+  uint64_t *vals;
+};
+/* the rows of entry e: where they start and how many (a big entry's header slot is not a row) */
+__device__ __forceinline__ uint32_t sp_entry_rows(const sp_args &a, const uint2 e, uint32_t &first) {
+  uint32_t cnt = e.y & 63u;
+  first = e.x;
+  if (cnt == GS_PT_BIG) {
+    cnt = a.rowid[first];
+    first += 1u;
+  }
+  return cnt;
+}
+__global__ void k_sp_count(sp_args a) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.entries) return;
+  uint32_t first;
+  a.count[i] = sp_entry_rows(a, a.tab[i], first);
+}
+/* a lane per entry; the rows of a big entry (63 .. 10^5 on a repeat-rich genome) are written by the whole wave, 64 at a time */
+__global__ void k_sp_fill(sp_args a) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = i < a.entries;
+  const uint32_t cnt = in ? a.count[i] : 0u;
+  uint32_t first = 0;
+  if (cnt) (void)sp_entry_rows(a, a.tab[i], first);
+  const uint32_t at = cnt ? a.start[i] : 0u;
+  const uint32_t obits = 2u * (a.k - a.x_len), gmask = a.g >= 16u ? 0xFFFFFFFFu : ((1u << (2u * a.g)) - 1u);
+  const uint32_t remmask = (1u << a.rem) - 1u;
+  auto put = [&](uint32_t e, uint32_t e_first, uint32_t e_at, uint32_t j) {
+    const uint32_t x = e >> obits, o = e & ((1u << obits) - 1u), r = e_first + j;
+    const uint32_t key = (a.g >= 16u ? 0u : x << (2u * a.g)) | (a.ctx[r] & gmask);
+    a.keys[e_at + j] = key;
+    a.vals[e_at + j] = (uint64_t)r | ((uint64_t)((o << a.rem) | (key & remmask)) << 32);
+  };
+  const bool big = cnt >= GS_PT_BIG;
+  if (!big)
+    for (uint32_t j = 0; j < cnt; j++) put((uint32_t)i, first, at, j);
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint64_t bb = __ballot(big); bb; bb &= bb - 1ull) {
+    const int src = __builtin_ctzll(bb);
+    const uint32_t e = (uint32_t)__shfl((int)(uint32_t)i, src), e_first = (uint32_t)__shfl((int)first, src);
+    const uint32_t e_at = (uint32_t)__shfl((int)at, src), e_cnt = (uint32_t)__shfl((int)cnt, src);
+    for (uint32_t j = lane; j < e_cnt; j += 64u) put(e, e_first, e_at, j);
+  }
+}
+/* off[t] = the first sorted row whose key's top bits are >= t, t = 0 .. 2^d (row `rows` closes the last bucket) */
+__global__ void k_sp_offsets(const uint32_t *keys, uint32_t rows, uint32_t rem, uint32_t d, uint32_t *off) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > rows) return;
+  const uint64_t top = i < rows ? (uint64_t)(keys[i] >> rem) : (1ull << d);
+  const uint64_t from = i == 0 ? 0ull : (uint64_t)(keys[i - 1] >> rem) + 1ull;
+  for (uint64_t t = from; t <= top; t++) off[t] = (uint32_t)i;
+}
+
+bool gs_pairtab_free_spaced(gs_index *ix, uint32_t slot) {
+  gs_pairtab_host &p = ix->pairtab[slot];
+  bool any = false;
+  for (int s = 0; s < 2; s++) {
+    for (int j = 6; j < 8; j++) {
+      if (p.mem[s][j]) {
+        hipFree(p.mem[s][j]);
+        any = true;
+      }
+      p.mem[s][j] = nullptr;
+    }
+    p.d[s].sp_off = nullptr;
+    p.d[s].sp_rows = nullptr;
+    p.d[s].sp_rem = 0;
+  }
+  p.bytes -= p.sp_bytes;
+  p.sp_bytes = 0;
+  p.spaced = false;
+  return any;
+}
+
+/* the direct part's bits for a table of `rows` rows whose keys have key_bits bits and whose payload keeps obits bits of O:
+ * 2^d >= rows, at most 2^28 offsets, and what the payload's second word has to hold (O, the other key bits) fits 32 bits;
+ * 0: no such d */
+static uint32_t sp_direct_bits(uint64_t rows, uint32_t key_bits, uint32_t obits) {
+  uint32_t d = 8;
+  while (d < 28 && (1ull << d) < rows) d++;
+  if (d > key_bits) d = key_bits;
+  if (key_bits - d + obits > 32u) d = key_bits + obits - 32u;
+  return d >= 1 && d <= 28 && d <= key_bits ? d : 0u;
+}
+
+static gs_status build_spaced(gs_index *ix, gs_pairtab_host &p, int s, uint32_t k, uint32_t x_len, uint32_t g, hipStream_t st) {
+  const uint64_t entries = 1ull << (2 * k);
+  const uint32_t key_bits = 2u * (x_len + g), obits = 2u * (k - x_len);
+  void **m = p.mem[s];
+  uint32_t *d_count = nullptr, *d_start = nullptr, *d_keys = nullptr, *d_keys2 = nullptr;
+  uint64_t *d_vals = nullptr;
+  void *d_tmp = nullptr;
+  struct cleanup_t {
+    void *const *v[6];
+    ~cleanup_t() {
+      for (void *const *q : v)
+        if (*q) hipFree(*q);
+    }
+  } cleanup{{(void **)&d_count, (void **)&d_start, (void **)&d_keys, (void **)&d_keys2, (void **)&d_vals, &d_tmp}};
+  auto nomem = [&]() {
+    (void)hipGetLastError();
+    return GS_ERR_NOMEM;
+  };
+  if (hipMalloc(&d_count, 4 * entries) != hipSuccess || hipMalloc(&d_start, 4 * entries) != hipSuccess) return nomem();
+  sp_args a;
+  memset(&a, 0, sizeof(a));
+  a.tab = p.d[s].tab;
+  a.ctx = p.d[s].ctx;
+  a.rowid = p.d[s].rowid;
+  a.k = k;
+  a.x_len = x_len;
+  a.g = g;
+  a.entries = entries;
+  a.count = d_count;
+  const uint32_t nb = (uint32_t)((entries + 255) / 256);
+  hipLaunchKernelGGL(k_sp_count, dim3(nb), dim3(256), 0, st, a);
+  size_t tmp_bytes = 0;
+  GS_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_count, d_start, 0u, entries, rocprim::plus<uint32_t>(), st));
+  if (hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16) != hipSuccess) return nomem();
+  GS_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_count, d_start, 0u, entries, rocprim::plus<uint32_t>(), st));
+  uint32_t last_start = 0, last_count = 0;
+  GS_HIP(hipMemcpyAsync(&last_start, d_start + entries - 1, 4, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipMemcpyAsync(&last_count, d_count + entries - 1, 4, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipStreamSynchronize(st));
+  (void)hipFree(d_tmp);
+  d_tmp = nullptr;
+  /* the rows are the slots of the pair table's row arrays without the header slots: the builder's own count bounds them, so
+   * the 32-bit scan above cannot have wrapped unseen */
+  const uint64_t rows = (uint64_t)last_start + last_count;
+  if (p.n_slots[s] >= 0xFFFFFFFFull || rows > p.n_slots[s]) return GS_ERR_UNSUPPORTED;
+  const uint32_t d = sp_direct_bits(rows, key_bits, obits);
+  if (!d) return GS_ERR_UNSUPPORTED;
+  const uint32_t rem = key_bits - d;
+  if (hipMalloc(&d_keys, 4 * rows + 16) != hipSuccess || hipMalloc(&d_keys2, 4 * rows + 16) != hipSuccess ||
+      hipMalloc(&d_vals, 8 * rows + 16) != hipSuccess || hipMalloc(&m[7], 8 * rows + 16) != hipSuccess ||
+      hipMalloc(&m[6], 4 * ((1ull << d) + 1)) != hipSuccess)
+    return nomem();
+  a.start = d_start;
+  a.rem = rem;
+  a.keys = d_keys;
+  a.vals = d_vals;
+  hipLaunchKernelGGL(k_sp_fill, dim3(nb), dim3(256), 0, st, a);
+  if (rows) {
+    tmp_bytes = 0;
+    GS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys, d_keys2, d_vals, (uint64_t *)m[7], rows, 0, key_bits, st));
+    if (hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16) != hipSuccess) return nomem();
+    GS_HIP(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_vals, (uint64_t *)m[7], rows, 0, key_bits, st));
+  }
+  hipLaunchKernelGGL(k_sp_offsets, dim3((uint32_t)((rows + 1 + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_keys2, (uint32_t)rows, rem, d,
+                     (uint32_t *)m[6]);
+  GS_HIP(hipStreamSynchronize(st));
+  GS_HIP(hipGetLastError());
+  gs_pairtab_dev &dv = p.d[s];
+  dv.sp_off = (const uint32_t *)m[6];
+  dv.sp_rows = (const uint2 *)m[7];
+  dv.sp_rem = rem;
+  p.sp_rows[s] = rows;
+  const uint64_t bytes = 8 * rows + 16 + 4 * ((1ull << d) + 1);
+  p.sp_bytes += bytes;
+  p.bytes += bytes;
+  if (gs_opt(ix, "GS_DEBUG"))
+    fprintf(stderr, "[gs] spaced table: strand %d, pair %u: %llu rows by %u key bits (|X|=%u, |R|=%u), %u direct, %.2f GB\n", s, p.code,
+            (unsigned long long)rows, key_bits, x_len, g, d, 1e-9 * (double)bytes);
+  return GS_OK;
+}
+
+gs_status gs_pairtab_ensure_spaced(gs_index *ix, uint32_t slot, uint32_t x_len, uint32_t g, hipStream_t st) {
+  gs_pairtab_host &p = ix->pairtab[slot];
+  const uint32_t k = ix->pt_k;
+  if (!p.valid) return GS_OK;
+  if (p.spaced && p.sp_x == x_len && p.sp_g == g) return GS_OK;
+  gs_pairtab_free_spaced(ix, slot);
+  if (k < 4 || x_len < 1 || x_len + 2 > k || g < 1 || 2 * (x_len + g) > 32 || g > 16) return GS_OK;
+  /* what the finished tables take (8 bytes per row and the offsets, both strands) and the sort's buffers while one is built */
+  const double rows_est = ((double)ix->strand[0].n + (double)ix->strand[1].n) / 16.0 * 1.5;
+  const double keep = 8.0 * rows_est + 2.0 * 4.0 * (double)(1ull << std::min(28u, 2u * (x_len + g)));
+  const double tmp = 8.0 * (double)(1ull << (2 * k)) + 24.0 * rows_est / 2.0 + 64e6;
+  size_t free_b = 0, total_b = 0;
+  GS_HIP(hipMemGetInfo(&free_b, &total_b));
+  double reserve = 64e9;
+  if (const char *e = gs_opt(ix, "GS_PAIRTAB_RESERVE_GB")) reserve = atof(e) * 1e9;
+  if (reserve > 0.25 * (double)total_b) reserve = 0.25 * (double)total_b;
+  double room = (double)free_b - reserve;
+  if (const char *e = gs_opt(ix, "GS_INDEX_BUDGET_GB")) {
+    const double left = atof(e) * 1e9 - (double)gs_index_device_bytes(ix);
+    if (left < room) room = left;
+  }
+  if (keep + tmp > room) {
+    if (gs_opt(ix, "GS_DEBUG")) fprintf(stderr, "[gs] spaced table %u: not enough free memory (%.1f GB), skipped\n", p.code, 1e-9 * (double)free_b);
+    return GS_OK;
+  }
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  const bool timed = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+  if (timed) (void)hipEventRecord(ev[0], st);
+  gs_status rc = GS_OK;
+  for (int s = 0; s < 2 && rc == GS_OK; s++) rc = build_spaced(ix, p, s, k, x_len, g, st);
+  if (timed) {
+    float ms = 0.f;
+    (void)hipEventRecord(ev[1], st);
+    (void)hipEventSynchronize(ev[1]);
+    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+    p.sp_build_ms = ms;
+  }
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+  (void)hipGetLastError();
+  if (rc != GS_OK) {
+    gs_pairtab_free_spaced(ix, slot);
+    return rc == GS_ERR_NOMEM || rc == GS_ERR_UNSUPPORTED ? GS_OK : rc; /* the batch goes on without them */
+  }
+  p.spaced = true;
+  p.sp_x = x_len;
+  p.sp_g = g;
+  if (gs_opt(ix, "GS_DEBUG")) fprintf(stderr, "[gs] spaced tables of pair %u: %.2f GB, built in %.1f ms\n", p.code, 1e-9 * (double)p.sp_bytes, p.sp_build_ms);
+  return GS_OK;
+}
+
+/* tests: the rows under `key` in the spaced table of (slot, strand): four words per row {row in the row arrays, O symbols,
+ * row of the strand's suffix array, context word}; info = {built, pair code, context depth, |X|, |R|, table depth k, key bits
+ * stored with the row, rows of the table} */
+extern "C" gs_status gs_debug_spaced_rows(gs_index *ix, uint32_t slot, int strand, uint32_t key, uint32_t *out, uint64_t cap, uint64_t *n,
+                                          uint32_t info[8]) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || slot > 1 || strand < 0 || strand > 1 || !n || !info || (cap && !out)) return GS_ERR_ARG;
+  const gs_pairtab_host &p = ix->pairtab[slot];
+  const gs_pairtab_dev &d = p.d[strand];
+  const uint32_t inf[8] = {p.valid && p.spaced ? 1u : 0u, p.code, p.v_rem, p.sp_x, p.sp_g, ix->pt_k, d.sp_rem, (uint32_t)p.sp_rows[strand]};
+  memcpy(info, inf, sizeof(inf));
+  *n = 0;
+  if (!inf[0]) return GS_OK;
+  const uint32_t key_bits = 2u * (p.sp_x + p.sp_g);
+  if (key_bits < 32u && (key >> key_bits) != 0u) return GS_ERR_ARG;
+  GS_HIP(hipSetDevice(ix->device));
+  uint32_t off[2] = {0, 0};
+  GS_HIP(hipMemcpy(off, d.sp_off + (key >> d.sp_rem), 8, hipMemcpyDeviceToHost));
+  if (off[1] < off[0] || off[1] > p.sp_rows[strand]) return GS_ERR_DEVICE;
+  std::vector<uint2> rows(off[1] - off[0]);
+  if (!rows.empty()) GS_HIP(hipMemcpy(rows.data(), d.sp_rows + off[0], 8 * rows.size(), hipMemcpyDeviceToHost));
+  const uint32_t remmask = (1u << d.sp_rem) - 1u;
+  for (const uint2 &r : rows) {
+    if ((r.y & remmask) != (key & remmask)) continue;
+    if (*n < cap) {
+      uint32_t w[2] = {0, 0};
+      GS_HIP(hipMemcpy(&w[0], d.rowid + r.x, 4, hipMemcpyDeviceToHost));
+      GS_HIP(hipMemcpy(&w[1], d.ctx + r.x, 4, hipMemcpyDeviceToHost));
+      uint32_t *o = out + 4 * *n;
+      o[0] = r.x;
+      o[1] = r.y >> d.sp_rem;
+      o[2] = w[0];
+      o[3] = w[1];
+    }
+    (*n)++;
+  }
   return GS_OK;
 }

@@ -66,8 +66,9 @@ static inline uint64_t recipe_word(uint32_t n, uint32_t lo, bool rot, uint32_t r
 /* this strand's seeds: variants of the first k-2 steps with j substitutions (ax of them among the first
  * nX steps, set X) x the two-symbol extensions the budget allows; two-sided (astar != nullptr): only
  * what has ax < astar[substitutions outside X] */
+/* no_xo: without the class (no substitution in X, all m in O) - the sites a spaced table's lookup finds (gs_seed.hip) */
 static void build_recipes_a(std::vector<uint64_t> &out, uint32_t k, uint32_t m, uint32_t nX, const uint32_t *astar, bool rot,
-                            bool pair8 = false) {
+                            bool pair8 = false, bool no_xo = false) {
   const uint32_t kp = k - 2, xmask = nX >= 32 ? 0xFFFFFFFFu : (1u << nX) - 1u;
   auto mine = [&](uint32_t ax, uint32_t o) { return !astar || (o < 8 && ax < astar[o]); };
   const uint32_t jmax = std::min(std::min(m, kp), 7u);
@@ -96,6 +97,7 @@ static void build_recipes_a(std::vector<uint64_t> &out, uint32_t k, uint32_t m, 
               if (e2) f[n++] = ((k - 2) << 2) | (e2 - 1);
               if (e1) f[n++] = ((k - 1) << 2) | (e1 - 1);
               if (n > m || n > 7 || !mine(ax + (e2 ? 1u : 0u), o0 + (e1 ? 1u : 0u))) continue;
+              if (no_xo && ax + (e2 ? 1u : 0u) == 0u && n == m) continue;
               out.push_back(recipe_word(n, 0, false, 0, f));
             }
         }
@@ -119,6 +121,7 @@ static void build_recipes_a(std::vector<uint64_t> &out, uint32_t k, uint32_t m, 
           if (e2) f[n++] = ((k - 2) << 2) | (e2 - 1);
           if (e1) f[n++] = ((k - 1) << 2) | (e1 - 1);
           if (n > m || n > 7 || !mine(ax, o0 + (n - j))) return;
+          if (no_xo && ax == 0u && n == m) return;
           out.push_back(recipe_word(n, 0, r, rs, f));
         };
         if (eb >= 2) { /* 16 neighbours of the plain table: 4 lines */
@@ -190,6 +193,20 @@ extern "C" gs_status gs_debug_seed_recipes(uint32_t k, uint32_t L, uint32_t P, u
   }
   return GS_OK;
 }
+/* the list this strand's seeds read through PAM-pair tables (rec_a8), whole or without the spaced tables' class */
+extern "C" gs_status gs_debug_seed_recipes_a8(uint32_t k, uint32_t m, uint32_t n_x, const uint32_t *astar, uint32_t trimmed, uint64_t *out,
+                                              uint64_t cap, uint64_t *count) {
+  if (k < 4 || k > 16 || m > 7 || n_x + 1 > k || !astar || !count) return GS_ERR_ARG;
+  try {
+    std::vector<uint64_t> all;
+    build_recipes_a(all, k, m, n_x, astar, true, true, trimmed != 0);
+    *count = all.size();
+    for (uint64_t i = 0; i < all.size() && i < cap && out; i++) out[i] = all[i];
+  } catch (const std::bad_alloc &) {
+    return GS_ERR_NOMEM;
+  }
+  return GS_OK;
+}
 extern "C" void gs_debug_choose_thresholds(uint32_t m, uint32_t n_x, uint32_t n_o, uint32_t n_r, double pam_expansions,
                                            double verify_a, double verify_b, uint32_t astar[8]) {
   gs_choose_astar(m, n_x, n_o, n_r, pam_expansions, astar, verify_a, verify_b);
@@ -221,7 +238,10 @@ gs_status gs_recipes_for(gs_index *ix, uint32_t L, uint32_t P, uint32_t m, uint3
     n_b = all.size() - n_full - n_a;
     build_recipes_a(all, k, m, v_rem, astar, rot, true); /* this strand's share read through PAM-pair tables */
     n_a8 = all.size() - n_full - n_a - n_b;
+    /* ... and without the class a spaced table answers, where this strand owns it (gs_enumerate.hip: run_search) */
+    if (m < 8 && astar[m] > 0) build_recipes_a(all, k, m, v_rem, astar, rot, true, true);
   }
+  const size_t n_a8s = all.size() - n_full - n_a - n_b - n_a8;
   if (all.size() >= (1ull << 31)) {
     gs_set_error("seed plan too large for this mismatch budget");
     return GS_ERR_UNSUPPORTED;
@@ -238,8 +258,9 @@ gs_status gs_recipes_for(gs_index *ix, uint32_t L, uint32_t P, uint32_t m, uint3
   R.n_a = (uint32_t)n_a;
   R.n_b = (uint32_t)n_b;
   R.n_a8 = (uint32_t)n_a8;
+  R.n_a8s = (uint32_t)n_a8s;
   R.a_rot_first = 31; /* of the list read through PAM-pair tables */
-  for (size_t i = n_full + n_a + n_b; i < all.size(); i++)
+  for (size_t i = n_full + n_a + n_b; i < n_full + n_a + n_b + n_a8; i++)
     if (all[i] & 64u) R.a_rot_first = std::min(R.a_rot_first, (uint32_t)(all[i] >> 7) & 31u);
   R.key[0] = key[0];
   R.key[1] = key[1];

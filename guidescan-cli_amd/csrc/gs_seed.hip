@@ -273,6 +273,7 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
   unsigned long long n_ovf = 0;
   uint32_t n_fail = 0, n_hpass = 0, n_two = 0;
   bool bailed = false;
+  uint32_t n_sp_items = 0, n_sp_rows = 0, n_sp_max = 0, n_sp_hits = 0; /* SIDE 1: the spaced lookups */
   uint32_t c_tab = 0, c_c16 = 0, c_ctx = 0, c_isa = 0, c_rec = 0;
   auto count_lines = [&](uint32_t &acc, bool act, const void *p) __attribute__((always_inline)) {
     if constexpr (CNT) {
@@ -466,16 +467,20 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
      * strand's ISA, or a PAM-pair table's row numbers -, its seed's path from the recipe, its record.  (Parking the hits in
      * LDS and resolving them 64 at a time, so that a pass does not wait for these dependent reads, changed nothing: 16.4 ms
      * against 16.3, profiles/r06_ab_seed_variants.txt - the waves that wait are covered by the SIMD's other seven) ---- */
-    auto resolve = [&](const bool on, const uint32_t e_x, const uint32_t e_y, const uint32_t w, const uint32_t e_w) __attribute__((always_inline)) {
+    /* (e_y: the seed's number, its path comes from the recipe - or SEED_HAS_PATH and the path itself in `given`: a spaced lookup's rows) */
+    constexpr uint32_t SEED_HAS_PATH = 0xFFFFFFFFu;
+    auto resolve = [&](const bool on, const uint32_t e_x, const uint32_t e_y, const uint32_t w, const uint32_t e_w, const uint64_t given) __attribute__((always_inline)) {
       const uint32_t n = (uint32_t)__popcll(__ballot(on));
-      const uint4 e = make_uint4(e_x, e_y, w, e_w);
+      struct {
+        uint32_t x, w;
+      } const e = {e_x, e_w};
       if constexpr (modeB) {
         /* word symbol j is guide symbol g-1-j, complemented; the site's row on THIS strand through SA -> ISA */
         uint64_t mmeta = 0;
         uint32_t rowA = 0;
         if (on) {
           const uint32_t pB = sv.sa[e.x];
-          const uint64_t sp = seed_path(e.y);
+          const uint64_t sp = seed_path(e_y);
           rowA = sd.isa[(sd.n - 1u) - (pB - g) - (L + P)];
           const uint64_t gpath = (uint64_t)seed_codes16(~w & gmask, ~qrem & gmask) << (52u + PB - 2u * g);
           mmeta = ((uint64_t)e.w << KSH) | sp | gpath;
@@ -488,7 +493,8 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
         if (on) {
           orow = arow[e.x];
           const uint64_t gpath = ((uint64_t)seed_rev16(seed_codes16(w & gmask, qrem)) << 32) >> (12u - PB + 2u * k);
-          base_meta = ((uint64_t)e.w << KSH) | seed_path(e.y) | gpath;
+          const uint64_t sp = e_y == SEED_HAS_PATH ? given : seed_path(e_y); /* (wave-uniform: a call passes one kind) */
+          base_meta = ((uint64_t)e.w << KSH) | sp | gpath;
         }
         if constexpr (CNT) c_isa += n;
         for (uint32_t pj = 0; pj < npams; ++pj) {
@@ -624,7 +630,7 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
           const bool gok = has && !excbad && kv + mmv <= m && mmv >= ((dd.y >> DSC_LO) & 7u);
           const uint64_t bh = __ballot(gok);
           if (!bh) continue;
-          resolve(gok, row, dd.z, w, kv + mmv);
+          resolve(gok, row, dd.z, w, kv + mmv, 0ull);
         }
       }
     };
@@ -781,6 +787,23 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
       const uint32_t pidx0 = dp[7], qhot = dp[12];
       const uint32_t gmask13 = g >= 13u ? 0x3FFFFFFu : gmask;
       uint32_t pslots = (meta >> 3) & 3u;
+      /* the spaced tables' share (no substitution in X, all m in O: R and the PAM pair are then the guide's own): ONE lookup
+       * per table keyed on (X, R) instead of the class's C(|O|, m) 3^m seeds.  The offsets are asked for here and used behind
+       * the recipe passes: the two dependent reads hide behind the item's own work */
+      const uint32_t obits = 2u * (k - sx), omask = (1u << obits) - 1u;
+      const uint32_t sp_key = a.spaced ? ((pidx0 >> obits) << (2u * g)) | qrem : 0u;
+      uint2 sp_o0 = make_uint2(0u, 0u), sp_o1 = make_uint2(0u, 0u);
+      if (a.spaced) {
+        if (pslots & 1u) {
+          const uint32_t *o = seed_sgprs(a.pt[0][strand].sp_off) + (sp_key >> a.pt[0][strand].sp_rem);
+          sp_o0 = make_uint2(o[0], o[1]);
+        }
+        if (pslots & 2u) {
+          const uint32_t *o = seed_sgprs(a.pt[1][strand].sp_off) + (sp_key >> a.pt[1][strand].sp_rem);
+          sp_o1 = make_uint2(o[0], o[1]);
+        }
+        if constexpr (CNT) c_tab += (pslots & 1u) + (pslots >> 1);
+      }
       fill_dtab();
       uint2 rc_ahead = make_uint2(0u, 0u);
       if (lane < nrec) rc_ahead = recs[lane];
@@ -838,6 +861,46 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
           if (bailed) break;
         }
       }
+      if (a.spaced) {
+        pslots = (meta >> 3) & 3u;
+        for (uint32_t s = 0; s < 2u && !bailed; ++s) {
+          if (!((pslots >> s) & 1u)) continue;
+          const gs_pairtab_dev &p = a.pt[s][strand];
+          const uint32_t lo = __builtin_amdgcn_readfirstlane(s ? sp_o1.x : sp_o0.x), hi = __builtin_amdgcn_readfirstlane(s ? sp_o1.y : sp_o0.y);
+          const uint32_t rem = p.sp_rem, remmask = (1u << rem) - 1u;
+          const uint2 *sprows = seed_sgprs(p.sp_rows);
+          vctx = seed_sgprs(p.ctx);
+          arow = seed_sgprs(p.rowid);
+          n_sp_items++;
+          if (hi > lo) {
+            n_sp_rows += hi - lo;
+            n_sp_max = hi - lo > n_sp_max ? hi - lo : n_sp_max;
+            if (((hi - lo) >> 3) >= a.share_min) n_hpass++;
+          }
+          for (uint32_t base = lo; base < hi; base += WAVE) {
+            if (guard_left == 0u) {
+              bailed = true;
+              break;
+            }
+            guard_left--;
+            const bool in = base + lane < hi;
+            uint2 pr = make_uint2(0u, 0u);
+            if (in) pr = sprows[base + lane];
+            count_lines(c_ctx, in, sprows + base + lane);
+            const uint32_t ox = ((pr.y >> rem) ^ pidx0) & omask;
+            const bool hit = in && ((pr.y ^ sp_key) & remmask) == 0u && (uint32_t)__popc((ox | (ox >> 1)) & 0x55555555u) == m;
+            const uint64_t bh = __ballot(hit);
+            if (!bh) continue;
+            uint32_t w = 0u;
+            if (hit) w = vctx[pr.x];
+            n_sp_hits += (uint32_t)__popcll(bh);
+            if constexpr (CNT) c_isa += (uint32_t)__popcll(bh);
+            /* the substitutions as seed_path spells a recipe's: the index holds step t at bits 2 (k-1-t), the path at PSG - 2 t */
+            const uint64_t opath = (uint64_t)seed_codes16((pr.y >> rem) & omask, pidx0 & omask) << (PSG + 2u - 2u * k);
+            resolve(hit, pr.x, SEED_HAS_PATH, w, m, opath);
+          }
+        }
+      }
       n_two++;
     }
 
@@ -856,6 +919,12 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
     if (n_fail) atomicAdd(&a.stats[6], (unsigned long long)n_fail);
     if (n_hpass) atomicAdd(a.hpass, n_hpass);
     if (bailed) atomicOr(a.err, 1u);
+    if (n_sp_items) {
+      atomicAdd(&a.spaced_ctr[0], n_sp_items);
+      atomicAdd(&a.spaced_ctr[1], n_sp_rows);
+      atomicMax(&a.spaced_ctr[2], n_sp_max);
+      atomicAdd(&a.spaced_ctr[3], n_sp_hits);
+    }
     if (n_two) {
       atomicAdd(&a.stats[4], (unsigned long long)n_two);
       atomicAdd(&a.stats[7], (unsigned long long)n_two);

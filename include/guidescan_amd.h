@@ -198,6 +198,11 @@ gs_status gs_index_last_counters(const gs_index *ix, uint64_t out[16]);
  * strand's side, [3] items a wave takes per visit to the work counter, [4] ... in the two seeding launches (0: another form
  * ran), [5] PAM-pair tables in use, [6] |X|, [7] rotated copies per strand table in place */
 gs_status gs_index_last_launch(const gs_index *ix, uint64_t out[8]);
+/* The spaced tables in the last gs_enumerate_device call (the seeding launches' lookups keyed on a guide's first |X| and last
+ * L - k symbols): [0] lookups (one per item and PAM-pair table; 0: the path did not run), [1] rows
+ * they read, [2] the most rows one lookup read, [3] rows that matched; and on the handle: [4] bytes of the tables,
+ * [5] microseconds their build took. */
+gs_status gs_index_last_spaced(const gs_index *ix, uint64_t out[6]);
 /* The last batch's heavy items (DESIGN.md sections 5.1, 5.3): [0] items of which at least one verification pass was
  * handed to other waves, [1] packages reserved in the queue, [2] packages the queue holds, [3] tickets the helping waves
  * drew; [4] guides with an item of more than 2^20 match records, which the per-guide tile ordering leaves to the
@@ -295,6 +300,16 @@ gs_status gs_debug_seed_recipes(uint32_t k, uint32_t L, uint32_t P, uint32_t m, 
                                 uint32_t deep, uint64_t *out, uint64_t cap, uint64_t counts[3]);
 void gs_debug_choose_thresholds(uint32_t m, uint32_t n_x, uint32_t n_o, uint32_t n_r, double pam_expansions,
                                 double verify_a, double verify_b, uint32_t astar[8]);
+/* This strand's share as it is read through PAM-pair tables (host only): the whole list, or (trimmed != 0) the list without
+ * the class "no substitution in X, all m in O", which a spaced table's lookup finds instead. */
+gs_status gs_debug_seed_recipes_a8(uint32_t k, uint32_t m, uint32_t n_x, const uint32_t *astar, uint32_t trimmed, uint64_t *out,
+                                   uint64_t cap, uint64_t *count);
+/* The rows under `key` (X symbols << 2 |R| | R symbols, both in consumption order) in the spaced table of a PAM-pair table
+ * slot and strand, four words per row: {row in the table's row arrays, its O symbols, its row in the strand's suffix array,
+ * its context word}; *n = rows under the key (out holds the first cap); info = {1 = the slot has spaced tables, pair code,
+ * context depth, |X|, |R|, table depth k, key bits stored with a row, rows of the table}.  Tests only. */
+gs_status gs_debug_spaced_rows(gs_index *ix, uint32_t slot, int strand, uint32_t key, uint32_t *out, uint64_t cap, uint64_t *n,
+                               uint32_t info[8]);
 /* What an item of the two seeding launches (gs_seed.hip) starts from: the 64-byte descriptor k_describe derives from a packed
  * guide record - q (2-bit codes in consumption order), four PAM patterns (3 bits per symbol, 4 = N) - for a batch shape
  * (table depth k, |X| = x_len, the PAM-pair codes of the table slots), as sixteen words: q lo, q hi, pam[4], meta, pidx0,
