@@ -184,6 +184,13 @@ def lib():
                                             C.POINTER(vp)]
     L.gs_debug_general_last.restype = i32
     L.gs_debug_general_last.argtypes = [vp, C.POINTER(u64)]
+    L.gs_debug_bulge_last.restype = i32
+    L.gs_debug_bulge_last.argtypes = [vp, C.POINTER(u64)]
+    L.gs_debug_bulge_seeds.restype = i32
+    L.gs_debug_bulge_seeds.argtypes = [C.c_char_p, u32, u32, u32, u32, u32, u32, u32, u32, vp, u64, C.POINTER(u64)]
+    L.gs_debug_bulge_verify.restype = i32
+    L.gs_debug_bulge_verify.argtypes = [u32, vp, u64, C.c_char_p, u32, C.c_char_p, u32, C.c_char_p, vp, u32, u32, u32, u32,
+                                        u32, u32, vp, u64, C.POINTER(u64)]
     L.gs_index_last_guide_flags.restype = i32
     L.gs_index_last_guide_flags.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.gs_format_guide_ex.restype = i32
@@ -259,12 +266,64 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_format_device_ids", "gs_enumerate_text_device", "gs_kmers_encode_ids", "gs_kmers_get_ids", "gs_kmers_csv",
            "gs_kmers_concat", "gs_decoder_open", "gs_decoder_close", "gs_decode_records", "gs_decode_records_device",
            "gs_decode_sam", "gs_debug_repr_doubles", "gs_debug_decode_tables",
-           "gs_index_last_spaced", "gs_debug_seed_recipes_a8", "gs_debug_spaced_rows"]
+           "gs_index_last_spaced", "gs_debug_seed_recipes_a8", "gs_debug_spaced_rows",
+           "gs_debug_bulge_last", "gs_debug_bulge_seeds", "gs_debug_bulge_verify"]
 
 
 def _check(rc):
     if rc != 0:
         raise GsError(rc, lib().gs_status_string(rc).decode())
+
+
+BULGE_SEED_DTYPE = np.dtype([("index", "<u4"), ("state", "<u4"), ("seq", "S32")])
+BULGE_MATCH_DTYPE = np.dtype([("state", "<u4"), ("consumed", "<u4"), ("seq", "S32")])
+
+
+def bulge_state(word):
+    """the fields of a state word of the bulge-aware search (gs_bulge_step.h)"""
+    word = int(word)
+    return dict(t=word & 63, mismatches=(word >> 6) & 7, dna_bulges=(word >> 9) & 7, rna_bulges=(word >> 12) & 7,
+                bulge_state=(word >> 15) & 3, bulge_size=(word >> 17) & 1, seq_len=(word >> 18) & 63)
+
+
+def bulge_seeds(guide, k, mismatches=0, rna_bulges=0, dna_bulges=0, start=False, prefix_len=0, prefix=0, count_only=False):
+    """the seeds of one guide in the seeded form of the bulge-aware search (gs_debug_bulge_seeds; host only): a
+    BULGE_SEED_DTYPE array, one entry per path of index.hpp:250-375's tree that consumes k genome symbols"""
+    g = guide.encode() if isinstance(guide, str) else bytes(guide)
+    flags = GS_FLAG_PAM_AT_START if start else 0
+    n = C.c_uint64(0)
+    _check(lib().gs_debug_bulge_seeds(g, len(g), k, mismatches, rna_bulges, dna_bulges, flags, prefix_len, prefix, None, 0,
+                                      C.byref(n)))
+    if count_only:
+        return int(n.value)
+    out = np.zeros(n.value, dtype=BULGE_SEED_DTYPE)
+    _check(lib().gs_debug_bulge_seeds(g, len(g), k, mismatches, rna_bulges, dna_bulges, flags, prefix_len, prefix,
+                                      out.ctypes.data, out.size, C.byref(n)))
+    assert n.value == out.size
+    return out
+
+
+def bulge_verify(state, seq, ctx_nibbles, guide, pam, k, alt_pams=(), mismatches=0, rna_bulges=0, dna_bulges=0, start=False):
+    """the matches one seed (state word, sequence bytes so far) reaches in a row whose 16-symbol left context is
+    ctx_nibbles (nearest first: 0..3 A,C,G,T, 4 N, 5 another symbol, 6 before the text start) - gs_debug_bulge_verify;
+    host only -> a BULGE_MATCH_DTYPE array"""
+    g = guide.encode() if isinstance(guide, str) else bytes(guide)
+    p = pam.encode() if isinstance(pam, str) else bytes(pam)
+    sq = np.frombuffer(bytes(seq).ljust(32, b"\0"), dtype=np.uint8).copy()
+    alts = "".join(alt_pams).encode()
+    lens = np.array([len(a) for a in alt_pams], dtype=np.uint32)
+    flags = GS_FLAG_PAM_AT_START if start else 0
+
+    def call(out, cap, n):
+        _check(lib().gs_debug_bulge_verify(int(state), sq.ctypes.data, int(ctx_nibbles), g, len(g), p if p else None, len(p),
+                                           alts if alt_pams else None, lens.ctypes.data if alt_pams else None,
+                                           len(alt_pams), k, mismatches, rna_bulges, dna_bulges, flags, out, cap, C.byref(n)))
+    n = C.c_uint64(0)
+    call(None, 0, n)
+    out = np.zeros(n.value, dtype=BULGE_MATCH_DTYPE)
+    call(out.ctypes.data, out.size, n)
+    assert n.value == out.size
+    return out
 
 
 def seed_recipes(k, L, P, m, n_x, astar=None, deep=False):
@@ -997,6 +1056,13 @@ class GenomeIndex:
         match records T, search passes, largest stack of any item, steps the room rule cut, steps without room]"""
         out = (C.c_uint64 * 8)()
         _check(lib().gs_debug_general_last(self._h, out))
+        return [int(x) for x in out]
+
+    def bulge_last(self):
+        """the same call's routing and the seeded form's counters (gs_debug_bulge_last): [guides seeded, guides walked,
+        seeds looked up, seeds with an empty interval, row nodes, interval nodes, exception-row lookups, largest stack]"""
+        out = (C.c_uint64 * 8)()
+        _check(lib().gs_debug_bulge_last(self._h, out))
         return [int(x) for x in out]
 
     def locked(self):

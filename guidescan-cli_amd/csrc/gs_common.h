@@ -225,6 +225,9 @@ struct gs_index {
   /* the last call of the general path (gs_debug_general_last): items, workgroups, the first pass's pool, records, search passes,
    * then k_search_general's three counters of the last pass: largest stack, steps the room rule cut, steps with no room at all */
   unsigned long long last_general[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  /* the same call's routing and the seeded form's counters (gs_debug_bulge_last): guides sent to the seeded form, guides that
+   * walked, seeds looked up, seeds with an empty interval, row nodes made, interval nodes made, exception-row lookups, largest stack */
+  unsigned long long last_bulge[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   std::vector<gs_nrun> nruns_text; /* 'N' runs of the forward text */
   gs_buffer w_cand;                /* literal-N candidate windows (device): kept from batch to batch of one shape */
   uint64_t cand_key = ~0ull;       /* (L, P, bucketed or not) w_cand was made for; ~0: nothing kept */

@@ -17,41 +17,10 @@
  * refuses, per guide, so that no input of the reference aborts a batch.
  */
 #include "gs_device.h"
+#include "gs_bulge_step.h" /* the node, record and argument layouts both forms of the search share */
 
 #include <rocprim/rocprim.hpp>
 
-#define GSTACK 1024 /* 48-byte nodes per wave: 48 KB, three single-wave workgroups per CU.  (512 nodes, six per CU: the room a pop of
-                        64 nodes needs - 11 children each - is never there, pops shrink to 17 lanes and the batch takes 3 x as long) */
-#define GFAN 12     /* children one node can push: 4 DNA-bulge + exact + 4 substitutions + RNA bulge + PAM hop (+1) */
-
-/* state word: t[5:0] mm[8:6] dna[11:9] rna[14:12] bulge_type[16:15] curr[17] slen[23:18] pamid[28:24] inpam[29] hop[30] */
-#define GM_T(m) ((m)&63u)
-#define GM_MM(m) (((m) >> 6) & 7u)
-#define GM_DNA(m) (((m) >> 9) & 7u)
-#define GM_RNA(m) (((m) >> 12) & 7u)
-#define GM_STATE(m) (((m) >> 15) & 3u)
-#define GM_CURR(m) (((m) >> 17) & 1u)
-#define GM_SLEN(m) (((m) >> 18) & 63u)
-#define GM_PAMID(m) (((m) >> 24) & 31u)
-#define GM_INPAM(m) (((m) >> 29) & 1u)
-#define GM_HOP(m) (((m) >> 30) & 1u)
-__device__ __forceinline__ uint32_t gm_make(uint32_t t, uint32_t mm, uint32_t dna, uint32_t rna, uint32_t state,
-                                            uint32_t curr, uint32_t slen, uint32_t pamid, uint32_t inpam,
-                                            uint32_t hop) {
-  return t | (mm << 6) | (dna << 9) | (rna << 12) | (state << 15) | (curr << 17) | (slen << 18) | (pamid << 24) |
-         (inpam << 29) | (hop << 30);
-}
-
-struct gs_gen_guide { /* one guide of the general path, prepared on the host */
-  uint8_t q[32];      /* query bytes in consumption order (process.hpp:63, index.hpp:218) */
-  uint8_t pam[8];     /* the guide's own PAM in consumption order */
-};
-struct gs_grec { /* one match, 48 bytes */
-  uint32_t seq[8]; /* match.sequence, bytes packed big-endian: word order == std::string order */
-  uint32_t sp, ep;
-  uint32_t meta; /* mm[2:0] dna[5:3] rna[8:6] index[9] slen[15:10] */
-  uint32_t g;
-};
 struct gs_grec_less {
   __host__ __device__ bool operator()(const gs_grec &a, const gs_grec &b) const {
     if (a.g != b.g) return a.g < b.g;
@@ -64,33 +33,6 @@ struct gs_grec_less {
     return a.sp < b.sp;
   }
 };
-
-struct gs_gsearch_args {
-  gs_strand_dev sd[2];
-  const gs_gen_guide *guides;
-  gs_grec *recs;             /* item s writes at recs[slot_off[s] ...]; nullptr = count only */
-  const uint64_t *slot_off;
-  /* slot_off == nullptr with recs: ONE pass - records go to recs[] in emission order through the counter pool_next
-   * (the device-wide sort that follows orders by guide first, so an item's records need not be neighbours);
-   * records beyond pool_cap are counted, not written: the host then runs the pass again with room for all */
-  unsigned long long *pool_next;
-  unsigned long long pool_cap;
-  uint32_t *counts;
-  uint32_t *work;   /* [0] work-queue head, [1] error flag (iteration bound hit), [4..5] pool_next, [8] the largest stack of any
-                       item, [9] steps the room rule cut, [10] steps without room for one lane's children (gs_debug_general_last) */
-  uint8_t alt[32][8]; /* alt PAM patterns in consumption order */
-  uint8_t plen[40];   /* symbols of pattern j (alt PAMs, then the guides' own at n_alt): the reference searches
-                         alt PAMs of any length next to the guides' PAM (process.hpp:51-56) */
-  uint32_t p_max;     /* the longest of them */
-  uint32_t n_items, L, P, m, n_alt, max_rna, max_dna;
-  uint32_t max_iter; /* per-item iteration bound */
-  uint32_t stack_cap; /* GS_GENERAL_STACK: `limit` is at most this many nodes (it can only lower the stack's use) */
-};
-
-__device__ __forceinline__ void gseq_append(uint32_t (&s)[8], uint32_t slen, uint32_t byte) {
-  if (slen < 32u) s[slen >> 2] |= byte << (8u * (3u - (slen & 3u)));
-}
-__device__ __forceinline__ uint32_t glower(uint32_t b) { return b | 0x20u; } /* A,C,G,T -> a,c,g,t */
 
 __global__ __launch_bounds__(WAVE) void k_search_general(gs_gsearch_args a) {
   __shared__ uint4 s_stack[GSTACK * 3];
@@ -109,7 +51,7 @@ __global__ __launch_bounds__(WAVE) void k_search_general(gs_gsearch_args a) {
     if (item >= a.n_items) break;
     const uint32_t n_guides = a.n_items >> 1;
     const uint32_t strand = item >= n_guides ? 1u : 0u;
-    const uint32_t guide = item - strand * n_guides;
+    const uint32_t guide = a.glist ? a.glist[item - strand * n_guides] : item - strand * n_guides;
     const uint32_t slot = 2u * guide + strand;
     const gs_gen_guide *gg = a.guides + guide;
     const gs_strand_dev &sd = a.sd[strand];
@@ -309,6 +251,9 @@ __global__ void k_gen_flags(const gs_grec *srt, uint64_t T, uint32_t *flag) {
     f = !(p.g == c.g && (p.meta & 7u) == (c.meta & 7u) && ((p.meta >> 9) & 1u) == ((c.meta >> 9) & 1u));
     if (!f)
       for (int i = 0; i < 8; i++) f = f || p.seq[i] != c.seq[i];
+    /* the seeded form's row records: one per row of a sequence, so the row is part of the key; duplicate paths to the same
+     * sequence still collapse, row by row */
+    if (!f) f = (c.meta & GREC_ROW) != 0u && p.sp != c.sp;
   }
   flag[r] = f ? 1u : 0u;
 }
@@ -342,7 +287,8 @@ __global__ __launch_bounds__(WAVE) void k_gen_locate(gs_glocate_args a) {
   gs_hit_ex *out = a.hits + a.offsets[m.g] + (a.hit_scan[r] - a.guide_first[m.g]);
   const uint32_t cnt = m.ep - m.sp + 1u;
   for (uint32_t h = lane_id(); h < cnt; h += WAVE) {
-    const uint64_t sa = a.sd[strand].sa[m.sp + h];
+    /* (a row record names the seed's row: the match begins GREC_CTX symbols before that suffix) */
+    const uint64_t sa = (uint64_t)a.sd[strand].sa[m.sp + h] - GREC_CTX(m.meta);
     gs_hit_ex o;
     o.pos = strand == 0 ? -(int64_t)sa : (int64_t)(a.genome_length - (sa + 1ull));
     for (int i = 0; i < 32; i++) o.seq[i] = (char)((m.seq[i >> 2] >> (8 * (3 - (i & 3)))) & 255u);
@@ -431,6 +377,7 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
   res->raw.assign(n, 0);
   if (n == 0) {
     memset(ix->last_general, 0, sizeof(ix->last_general));
+    memset(ix->last_bulge, 0, sizeof(ix->last_bulge));
     guard.p = nullptr;
     *out = res;
     return GS_OK;
@@ -444,7 +391,7 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
     gs_status get(size_t b) { return hipMalloc(&p, b ? b : 16) == hipSuccess ? GS_OK : GS_ERR_NOMEM; }
   };
   dbuf d_g, d_cnt, d_misc, d_off, d_a, d_b, d_flag, d_pos, d_uq, d_c64, d_scan, d_nm, d_nh, d_first, d_frec, d_goff,
-      d_hits, d_tmp;
+      d_hits, d_tmp, d_gl;
   /* query = reverse_complement(sequence) consumed right to left == complement of the guide left to
    * right (process.hpp:63, index.hpp:218); with --start the guide itself right to left; PAMs likewise */
   std::vector<gs_gen_guide> hg(n);
@@ -471,9 +418,9 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
   }
   GS_TRY(d_g.get(sizeof(gs_gen_guide) * n));
   GS_TRY(d_cnt.get(8 * n));
-  GS_TRY(d_misc.get(64));
+  GS_TRY(d_misc.get(256)); /* the walk's 16 words, then the seeded form's 16 and its five 64-bit counters (gs_bsearch_args::bwork) */
   GS_HIP(hipMemcpy(d_g.p, hg.data(), sizeof(gs_gen_guide) * n, hipMemcpyHostToDevice));
-  GS_HIP(hipMemset(d_misc.p, 0, 64));
+  GS_HIP(hipMemset(d_misc.p, 0, 256));
   sa.sd[0] = ix->strand[0].d;
   sa.sd[1] = ix->strand[1].d;
   sa.guides = (const gs_gen_guide *)d_g.p;
@@ -492,8 +439,46 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
   sa.stack_cap = 0xFFFFFFFFu;
   if (const char *e = gs_opt(ix, "GS_GENERAL_STACK")) sa.stack_cap = (uint32_t)std::min(std::max(1ll, atoll(e)), (long long)GSTACK);
   const uint32_t grid_max = (uint32_t)gs_num_cus(ix->device) * 3u; /* 48 KB of LDS per single-wave workgroup */
-  uint32_t grid = 2 * n32;
+  /* ---- which form searches which guide.  GS_BULGE_FORM=1: the seeded form (gs_bulge.hip) where the batch and the guide are
+   * eligible - the strand tables and the context arrays exist, every pattern symbol is one of A,C,G,T,N, every seed lies in
+   * the guide stage (L - rna_bulges >= k) and the context holds the rest of any match (L + dna_bulges + p_max - k <= 16);
+   * the guide's symbols are A,C,G,T.  Everything else walks, in the same call, into the same pool. */
+  uint32_t n_seed = 0, n_walk = n32;
+  gs_bsearch_args bs;
+  memset(&bs, 0, sizeof(bs));
+  {
+    const char *form = gs_opt(ix, "GS_BULGE_FORM");
+    const uint32_t k = ix->pt_k;
+    bool ok = form && atoi(form) == 1 && k != 0 && ix->strand[0].d.ptab && ix->strand[1].d.ptab && ix->strand[0].d.ctx &&
+              ix->strand[1].d.ctx && L >= rna_bulges + k && L + dna_bulges + p_max <= 16 + k;
+    auto acgtn = [](uint8_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'N'; };
+    for (uint32_t j = 0; ok && j < sa.n_alt; j++)
+      for (uint32_t u = 0; u < sa.plen[j]; u++) ok = ok && acgtn(sa.alt[j][u]);
+    for (uint64_t g = 0; ok && g < n; g++)
+      for (uint32_t u = 0; u < P; u++) ok = ok && acgtn(hg[g].pam[u]);
+    if (ok) {
+      std::vector<uint32_t> gl(n); /* the seeded guides from the front, the walking ones from the back */
+      for (uint32_t g = 0; g < n32; g++) {
+        bool base = true;
+        for (uint32_t t = 0; t < L; t++) base = base && acgtn(hg[g].q[t]) && hg[g].q[t] != 'N';
+        if (base)
+          gl[n_seed++] = g;
+        else
+          gl[n32 - 1u - (g - n_seed)] = g;
+      }
+      n_walk = n32 - n_seed;
+      GS_TRY(d_gl.get(4 * n));
+      GS_HIP(hipMemcpy(d_gl.p, gl.data(), 4 * n, hipMemcpyHostToDevice));
+    }
+    bs.k = k;
+    bs.rows = GS_BULGE_ROWS_DEFAULT;
+    if (const char *e = gs_opt(ix, "GS_BULGE_ROWS")) bs.rows = (uint32_t)std::min(std::max(0ll, atoll(e)), 0x7FFFFFFFll);
+    bs.bwork = (uint32_t *)d_misc.p + 16;
+  }
+  uint32_t grid = 2 * n_walk;
   if (grid > grid_max) grid = grid_max;
+  uint32_t grid_b = 2 * n_seed;
+  if (grid_b > grid_max) grid_b = grid_max;
   /* ONE search pass: records go to a pool through an atomic counter (the sort below orders by guide first).  The pool
    * is sized by a guess - 256 records per guide - and what does not fit is only counted: the pass then runs again with
    * room for all (the first version always searched twice: a counting pass, then a filling pass at exact offsets) */
@@ -521,28 +506,48 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
       cap = 1u << 12;
     }
     if (!d_a.p) GS_TRY(d_a.get(sizeof(gs_grec) * cap));
-    GS_HIP(hipMemset(d_misc.p, 0, 64));
+    GS_HIP(hipMemset(d_misc.p, 0, 256));
     sa.recs = (gs_grec *)d_a.p;
     sa.slot_off = nullptr;
     sa.pool_next = (unsigned long long *)((char *)d_misc.p + 16);
     sa.pool_cap = cap;
-    hipLaunchKernelGGL(k_search_general, dim3(grid), dim3(WAVE), 0, st, sa);
-    uint32_t h_misc[16] = {0};
-    GS_HIP(hipMemcpy(h_misc, d_misc.p, 64, hipMemcpyDeviceToHost));
+    if (n_seed) { /* the eligible guides: the seeded form, into the same pool */
+      bs.g = sa;
+      bs.g.glist = (const uint32_t *)d_gl.p;
+      bs.g.n_items = 2 * n_seed;
+      GS_TRY(gs_bulge_launch(bs, grid_b, st));
+      sa.glist = (const uint32_t *)d_gl.p + n_seed;
+      sa.n_items = 2 * n_walk;
+    }
+    if (n_walk) hipLaunchKernelGGL(k_search_general, dim3(grid), dim3(WAVE), 0, st, sa);
+    uint32_t h_misc[64] = {0};
+    GS_HIP(hipMemcpy(h_misc, d_misc.p, 256, hipMemcpyDeviceToHost));
     {
+      /* both reports of the pass, before anything can end the call: the two always speak of the same pass */
+      unsigned long long c64[5];
+      memcpy(c64, h_misc + 32, sizeof(c64));
+      const unsigned long long lb[8] = {n_seed, n_walk, c64[0], c64[1], c64[2], c64[3], c64[4], h_misc[23]};
+      memcpy(ix->last_bulge, lb, sizeof(lb));
       const unsigned long long lg[8] = {sa.n_items, grid, cap_first, ((unsigned long long)h_misc[5] << 32) | h_misc[4],
                                         (unsigned long long)attempt + 1u, h_misc[8], h_misc[9], h_misc[10]};
       memcpy(ix->last_general, lg, sizeof(lg));
     }
-    if (h_misc[1]) {
-      gs_set_error("internal: general search exceeded its iteration bound");
-      return GS_ERR_DEVICE;
-    }
     T = ((uint64_t)h_misc[5] << 32) | h_misc[4];
-    if (T <= cap) break;
-    if (attempt == 1) {
-      gs_set_error("internal: general search found more records the second time");
-      return GS_ERR_DEVICE;
+    const char *failed = (h_misc[17] & 2u)                    ? "internal: seeded bulge search pushed beyond its stack"
+                         : (h_misc[1] | (h_misc[17] & 1u))    ? "internal: general search exceeded its iteration bound"
+                         : (T > cap && attempt == 1)          ? "internal: general search found more records the second time"
+                                                              : nullptr;
+    if (failed || T <= cap) { /* the call's last pass: one GS_DEBUG line per call */
+      if (gs_opt(ix, "GS_DEBUG"))
+        fprintf(stderr, "[gs] bulge search: form %s, guides seeded %u walked %u, seeds %llu (empty %llu), row nodes %llu, interval nodes "
+                        "%llu, exception lookups %llu, largest stack %llu, rows threshold %u, passes %d\n",
+                n_seed ? "seeded" : "walk", n_seed, n_walk, ix->last_bulge[2], ix->last_bulge[3], ix->last_bulge[4], ix->last_bulge[5],
+                ix->last_bulge[6], ix->last_bulge[7], bs.rows, attempt + 1);
+      if (failed) {
+        gs_set_error(failed);
+        return GS_ERR_DEVICE;
+      }
+      break;
     }
     cap = T;
   }
@@ -680,6 +685,12 @@ extern "C" gs_status gs_debug_general_last(const gs_index *ix, uint64_t out[8]) 
   GS_HANDLE_LOCK(ix);
   if (!ix || !out) return GS_ERR_ARG;
   for (int i = 0; i < 8; i++) out[i] = ix->last_general[i];
+  return GS_OK;
+}
+extern "C" gs_status gs_debug_bulge_last(const gs_index *ix, uint64_t out[8]) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !out) return GS_ERR_ARG;
+  for (int i = 0; i < 8; i++) out[i] = ix->last_bulge[i];
   return GS_OK;
 }
 extern "C" gs_status gs_result_ex_get(const gs_result_ex *r, uint64_t *n_guides, const uint64_t **offsets,

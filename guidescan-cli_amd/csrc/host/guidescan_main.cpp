@@ -256,13 +256,17 @@ bool read_kmers(const std::string &path, std::vector<kmer_row> &rows, std::strin
   return true;
 }
 
+/* --bulge-form's default.  Measured at hg38 size (profiles/bulge_seeded.json): 4,096 guides at -m 1 with one
+ * bulge of each kind take the walk 0.22 s and the seeded form 1.10 s at best, so the walk stays the default */
+static const char *const BULGE_FORM_DEFAULT = "walk";
+
 int usage() {
   std::cerr << "usage: guidescan index [--index PREFIX] [--store-sa] [--sdsl] [--device D] GENOME.fa\n"
                "       guidescan kmers PREFIX -o KMERS [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S]\n"
                "                 [--start] [--chromosomes a,b,...] [--device D]\n"
                "       guidescan enumerate PREFIX (-f KMERS | --all-candidates) -o OUT [-m N] [-a PAM]... [--format csv|sam|bam]\n"
                "                 [--mode succinct|complete] [--max-off-targets N] [--start]\n"
-               "                 [--rna-bulges N] [--dna-bulges N] [-t THRESHOLD] [-n FORMAT_THREADS]\n"
+               "                 [--rna-bulges N] [--dna-bulges N] [--bulge-form walk|seeded] [-t THRESHOLD] [-n FORMAT_THREADS]\n"
                "                 [--device D] [--gpus N] [--batch-size B] [--encoder host|gpu]\n"
                "                 with --all-candidates: [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S]\n"
                "                 [--chromosomes a,b,...]\n"
@@ -851,6 +855,8 @@ int do_enumerate(int argc, char **argv) {
   /* GS_ENCODER: the default of --encoder (the end-to-end rows of a benchmark run either way with one command line) */
   std::string encoder = getenv("GS_ENCODER") ? getenv("GS_ENCODER") : "host";
   std::vector<std::string> alt_pams;
+  /* which form of the bulge-aware search serves a job with a bulge budget (gs_enumerate_general): the same lines either way */
+  std::string bulge_form = BULGE_FORM_DEFAULT;
   long long mismatches = 3, max_off = -1, threshold = -1, rna = 0, dna = 0;
   int device = 0, gpus = 1;
   size_t batch_size = 0;
@@ -880,6 +886,7 @@ int do_enumerate(int argc, char **argv) {
     else if (a == "-t" || a == "--threshold") threshold = atoll(need("-t"));
     else if (a == "--rna-bulges") rna = atoll(need("--rna-bulges"));
     else if (a == "--dna-bulges") dna = atoll(need("--dna-bulges"));
+    else if (a == "--bulge-form") bulge_form = need("--bulge-form");
     else if (a == "--max-off-targets") max_off = atoll(need("--max-off-targets"));
     else if (a == "--format") format = need("--format");
     else if (a == "--mode") mode = need("--mode");
@@ -907,6 +914,7 @@ int do_enumerate(int argc, char **argv) {
   if ((format != "csv" && format != "sam" && format != "bam") || (mode != "succinct" && mode != "complete")) return usage();
   if (gpus < 1 || mismatches < 0 || rna < 0 || dna < 0) return usage();
   if (encoder != "host" && encoder != "gpu") return usage();
+  if (bulge_form != "walk" && bulge_form != "seeded") return usage();
   enumerate_job job;
   job.encoder_gpu = encoder == "gpu";
   std::string err;
@@ -1037,6 +1045,8 @@ int do_enumerate(int argc, char **argv) {
       }
   }
   text = std::string();
+  if (rna > 0 || dna > 0)
+    for (gs_index *p : ix) gs_index_set_option(p, "GS_BULGE_FORM", bulge_form == "seeded" ? "1" : "0");
   std::cout << "Built the forward and reverse index on " << gpus << " device(s) from " << device << " in "
             << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s\n";
 

@@ -335,6 +335,41 @@ void gs_debug_search_form(const int64_t in[18], uint32_t out[6]);
  * lanes, steps that found no room for one lane's children (the pop is then one node)}.  A call that was refused
  * before its launch leaves the words as they were. */
 gs_status gs_debug_general_last(const gs_index *ix, uint64_t out[8]);
+/* The same call's routing between the two forms of the search, and what the seeded form's kernel met (tests pin them):
+ * out = {guides sent to the seeded form, guides sent to the walk, seeds looked up in the strand tables (the depth-k nodes of
+ * index.hpp:250-375's tree that the batch reached), seeds whose interval was empty, row nodes made, interval nodes made,
+ * exception-row lookups, the largest number of nodes any item's stack held}; the kernel's words are those of the last pass. */
+gs_status gs_debug_bulge_last(const gs_index *ix, uint64_t out[8]);
+/* The seeds of one guide as data (host only, no device needed): the depth-k nodes of the bulge-aware recursion
+ * (index.hpp:250-375, max_bulge_size = 1) with every base taken as present - each path stops where it has consumed k genome
+ * symbols.  One entry per path, duplicates included, in no particular order: the index into the strand table (consumption
+ * step t at bits 2(k-1-t)), the state word (t[5:0] mismatches[8:6] dna_bulges[11:9] rna_bulges[14:12] bulge state[16:15]
+ * bulge size[17] sequence length[23:18]) and match.sequence so far.  guide: L symbols of A,C,G,T; flags:
+ * GS_FLAG_PAM_AT_START.  prefix_len != 0 lists one sub-tree only: the paths whose first prefix_len consumed genome symbols are
+ * `prefix` (2 bits each, the first consumed highest - the top bits of the index); at k = 14 a guide has millions of seeds.
+ * *n = the seeds there are (out holds the first cap).  The function runs the transition function
+ * the seeded kernel runs (gs_bulge_step.h). */
+typedef struct gs_bulge_seed {
+  uint32_t index, state;
+  uint8_t seq[32];
+} gs_bulge_seed;
+gs_status gs_debug_bulge_seeds(const char *guide, uint32_t L, uint32_t k, uint32_t mismatches, uint32_t rna_bulges,
+                               uint32_t dna_bulges, uint32_t flags, uint32_t prefix_len, uint32_t prefix, gs_bulge_seed *out,
+                               uint64_t cap, uint64_t *n);
+/* The matches one seed reaches in one row, as data (host only): the rest of the same recursion, and the PAM stage
+ * (index.hpp:297-314 -> :125-170, alt PAMs first as process.hpp:51-56), run from a seed's state and sequence against the
+ * row's 16-symbol left context given as nibbles, nearest first: 0..3 A,C,G,T, 4 'N', 5 any other symbol, 6 before the
+ * text start.  One entry per path, duplicates included: the final state word, match.sequence, and the context symbols the
+ * match consumed (it begins that many symbols before the row's suffix).  Patterns over A,C,G,T,N; alt_pams: the n_alt
+ * patterns back to back, alt_lens[j] symbols each. */
+typedef struct gs_bulge_match {
+  uint32_t state, consumed;
+  uint8_t seq[32];
+} gs_bulge_match;
+gs_status gs_debug_bulge_verify(uint32_t state, const uint8_t seq[32], uint64_t ctx_nibbles, const char *guide, uint32_t L,
+                                const char *guide_pam, uint32_t P, const char *alt_pams, const uint32_t *alt_lens,
+                                uint32_t n_alt, uint32_t k, uint32_t mismatches, uint32_t rna_bulges, uint32_t dna_bulges,
+                                uint32_t flags, gs_bulge_match *out, uint64_t cap, uint64_t *n);
 
 /* Self-check of a resident index from the genome text alone (no suffix-array builder involved):
  * the suffix array of `strand` is a permutation of [0, n) (all rows), n_samples evenly spread
@@ -434,7 +469,14 @@ typedef struct gs_result_ex gs_result_ex;
  * fast path does not encode: guide symbols outside A,C,G,T (matched literally, else charged a
  * mismatch, :218-247), PAM symbols other than 'N' as literals (:125-170), up to 31 alt PAMs
  * (process.hpp:51-56).  Same set ordering and resolve() expansion; hits per guide in canonical order.
- * A slow path (one node per lane, comparator sort): gs_enumerate reports which guides need it. */
+ * A slow path (one node per lane, comparator sort): gs_enumerate reports which guides need it.
+ * Two forms of the search, the same result byte for byte.  The walk (the default) descends from the root with two Occ-block
+ * reads per node.  The seeded form (the handle's switch GS_BULGE_FORM=1) takes every path's first k = table depth genome
+ * symbols without reading anything, looks the k-mer up in the strand's interval table, and resolves a seed of at most
+ * GS_BULGE_ROWS rows (default 8; 0: never) row by row against the 16-symbol left context the index keeps per row; a
+ * larger seed is walked on.  It serves the guides over A,C,G,T of a batch whose patterns are over A,C,G,T,N, with
+ * L - rna_bulges >= k and L + dna_bulges + (longest pattern) - k <= 16; every other guide of the call walks.
+ * gs_debug_bulge_last reports the routing. */
 gs_status gs_enumerate_general(gs_index *ix, const char *guides, uint64_t n, uint32_t L,
                                const char *guide_pams, uint32_t P, const char *alt_pams, uint32_t n_alt,
                                uint32_t mismatches, uint32_t rna_bulges, uint32_t dna_bulges,
