@@ -67,6 +67,8 @@ class GsKmer(C.Structure):
 
 GS_TEXT_SAM = 0x100
 GS_TEXT_COMPLETE = 0x200
+GS_TEXT_BAM = 0x800    # gs_format_device / gs_enumerate_text: BAM alignment blocks in place of SAM lines
+GS_TEXT_BGZF = 0x1000  # with GS_TEXT_BAM: the blocks as BGZF members
 GS_DECODE_NO_HEADER = 0x400
 
 
@@ -241,6 +243,14 @@ def lib():
     L.gs_decode_sam.argtypes = [vp, vp, u64, u32, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
     L.gs_debug_repr_doubles.restype = i32
     L.gs_debug_repr_doubles.argtypes = [vp, u64, vp]
+    L.gs_bgzf_compress_device.restype = i32
+    L.gs_bgzf_compress_device.argtypes = [vp, vp, u64, vp, C.POINTER(vp), C.POINTER(u64)]
+    L.gs_bgzf_compress.restype = i32
+    L.gs_bgzf_compress.argtypes = [vp, vp, u64, C.POINTER(vp), C.POINTER(u64)]
+    L.gs_debug_huffman_lengths.restype = i32
+    L.gs_debug_huffman_lengths.argtypes = [vp, u32, u32, vp]
+    L.gs_debug_sp_float.restype = C.c_float
+    L.gs_debug_sp_float.argtypes = [u32]
     L.gs_debug_decode_tables.restype = i32
     L.gs_debug_decode_tables.argtypes = [vp, vp]
     L.gs_status_string.restype = C.c_char_p
@@ -267,7 +277,8 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_kmers_concat", "gs_decoder_open", "gs_decoder_close", "gs_decode_records", "gs_decode_records_device",
            "gs_decode_sam", "gs_debug_repr_doubles", "gs_debug_decode_tables",
            "gs_index_last_spaced", "gs_debug_seed_recipes_a8", "gs_debug_spaced_rows",
-           "gs_debug_bulge_last", "gs_debug_bulge_seeds", "gs_debug_bulge_verify"]
+           "gs_debug_bulge_last", "gs_debug_bulge_seeds", "gs_debug_bulge_verify",
+           "gs_bgzf_compress_device", "gs_bgzf_compress", "gs_debug_huffman_lengths", "gs_debug_sp_float"]
 
 
 def _check(rc):
@@ -592,6 +603,20 @@ def repr_doubles(values) -> list:
     return [r.tobytes().rstrip(b"\0").decode() for r in out]
 
 
+def huffman_lengths(freq, max_len=15) -> np.ndarray:
+    """the code lengths the BGZF compressor gives symbols with these counts, none above max_len (gs_debug_huffman_lengths;
+    host only: the function its kernel runs)"""
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    out = np.zeros(f.shape[0], np.uint8)
+    _check(lib().gs_debug_huffman_lengths(f.ctypes.data, f.shape[0], max_len, out.ctypes.data))
+    return out
+
+
+def sp_float(q) -> float:
+    """the float a BAM record's sp:f tag stores for a specificity printed as q / 10^6 (gs_debug_sp_float; host only)"""
+    return float(lib().gs_debug_sp_float(int(q)))
+
+
 def decode_tables():
     """the CFD tables the decoder uploads, keyed as the reference's score tables are -> (mm {key: float}, pam {pair: float})"""
     mm, pam = np.zeros(320), np.zeros(16)
@@ -908,16 +933,17 @@ class GenomeIndex:
                                      d_offsets_ptr, d_hits_ptr, stream, d_cfd_ptr, d_spec_ptr))
 
     def format_device(self, gs, d_guides_ptr, n, L, d_pams_ptr, P, ids, senses, skip, d_offsets_ptr, d_hits_ptr,
-                      d_spec_ptr, mismatches, sam=False, complete=True, start=False, max_off_targets=-1, stream=None):
+                      d_spec_ptr, mismatches, sam=False, complete=True, start=False, max_off_targets=-1, stream=None, bam=False, bgzf=False):
         """the database text of a fast-path batch encoded in HBM (gs_format_device): raw device addresses in (ids,
         senses and skip are host sequences, the last two may be None), (d_text_ptr, length) out - device memory of
-        the handle, valid until the next call on it; the bytes are those of format_guides"""
+        the handle, valid until the next call on it; the bytes are those of format_guides.  bam=True (in place of sam):
+        the SAM lines as BAM alignment blocks; bgzf=True with it: the blocks' BGZF members"""
         blob, off = _id_blob(ids)
         if len(ids) != n:
             raise ValueError("one id per guide")
         se, sk = _bytes_or_none(senses, n), _bytes_or_none(skip, n)
         flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
-                 (GS_FLAG_PAM_AT_START if start else 0))
+                 (GS_FLAG_PAM_AT_START if start else 0) | (GS_TEXT_BAM if bam else 0) | (GS_TEXT_BGZF if bgzf else 0))
         d_text, ln = C.c_void_p(), C.c_uint64()
         keep = C.create_string_buffer(blob, len(blob) + 1)
         _check(lib().gs_format_device(self._h, C.byref(gs), d_guides_ptr, n, L, d_pams_ptr, P, C.addressof(keep),
@@ -927,7 +953,7 @@ class GenomeIndex:
         return d_text.value, int(ln.value)
 
     def enumerate_text(self, seqs, pams, ids, senses, gs, mismatches=3, alt_pams=(), start=False, sam=False,
-                       complete=True, max_off_targets=-1, skip=None) -> bytes:
+                       complete=True, max_off_targets=-1, skip=None, bam=False, bgzf=False) -> bytes:
         """guides in, database text out (gs_enumerate_text): search, scoring and encoding on the device.  Raises
         GsError with status 3 (GS_ERR_UNSUPPORTED) when a guide of the batch needs the general path."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
@@ -944,7 +970,7 @@ class GenomeIndex:
         blob, off = _id_blob(ids)
         se, sk = _bytes_or_none(senses, n), _bytes_or_none(skip, n)
         flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
-                 (GS_FLAG_PAM_AT_START if start else 0))
+                 (GS_FLAG_PAM_AT_START if start else 0) | (GS_TEXT_BAM if bam else 0) | (GS_TEXT_BGZF if bgzf else 0))
         keep = C.create_string_buffer(blob, len(blob) + 1)
         out, ln = C.c_void_p(), C.c_uint64()
         _check(lib().gs_enumerate_text(self._h, seqs.ctypes.data, n, L, pams.ctypes.data if P else None, P,
@@ -958,12 +984,12 @@ class GenomeIndex:
 
     def format_device_ids(self, gs, d_guides_ptr, n, L, d_pams_ptr, P, d_ids_ptr, d_id_offsets_ptr, d_senses_ptr, skip,
                           d_offsets_ptr, d_hits_ptr, d_spec_ptr, mismatches, sam=False, complete=True, start=False,
-                          max_off_targets=-1, stream=None):
+                          max_off_targets=-1, stream=None, bam=False, bgzf=False):
         """format_device with ids, id offsets and senses that are in HBM already (gs_format_device_ids): raw device
         addresses; `skip` stays a host sequence or None"""
         sk = _bytes_or_none(skip, n)
         flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
-                 (GS_FLAG_PAM_AT_START if start else 0))
+                 (GS_FLAG_PAM_AT_START if start else 0) | (GS_TEXT_BAM if bam else 0) | (GS_TEXT_BGZF if bgzf else 0))
         d_text, ln = C.c_void_p(), C.c_uint64()
         _check(lib().gs_format_device_ids(self._h, C.byref(gs), d_guides_ptr, n, L, d_pams_ptr, P, d_ids_ptr,
                                           d_id_offsets_ptr, d_senses_ptr, sk.ctypes.data if sk is not None else None,
@@ -973,13 +999,13 @@ class GenomeIndex:
 
     def enumerate_text_device(self, d_guides_ptr, n, L, d_pams_ptr, P, d_ids_ptr, d_id_offsets_ptr, d_senses_ptr, gs,
                               mismatches=3, alt_pams=(), start=False, sam=False, complete=True, max_off_targets=-1,
-                              skip=None) -> bytes:
+                              skip=None, bam=False, bgzf=False) -> bytes:
         """enumerate_text over guides, ids and senses in HBM (gs_enumerate_text_device): only the text comes back.
         Raises GsError with status 3 when a guide needs the general path or 2L + 3P > 59."""
         alt = b"".join(p.encode() for p in alt_pams)
         sk = _bytes_or_none(skip, n)
         flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
-                 (GS_FLAG_PAM_AT_START if start else 0))
+                 (GS_FLAG_PAM_AT_START if start else 0) | (GS_TEXT_BAM if bam else 0) | (GS_TEXT_BGZF if bgzf else 0))
         out, ln = C.c_void_p(), C.c_uint64()
         _check(lib().gs_enumerate_text_device(self._h, d_guides_ptr, n, L, d_pams_ptr, P, alt if alt_pams else None,
                                               len(alt_pams), mismatches, flags, max_off_targets, C.byref(gs), d_ids_ptr,
@@ -999,6 +1025,25 @@ class GenomeIndex:
                                               len(alt_pams), mismatches, flags, -1, C.byref(gs), None, None, None, None,
                                               None, None, None, raw.ctypes.data))
         return raw
+
+    def bgzf_compress(self, raw) -> bytes:
+        """BGZF members of `raw` (bytes or a uint8 array), compressed on the device; no end-of-file block
+        (gs_bgzf_compress)"""
+        a = np.frombuffer(bytes(raw), dtype=np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw, dtype=np.uint8)
+        out, ln = C.c_void_p(), C.c_uint64()
+        _check(lib().gs_bgzf_compress(self._h, a.ctypes.data if a.size else None, a.size, C.byref(out), C.byref(ln)))
+        try:
+            return C.string_at(out.value, ln.value) if ln.value else b""
+        finally:
+            if out.value:
+                lib().gs_free(out)
+
+    def bgzf_compress_device(self, d_raw_ptr, raw_len, stream=None):
+        """BGZF members of raw_len bytes that are in HBM: (device pointer owned by the handle, length)
+        (gs_bgzf_compress_device)"""
+        out, ln = C.c_void_p(), C.c_uint64()
+        _check(lib().gs_bgzf_compress_device(self._h, d_raw_ptr, raw_len, stream, C.byref(out), C.byref(ln)))
+        return out.value, ln.value
 
     def last_text_offsets(self, n):
         """byte offset at which each guide's lines begin in the text of the last format_device / enumerate_text of n

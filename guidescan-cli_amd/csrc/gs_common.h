@@ -194,7 +194,9 @@ struct gs_index {
       w_cls, w_desc, w_sched, /* gs_seed.hip: descriptors per guide; work counters, histograms, the two schedules */
       w_t_plan, w_t_tiles, w_t_buckets, w_t_chunkof, w_t_big, w_t_rel, w_t_tab, w_t_excl, w_t_spill, w_b_redo_pos2,
       /* gs_textdev.hip: what gs_format_device uploads, its scratch, the of:H: fields, the text it returns; gs_enumerate_text's specificities */
-      w_text_in, w_text_tmp, w_text_hex, w_text, w_text_spec, w_text_goff /* per-guide text offsets */;
+      w_text_in, w_text_tmp, w_text_hex, w_text, w_text_spec, w_text_goff /* per-guide text offsets */,
+      /* gs_bgzf.hip: what gs_bgzf_compress uploads; token lists, sizes and the pieces' streams; the members it returns */
+      w_bgzf_in, w_bgzf_tmp, w_bgzf_out;
   uint32_t share_backoff = 0; /* batches this handle still runs without sharing after a sharing launch was not resident as a whole */
   bool share_timed_out = false; /* a helping wave gave up waiting for a package (k_search_body): the call fails, gs_enumerate_device redoes the batch without sharing */
   uint32_t opt_share_min = 512, opt_share_max = 2048; /* groups of eight rows: a verification pass of share_min or more is handed out, in packages of at most share_max (0: items are never shared) */

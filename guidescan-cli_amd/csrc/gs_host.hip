@@ -267,7 +267,12 @@ static gs_status enumerate_text(gs_index *ix, bool on_device, const void *guides
   const void *d_off = nullptr, *d_hits = nullptr, *d_text = nullptr;
   gs_result_view v;
   memset(&v, 0, sizeof v);
-  const uint32_t tflags = flags & (GS_TEXT_SAM | GS_TEXT_COMPLETE), sflags = flags & ~(GS_TEXT_SAM | GS_TEXT_COMPLETE);
+  const uint32_t text_bits = GS_TEXT_SAM | GS_TEXT_COMPLETE | GS_TEXT_BAM | GS_TEXT_BGZF;
+  const uint32_t tflags = flags & text_bits, sflags = flags & ~text_bits;
+  if ((tflags & GS_TEXT_BAM) && (tflags & GS_TEXT_SAM)) return GS_ERR_ARG;
+  if ((tflags & GS_TEXT_BGZF) && !(tflags & GS_TEXT_BAM)) return GS_ERR_ARG;
+  /* BAM records carry the SAM line's specificity */
+  const uint32_t score_flags = ((tflags & (GS_TEXT_SAM | GS_TEXT_BAM)) ? GS_TEXT_SAM : 0u) | (sflags & GS_FLAG_PAM_AT_START);
   rc = gs_enumerate_device(ix, d_g, n, L, d_p, P, alt_pams, n_alt, mismatches, sflags, nullptr, &d_off, &d_hits, &v);
   if (rc != GS_OK) return rc;
   if (stats) *stats = v;
@@ -285,7 +290,7 @@ static gs_status enumerate_text(gs_index *ix, bool on_device, const void *guides
   }
   uint64_t tl = 0;
   if (n) {
-    rc = gs_score_device(ix, d_g, n, L, P, tflags | (sflags & GS_FLAG_PAM_AT_START), max_off_targets, gs, d_off, d_hits, nullptr,
+    rc = gs_score_device(ix, d_g, n, L, P, score_flags, max_off_targets, gs, d_off, d_hits, nullptr,
                          nullptr, ix->w_text_spec.p);
     if (rc != GS_OK) return rc;
     const uint32_t fflags = tflags | (sflags & GS_FLAG_PAM_AT_START);

@@ -18,8 +18,11 @@
  * per distance (the cap counts kept hits, after the boundary drop: printer.hpp:129 - the CSV cap counts raw indices,
  * :259), and the of:H: field, which is composed once per guide into a scratch span (k_tx_sam_hex) and copied into each
  * of the guide's lines by the whole wave.
+ * GS_TEXT_BAM: a third row routine over the same sinks and the same SAM tables writes each SAM line as the BAM alignment
+ * block host/bam_writer.hpp makes of it (tx_bam_row); GS_TEXT_BGZF hands the blocks to gs_bgzf.hip.
  */
 #include "gs_device.h"
+#include "gs_bgzf_huff.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -30,6 +33,7 @@
 #define TX_MAX_ROW (1u << 25)    /* a row of this many bytes or more is refused: 64 of them stay below 2^31 */
 #define TX_ERR_ARG 1u
 #define TX_ERR_BIG 2u
+#define TX_ERR_ID 4u /* BAM: an id of more than 254 bytes (l_read_name is one byte and counts the NUL) */
 
 struct tx_args {
   const uint8_t *guides, *pams;   /* n*L, n*P ASCII */
@@ -54,6 +58,7 @@ struct tx_args {
   uint64_t slots, off0, n_hits;
   long long max_off, delim;
   uint32_t n, L, P, n_chr, m, start, sam, complete;
+  uint32_t bam; /* with sam: the lines as BAM alignment blocks (tx_bam_row) */
 };
 
 /* ---- small pieces -------------------------------------------------------------------------------------------- */
@@ -260,6 +265,8 @@ __device__ __forceinline__ void tx_guide_row(S &o, const tx_args &a, uint32_t g,
   if (nh) {
     if (!tx_spec_ok(__float_as_uint(a.spec[g]))) err |= TX_ERR_ARG;
     if ((uint32_t)(a.hits[a.offsets[g + 1u] - 1u].key >> 61) > a.m) err |= TX_ERR_ARG; /* the last hit has the largest distance */
+    /* BAM: a guide with lines (its first hit is at distance 0) whose id a record cannot hold */
+    if (a.bam && (uint32_t)(a.hits[a.offsets[g]].key >> 61) == 0u && a.id_off[g + 1u] > a.id_off[g] + 254u) err |= TX_ERR_ID;
     return;
   }
   if (a.sam) return;
@@ -383,12 +390,108 @@ __device__ __forceinline__ void tx_sam_row(S &o, const tx_args &a, uint32_t g, u
   o.ch('\n');
 }
 
+/* the same line as one BAM alignment block (SAMv1 section 4.2), field for field what host/bam_writer.hpp: bam::record
+ * derives from the SAM line above: the route of manual/manual.tex:581-582 over the lines of printer.hpp:302-360 */
+template <class S>
+__device__ __forceinline__ void tx_le(S &o, uint32_t v, uint32_t bytes) {
+  for (uint32_t i = 0; i < bytes; i++) o.ch((v >> (8u * i)) & 255u);
+}
+__device__ __forceinline__ uint32_t tx_reg2bin(uint32_t beg, uint32_t end) { /* SAMv1 section 5.3; beg < end <= 2^31 */
+  --end;
+  if (beg >> 14 == end >> 14) return 4681u + (beg >> 14);
+  if (beg >> 17 == end >> 17) return 585u + (beg >> 17);
+  if (beg >> 20 == end >> 20) return 73u + (beg >> 20);
+  if (beg >> 23 == end >> 23) return 9u + (beg >> 23);
+  if (beg >> 26 == end >> 26) return 1u + (beg >> 26);
+  return 0u;
+}
+__device__ __forceinline__ uint32_t tx_nt16(uint32_t c) { /* =ACMGRSVTWYHKDBN, lower case as upper, anything else N */
+  if (c >= 'a' && c <= 'z') c -= 32u;
+  switch (c) {
+    case '=': return 0;
+    case 'A': return 1;
+    case 'C': return 2;
+    case 'M': return 3;
+    case 'G': return 4;
+    case 'R': return 5;
+    case 'S': return 6;
+    case 'V': return 7;
+    case 'T': return 8;
+    case 'W': return 9;
+    case 'Y': return 10;
+    case 'H': return 11;
+    case 'K': return 12;
+    case 'D': return 13;
+    case 'B': return 14;
+    default: return 15;
+  }
+}
+/* symbol i of the line's SEQ field: the sequence as printed, or its reverse complement */
+__device__ __forceinline__ uint32_t tx_seq_at(const tx_args &a, uint32_t g, uint32_t i, bool pos_sense) {
+  const uint8_t *gd = a.guides + (size_t)g * a.L, *pm = a.pams + (size_t)g * a.P;
+  const uint32_t lp = a.L + a.P, j = pos_sense ? i : lp - 1u - i;
+  const uint32_t c = a.start ? (j < a.P ? pm[j] : gd[j - a.P]) : (j < a.L ? gd[j] : pm[j - a.L]);
+  return pos_sense ? c : tx_comp(c);
+}
+template <class S>
+__device__ __forceinline__ void tx_bam_row(S &o, const tx_args &a, uint32_t g, uint64_t h) {
+  if (a.skip && a.skip[g]) return;
+  const gs_hit hit = a.hits[h];
+  if ((uint32_t)(hit.key >> 61) != 0u) return;
+  const bool pos_sense = a.senses ? a.senses[g] != 0 : true;
+  const tx_loc loc = tx_resolve(a, (long long)hit.pos);
+  const uint64_t ib = a.id_off[g], ie = a.id_off[g + 1u];
+  const uint32_t idn = ie >= ib ? (uint32_t)(ie - ib) : 0u, lp = a.L + a.P; /* idn > 254: GS_ERR_ARG from the guide's slot */
+  const uint64_t hexn = a.complete ? 16u * (a.hex_off[g + 1u] - a.hex_off[g]) : 0u;
+  uint32_t tags = 7u; /* sp */
+  for (uint32_t d = 0; d <= a.m; d++) {
+    const uint32_t v = a.cnt[(size_t)g * 8u + d];
+    tags += 3u + (v <= 255u ? 1u : v <= 65535u ? 2u : 4u);
+  }
+  const uint64_t body = 32ull + idn + 1u + 4u + (lp + 1u) / 2u + lp + tags + (a.complete ? 4ull + hexn : 0ull);
+  const int32_t pos = loc.c >= 0 ? (int32_t)(loc.s - 1) : -1; /* POS - 1; the reference prints 0 with its empty RNAME */
+  tx_le(o, (uint32_t)body, 4);
+  tx_le(o, (uint32_t)(loc.c >= 0 ? loc.c : -1), 4);
+  tx_le(o, (uint32_t)pos, 4);
+  o.ch((idn + 1u) & 255u);
+  o.ch(100);
+  tx_le(o, pos < 0 ? 4680u : tx_reg2bin((uint32_t)pos, (uint32_t)pos + lp), 2);
+  tx_le(o, 1u, 2);
+  tx_le(o, pos_sense ? 0u : 16u, 2);
+  tx_le(o, lp, 4);
+  tx_le(o, 0xFFFFFFFFu, 4);
+  tx_le(o, 0xFFFFFFFFu, 4);
+  tx_le(o, 0u, 4);
+  tx_id(o, a, g);
+  o.ch(0);
+  tx_le(o, lp << 4, 4);
+  for (uint32_t i = 0; i < lp; i += 2u)
+    o.ch((tx_nt16(tx_seq_at(a, g, i, pos_sense)) << 4) | (i + 1u < lp ? tx_nt16(tx_seq_at(a, g, i + 1u, pos_sense)) : 0u));
+  for (uint32_t i = 0; i < lp; i++) o.ch(0xFF);
+  for (uint32_t d = 0; d <= a.m; d++) {
+    const uint32_t v = a.cnt[(size_t)g * 8u + d]; /* unfiltered */
+    o.ch('k');
+    o.ch('0' + d);
+    o.ch(v <= 255u ? 'C' : v <= 65535u ? 'S' : 'I');
+    tx_le(o, v, v <= 255u ? 1u : v <= 65535u ? 2u : 4u);
+  }
+  if (a.complete) {
+    TX_LIT(o, "ofH");
+    o.span(a.hex + 16u * a.hex_off[g], hexn);
+    o.ch(0);
+  }
+  TX_LIT(o, "spf");
+  tx_le(o, gb_sp_float_bits(tx_spec_q(__float_as_uint(a.spec[g]))), 4);
+}
+
 template <class S>
 __device__ __forceinline__ void tx_slot_row(S &o, const tx_args &a, uint64_t s0, uint64_t s, uint32_t &err) {
   const uint32_t g = tx_guide_of(a, s0, s);
   const uint64_t gs0 = tx_slot_of(a, g);
   if (s == gs0)
     tx_guide_row(o, a, g, err);
+  else if (a.bam)
+    tx_bam_row(o, a, g, a.offsets[g] + (s - gs0 - 1u));
   else if (a.sam)
     tx_sam_row(o, a, g, a.offsets[g] + (s - gs0 - 1u));
   else
@@ -580,6 +683,8 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
   *d_text = nullptr;
   *text_len = 0;
   ix->tx_n = 0;
+  if ((flags & GS_TEXT_BAM) && (flags & GS_TEXT_SAM)) return GS_ERR_ARG;
+  if ((flags & GS_TEXT_BGZF) && !(flags & GS_TEXT_BAM)) return GS_ERR_ARG;
   if (n == 0) return GS_OK;
   try {
     hipStream_t st = (hipStream_t)stream;
@@ -619,14 +724,14 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
     const uint64_t nh = ends[1] - ends[0];
     if (nh && !d_hits) return GS_ERR_ARG;
     ix->tx_n = 0;
-    if (nh >= (1ull << 32) && (flags & GS_TEXT_SAM)) { /* the SAM side tables count hits in 32 bits */
+    if (nh >= (1ull << 32) && (flags & (GS_TEXT_SAM | GS_TEXT_BAM))) { /* the SAM side tables count hits in 32 bits */
       gs_set_error("gs_format_device: SAM text of 2^32 hits or more in one batch");
       return GS_ERR_UNSUPPORTED;
     }
     const uint64_t slots = nh + n;
     if ((slots + WAVE - 1) / WAVE >= (1ull << 31)) return GS_ERR_UNSUPPORTED;
     const uint32_t n_tiles = (uint32_t)((slots + WAVE - 1) / WAVE);
-    const bool sam = (flags & GS_TEXT_SAM) != 0, complete = (flags & GS_TEXT_COMPLETE) != 0;
+    const bool bam = (flags & GS_TEXT_BAM) != 0, sam = bam || (flags & GS_TEXT_SAM) != 0, complete = (flags & GS_TEXT_COMPLETE) != 0;
 
     /* scratch: lengths, tile sums and offsets, the scans' temporary storage, the SAM tables */
     size_t tb_tiles = 0, tb_hits = 0, tb_guides = 0;
@@ -684,6 +789,7 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
     a.m = mismatches;
     a.start = (flags & GS_FLAG_PAM_AT_START) ? 1u : 0u;
     a.sam = sam ? 1u : 0u;
+    a.bam = bam ? 1u : 0u;
     a.complete = complete ? 1u : 0u;
 
     const uint32_t cus = (uint32_t)gs_num_cus(ix->device);
@@ -718,6 +824,10 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
       gs_set_error("gs_format_device: a specificity outside [0, 1], a distance beyond `mismatches`, a key that does not decode or id offsets that descend");
       return GS_ERR_ARG;
     }
+    if (err & TX_ERR_ID) {
+      gs_set_error("gs_format_device: an id of more than 254 bytes: a BAM record's l_read_name is one byte");
+      return GS_ERR_ARG;
+    }
     if (err & TX_ERR_BIG) {
       gs_set_error("gs_format_device: a line of 32 MB or more");
       return GS_ERR_UNSUPPORTED;
@@ -734,6 +844,8 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
     *d_text = ix->w_text.p;
     *text_len = total;
     ix->tx_n = n;
+    /* the records as BGZF members (gs_bgzf.hip): its output is a buffer of its own */
+    if (flags & GS_TEXT_BGZF) return gs_bgzf_compress_device(ix, ix->w_text.p, total, stream, d_text, text_len);
     return GS_OK;
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;

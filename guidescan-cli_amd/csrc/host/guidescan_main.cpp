@@ -23,6 +23,9 @@
  *       `enumerate -f` writes for that kmers file.  With --encoder gpu on one device the candidates, their ids and
  *       senses stay in HBM from the scan to the text (gs_enumerate_text_device); any other batch is copied to the
  *       host and takes the route of a kmers file's batch.
+ *       --format bam --bgzf gpu: batches that are all fast path leave the device as BGZF members (BAM records and
+ *       deflate made in HBM: gs_enumerate_text with GS_TEXT_BAM | GS_TEXT_BGZF); any other batch, and every batch
+ *       under the default --bgzf host, takes bam_writer.hpp's records and zlib.  Same records either way.
  *       --gpus N: one index per device (devices D .. D+N-1), one host thread per device pulling batches
  *       from a shared queue, output written in input order (src/guidescan.cxx:226-251 is the
  *       reference's fan-out over threads).  On every device the search of batch i+1 overlaps the text
@@ -267,7 +270,7 @@ int usage() {
                "       guidescan enumerate PREFIX (-f KMERS | --all-candidates) -o OUT [-m N] [-a PAM]... [--format csv|sam|bam]\n"
                "                 [--mode succinct|complete] [--max-off-targets N] [--start]\n"
                "                 [--rna-bulges N] [--dna-bulges N] [--bulge-form walk|seeded] [-t THRESHOLD] [-n FORMAT_THREADS]\n"
-               "                 [--device D] [--gpus N] [--batch-size B] [--encoder host|gpu]\n"
+               "                 [--device D] [--gpus N] [--batch-size B] [--encoder host|gpu] [--bgzf host|gpu]\n"
                "                 with --all-candidates: [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S]\n"
                "                 [--chromosomes a,b,...]\n"
                "       guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--verbose]\n"
@@ -450,6 +453,7 @@ struct batch {
   uint64_t text_len = 0;
   bool text_done = false;
   std::vector<uint64_t> text_goff; /* --format bam: where each guide begins in it, n + 1 entries */
+  bool text_members = false; /* --bgzf gpu: `text` holds the batch's BGZF members, ready for the file */
   std::string error;
   bool handed = false; /* a device thread took it (set under enumerate_job::mtx) */
   bool ready = false;
@@ -500,6 +504,12 @@ struct enumerate_job {
    * CSV / SAM encoder in HBM), any other batch - and one that answers GS_ERR_UNSUPPORTED - takes the host encoders */
   bool encoder_gpu = false;
   size_t enc_device = 0; /* batches the device encoded (under mtx); every other batch went to the host encoders */
+  /* --bgzf gpu (with --format bam): a batch that is all fast path leaves the device as BGZF members (gs_enumerate_text with
+   * GS_TEXT_BAM | GS_TEXT_BGZF: search, scoring, the record encoder and the compressor in HBM); any other batch takes the
+   * host's records and zlib.  Members are independent, so the file is one BAM either way. */
+  bool bgzf_gpu = false;
+  size_t bgzf_device = 0; /* batches the device compressed (under mtx) */
+  uint32_t text_flags() const { return bgzf_gpu ? (tflags & ~GS_TEXT_SAM) | GS_TEXT_BAM | GS_TEXT_BGZF : tflags; }
 };
 
 /* a part's SAM text -> BGZF-compressed BAM records (in place: the text is released) */
@@ -525,8 +535,9 @@ static void format_batch(enumerate_job &job, batch &b) {
     unsigned nt = job.bam ? job.fmt_threads : 1;
     if (nt < 1) nt = 1;
     if (nt > n) nt = (unsigned)n;
+    if (b.text_members) nt = 1;
     b.parts.assign(nt, text_part());
-    if (!job.bam) {
+    if (!job.bam || b.text_members) {
       b.parts[0].p = b.text;
       b.parts[0].n = (size_t)b.text_len;
       b.text = nullptr;
@@ -681,14 +692,14 @@ static bool search_batch_device(enumerate_job &job, gs_index *ix, batch &b, std:
     b.skip.assign(n, 0);
     for (size_t g = 0; g < n; g++) b.skip[g] = raw[g] > 1;
   }
-  rc = gs_enumerate_text_device(ix, d_g, n, cs.L, d_p, cs.P, job.alts.data(), n_alt, job.mismatches, job.sflags | job.tflags,
+  rc = gs_enumerate_text_device(ix, d_g, n, cs.L, d_p, cs.P, job.alts.data(), n_alt, job.mismatches, job.sflags | job.text_flags(),
                                 job.max_off, &job.cgs, cs.d_ids, cs.d_id_off + b.lo, cs.d_sense + b.lo,
                                 b.skip.empty() ? nullptr : (const uint8_t *)b.skip.data(), &b.text, &b.text_len, nullptr, nullptr);
   if (rc == GS_ERR_UNSUPPORTED) {
     b.skip.clear();
     return false;
   }
-  if (rc == GS_OK && job.bam) { /* this thread alone uses the handle: the last text is still this one */
+  if (rc == GS_OK && job.bam && !job.bgzf_gpu) { /* this thread alone uses the handle: the last text is still this one */
     b.text_goff.resize(n + 1);
     rc = gs_index_last_text_offsets(ix, b.text_goff.data(), n);
   }
@@ -699,7 +710,9 @@ static bool search_batch_device(enumerate_job &job, gs_index *ix, batch &b, std:
   {
     std::lock_guard<std::mutex> lk(job.mtx);
     job.enc_device++;
+    if (job.bgzf_gpu) job.bgzf_device++;
   }
+  b.text_members = job.bgzf_gpu;
   b.text_done = true;
   return true;
 }
@@ -791,7 +804,7 @@ static std::string search_batch_as(enumerate_job &job, gs_index *ix, batch &b, b
     for (size_t g = 0; g < n; g++) b.gen_of[g] = (uint32_t)g;
     return "";
   }
-  if (job.encoder_gpu && job.mismatches <= 7) {
+  if ((job.encoder_gpu || job.bgzf_gpu) && job.mismatches <= 7) {
     std::string ids;
     std::vector<uint64_t> id_off(n + 1, 0);
     std::vector<uint8_t> senses(n);
@@ -802,13 +815,15 @@ static std::string search_batch_as(enumerate_job &job, gs_index *ix, batch &b, b
       senses[g] = k.sense == "+" ? 1 : 0;
     }
     rc = gs_enumerate_text(ix, b.seqs.data(), n, L, b.pams.data(), P, job.alts.data(), n_alt, job.mismatches,
-                           job.sflags | job.tflags, job.max_off, &job.cgs, ids.data(), id_off.data(), senses.data(),
+                           job.sflags | job.text_flags(), job.max_off, &job.cgs, ids.data(), id_off.data(), senses.data(),
                            b.skip.empty() ? nullptr : (const uint8_t *)b.skip.data(), &b.text, &b.text_len, nullptr);
     {
       std::lock_guard<std::mutex> lk(job.mtx);
       if (rc == GS_OK) job.enc_device++;
+      if (rc == GS_OK && job.bgzf_gpu) job.bgzf_device++;
     }
-    if (rc == GS_OK && job.bam) { /* this thread alone uses the handle: the last text is still this one */
+    b.text_members = rc == GS_OK && job.bgzf_gpu;
+    if (rc == GS_OK && job.bam && !job.bgzf_gpu) { /* this thread alone uses the handle: the last text is still this one */
       b.text_goff.resize(n + 1);
       rc = gs_index_last_text_offsets(ix, b.text_goff.data(), n);
       if (rc != GS_OK) return gs_status_string(rc);
@@ -854,6 +869,7 @@ int do_enumerate(int argc, char **argv) {
   std::string prefix, kmers_file, output, format = "csv", mode = "complete";
   /* GS_ENCODER: the default of --encoder (the end-to-end rows of a benchmark run either way with one command line) */
   std::string encoder = getenv("GS_ENCODER") ? getenv("GS_ENCODER") : "host";
+  std::string bgzf = "host";
   std::vector<std::string> alt_pams;
   /* which form of the bulge-aware search serves a job with a bulge budget (gs_enumerate_general): the same lines either way */
   std::string bulge_form = BULGE_FORM_DEFAULT;
@@ -896,6 +912,7 @@ int do_enumerate(int argc, char **argv) {
     else if (a == "--gpus") gpus = atoi(need("--gpus"));
     else if (a == "--batch-size") batch_size = (size_t)atoll(need("--batch-size"));
     else if (a == "--encoder") encoder = need("--encoder");
+    else if (a == "--bgzf") bgzf = need("--bgzf");
     else if (!a.empty() && a[0] != '-' && prefix.empty()) prefix = a;
     else return usage();
   }
@@ -914,9 +931,11 @@ int do_enumerate(int argc, char **argv) {
   if ((format != "csv" && format != "sam" && format != "bam") || (mode != "succinct" && mode != "complete")) return usage();
   if (gpus < 1 || mismatches < 0 || rna < 0 || dna < 0) return usage();
   if (encoder != "host" && encoder != "gpu") return usage();
+  if ((bgzf != "host" && bgzf != "gpu") || (bgzf == "gpu" && format != "bam")) return usage();
   if (bulge_form != "walk" && bulge_form != "seeded") return usage();
   enumerate_job job;
   job.encoder_gpu = encoder == "gpu";
+  job.bgzf_gpu = bgzf == "gpu";
   std::string err;
   if (!read_gs(prefix + ".gs", job.gs, err)) {
     std::cerr << "error: " << err << "\n";
@@ -998,7 +1017,7 @@ int do_enumerate(int argc, char **argv) {
     cand.P = (uint32_t)co.pam.size();
     job.cand = &cand;
     /* 2L + 3P > 59: no batch fits the fast path's key, every one takes the host route */
-    job.cand_device = job.encoder_gpu && gpus == 1 && cand.L <= 31 && 2 * cand.L + 3 * cand.P <= 59;
+    job.cand_device = (job.encoder_gpu || job.bgzf_gpu) && gpus == 1 && cand.L <= 31 && 2 * cand.L + 3 * cand.P <= 59;
     std::cout << "Scanned " << cand.n << " candidate(s) of " << sel.size() << " chromosome(s) in "
               << std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count() << " s\n";
   } else {
@@ -1243,6 +1262,9 @@ int do_enumerate(int argc, char **argv) {
   if (job.encoder_gpu)
     std::cout << "Encoder: gpu (" << job.enc_device << " batch(es) encoded on the device, " << job.batches.size() - job.enc_device
               << " by the host encoders)\n";
+  if (job.bgzf_gpu)
+    std::cout << "encoder: bgzf gpu (" << job.bgzf_device << " batch(es) compressed on the device, " << job.batches.size() - job.bgzf_device
+              << " by the host's zlib)\n";
   for (gs_index *p : ix) gs_index_close(p);
   /* only a regular file is ever removed: -o /dev/stdout, a FIFO or a device node stays (written through pwrite they
    * fail with ESPIPE, and unlinking them would delete the node itself) */

@@ -417,6 +417,11 @@ typedef struct { /* the kmer fields the printers use, include/genomics/structure
 
 #define GS_TEXT_SAM 0x100u      /* --format sam (default csv) */
 #define GS_TEXT_COMPLETE 0x200u /* --mode complete */
+/* gs_format_device / gs_enumerate_text only.  GS_TEXT_BAM: the SAM lines as uncompressed BAM alignment blocks, no header
+ * block - what `samtools view -b` (manual/manual.tex:581-582) stores for the lines of printer.hpp:302-360; not together
+ * with GS_TEXT_SAM.  GS_TEXT_BGZF (only with GS_TEXT_BAM): those blocks as BGZF members (gs_bgzf_compress_device). */
+#define GS_TEXT_BAM 0x800u
+#define GS_TEXT_BGZF 0x1000u
 
 /* The database lines of one guide from its hit list (as returned by gs_enumerate, canonical
  * order).  Byte-exact replacement of get_csv_lines / get_sam_lines
@@ -544,7 +549,14 @@ gs_status gs_score(gs_index *ix, const char *guides, uint64_t n, uint32_t L, uin
  *   d_offsets, d_hits      : what gs_enumerate_device returned, or any CSR hit list in that layout (d_offsets[0] need
  *                            not be 0: hits are indexed by the offsets' values)
  *   d_specificity          : float[n] of gs_score_device for the same flags and max_off_targets
- *   flags                  : GS_FLAG_PAM_AT_START | GS_TEXT_SAM | GS_TEXT_COMPLETE
+ *   flags                  : GS_FLAG_PAM_AT_START | GS_TEXT_SAM | GS_TEXT_COMPLETE, or GS_TEXT_BAM [| GS_TEXT_BGZF] in
+ *                            place of GS_TEXT_SAM: one BAM alignment block per SAM line, byte for byte the block
+ *                            `guidescan sam2bam` makes of that line (refID -1, pos -1, bin 4680 for the reference's
+ *                            empty RNAME; MAPQ 100; one CIGAR op; quality 0xFF; k0..km as C, S or I; of:H in
+ *                            complete mode; sp:f the float nearest to the six printed decimals), d_specificity under
+ *                            the SAM rule; with GS_TEXT_BGZF *d_text holds the blocks' BGZF members instead.  An id of
+ *                            more than 254 bytes is GS_ERR_ARG; so are GS_TEXT_BAM with GS_TEXT_SAM, and GS_TEXT_BGZF
+ *                            without GS_TEXT_BAM.  gs_index_last_text_offsets gives the guides' places in the blocks.
  * *d_text (device memory owned by the handle, valid until the next call on it) holds *text_len bytes, no terminator.
  * GS_ERR_ARG, reported by the device together with the length: a specificity outside [0, 1] (gs_score_device never
  * produces one), a hit whose distance exceeds `mismatches`, a key that does not decode. */
@@ -572,7 +584,9 @@ gs_status gs_index_last_text_offsets(gs_index *ix, uint64_t *out, uint64_t n);
  * copied back through page-locked staging.  Replaces, for a batch, the per-guide pipeline from the search to the
  * output lines (include/genomics/process.hpp:35-158 with printer.hpp:115-360).  Host pointers in; *text is malloc'ed
  * (NUL terminated, *len bytes before the terminator): release with gs_free.  flags: those of gs_enumerate plus
- * GS_TEXT_SAM / GS_TEXT_COMPLETE.  GS_ERR_UNSUPPORTED and no text when a guide of the batch carries
+ * GS_TEXT_SAM / GS_TEXT_COMPLETE, or GS_TEXT_BAM [| GS_TEXT_BGZF] as gs_format_device takes them: *text then holds the
+ * batch's BAM alignment blocks, or their BGZF members - search, scoring, records and compressor all inside the library, the
+ * step of manual/manual.tex:581-582 over the lines of printer.hpp:302-360.  GS_ERR_UNSUPPORTED and no text when a guide of the batch carries
  * GS_GUIDE_NEEDS_GENERAL: the caller takes gs_enumerate + gs_enumerate_general + the host encoders for that batch.
  * stats (or NULL): the search's counters and timings; its pointers are NULL. */
 gs_status gs_enumerate_text(gs_index *ix, const char *guides, uint64_t n, uint32_t L, const char *guide_pams, uint32_t P,
@@ -593,6 +607,34 @@ gs_status gs_enumerate_text_device(gs_index *ix, const void *d_guides, uint64_t 
                                    int64_t max_off_targets, const gs_genome_structure *gs, const void *d_ids,
                                    const void *d_id_offsets, const void *d_senses, const uint8_t *skip, char **text,
                                    uint64_t *len, gs_result_view *stats, uint32_t *raw_hits);
+
+/* ---- BGZF on the device: the compression step of a BAM database ---------------------------------- */
+
+/* raw_len bytes in HBM -> BGZF members in HBM, back to back, no end-of-file block.  The reference writes SAM text only
+ * (include/genomics/printer.hpp:302-360) and its manual sends the user to `samtools view -b` for the BAM database
+ * (manual/manual.tex:581-582): this is that step's compressor, for bytes that are on the device already.
+ * `raw` is cut every 0xff00 bytes from its start (the last piece may be shorter; raw_len == 0 gives *out_len == 0).  Each
+ * piece becomes one gzip member: the 18-byte header 1f 8b 08 04 00000000 00 ff 0600 'B' 'C' 0200 BSIZE, one deflate
+ * block, the CRC-32 of the piece and ISIZE.  The block holds LZ77 matches (window 32,768, lengths 3..258) in dynamic
+ * Huffman codes; its header gives the code-length code's symbols 0..15 four bits each and writes every length without
+ * the repeat symbols.  A piece whose dynamic block would not be smaller is one stored block, so a member is never more
+ * than its piece + 31 bytes.  The bytes are a function of `raw` alone: the same on every call, and member k is what
+ * piece k gives by itself.  The handle lends its workspace and its lock; the index is not read.  *d_out belongs to the
+ * handle until its next gs_bgzf_compress* call; it is not the buffer gs_format_device returns. */
+gs_status gs_bgzf_compress_device(gs_index *ix, const void *d_raw, uint64_t raw_len, void *stream, const void **d_out,
+                                  uint64_t *out_len);
+/* The same with host pointers (manual/manual.tex:581-582, printer.hpp:302-360 as above); *out is malloc'ed: release
+ * with gs_free. */
+gs_status gs_bgzf_compress(gs_index *ix, const void *raw, uint64_t raw_len, uint8_t **out, uint64_t *out_len);
+/* Host only: the code lengths the compressor gives n (<= 288) symbols with counts freq[i] (< 2^23), none above max_len
+ * (<= 15): the function its kernel runs between the match search and the bit writer.  A complete code (Kraft sum 1)
+ * over the symbols with a count; one such symbol gets length 1, none gives all zeros.  GS_ERR_ARG when the symbols with
+ * a count do not fit max_len bits. */
+gs_status gs_debug_huffman_lengths(const uint32_t *freq, uint32_t n, uint32_t max_len, uint8_t *len);
+/* Host only: the float nearest to q / 10^6 (ties to even) for a specificity printed as the integer q of its six
+ * decimals, 0 <= q <= 10^6 (larger: 1.0): what the sp:f tag of a BAM record made from the SAM line of
+ * printer.hpp:302-360 stores (manual/manual.tex:581-582). */
+float gs_debug_sp_float(uint32_t q);
 
 /* ---- candidate-guide generation on the device ------------------- */
 
