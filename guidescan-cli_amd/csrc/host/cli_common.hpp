@@ -1,0 +1,200 @@
+/*
+ * cli_common.hpp -- what `guidescan index`, `kmers` and `enumerate` share: the readers of PREFIX.gs, PREFIX.dna and the
+ * kmers file, the options of the candidate scan, and the guard that closes a command's index handles.
+ */
+#ifndef GS_CLI_COMMON_HPP
+#define GS_CLI_COMMON_HPP
+
+#include <algorithm>
+#include <cstdlib>
+#include <fstream>
+#include <iostream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "guidescan_amd.h"
+
+namespace cli {
+
+struct genome_structure {
+  std::vector<std::string> names;
+  std::vector<uint64_t> lengths;
+};
+
+inline bool read_gs(const std::string &path, genome_structure &gs, std::string &err) { /* seq_io.cxx:124-144 */
+  std::ifstream in(path);
+  if (!in) {
+    err = "No genome structure file " + path;
+    return false;
+  }
+  std::string name, len;
+  while (std::getline(in, name) && std::getline(in, len)) {
+    char *end = nullptr;
+    const unsigned long long v = strtoull(len.c_str(), &end, 10);
+    if (end == len.c_str() || (*end && *end != '\r')) {
+      err = "malformed genome structure file " + path + ": length '" + len + "' of " + name;
+      return false;
+    }
+    gs.names.push_back(name);
+    gs.lengths.push_back(v);
+  }
+  return true;
+}
+
+/* what the candidate scan takes (scripts/generate_kmers.py:14-47) */
+struct candidate_opts {
+  std::string pam = "NGG", prefix;
+  long long k = 20, min_chr = 0;
+  bool start = false, have_chromosomes = false;
+  std::vector<std::string> chromosomes;
+};
+inline std::vector<std::string> split_commas(const std::string &v) {
+  std::vector<std::string> out;
+  std::stringstream ss(v);
+  std::string f;
+  while (std::getline(ss, f, ',')) out.push_back(f);
+  return out;
+}
+inline bool read_file(const std::string &path, std::string &text) {
+  std::ifstream in(path, std::ios::binary | std::ios::ate);
+  if (!in) return false;
+  text.resize((size_t)in.tellg());
+  in.seekg(0);
+  in.read(&text[0], (std::streamsize)text.size());
+  return (bool)in;
+}
+/* the chromosomes a candidate scan takes, in .gs order, and where each begins in the .dna text */
+inline bool select_chromosomes(const std::string &prefix, const genome_structure &gs, uint64_t dna_size, const candidate_opts &co,
+                        std::vector<size_t> &sel, std::vector<uint64_t> &begin, std::string &err) {
+  begin.assign(gs.lengths.size() + 1, 0);
+  for (size_t c = 0; c < gs.lengths.size(); c++) begin[c + 1] = begin[c] + gs.lengths[c];
+  if (begin.back() != dna_size) {
+    /* the reference counts untrimmed line lengths (seq_io.cxx:103): blanks at line ends make the two disagree */
+    err = "the chromosome lengths in " + prefix + ".gs sum to " + std::to_string(begin.back()) + " but " + prefix + ".dna holds " +
+          std::to_string(dna_size) + " bases: the chromosomes cannot be cut from it";
+    return false;
+  }
+  for (const std::string &want : co.chromosomes) {
+    bool found = false;
+    for (const std::string &n : gs.names) found = found || n == want;
+    if (!found) {
+      err = "--chromosomes: no chromosome named '" + want + "' in " + prefix + ".gs";
+      return false;
+    }
+  }
+  for (size_t c = 0; c < gs.names.size(); c++) {
+    if ((long long)gs.lengths[c] < co.min_chr) continue; /* scripts/generate_kmers.py:132 */
+    if (co.have_chromosomes && std::find(co.chromosomes.begin(), co.chromosomes.end(), gs.names[c]) == co.chromosomes.end()) continue;
+    sel.push_back(c);
+  }
+  return true;
+}
+/* one of the candidate options? (i advances over its value) */
+inline bool candidate_option(const std::string &a, int &i, int argc, char **argv, candidate_opts &co, bool &bad) {
+  auto val = [&]() -> const char * {
+    if (i + 1 >= argc) {
+      std::cerr << "error: " << a << " needs a value\n";
+      bad = true;
+      return "";
+    }
+    return argv[++i];
+  };
+  if (a == "--pam") co.pam = val();
+  else if (a == "--kmer-length") co.k = atoll(val());
+  else if (a == "--min-chr-length") co.min_chr = atoll(val());
+  else if (a == "--prefix") co.prefix = val();
+  else if (a == "--chromosomes") {
+    co.have_chromosomes = true;
+    for (auto &n : split_commas(val())) co.chromosomes.push_back(n);
+  } else return false;
+  return true;
+}
+
+struct kmer_row {
+  std::string id, sequence, pam, chromosome, sense;
+  long long position;
+};
+
+inline std::string trim_field(const std::string &s) { /* include/csv.hpp:1110-1116: ' ' and '\t' */
+  size_t b = 0, e = s.size();
+  while (b < e && (s[b] == ' ' || s[b] == '\t')) b++;
+  while (e > b && (s[e - 1] == ' ' || s[e - 1] == '\t')) e--;
+  return s.substr(b, e - b);
+}
+inline std::vector<std::string> split_csv(const std::string &line) {
+  std::vector<std::string> out;
+  size_t b = 0;
+  for (;;) {
+    const size_t c = line.find(',', b);
+    out.push_back(trim_field(line.substr(b, c == std::string::npos ? std::string::npos : c - b)));
+    if (c == std::string::npos) break;
+    b = c + 1;
+  }
+  return out;
+}
+/* src/genomics/kmer.cxx:9-25 */
+inline bool read_kmers(const std::string &path, std::vector<kmer_row> &rows, std::string &err) {
+  std::ifstream in(path);
+  if (!in) {
+    err = "cannot open kmers file";
+    return false;
+  }
+  std::string line;
+  if (!std::getline(in, line)) {
+    err = "empty kmers file";
+    return false;
+  }
+  if (!line.empty() && line.back() == '\r') line.pop_back();
+  const std::vector<std::string> header = split_csv(line);
+  const char *want[6] = {"id", "sequence", "pam", "chromosome", "position", "sense"};
+  int col[6];
+  for (int i = 0; i < 6; i++) {
+    col[i] = -1;
+    for (size_t j = 0; j < header.size(); j++)
+      if (header[j] == want[i]) col[i] = (int)j;
+    if (col[i] < 0) {
+      err = std::string("kmers file lacks column ") + want[i];
+      return false;
+    }
+  }
+  while (std::getline(in, line)) {
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.empty()) continue;
+    const std::vector<std::string> f = split_csv(line);
+    if (f.size() < header.size()) {
+      err = "kmers row with too few columns: " + line;
+      return false;
+    }
+    kmer_row r;
+    r.id = f[col[0]];
+    r.sequence = f[col[1]];
+    r.pam = f[col[2]];
+    r.chromosome = f[col[3]];
+    char *end = nullptr;
+    r.position = strtoll(f[col[4]].c_str(), &end, 10);
+    if (end == f[col[4]].c_str() || *end) {
+      err = "kmers position is not an integer: " + f[col[4]];
+      return false;
+    }
+    r.sense = f[col[5]];
+    rows.push_back(std::move(r));
+  }
+  return true;
+}
+
+/* the index handles of a command, one per device: closed when the command returns, whichever way */
+struct index_set {
+  std::vector<gs_index *> ix;
+  explicit index_set(size_t n) : ix(n, nullptr) {}
+  index_set(const index_set &) = delete;
+  index_set &operator=(const index_set &) = delete;
+  ~index_set() {
+    for (gs_index *p : ix)
+      if (p) gs_index_close(p);
+  }
+};
+
+}  // namespace cli
+
+#endif

@@ -132,7 +132,7 @@ namespace genomics {
                           uint32_t flags, std::vector<off_target_lists>* lists, std::vector<uint32_t>* raw) {
       /* the fast path carries match sequences of up to 59 key bits (23-mers with a four-symbol PAM: 58); where a batch
        * needs what only 52 bits allow (a shallow table, the device-wide ordering) it says GS_ERR_UNSUPPORTED and the
-       * general path - 100 x slower - takes the batch, as in host/guidescan_main.cpp */
+       * general path - 100 x slower - takes the batch, as in host/enumerate_cmd.hpp */
       bool general = rna != 0 || dna != 0 || 2 * L + 3 * P > 59;
       if (P)
         for (const auto& a : opts.alt_pams) general = general || a.size() != P;

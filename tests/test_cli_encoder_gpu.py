@@ -33,9 +33,9 @@ def indexed(toy, tmp_path_factory):
     return d
 
 
-def enumerate_twice(indexed, kmers, name, opts, batch_size=None):
+def enumerate_twice(indexed, kmers, name, opts, batch_size=None, env_extra=None):
     """-> (file written by the host encoders, file written with --encoder gpu, the gpu run's stdout)"""
-    env = dict(os.environ)
+    env = dict(os.environ, **(env_extra or {}))
     env.pop("GS_ENCODER", None)
     ext = "bam" if "bam" in opts else "sam" if "sam" in opts else "csv"
     outs, log = [], ""
@@ -90,12 +90,17 @@ def test_bam_is_the_same_file_with_ids_that_repeat(toy, indexed):
     assert gpu == host and encoded(log)[0] >= 2
 
 
-def test_a_batch_with_an_n_guide_falls_back_to_the_host_encoders(toy, indexed):
+def kmers_with_an_n_guide(toy, indexed):
     lines = (toy["dir"] / "kmers.csv").read_text().splitlines()
     f = lines[1].split(",")
     f[0], f[1] = "withN", f[1][:7] + "N" + f[1][8:]
     kmers = indexed / "kmers_n.csv"
     kmers.write_text("\n".join(lines[:4] + [",".join(f)] + lines[4:]) + "\n")
+    return kmers
+
+
+def test_a_batch_with_an_n_guide_falls_back_to_the_host_encoders(toy, indexed):
+    kmers = kmers_with_an_n_guide(toy, indexed)
     for name, opts in (("n_csv", ["-m", "2"]), ("n_sam", ["-m", "2", "--format", "sam"])):
         host, gpu, log = enumerate_twice(indexed, kmers, name, opts)
         assert gpu == host
@@ -107,3 +112,19 @@ def test_a_batch_with_an_n_guide_falls_back_to_the_host_encoders(toy, indexed):
     assert gpu == host
     on_device, on_host = encoded(log)
     assert on_device >= 1 and on_host == 1
+
+
+def test_two_workers_mixed_routes_and_the_threshold_keep_the_reference_file(toy, indexed):
+    """two device threads on one GPU pull batches of five guides: the batch that holds the N guide is counted for the
+    threshold through the fast path and, for that guide, the general path, then answers unsupported to the device encoder
+    and is redone by the host encoders, while the batches around it leave the device as text.  The writer must put them
+    back in input order: without the N guide's own lines both files are the reference's."""
+    kmers = kmers_with_an_n_guide(toy, indexed)
+    host, gpu, log = enumerate_twice(indexed, kmers, "n_t1_two_workers", ["-m", "2", "-t", "1", "--gpus", "2", "-n", "2"], batch_size=5,
+                                     env_extra={"GS_CLI_SAME_DEVICE": "1"})
+    assert gpu == host
+    gold = (toy["dir"] / "ref_m2_csv_t1.csv").read_bytes()
+    for got in (host, gpu):
+        assert b"".join(ln for ln in got.splitlines(keepends=True) if not ln.startswith(b"withN,")) == gold
+    on_device, on_host = encoded(log)
+    assert on_device >= 2 and on_host == 1

@@ -73,11 +73,22 @@ def test_usage_names_the_commands():
     assert r.returncode == 2 and "usage:" in r.stderr
 
 
+def test_a_rejected_alt_pam_is_an_option_error_and_leaves_no_output_file(tmp_path):
+    """-a takes 1 to 8 symbols: checked with the other options, before anything is read, built or created"""
+    out = tmp_path / "o.csv"
+    for bad in ("NNNNNNNNN", ""):
+        r = subprocess.run([str(CLI), "enumerate", str(tmp_path / "no_such_index"), "-f", str(tmp_path / "no_such_kmers.csv"), "-o", str(out),
+                            "-a", "NAG", "-a", bad], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 1 and r.stderr == f"error: alt PAM {bad}: 1 to 8 symbols\n"
+        assert not out.exists()
+
+
 def test_the_new_code_reads_no_environment_variable():
     """tests/test_abi.py's rule (no getenv in the library) for the files this feature touches, and for every getenv of the
     CLI: --all-candidates and `kmers` added none (GS_ENCODER and GS_CLI_SAME_DEVICE were there before)"""
     csrc = ol.ROOT / "guidescan-cli_amd" / "csrc"
     for name in ("gs_kmers.hip", "gs_textdev.hip", "gs_host.hip"):
         assert not re.findall(r"\bgetenv\s*\(", (csrc / name).read_text()), name
-    cli = (csrc / "host" / "guidescan_main.cpp").read_text()
+    cli = "".join(p.read_text() for p in sorted((csrc / "host").iterdir()))  # the CLI is every file under host/
+    assert len(re.findall(r"\bgetenv\b", cli)) == len(re.findall(r'getenv\("\w+"\)', cli))
     assert set(re.findall(r'getenv\("(\w+)"\)', cli)) == {"GS_ENCODER", "GS_CLI_SAME_DEVICE"}
