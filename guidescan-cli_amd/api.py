@@ -70,6 +70,7 @@ GS_TEXT_COMPLETE = 0x200
 GS_TEXT_BAM = 0x800    # gs_format_device / gs_enumerate_text: BAM alignment blocks in place of SAM lines
 GS_TEXT_BGZF = 0x1000  # with GS_TEXT_BAM: the blocks as BGZF members
 GS_DECODE_NO_HEADER = 0x400
+GS_DECODE_BAM_END = 0x2000  # gs_decode_bam: the data ends with these members (a cut record is an error)
 
 
 class GsDecodeBatch(C.Structure):
@@ -247,6 +248,22 @@ def lib():
     L.gs_bgzf_compress_device.argtypes = [vp, vp, u64, vp, C.POINTER(vp), C.POINTER(u64)]
     L.gs_bgzf_compress.restype = i32
     L.gs_bgzf_compress.argtypes = [vp, vp, u64, C.POINTER(vp), C.POINTER(u64)]
+    L.gs_bgzf_inflate.restype = i32
+    L.gs_bgzf_inflate.argtypes = [i32, vp, u64, C.POINTER(vp), C.POINTER(u64)]
+    L.gs_bgzf_inflate_device.restype = i32
+    L.gs_bgzf_inflate_device.argtypes = [vp, vp, u64, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    L.gs_bgzf_inflate_base.restype = i32
+    L.gs_bgzf_inflate_base.argtypes = [vp, u64, u64]
+    L.gs_debug_inflate_member.restype = i32
+    L.gs_debug_inflate_member.argtypes = [vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u32)]
+    L.gs_debug_bgzf_members.restype = i32
+    L.gs_debug_bgzf_members.argtypes = [vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u32)]
+    L.gs_decode_bam.restype = i32
+    L.gs_decode_bam.argtypes = [vp, vp, u64, u64, vp, u32, u32, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.gs_decode_bam_device.restype = i32
+    L.gs_decode_bam_device.argtypes = L.gs_decode_bam.argtypes
+    L.gs_debug_decode_bam_last.restype = i32
+    L.gs_debug_decode_bam_last.argtypes = [vp, vp, vp]
     L.gs_debug_huffman_lengths.restype = i32
     L.gs_debug_huffman_lengths.argtypes = [vp, u32, u32, vp]
     L.gs_debug_sp_float.restype = C.c_float
@@ -278,7 +295,9 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_decode_sam", "gs_debug_repr_doubles", "gs_debug_decode_tables",
            "gs_index_last_spaced", "gs_debug_seed_recipes_a8", "gs_debug_spaced_rows",
            "gs_debug_bulge_last", "gs_debug_bulge_seeds", "gs_debug_bulge_verify",
-           "gs_bgzf_compress_device", "gs_bgzf_compress", "gs_debug_huffman_lengths", "gs_debug_sp_float"]
+           "gs_bgzf_compress_device", "gs_bgzf_compress", "gs_debug_huffman_lengths", "gs_debug_sp_float",
+           "gs_bgzf_inflate", "gs_bgzf_inflate_device", "gs_bgzf_inflate_base", "gs_debug_inflate_member", "gs_debug_bgzf_members",
+           "gs_decode_bam", "gs_decode_bam_device", "gs_debug_decode_bam_last"]
 
 
 def _check(rc):
@@ -612,6 +631,42 @@ def huffman_lengths(freq, max_len=15) -> np.ndarray:
     return out
 
 
+def inflate_bgzf(data: bytes, device=0) -> bytes:
+    """the bytes of BGZF members, inflated on the GPU (gs_bgzf_inflate); GsError(GS_ERR_FORMAT) names the first member
+    that fails, its byte offset and the reason"""
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(lib().gs_bgzf_inflate(device, data, len(data), C.byref(out), C.byref(ln)))
+    raw = C.string_at(out, ln.value)
+    lib().gs_free(out)
+    return raw
+
+
+def inflate_member(member: bytes):
+    """one BGZF member through the function the inflate kernel's lane runs (gs_debug_inflate_member; host only)
+    -> (bytes made, reason: 0 when the member is sound)"""
+    isize = int.from_bytes(member[-4:], "little") if len(member) >= 4 else 0
+    cap = min(isize, 65536)
+    out = np.zeros(max(cap, 1), np.uint8)
+    ln, reason = C.c_uint64(), C.c_uint32()
+    rc = lib().gs_debug_inflate_member(member, len(member), out.ctypes.data, cap, C.byref(ln), C.byref(reason))
+    if rc != 0 and reason.value == 0:
+        _check(rc)
+    return out[:ln.value].tobytes(), reason.value
+
+
+def bgzf_members(data: bytes):
+    """the member table's walk (gs_debug_bgzf_members; host only) -> ([(offset, ISIZE)], reason); a refused member ends the
+    list, reason says why"""
+    n, reason = C.c_uint64(), C.c_uint32()
+    rc = lib().gs_debug_bgzf_members(data, len(data), None, None, 0, C.byref(n), C.byref(reason))
+    cap = n.value
+    off, isz = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint32)
+    rc = lib().gs_debug_bgzf_members(data, len(data), off.ctypes.data, isz.ctypes.data, cap, C.byref(n), C.byref(reason))
+    if rc != 0 and reason.value == 0:
+        _check(rc)
+    return [(int(off[i]), int(isz[i])) for i in range(cap)], reason.value
+
+
 def sp_float(q) -> float:
     """the float a BAM record's sp:f tag stores for a specificity printed as q / 10^6 (gs_debug_sp_float; host only)"""
     return float(lib().gs_debug_sp_float(int(q)))
@@ -704,6 +759,56 @@ class Decoder:
         s = C.string_at(out, ln.value).decode("latin-1")
         lib().gs_free(out)
         return s
+
+    def inflate_base(self, members_before=0, bytes_before=0):
+        """where the next calls' members lie in their file: added to the index and offset an error names (gs_bgzf_inflate_base)"""
+        _check(lib().gs_bgzf_inflate_base(self._h, members_before, bytes_before))
+
+    def inflate_bgzf(self, data: bytes, keep=0) -> bytes:
+        """BGZF members inflated into the decoder's workspace (gs_bgzf_inflate_device), `keep` bytes of the call before in
+        front; copied back from HBM here"""
+        out, ln, nm = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _check(lib().gs_bgzf_inflate_device(self._h, data, len(data), keep, C.byref(out), C.byref(ln), C.byref(nm)))
+        self.last_members = nm.value
+        if ln.value == 0:
+            return b""
+        hip = C.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        host = np.empty(ln.value, dtype=np.uint8)
+        if hip.hipMemcpy(host.ctypes.data, out, ln.value, 2) != 0:
+            raise GsError(2, "copy of the inflated bytes")
+        return host.tobytes()
+
+    def decode_bam(self, bgzf: bytes, skip=0, ref_to_sq=(), complete=False, first_record=0, end=False, on_device=False):
+        """whole BGZF members of a BAM database -> (rows without the header line, complete records, bytes of a cut record
+        that the decoder keeps for the next call) (gs_decode_bam; on_device: gs_decode_bam_device, the text copied back
+        here).  skip: inflated bytes of the BAM header, in the first call of a file; ref_to_sq: the binary reference
+        list's entries as indices into sq (negative: none); end: the data ends here"""
+        flags = (GS_TEXT_COMPLETE if complete else 0) | (GS_DECODE_BAM_END if end else 0)
+        m = np.ascontiguousarray(ref_to_sq, dtype=np.int32)
+        out, ln, n, tail = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        fn = lib().gs_decode_bam_device if on_device else lib().gs_decode_bam
+        _check(fn(self._h, bgzf, len(bgzf), skip, m.ctypes.data if m.size else None, m.size, flags, first_record,
+                  C.byref(out), C.byref(ln), C.byref(n), C.byref(tail)))
+        if on_device:
+            host = np.empty(ln.value, dtype=np.uint8)
+            if ln.value:
+                hip = C.CDLL("libamdhip64.so")
+                hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+                if hip.hipMemcpy(host.ctypes.data, out, ln.value, 2) != 0:
+                    raise GsError(2, "copy of the decoded text")
+            text = host.tobytes().decode("latin-1")
+        else:
+            text = C.string_at(out, ln.value).decode("latin-1")
+            lib().gs_free(out)
+        return text, n.value, tail.value
+
+    def decode_bam_last(self):
+        """the last decode_bam call: ({members, compressed, inflated, records}, {inflate, starts, fields, decode} in ms)"""
+        c, ms = np.zeros(4, np.uint64), np.zeros(4, np.float64)
+        _check(lib().gs_debug_decode_bam_last(self._h, c.ctypes.data, ms.ctypes.data))
+        return (dict(zip(("members", "compressed", "inflated", "records"), (int(x) for x in c))),
+                dict(zip(("inflate", "starts", "fields", "decode"), (float(x) for x in ms))))
 
     def close(self):
         if self._h:

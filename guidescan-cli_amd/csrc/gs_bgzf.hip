@@ -17,12 +17,14 @@
  *             A block that would not be smaller than the stored form is stored.
  *   bits      header fields and tokens are one list of (value, width) items, 64 per step: a scan of the widths gives
  *             the bit offsets, every lane ORs its value into an LDS window, whole words go out, the open word is carried.
- *   CRC-32    every lane folds a slice byte by byte, multiplies by x^(8 * bytes behind the slice) and the wave XORs.
+ *   CRC-32    every lane folds a slice byte by byte, multiplies by x^(8 * bytes behind the slice) and the wave XORs
+ *             (gs_bgzf_crc.h: the inflater checks members with the same routine).
  * k_bgzf_pack then lays the members back to back at the prefix sums of their sizes.
  * Nothing depends on timing: the bytes of member k are a function of piece k alone.  No workgroup waits for another.
  */
 #include "gs_device.h"
 #include "gs_bgzf_huff.h"
+#include "gs_bgzf_crc.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -92,11 +94,7 @@ __global__ __launch_bounds__(WAVE) void k_bgzf_piece(const uint8_t *raw, uint64_
   __shared__ gb_plan s_plan;
   const uint32_t lane = lane_id();
   uint32_t *tok = tokens + (size_t)blockIdx.x * BZ_PIECE;
-  for (uint32_t i = lane; i < 256u; i += WAVE) { /* the byte table of the reflected polynomial */
-    uint32_t c = i;
-    for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
-    s_crc[i] = c;
-  }
+  gb_crc_table(s_crc);
   for (uint32_t piece = blockIdx.x; piece < n_pieces; piece += gridDim.x) {
     const uint8_t *d = raw + (uint64_t)piece * BZ_PIECE;
     const uint64_t left = raw_len - (uint64_t)piece * BZ_PIECE;
@@ -223,16 +221,11 @@ __global__ __launch_bounds__(WAVE) void k_bgzf_piece(const uint8_t *raw, uint64_
     }
 
     /* ---- CRC-32 ---- */
-    const uint32_t slice = ((n + WAVE - 1u) / WAVE + 3u) & ~3u;
-    const uint32_t b0 = lane * slice < n ? lane * slice : n, b1 = b0 + slice < n ? b0 + slice : n;
-    uint32_t crc = lane == 0u ? 0xFFFFFFFFu : 0u;
-    for (uint32_t i = b0; i < b1; i++) crc = s_crc[(crc ^ d[i]) & 255u] ^ (crc >> 8);
-    crc = gb_crc_mul(gb_crc_shift(n - b1), crc);
-    for (int o = 32; o >= 1; o >>= 1) crc ^= (uint32_t)__shfl_xor((int)crc, o);
+    const uint32_t crc = gb_crc_wave(d, n, s_crc); /* gs_bgzf_crc.h */
     if (lane == 0u) {
       bz_meta m;
       m.len = stored ? n + 5u : dyn_bytes;
-      m.crc = crc ^ 0xFFFFFFFFu;
+      m.crc = crc;
       m.stored = stored ? 1u : 0u;
       m.pad = 0u;
       meta[piece] = m;

@@ -36,6 +36,7 @@
 #include "cfd_table.h"
 #include "gs_pow5_table.h"
 #include "gs_repr.h"
+#include "gs_decoder.h"
 
 #define DC_WAVES 4
 #define DC_LDS 12288u         /* bytes of a wave's slice */
@@ -54,20 +55,6 @@
 
 __constant__ double c_dc_mm[320]; /* [(r * 4 + d) * 20 + i]: r of A,C,G,U, d of A,C,G,T */
 __constant__ double c_dc_pam[16];
-
-struct gs_decoder {
-  std::recursive_mutex mtx;
-  int device = 0;
-  uint32_t n_chr = 0;
-  uint64_t total = 0;
-  std::vector<std::string> names;
-  gs_buffer text, tabs; /* the FASTA bytes; prefix sums, text offsets, record lengths, name offsets, names, powers of five */
-  const uint64_t *d_cum = nullptr, *d_toff = nullptr, *d_flen = nullptr;
-  const uint32_t *d_name_off = nullptr;
-  const uint8_t *d_names = nullptr;
-  gs_pow5_tables pw{nullptr, nullptr};
-  gs_buffer w_in, w_tmp, w_text;
-};
 
 struct dc_args {
   /* the batch */
@@ -617,6 +604,12 @@ extern "C" void gs_decoder_close(gs_decoder *d) {
   gs_buffer_free(d->w_in);
   gs_buffer_free(d->w_tmp);
   gs_buffer_free(d->w_text);
+  gs_buffer_free(d->w_bi_in);
+  gs_buffer_free(d->w_bi_tmp);
+  gs_buffer_free(d->w_inf[0]);
+  gs_buffer_free(d->w_inf[1]);
+  gs_buffer_free(d->w_bs_tmp);
+  gs_buffer_free(d->w_bs_rec);
   delete d;
 }
 
@@ -631,7 +624,6 @@ static gs_status decode_device(gs_decoder *d, const gs_decode_batch *b, uint32_t
   hipStream_t st = nullptr;
   GS_HIP(hipSetDevice(d->device));
   gs_status rc;
-  const bool complete = (flags & GS_TEXT_COMPLETE) != 0;
   /* the words of each record: whole groups of 16 digits (what is left over fails on the device, with the record) */
   std::vector<uint64_t> word_off(n + 1, 0);
   for (uint64_t r = 0; r < n; r++) {
@@ -668,7 +660,37 @@ static gs_status decode_device(gs_decoder *d, const gs_decode_batch *b, uint32_t
   uint8_t *din = (uint8_t *)d->w_in.p;
   GS_HIP(hipMemcpyAsync(din, host.data(), i_hex, hipMemcpyHostToDevice, st));
   if (hxb) GS_HIP(hipMemcpyAsync(din + i_hex, b->hex + hx0, hxb, hipMemcpyHostToDevice, st));
+  gs_decode_batch_dev db;
+  db.ids = din + i_ids;
+  db.seqs = din + i_seqs;
+  db.hex = din + i_hex;
+  db.reverse = din + i_rev;
+  db.id_off = (const uint64_t *)(din + i_idoff);
+  db.seq_off = (const uint64_t *)(din + i_sqoff);
+  db.hex_off = (const uint64_t *)(din + i_hxoff);
+  db.word_off = (const uint64_t *)(din + i_woff);
+  db.chr = (const int32_t *)(din + i_chr);
+  db.pos0 = (const int64_t *)(din + i_pos);
+  return gs_decode_run_device(d, db, n, nw, flags, first_record, b, d_text, text_len, n_rows);
+}
 
+/* the kernels over a batch whose arrays are in HBM already (decode_device uploads them; gs_bamsplit.hip makes them there).
+ * hb: the same batch on the host, or nullptr: the id of a record that fails is then fetched from the device */
+gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uint64_t n, uint64_t nw, uint32_t flags, uint64_t first_record,
+                               const gs_decode_batch *b, const void **d_text, uint64_t *text_len, uint64_t *n_rows) {
+  *d_text = nullptr;
+  *text_len = 0;
+  if (n_rows) *n_rows = 0;
+  if (n == 0) return GS_OK;
+  if (n >= (1ull << 31)) return GS_ERR_UNSUPPORTED;
+  if (nw >= DC_NONE - 1u) {
+    gs_set_error("gs_decode: 2^32 off-target words or more in one batch");
+    return GS_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = nullptr;
+  GS_HIP(hipSetDevice(d->device));
+  gs_status rc;
+  const bool complete = (flags & GS_TEXT_COMPLETE) != 0;
   const uint64_t slots = complete ? nw : n;
   const uint32_t n_tiles = (uint32_t)((slots + WAVE - 1) / WAVE);
   size_t tb_next = 0, tb_rank = 0, tb_tiles = 0;
@@ -686,16 +708,16 @@ static gs_status decode_device(gs_decoder *d, const gs_decode_batch *b, uint32_t
 
   dc_args a;
   memset(&a, 0, sizeof a);
-  a.ids = din + i_ids;
-  a.seqs = din + i_seqs;
-  a.hex = din + i_hex;
-  a.reverse = din + i_rev;
-  a.id_off = (const uint64_t *)(din + i_idoff);
-  a.seq_off = (const uint64_t *)(din + i_sqoff);
-  a.hex_off = (const uint64_t *)(din + i_hxoff);
-  a.word_off = (const uint64_t *)(din + i_woff);
-  a.chr = (const int32_t *)(din + i_chr);
-  a.pos0 = (const int64_t *)(din + i_pos);
+  a.ids = db.ids;
+  a.seqs = db.seqs;
+  a.hex = db.hex;
+  a.reverse = db.reverse;
+  a.id_off = db.id_off;
+  a.seq_off = db.seq_off;
+  a.hex_off = db.hex_off;
+  a.word_off = db.word_off;
+  a.chr = db.chr;
+  a.pos0 = db.pos0;
   a.text = (const uint8_t *)d->text.p;
   a.names = d->d_names;
   a.cum = d->d_cum;
@@ -757,7 +779,15 @@ static gs_status decode_device(gs_decoder *d, const gs_decode_batch *b, uint32_t
       gs_set_error("gs_decode: a row of 32 MB or more");
       return GS_ERR_UNSUPPORTED;
     }
-    return dc_record_error(b, first_record, err >> 8, reason);
+    if (b) return dc_record_error(b, first_record, err >> 8, reason);
+    /* the batch is in HBM only: the record's id comes back for the message */
+    const uint64_t r = err >> 8;
+    uint64_t span[2] = {0, 0};
+    GS_HIP(hipMemcpy(span, db.id_off + r, 16, hipMemcpyDeviceToHost));
+    std::string id((size_t)(span[1] - span[0]), '\0');
+    if (!id.empty()) GS_HIP(hipMemcpy(&id[0], db.ids + span[0], id.size(), hipMemcpyDeviceToHost));
+    gs_set_error("gs_decode: record " + std::to_string(first_record + r) + " (" + id + "): " + dc_reasons[reason < 9 ? reason : 0]);
+    return GS_ERR_FORMAT;
   }
   if ((rc = gs_reserve(d->w_text, total + 16)) != GS_OK) return rc;
   a.out = (char *)d->w_text.p;

@@ -1,0 +1,47 @@
+/* gs_decoder.h -- the decoder object of gs_decode.hip, shared with the units that lend its workspace and its lock
+ * (gs_bgzf_inflate.hip: the inflated bytes of a BAM database stay in HBM between its calls) */
+#ifndef GS_DECODER_H
+#define GS_DECODER_H
+
+#include "gs_common.h"
+#include "gs_repr.h"
+
+struct gs_decoder {
+  std::recursive_mutex mtx;
+  int device = 0;
+  uint32_t n_chr = 0;
+  uint64_t total = 0;
+  std::vector<std::string> names;
+  gs_buffer text, tabs; /* the FASTA bytes; prefix sums, text offsets, record lengths, name offsets, names, powers of five */
+  const uint64_t *d_cum = nullptr, *d_toff = nullptr, *d_flen = nullptr;
+  const uint32_t *d_name_off = nullptr;
+  const uint8_t *d_names = nullptr;
+  gs_pow5_tables pw{nullptr, nullptr};
+  gs_buffer w_in, w_tmp, w_text;
+  /* gs_bgzf_inflate.hip: the compressed bytes and the member table; reasons; the inflated bytes of the last two calls (the
+   * later call takes the tail of the earlier one in front), which of the two is the last, and its length */
+  gs_buffer w_bi_in, w_bi_tmp, w_inf[2];
+  uint32_t inf_cur = 0;
+  uint64_t inf_len = 0;
+  uint64_t inf_base_member = 0, inf_base_byte = 0; /* gs_bgzf_inflate_base: what a message adds to a member's index and offset */
+  /* gs_bamsplit.hip: record starts (sized by the bytes); the records' sizes and their scans (sized by the records found); the bytes of a cut record the last gs_decode_bam
+   * call left at the end of w_inf[inf_cur]; the last call's members, compressed bytes, inflated bytes, records and the
+   * milliseconds of its stages (inflate with the upload, record starts, fields, the decoder's kernels) */
+  gs_buffer w_bs_tmp, w_bs_rec;
+  uint64_t bam_tail = 0;
+  uint64_t last_bam[4] = {0, 0, 0, 0};
+  double last_bam_ms[4] = {0, 0, 0, 0};
+};
+
+/* a batch of gs_decode_batch's arrays in HBM, with the word offsets (hex digits / 16, prefix-summed) */
+struct gs_decode_batch_dev {
+  const uint8_t *ids, *seqs, *hex, *reverse;
+  const uint64_t *id_off, *seq_off, *hex_off, *word_off;
+  const int32_t *chr;
+  const int64_t *pos0;
+};
+/* gs_decode.hip */
+gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uint64_t n, uint64_t nw, uint32_t flags, uint64_t first_record,
+                               const gs_decode_batch *host_batch, const void **d_text, uint64_t *text_len, uint64_t *n_rows);
+
+#endif

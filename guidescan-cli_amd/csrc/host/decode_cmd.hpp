@@ -1,6 +1,6 @@
 /*
- * decode_cmd.hpp -- `guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--verbose]
- * DATABASE GENOME.fa`: the CSV
+ * decode_cmd.hpp -- `guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--bgzf host|gpu]
+ * [--verbose] DATABASE GENOME.fa`: the CSV
  * that the reference's scripts/decode_database.py prints for a SAM/BAM off-target database (manual, "Off-Target
  * Databases"), through the device decoder (gs_decoder_open / gs_decode_sam / gs_decode_records).  Control plane only:
  * the FASTA records are read and handed over once (SeqIO.to_dict, :223), the database is read in batches of whole
@@ -11,6 +11,14 @@
  * streams to stdout, so the header line and the rows of earlier batches have already gone out when a later batch
  * fails (usage() says so): only -o gives all or nothing.  --batch-size: records per batch (2^20; a batch also ends at 256 MB of
  * lines or hex digits).  --verbose: one line on stderr with the seconds of each stage.
+ * --bgzf gpu (BAM only; on a SAM database a usage error): the BGZF members are inflated, the records found and split
+ * into the decoder's arrays on the device (gs_decode_bam).  The host still reads the BAM header with bgzf_reader (header
+ * text, reference list, where the first record begins); the file is then read in groups of whole members by their BSIZE
+ * fields, a group of about --batch-size records (judged by the bytes per record of the groups before it; 36 bytes, the
+ * least a record takes, for the first) or 256 MB of inflated bytes by the ISIZE sums.  The table is byte for byte that
+ * of --bgzf host.  A damaged file ends with exit status 1 and the library's message: the member that does not inflate
+ * (its index and byte offset in the file, the reason) or the record that is
+ * malformed (index in the file, decode_bam_file's words).  --verbose then adds the members and bytes inflated on the device.
  */
 #ifndef GS_DECODE_CMD_HPP
 #define GS_DECODE_CMD_HPP
@@ -18,6 +26,7 @@
 #include <time.h>
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -326,37 +335,40 @@ inline bool decode_sam_file(job &j, const std::string &path, int device, const f
   return j.flush_sam(lines);
 }
 
-inline bool decode_bam_file(job &j, const std::string &path, int device, const fasta_records &fa, uint64_t batch_records, size_t batch_bytes) {
-  bgzf_reader rd(path);
-  if (!rd.open_ok) {
-    j.err = "cannot read " + path;
-    return false;
-  }
-  auto malformed = [&](const char *what) {
-    j.err = "malformed BAM file " + path + ": " + what;
-    return false;
-  };
+/* what stands in front of a BAM file's records (SAMv1 section 4.2) */
+struct bam_header {
+  sq_list refs, sq;               /* the binary reference list; the @SQ lines of the text header */
+  std::vector<int32_t> ref_to_sq; /* refID -> the decoder's chromosome, negative: none */
+  bool from_text = false;         /* the decoder's chromosomes are the @SQ lines */
+  int32_t n_ref = 0;
+  uint64_t bytes = 0;             /* inflated bytes up to the first record */
+};
+/* -> nullptr, or what is wrong */
+inline const char *read_bam_header(bgzf_reader &rd, bam_header &h) {
+  sq_list &refs = h.refs, &sq = h.sq;
+  std::vector<int32_t> &ref_to_sq = h.ref_to_sq;
   char magic[4];
   int32_t l_text = 0, n_ref = 0;
-  if (!rd.read(magic, 4) || memcmp(magic, "BAM\1", 4) || !rd.read(&l_text, 4) || l_text < 0) return malformed("no BAM header");
+  if (!rd.read(magic, 4) || memcmp(magic, "BAM\1", 4) || !rd.read(&l_text, 4) || l_text < 0) return "no BAM header";
   std::string head((size_t)l_text, '\0');
-  if (l_text && !rd.read(&head[0], (size_t)l_text)) return malformed("the header text is cut");
+  if (l_text && !rd.read(&head[0], (size_t)l_text)) return "the header text is cut";
   head.resize(strlen(head.c_str()));
-  if (!rd.read(&n_ref, 4) || n_ref < 0) return malformed("no reference list");
-  sq_list refs, sq;
+  if (!rd.read(&n_ref, 4) || n_ref < 0) return "no reference list";
+  h.bytes = 12ull + (uint64_t)l_text;
   for (int32_t i = 0; i < n_ref; i++) {
     int32_t l_name = 0, l_ref = 0;
-    if (!rd.read(&l_name, 4) || l_name < 1) return malformed("a reference name");
+    if (!rd.read(&l_name, 4) || l_name < 1) return "a reference name";
     std::string name((size_t)l_name, '\0');
-    if (!rd.read(&name[0], (size_t)l_name) || !rd.read(&l_ref, 4)) return malformed("a reference");
+    if (!rd.read(&name[0], (size_t)l_name) || !rd.read(&l_ref, 4)) return "a reference";
     name.resize(strlen(name.c_str()));
     refs.names.push_back(name);
     refs.lengths.push_back((uint64_t)(uint32_t)l_ref);
+    h.bytes += 8ull + (uint64_t)l_name;
   }
   read_sq(head, sq);
   /* refID indexes the binary list; the decoder's chromosomes are the @SQ lines when the text header has them */
   const bool from_text = !sq.names.empty();
-  std::vector<int32_t> ref_to_sq((size_t)n_ref, -2);
+  ref_to_sq.assign((size_t)n_ref, -2);
   if (from_text) {
     std::map<std::string, int32_t> first;
     for (size_t c = 0; c < sq.names.size(); c++) first.emplace(sq.names[c], (int32_t)c);
@@ -367,6 +379,27 @@ inline bool decode_bam_file(job &j, const std::string &path, int device, const f
   } else {
     for (int32_t i = 0; i < n_ref; i++) ref_to_sq[(size_t)i] = i;
   }
+  h.from_text = from_text;
+  h.n_ref = n_ref;
+  return nullptr;
+}
+
+inline bool decode_bam_file(job &j, const std::string &path, int device, const fasta_records &fa, uint64_t batch_records, size_t batch_bytes) {
+  bgzf_reader rd(path);
+  if (!rd.open_ok) {
+    j.err = "cannot read " + path;
+    return false;
+  }
+  auto malformed = [&](const char *what) {
+    j.err = "malformed BAM file " + path + ": " + what;
+    return false;
+  };
+  bam_header hd;
+  if (const char *what = read_bam_header(rd, hd)) return malformed(what);
+  const sq_list &refs = hd.refs, &sq = hd.sq;
+  const std::vector<int32_t> &ref_to_sq = hd.ref_to_sq;
+  const bool from_text = hd.from_text;
+  const int32_t n_ref = hd.n_ref;
   if (!open_decoder(j, device, from_text ? sq : refs, fa)) return false;
   record_batch b;
   std::vector<unsigned char> rec;
@@ -438,9 +471,121 @@ inline bool decode_bam_file(job &j, const std::string &path, int device, const f
   return j.flush_records(b);
 }
 
+/* the member at p, `avail` bytes there (SAMv1 section 4.1) -> its size and ISIZE; 0: it is cut; -1: no BGZF member.  The
+ * library checks the members again, and in full */
+inline long bgzf_member_size(const unsigned char *p, size_t avail, uint32_t *isize) {
+  if (avail < 12) return 0;
+  if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || p[3] != 4) return -1;
+  const size_t xlen = (size_t)p[10] | ((size_t)p[11] << 8);
+  if (12 + xlen > avail) return 0;
+  for (size_t q = 12; q + 4 <= 12 + xlen;) {
+    const size_t slen = (size_t)p[q + 2] | ((size_t)p[q + 3] << 8);
+    if (q + 4 + slen > 12 + xlen) break;
+    if (p[q] == 'B' && p[q + 1] == 'C' && slen == 2) {
+      const size_t size = ((size_t)p[q + 4] | ((size_t)p[q + 5] << 8)) + 1;
+      if (size < 12 + xlen + 8) return -1;
+      if (size > avail) return 0;
+      *isize = (uint32_t)p[size - 4] | ((uint32_t)p[size - 3] << 8) | ((uint32_t)p[size - 2] << 16) | ((uint32_t)p[size - 1] << 24);
+      return (long)size;
+    }
+    q += 4 + slen;
+  }
+  return -1;
+}
+
+/* --bgzf gpu: the header on the host, then groups of whole members through gs_decode_bam */
+inline bool decode_bam_file_gpu(job &j, const std::string &path, int device, const fasta_records &fa, uint64_t batch_records, size_t batch_bytes,
+                                uint64_t *members, uint64_t *inflated) {
+  auto malformed = [&](const char *what) {
+    j.err = "malformed BAM file " + path + ": " + what;
+    return false;
+  };
+  bam_header hd;
+  {
+    bgzf_reader rd(path);
+    if (!rd.open_ok) {
+      j.err = "cannot read " + path;
+      return false;
+    }
+    if (const char *what = read_bam_header(rd, hd)) return malformed(what);
+  }
+  if (!open_decoder(j, device, hd.from_text ? hd.sq : hd.refs, fa)) return false;
+  std::ifstream in(path, std::ios::binary);
+  if (!in) {
+    j.err = "cannot read " + path;
+    return false;
+  }
+  std::vector<unsigned char> buf;
+  size_t have = 0; /* bytes of buf that are file bytes not yet handed over */
+  bool at_eof = false;
+  auto fill = [&](size_t want) { /* `want` bytes in buf, or all there are */
+    if (buf.size() < want) buf.resize(want + (want >> 1));
+    while (have < want && !at_eof) {
+      in.read((char *)buf.data() + have, (std::streamsize)(buf.size() - have));
+      const size_t got = (size_t)in.gcount();
+      have += got;
+      if (got == 0) at_eof = true;
+    }
+  };
+  uint64_t seen_bytes = 0, seen_records = 0; /* inflated record bytes and records of the groups so far */
+  uint64_t file_at = 0;                      /* where the group begins in the file */
+  bool first = true;
+  for (;;) {
+    /* a group: members until their ISIZE sum reaches the target; the first holds the header at least */
+    const uint64_t per_record = seen_records ? (seen_bytes + seen_records - 1) / seen_records : 36;
+    const uint64_t by_records = batch_records > (uint64_t)batch_bytes / per_record ? (uint64_t)batch_bytes : batch_records * per_record;
+    const uint64_t target = std::min<uint64_t>(batch_bytes, by_records) + (first ? hd.bytes : 0);
+    size_t glen = 0;
+    uint64_t isum = 0, n_members = 0;
+    for (;;) {
+      fill(glen + 65536);
+      if (glen == have) break; /* the end of the file */
+      uint32_t isize = 0;
+      const long size = bgzf_member_size(buf.data() + glen, have - glen, &isize);
+      if (size < 0) return malformed("a BGZF block's header");
+      if (size == 0) return malformed("a BGZF block is cut");
+      glen += (size_t)size;
+      isum += isize;
+      n_members++;
+      if (isum >= target && (!first || isum > hd.bytes)) break;
+    }
+    if (first && isum < hd.bytes) return malformed("the header is cut");
+    if (glen == 0) break;
+    fill(glen + 1);
+    const bool last = glen == have;
+    char *text = nullptr;
+    uint64_t len = 0, n = 0, tail = 0;
+    gs_bgzf_inflate_base(j.dec, *members, file_at); /* a member that fails is named by its place in the file */
+    const double t0 = now_s();
+    const gs_status rc = gs_decode_bam(j.dec, buf.data(), glen, first ? hd.bytes : 0, hd.ref_to_sq.data(), (uint32_t)hd.n_ref,
+                                       j.flags | (last ? GS_DECODE_BAM_END : 0u), j.done, &text, &len, &n, &tail);
+    j.t_decode += now_s() - t0;
+    if (rc != GS_OK) {
+      j.err = rc == GS_ERR_FORMAT ? "malformed BAM file " + path + ": " + gs_status_string(rc) : std::string(gs_status_string(rc));
+      return false;
+    }
+    const bool ok = j.write(text, len);
+    gs_free(text);
+    if (!ok) return false;
+    j.done += n;
+    seen_records += n;
+    seen_bytes += isum - (first ? hd.bytes : 0);
+    *members += n_members;
+    *inflated += isum;
+    file_at += glen;
+    memmove(buf.data(), buf.data() + glen, have - glen);
+    have -= glen;
+    first = false;
+    if (last) break;
+  }
+  if (!ends_with_bgzf_eof(path)) /* as decode_bam_file */
+    std::cerr << "warning: " << path << " has no BGZF end-of-file block and may be cut short\n";
+  return true;
+}
+
 /* -> exit status; 2 = usage */
 inline int run(int argc, char **argv) {
-  std::string mode = "succinct", output, database, fasta;
+  std::string mode = "succinct", output, database, fasta, bgzf = "host";
   int device = 0;
   bool verbose = false;
   long long batch_records = 1 << 20;
@@ -456,6 +601,8 @@ inline int run(int argc, char **argv) {
     } else if (a == "--batch-size" && i + 1 < argc) {
       batch_records = strtoll(argv[++i], &end, 10);
       if (*end || end == argv[i] || batch_records < 1) return 2;
+    } else if (a == "--bgzf" && i + 1 < argc) {
+      bgzf = argv[++i];
     } else if (a == "--verbose") {
       verbose = true;
     } else if (a == "-o" && i + 1 < argc) {
@@ -466,7 +613,7 @@ inline int run(int argc, char **argv) {
       return 2;
     }
   }
-  if (positional.size() != 2 || (mode != "succinct" && mode != "complete")) return 2;
+  if (positional.size() != 2 || (mode != "succinct" && mode != "complete") || (bgzf != "host" && bgzf != "gpu")) return 2;
   database = positional[0];
   fasta = positional[1];
   job j;
@@ -480,6 +627,8 @@ inline int run(int argc, char **argv) {
     }
     in.read((char *)magic, 2);
   }
+  const bool is_bam = magic[0] == 0x1f && magic[1] == 0x8b;
+  if (bgzf == "gpu" && !is_bam) return 2; /* --bgzf is about BAM databases */
   const double t_start = now_s();
   fasta_records fa;
   if (!read_fasta(fasta, fa, j.err)) {
@@ -493,8 +642,10 @@ inline int run(int argc, char **argv) {
     return 1;
   }
   const size_t batch_bytes = (size_t)256 << 20;
-  bool ok = (magic[0] == 0x1f && magic[1] == 0x8b) ? decode_bam_file(j, database, device, fa, (uint64_t)batch_records, batch_bytes)
-                                                   : decode_sam_file(j, database, device, fa, (uint64_t)batch_records, batch_bytes);
+  uint64_t dev_members = 0, dev_inflated = 0;
+  bool ok = !is_bam          ? decode_sam_file(j, database, device, fa, (uint64_t)batch_records, batch_bytes)
+            : bgzf == "gpu" ? decode_bam_file_gpu(j, database, device, fa, (uint64_t)batch_records, batch_bytes, &dev_members, &dev_inflated)
+                            : decode_bam_file(j, database, device, fa, (uint64_t)batch_records, batch_bytes);
   if (j.dec) gs_decoder_close(j.dec);
   if (ok && fflush(j.out) != 0) {
     ok = false;
@@ -509,8 +660,12 @@ inline int run(int argc, char **argv) {
   if (verbose) { /* stderr: stdout may be the table */
     const double all = now_s() - t_start;
     fprintf(stderr, "Decoded %llu records in %.3f s: FASTA read %.3f s, library calls (decoder's batches, text back) %.3f s, output writes %.3f s, "
-                    "database read and decoder set-up %.3f s\n",
+                    "database read and decoder set-up %.3f s",
             (unsigned long long)j.done, all, t_fasta, j.t_decode, j.t_write, all - t_fasta - j.t_decode - j.t_write);
+    if (bgzf == "gpu")
+      fprintf(stderr, "; bgzf gpu: %llu members, %llu bytes inflated on the device", (unsigned long long)dev_members,
+              (unsigned long long)dev_inflated);
+    fprintf(stderr, "\n");
   }
   return 0;
 }

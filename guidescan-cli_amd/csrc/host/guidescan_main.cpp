@@ -33,7 +33,7 @@
  *       from a shared queue, output written in input order (src/guidescan.cxx:226-251 is the
  *       reference's fan-out over threads).  On every device the search of batch i+1 overlaps the text
  *       formatting of batch i.
- *   guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] DATABASE GENOME.fa
+ *   guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--bgzf host|gpu] DATABASE GENOME.fa
  *       the CSV scripts/decode_database.py prints for a SAM/BAM database, decoded on the device (decode_cmd.hpp);
  *       stdout unless -o.  SEQ of at most 32 symbols.  The table streams, so only -o is all or nothing: stdout has
  *       the header and the earlier batches' rows when a later record fails.
@@ -106,7 +106,8 @@ int usage() {
                "                 with --all-candidates: [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S]\n"
                "                 [--chromosomes a,b,...]\n"
                "       guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--verbose]\n"
-               "                 DATABASE GENOME.fa\n"
+               "                 [--bgzf host|gpu] DATABASE GENOME.fa\n"
+               "                 --bgzf gpu (a BAM database only): the file is inflated and split into records on the device.\n"
                "                 a stored guide (SEQ) may have at most 32 symbols.  The table streams: without -o the header\n"
                "                 and the rows of earlier batches are on stdout already when a later record fails (exit\n"
                "                 status 1); with -o a failure leaves no file.\n";

@@ -181,6 +181,89 @@ def read_bam(path):
     return sq, recs
 
 
+def bam_header(data: bytes):
+    """the head of a BAM file's inflated bytes -> (sq, ref_to_sq, header bytes): the @SQ lines of the text header, or the
+    binary reference list without them; each binary reference's index in sq, -1 when no @SQ line names it"""
+    if data[:4] != b"BAM\1":
+        raise ValueError("not a BAM file")
+    (l_text,) = struct.unpack_from("<i", data, 4)
+    header = data[8:8 + l_text].split(b"\0")[0].decode()
+    at = 8 + l_text
+    (n_ref,) = struct.unpack_from("<i", data, at)
+    at += 4
+    refs = []
+    for _ in range(n_ref):
+        (l_name,) = struct.unpack_from("<i", data, at)
+        name = data[at + 4:at + 4 + l_name].split(b"\0")[0].decode()
+        (l_ref,) = struct.unpack_from("<I", data, at + 4 + l_name)
+        refs.append((name, l_ref))
+        at += 8 + l_name
+    sq, _ = parse_sam(header)
+    if not sq:
+        return refs, list(range(n_ref)), at
+    first = {}
+    for i, (n, _) in enumerate(sq):
+        first.setdefault(n, i)
+    return sq, [first.get(n, -1) for n, _ in refs], at
+
+
+def bgzf_member_sizes(data: bytes):
+    """the sizes of the BGZF members of a file's bytes, by their BSIZE fields (SAMv1 section 4.1)"""
+    from importlib import import_module
+    members, reason = import_module("guidescan-cli_amd.api").bgzf_members(data)
+    if reason:
+        raise ValueError(f"member {len(members)} is no BGZF member")
+    offs = [o for o, _ in members] + [len(data)]
+    return [offs[i + 1] - offs[i] for i in range(len(members))]
+
+
+def inflate_bgzf(data: bytes, device=0) -> bytes:
+    """BGZF members inflated on the GPU (api.inflate_bgzf over gs_bgzf_inflate)"""
+    from importlib import import_module
+    return import_module("guidescan-cli_amd.api").inflate_bgzf(data, device=device)
+
+
+def decode_bam(db_path, fasta_path, mode="succinct", device=0, group_members=None) -> str:
+    """the text `decode_database.py DB.bam FASTA --mode MODE` prints, with the BAM file inflated, split and decoded on the
+    GPU (api.Decoder.decode_bam over gs_decode_bam).  The header is read on the host.  group_members: members per
+    call (None: the whole file in one); the text does not depend on it."""
+    if mode not in ("succinct", "complete"):
+        raise ValueError("mode is succinct or complete")
+    data = Path(db_path).read_bytes()
+    sizes = bgzf_member_sizes(data)
+    head, n_head = b"", 0   # the members that hold the header, inflated on the host
+    while True:
+        try:
+            sq, ref_to_sq, skip = bam_header(head)
+            break
+        except (struct.error, ValueError, IndexError):
+            if n_head == len(sizes):
+                raise ValueError("no BAM header") from None
+            at = sum(sizes[:n_head])
+            head += gzip.decompress(data[at:at + sizes[n_head]])
+            n_head += 1
+    fasta = parse_fasta_records(fasta_path)
+    from importlib import import_module
+    api = import_module("guidescan-cli_amd.api")
+    complete = mode == "complete"
+    step = group_members or len(sizes) or 1
+    out, done, at, k = [], 0, 0, 0
+    with api.Decoder(sq, fasta, device=device) as dec:
+        while k < len(sizes) or k == 0:
+            take = max(step, n_head) if k == 0 else step
+            nbytes = sum(sizes[k:k + take])
+            last = k + take >= len(sizes)
+            text, n, _ = dec.decode_bam(data[at:at + nbytes], skip=skip if k == 0 else 0, ref_to_sq=ref_to_sq, complete=complete,
+                                        first_record=done, end=last)
+            out.append(text)
+            done += n
+            at += nbytes
+            k += take
+            if last:
+                break
+    return (COMPLETE_HEADER if complete else SUCCINCT_HEADER) + "\n" + "".join(out)
+
+
 def off_target_words(hexs, delim, record):
     """-> [(distance, word)] in list order"""
     if hexs is None:

@@ -722,6 +722,70 @@ gs_status gs_debug_repr_doubles(const double *v, uint64_t n, char *out);
 /* Host only: the CFD tables the decoder uploads: mm[(r * 4 + d) * 20 + i] for the key r{ACGU}:d{ACGT},i+1 (320), pam[16] */
 gs_status gs_debug_decode_tables(double *mm, double *pam);
 
+/* ---- BGZF on the device, the other way: the inflate step of reading a BAM database ---------------------------- */
+
+/* BGZF members (SAMv1 section 4.1: gzip members with the BC subfield, what `samtools view -b` of manual/manual.tex:581-582
+ * and gs_bgzf_compress write; SAMv1 section 4.2 is what they hold), back to back in host memory -> their bytes, inflated
+ * on the device: the mirror of gs_bgzf_compress, and the first step of scripts/decode_database.py's pysam.AlignmentFile on
+ * a BAM database.  Any writer's members are taken: several deflate blocks, stored, fixed and dynamic ones.  A zero-length
+ * member (the end-of-file block) gives no bytes.  The host walks the members (1f 8b 08 04, XLEN, the BC subfield among
+ * any others, BSIZE; CRC-32 and ISIZE from the trailer); a wave inflates a member and checks its CRC-32.  GS_ERR_FORMAT:
+ * gs_status_string names the first failing member's index, its byte offset in `bgzf` and the reason (a BSIZE that runs
+ * past the data, no BC subfield, ISIZE above 65,536, a damaged deflate stream, a wrong CRC-32 or ISIZE); no bytes then.
+ * *out is malloc'ed: release with gs_free. */
+gs_status gs_bgzf_inflate(int device, const void *bgzf, uint64_t len, uint8_t **out, uint64_t *out_len);
+/* The same (SAMv1 sections 4.1 and 4.2, scripts/decode_database.py as above) with the result left in the decoder's
+ * workspace: *d_out holds the last `keep` bytes of what the call before left (the tail of a BAM record cut by the end of
+ * that group of members; keep <= its length), then the bytes of these members; *out_len counts both.  *d_out belongs to
+ * the decoder until the call after the next one.  *n_members (may be NULL): members inflated.  A failed call leaves
+ * what the call before left. */
+gs_status gs_bgzf_inflate_device(gs_decoder *dec, const void *bgzf, uint64_t len, uint64_t keep, const void **d_out,
+                                 uint64_t *out_len, uint64_t *n_members);
+/* Where the bytes of the decoder's next gs_bgzf_inflate_device / gs_decode_bam* calls lie in their file (SAMv1 section 4.1; a
+ * file that scripts/decode_database.py would read whole is handed over in groups of members): the members and the bytes in
+ * front of them.  They are added to the index and the offset in the message of a member that fails, which then names
+ * the member in the file.  They stay until set again; 0, 0 at first. */
+gs_status gs_bgzf_inflate_base(gs_decoder *dec, uint64_t members_before, uint64_t bytes_before);
+/* Host only: one whole member (header, deflate stream, trailer; SAMv1 section 4.1, as pysam reads it for
+ * scripts/decode_database.py) through the function the kernel's lane runs (gs_bgzf_inflate.h).  out[cap] takes ISIZE
+ * bytes (GS_ERR_ARG when cap is smaller).  *reason: 0, or why the member fails (then GS_ERR_FORMAT); *out_len: the bytes
+ * made up to there. */
+gs_status gs_debug_inflate_member(const void *member, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *reason);
+/* Host only: the member table's walk over bgzf[0, len) (SAMv1 section 4.1; scripts/decode_database.py reads such files
+ * through pysam): *n members, the first `cap` of them with their offsets and ISIZE (either array may be NULL).
+ * GS_ERR_FORMAT and *reason when a member is refused; *n is then its index. */
+gs_status gs_debug_bgzf_members(const void *bgzf, uint64_t len, uint64_t *member_off, uint32_t *isize, uint64_t cap, uint64_t *n,
+                                uint32_t *reason);
+
+#define GS_DECODE_BAM_END 0x2000u /* gs_decode_bam: the data ends with these members */
+
+/* A BAM database's records, still compressed, to the rows scripts/decode_database.py prints for them, on the device all
+ * the way: the BGZF members (SAMv1 section 4.1) are inflated as by gs_bgzf_inflate_device, the alignment records (SAMv1
+ * section 4.2) are found by following their block_size fields and split into the arrays of gs_decode_batch in HBM
+ * (read_name without its NUL, SEQ as =ACMGRSVTWYHKDBN letters, FLAG & 16, refID through ref_to_sq, pos, the last of:H:
+ * tag), then the kernels of gs_decode_records run.  bgzf: whole members.  skip: the inflated bytes of these members that
+ * belong to the BAM header (magic, text, reference list); a call with skip != 0 begins a file, and a file's header lies
+ * within its first call.  ref_to_sq[n_ref]: the binary reference list's entries as indices of the decoder's
+ * chromosomes, negative: no @SQ line (such a record, like one with a negative refID, prints None).  Rows only, no header
+ * line; flags: GS_TEXT_COMPLETE, GS_DECODE_BAM_END.  *n_records: the complete records of this call (the next call's
+ * first_record grows by it); *tail: the bytes of a record cut by the end of these members.  The decoder keeps them
+ * and the next call's records begin with them, so a file streams in groups of members and the output does not depend
+ * on where the groups are cut.  With GS_DECODE_BAM_END a tail is an error.  GS_ERR_FORMAT names the first record in
+ * file order that is malformed, by index and with decode_bam_file's words - "a record shorter than its fixed part",
+ * "a record's fields outrun it", "a record's reference is beyond the list", "a text tag without its end", "an array
+ * tag", "a tag of unknown type", "a tag outruns its record", "a record is cut", "a record's size" - or the member
+ * that does not inflate, or what gs_decode_records reports.  *text is malloc'ed (NUL terminated): gs_free. */
+gs_status gs_decode_bam(gs_decoder *dec, const void *bgzf, uint64_t len, uint64_t skip, const int32_t *ref_to_sq, uint32_t n_ref,
+                        uint32_t flags, uint64_t first_record, char **text, uint64_t *text_len, uint64_t *n_records, uint64_t *tail);
+/* the same (SAMv1 sections 4.1 and 4.2, scripts/decode_database.py) with the text left in HBM: *d_text belongs to the
+ * decoder and is valid until its next call */
+gs_status gs_decode_bam_device(gs_decoder *dec, const void *bgzf, uint64_t len, uint64_t skip, const int32_t *ref_to_sq,
+                               uint32_t n_ref, uint32_t flags, uint64_t first_record, const void **d_text, uint64_t *text_len,
+                               uint64_t *n_records, uint64_t *tail);
+/* The last gs_decode_bam* call of this decoder: counts[4] = members, compressed bytes, inflated bytes, records;
+ * ms[4] = milliseconds of inflate (with the upload), record starts, fields, the decoder's kernels. */
+gs_status gs_debug_decode_bam_last(gs_decoder *dec, uint64_t *counts, double *ms);
+
 const char *gs_status_string(gs_status s);
 const char *gs_version(void);
 
