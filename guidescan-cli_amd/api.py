@@ -270,6 +270,30 @@ def lib():
     L.gs_debug_sp_float.argtypes = [u32]
     L.gs_debug_decode_tables.restype = i32
     L.gs_debug_decode_tables.argtypes = [vp, vp]
+    L.gs_fasta_parse.restype = i32
+    L.gs_fasta_parse.argtypes = [i32, vp, u64, u32, C.POINTER(vp)]
+    L.gs_fasta_parse_file.restype = i32
+    L.gs_fasta_parse_file.argtypes = [i32, C.c_char_p, u32, C.POINTER(vp)]
+    L.gs_fasta_parse_device.restype = i32
+    L.gs_fasta_parse_device.argtypes = [i32, vp, u64, u32, vp, C.POINTER(vp)]
+    L.gs_fasta_info.restype = i32
+    L.gs_fasta_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.gs_fasta_records.restype = i32
+    L.gs_fasta_records.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.gs_fasta_text.restype = i32
+    L.gs_fasta_text.argtypes = [vp, i32, C.POINTER(vp)]
+    L.gs_fasta_free.restype = None
+    L.gs_fasta_free.argtypes = [vp]
+    L.gs_decoder_open_fasta.restype = i32
+    L.gs_decoder_open_fasta.argtypes = [i32, vp, C.POINTER(GsGenomeStructure), C.POINTER(vp)]
+    L.gs_debug_fasta_tile_bytes.restype = u64
+    L.gs_debug_fasta_tile_bytes.argtypes = []
+    L.gs_debug_fasta_host.restype = i32
+    L.gs_debug_fasta_host.argtypes = [vp, u64, u32, u64, C.POINTER(vp)]
+    L.gs_debug_fasta_chunk_bytes.restype = u64
+    L.gs_debug_fasta_chunk_bytes.argtypes = [u64]
+    L.gs_debug_fasta_ms.restype = i32
+    L.gs_debug_fasta_ms.argtypes = [vp, vp]
     L.gs_status_string.restype = C.c_char_p
     L.gs_status_string.argtypes = [i32]
     L.gs_version.restype = C.c_char_p
@@ -297,7 +321,10 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_debug_bulge_last", "gs_debug_bulge_seeds", "gs_debug_bulge_verify",
            "gs_bgzf_compress_device", "gs_bgzf_compress", "gs_debug_huffman_lengths", "gs_debug_sp_float",
            "gs_bgzf_inflate", "gs_bgzf_inflate_device", "gs_bgzf_inflate_base", "gs_debug_inflate_member", "gs_debug_bgzf_members",
-           "gs_decode_bam", "gs_decode_bam_device", "gs_debug_decode_bam_last"]
+           "gs_decode_bam", "gs_decode_bam_device", "gs_debug_decode_bam_last",
+           "gs_fasta_parse", "gs_fasta_parse_file", "gs_fasta_parse_device", "gs_fasta_info", "gs_fasta_records", "gs_fasta_text",
+           "gs_fasta_free", "gs_decoder_open_fasta", "gs_debug_fasta_tile_bytes", "gs_debug_fasta_host",
+           "gs_debug_fasta_chunk_bytes", "gs_debug_fasta_ms"]
 
 
 def _check(rc):
@@ -681,13 +708,147 @@ def decode_tables():
     return keys, {a + b: float(pam[ai * 4 + bi]) for ai, a in enumerate("ACGT") for bi, b in enumerate("ACGT")}
 
 
+FASTA_RULES = {"index": 0, "records": 1}
+
+
+class DeviceFasta:
+    """A FASTA file parsed on one GPU (gs_fasta_parse*): the text stays in HBM until close().  rules: "index" (what
+    `guidescan index` reads, seqio.parse_fasta) or "records" (SeqIO.to_dict, what `guidescan decode` reads)."""
+
+    def __init__(self, handle, rules):
+        self._h = handle
+        self.rules = rules
+
+    @classmethod
+    def parse(cls, src, rules="index", device=0):
+        """src: a path (read in chunks through page-locked staging), or the file's bytes (bytes or a uint8 array)"""
+        h = C.c_void_p()
+        if isinstance(src, (str, os.PathLike)):
+            _check(lib().gs_fasta_parse_file(device, os.fsencode(src), FASTA_RULES[rules], C.byref(h)))
+        else:
+            raw = np.frombuffer(src, dtype=np.uint8) if isinstance(src, (bytes, bytearray, memoryview)) else np.ascontiguousarray(src, dtype=np.uint8)
+            _check(lib().gs_fasta_parse(device, raw.ctypes.data if raw.size else None, raw.size, FASTA_RULES[rules], C.byref(h)))
+        return cls(h, rules)
+
+    @classmethod
+    def parse_device(cls, d_raw_ptr, length, rules="index", device=0, stream=None):
+        """the raw bytes are in HBM already (d_raw_ptr: a device address)"""
+        h = C.c_void_p()
+        _check(lib().gs_fasta_parse_device(device, d_raw_ptr if length else None, length, FASTA_RULES[rules], stream, C.byref(h)))
+        return cls(h, rules)
+
+    @classmethod
+    def host_model(cls, raw: bytes, rules, tile_bytes):
+        """gs_debug_fasta_host: the device passes run on the host with tiles of any size; no GPU"""
+        h = C.c_void_p()
+        raw = bytes(raw)
+        _check(lib().gs_debug_fasta_host(raw if raw else None, len(raw), FASTA_RULES[rules], tile_bytes, C.byref(h)))
+        return cls(h, rules)
+
+    def info(self):
+        """(records, bytes of the text, bytes of all names)"""
+        n, tl, nb = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().gs_fasta_info(self._h, C.byref(n), C.byref(tl), C.byref(nb)))
+        return n.value, tl.value, nb.value
+
+    def records(self):
+        """{title_off, title_len, text_off, text_len, line_len: uint64 arrays; names: list of bytes}"""
+        n, _, nb = self.info()
+        cols = {k: np.zeros(n, dtype=np.uint64) for k in ("title_off", "title_len", "text_off", "text_len", "line_len")}
+        name_off, names = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(nb, 1), dtype=np.uint8)
+        _check(lib().gs_fasta_records(self._h, *(cols[k].ctypes.data for k in ("title_off", "title_len", "text_off", "text_len", "line_len")),
+                                      name_off.ctypes.data, names.ctypes.data))
+        blob = names.tobytes()
+        cols["names"] = [blob[int(name_off[r]):int(name_off[r + 1])] for r in range(n)]
+        return cols
+
+    def text(self) -> np.ndarray:
+        """the text, copied to the host (uint8)"""
+        p = C.c_void_p()
+        _check(lib().gs_fasta_text(self._h, 0, C.byref(p)))
+        tl = self.info()[1]
+        return np.frombuffer(C.string_at(p, tl), dtype=np.uint8).copy() if tl else np.zeros(0, dtype=np.uint8)
+
+    def text_device_ptr(self) -> int:
+        p = C.c_void_p()
+        _check(lib().gs_fasta_text(self._h, 1, C.byref(p)))
+        return p.value or 0
+
+    def ms(self):
+        """milliseconds of the object's making, by host clocks: file reads, waits for the uploads, "kernels" = the device
+        stage (its allocations, the five passes, the waits for their results), title gather with the names; "passes": the
+        five passes alone, by events in the stream (tile summaries, their two scans, tile counts, the counts' scan, emit)"""
+        v = np.zeros(9, np.float64)
+        _check(lib().gs_debug_fasta_ms(self._h, v.ctypes.data))
+        out = dict(zip(("read", "upload", "kernels", "names"), (float(x) for x in v[:4])))
+        out["passes"] = dict(zip(("summaries", "summary_scans", "counts", "count_scan", "emit"), (float(x) for x in v[4:])))
+        return out
+
+    def close(self):
+        if self._h:
+            lib().gs_fasta_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _fasta_result(fa):
+    rec = fa.records()
+    text = fa.text()
+    if fa.rules == "index":
+        return text, [n.decode("latin-1") for n in rec["names"]], [int(x) for x in rec["line_len"]]
+    blob = text.tobytes()
+    return {n.decode("latin-1"): blob[int(o):int(o) + int(l)] for n, o, l in zip(rec["names"], rec["text_off"], rec["text_len"])}
+
+
+def parse_fasta_device(path_or_bytes, rules="index", device=0):
+    """A FASTA file parsed on the GPU.  rules="index": (text uint8[L], names, lengths), the tuple of seqio.parse_fasta;
+    rules="records": {name: symbols as bytes}, what SeqIO.to_dict holds (a name twice: GsError, GS_ERR_FORMAT)."""
+    with DeviceFasta.parse(path_or_bytes, rules, device) as fa:
+        return _fasta_result(fa)
+
+
+def parse_fasta_model_tiles(raw: bytes, rules, tile_bytes):
+    """the same result from the host model of the device passes with tiles of tile_bytes (gs_debug_fasta_host), plus the
+    record table: (result as parse_fasta_device, records dict of DeviceFasta.records)"""
+    with DeviceFasta.host_model(raw, rules, tile_bytes) as fa:
+        return _fasta_result(fa), fa.records()
+
+
+def fasta_tile_bytes() -> int:
+    return int(lib().gs_debug_fasta_tile_bytes())
+
+
+def fasta_chunk_bytes(set_to=0) -> int:
+    """the staging chunk of gs_fasta_parse_file; set_to != 0 replaces it for the process"""
+    return int(lib().gs_debug_fasta_chunk_bytes(set_to))
+
+
 class Decoder:
     """A SAM/BAM database's decoder on one GPU (gs_decoder_open): sq = [(name, LN)] of the @SQ lines, fasta =
-    {name: symbols} of the genome's FASTA records (decode.parse_fasta_records).  decode_records() takes
+    {name: symbols} of the genome's FASTA records (decode.parse_fasta_records), or a DeviceFasta parsed under the
+    "records" rules, whose text then goes to the decoder inside HBM (gs_decoder_open_fasta).  decode_records() takes
     decode.Record objects and returns the rows scripts/decode_database.py prints, without the header line."""
 
     def __init__(self, sq, fasta, device=0):
         names = [n for n, _ in sq]
+        if isinstance(fasta, DeviceFasta):
+            self.names = names
+            gs = self._gs = make_genome_structure(names, [n for _, n in sq])
+            h = C.c_void_p()
+            _check(lib().gs_decoder_open_fasta(device, fasta._h, C.byref(gs), C.byref(h)))
+            self._h = h
+            return
         parts, off, ln, at = [], [], [], 0
         for n in names:
             if n in fasta:

@@ -525,6 +525,11 @@ gs_status dc_record_error(const gs_decode_batch *b, uint64_t first_record, uint6
 
 extern "C" gs_status gs_decoder_open(int device, const uint8_t *text, uint64_t len, const gs_genome_structure *sq,
                                      const uint64_t *chr_text_off, const uint64_t *chr_text_len, gs_decoder **out) {
+  return gs_decoder_open_text(device, text, len, 0, sq, chr_text_off, chr_text_len, out);
+}
+
+gs_status gs_decoder_open_text(int device, const uint8_t *text, uint64_t len, int text_on_device, const gs_genome_structure *sq,
+                               const uint64_t *chr_text_off, const uint64_t *chr_text_len, gs_decoder **out) {
   if (!out || !sq || (len && !text) || (sq->n_chr && (!sq->chr_names || !sq->chr_lengths || !chr_text_off || !chr_text_len))) return GS_ERR_ARG;
   *out = nullptr;
   for (uint32_t c = 0; c < sq->n_chr; c++) {
@@ -574,7 +579,7 @@ extern "C" gs_status gs_decoder_open(int device, const uint8_t *text, uint64_t l
     d->pw.pow5 = (const uint64_t(*)[2])(dt + i_p5);
     d->pw.pow5_inv = (const uint64_t(*)[2])(dt + i_p5i);
     hipError_t e = hipMemcpy(d->tabs.p, host.data(), in.at, hipMemcpyHostToDevice);
-    if (e == hipSuccess && len) e = hipMemcpy(d->text.p, text, len, hipMemcpyHostToDevice);
+    if (e == hipSuccess && len) e = hipMemcpy(d->text.p, text, len, text_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
     if (e == hipSuccess && len) { /* .upper() once, in place: the slices are printed upper-cased (:59); the buffer has 16 bytes to spare */
       const uint64_t n16 = (len + 15) / 16;
       const uint32_t g = (uint32_t)std::min<uint64_t>((n16 + 255) / 256, (uint64_t)gs_num_cus(device) * 32u);

@@ -41,6 +41,9 @@ struct gs_decode_batch_dev {
   const int64_t *pos0;
 };
 /* gs_decode.hip */
+/* gs_decoder_open with the text in host memory or, text_on_device != 0, in HBM already (gs_fasta.hip: copied device to device) */
+gs_status gs_decoder_open_text(int device, const uint8_t *text, uint64_t len, int text_on_device, const gs_genome_structure *sq,
+                               const uint64_t *chr_text_off, const uint64_t *chr_text_len, gs_decoder **out);
 gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uint64_t n, uint64_t nw, uint32_t flags, uint64_t first_record,
                                const gs_decode_batch *host_batch, const void **d_text, uint64_t *text_len, uint64_t *n_rows);
 

@@ -1,6 +1,6 @@
 /*
  * decode_cmd.hpp -- `guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--bgzf host|gpu]
- * [--verbose] DATABASE GENOME.fa`: the CSV
+ * [--fasta host|gpu] [--verbose] DATABASE GENOME.fa`: the CSV
  * that the reference's scripts/decode_database.py prints for a SAM/BAM off-target database (manual, "Off-Target
  * Databases"), through the device decoder (gs_decoder_open / gs_decode_sam / gs_decode_records).  Control plane only:
  * the FASTA records are read and handed over once (SeqIO.to_dict, :223), the database is read in batches of whole
@@ -19,6 +19,11 @@
  * of --bgzf host.  A damaged file ends with exit status 1 and the library's message: the member that does not inflate
  * (its index and byte offset in the file, the reason) or the record that is
  * malformed (index in the file, decode_bam_file's words).  --verbose then adds the members and bytes inflated on the device.
+ * --fasta gpu: GENOME.fa is parsed on the device (gs_fasta_parse_file under GS_FASTA_RECORD_RULES: read in chunks, uploaded
+ * while the next chunk is read) and its text goes to the decoder inside HBM (gs_decoder_open_fasta); read_fasta does not
+ * run.  The table and the messages are those of --fasta host, with one difference: GENOME.fa must be a regular file (the
+ * device buffer is sized from its length), so a pipe or a process substitution, which read_fasta takes, is "cannot read".
+ * --verbose's "FASTA read" then covers file read, upload and the device stage, and a second line gives them apart.
  */
 #ifndef GS_DECODE_CMD_HPP
 #define GS_DECODE_CMD_HPP
@@ -37,6 +42,7 @@
 #include <vector>
 
 #include "guidescan_amd.h"
+#include "fasta_names.hpp"
 
 namespace decode_cmd {
 
@@ -72,11 +78,9 @@ inline bool read_fasta(const std::string &path, fasta_records &fa, std::string &
     const size_t end = nl ? (size_t)(nl - t.data()) : size;
     if (t[r] == '>') {
       close_record();
-      size_t b = r + 1, e;
-      while (b < end && isspace((unsigned char)t[b])) b++;
-      e = b;
-      while (e < end && !isspace((unsigned char)t[e])) e++;
-      name = t.substr(b, e - b);
+      size_t b, n;
+      fasta_names::record_name(t.data() + r, end - r, &b, &n);
+      name = t.substr(r + b, n);
       if (fa.where.count(name)) {
         err = "FASTA record '" + name + "' occurs twice in " + path;
         return false;
@@ -207,6 +211,7 @@ inline double now_s() {
 struct job {
   double t_decode = 0, t_write = 0; /* seconds in the library's calls, in the output's writes */
   gs_decoder *dec = nullptr;
+  gs_fasta *gfa = nullptr; /* --fasta gpu: the parsed file, until the decoder has its text */
   uint32_t flags = 0;
   uint64_t done = 0; /* records decoded so far */
   FILE *out = nullptr;
@@ -292,7 +297,14 @@ inline bool open_decoder(job &j, int device, const sq_list &sq, const fasta_reco
   gs.chr_names = names.data();
   gs.chr_lengths = sq.lengths.data();
   gs.n_chr = (uint32_t)names.size();
-  const gs_status rc = gs_decoder_open(device, (const uint8_t *)fa.text.data(), fa.text.size(), &gs, off.data(), len.data(), &j.dec);
+  gs_status rc;
+  if (j.gfa) {
+    rc = gs_decoder_open_fasta(device, j.gfa, &gs, &j.dec);
+    gs_fasta_free(j.gfa); /* the decoder has its own copy */
+    j.gfa = nullptr;
+  } else {
+    rc = gs_decoder_open(device, (const uint8_t *)fa.text.data(), fa.text.size(), &gs, off.data(), len.data(), &j.dec);
+  }
   if (rc != GS_OK) {
     j.err = gs_status_string(rc);
     return false;
@@ -585,7 +597,7 @@ inline bool decode_bam_file_gpu(job &j, const std::string &path, int device, con
 
 /* -> exit status; 2 = usage */
 inline int run(int argc, char **argv) {
-  std::string mode = "succinct", output, database, fasta, bgzf = "host";
+  std::string mode = "succinct", output, database, fasta, bgzf = "host", fasta_on = "host";
   int device = 0;
   bool verbose = false;
   long long batch_records = 1 << 20;
@@ -603,6 +615,8 @@ inline int run(int argc, char **argv) {
       if (*end || end == argv[i] || batch_records < 1) return 2;
     } else if (a == "--bgzf" && i + 1 < argc) {
       bgzf = argv[++i];
+    } else if (a == "--fasta" && i + 1 < argc) {
+      fasta_on = argv[++i];
     } else if (a == "--verbose") {
       verbose = true;
     } else if (a == "-o" && i + 1 < argc) {
@@ -613,7 +627,9 @@ inline int run(int argc, char **argv) {
       return 2;
     }
   }
-  if (positional.size() != 2 || (mode != "succinct" && mode != "complete") || (bgzf != "host" && bgzf != "gpu")) return 2;
+  if (positional.size() != 2 || (mode != "succinct" && mode != "complete") || (bgzf != "host" && bgzf != "gpu") ||
+      (fasta_on != "host" && fasta_on != "gpu"))
+    return 2;
   database = positional[0];
   fasta = positional[1];
   job j;
@@ -631,7 +647,15 @@ inline int run(int argc, char **argv) {
   if (bgzf == "gpu" && !is_bam) return 2; /* --bgzf is about BAM databases */
   const double t_start = now_s();
   fasta_records fa;
-  if (!read_fasta(fasta, fa, j.err)) {
+  double fasta_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (fasta_on == "gpu") {
+    const gs_status rc = gs_fasta_parse_file(device, fasta.c_str(), GS_FASTA_RECORD_RULES, &j.gfa);
+    if (rc != GS_OK) { /* read_fasta's words */
+      std::cerr << "error: " << gs_status_string(rc) << (rc == GS_ERR_FORMAT ? " in " + fasta : std::string()) << "\n";
+      return 1;
+    }
+    gs_debug_fasta_ms(j.gfa, fasta_ms);
+  } else if (!read_fasta(fasta, fa, j.err)) {
     std::cerr << "error: " << j.err << "\n";
     return 1;
   }
@@ -639,6 +663,7 @@ inline int run(int argc, char **argv) {
   j.out = output.empty() ? stdout : fopen(output.c_str(), "wb");
   if (!j.out) {
     std::cerr << "error: cannot write " << output << "\n";
+    gs_fasta_free(j.gfa);
     return 1;
   }
   const size_t batch_bytes = (size_t)256 << 20;
@@ -647,6 +672,7 @@ inline int run(int argc, char **argv) {
             : bgzf == "gpu" ? decode_bam_file_gpu(j, database, device, fa, (uint64_t)batch_records, batch_bytes, &dev_members, &dev_inflated)
                             : decode_bam_file(j, database, device, fa, (uint64_t)batch_records, batch_bytes);
   if (j.dec) gs_decoder_close(j.dec);
+  gs_fasta_free(j.gfa); /* still there when the database failed before the decoder was opened */
   if (ok && fflush(j.out) != 0) {
     ok = false;
     j.err = "cannot write the output";
@@ -666,6 +692,11 @@ inline int run(int argc, char **argv) {
       fprintf(stderr, "; bgzf gpu: %llu members, %llu bytes inflated on the device", (unsigned long long)dev_members,
               (unsigned long long)dev_inflated);
     fprintf(stderr, "\n");
+    if (fasta_on == "gpu")
+      fprintf(stderr, "fasta gpu: file reads %.3f s, waits for the uploads %.3f s, device stage %.3f s (its five passes %.3f s), titles and names "
+                      "%.3f s\n",
+              1e-3 * fasta_ms[0], 1e-3 * fasta_ms[1], 1e-3 * fasta_ms[2],
+              1e-3 * (fasta_ms[4] + fasta_ms[5] + fasta_ms[6] + fasta_ms[7] + fasta_ms[8]), 1e-3 * fasta_ms[3]);
   }
   return 0;
 }

@@ -6,7 +6,7 @@
  * pipeline of batch_pipeline.hpp, `decode` is decode_cmd.hpp, the readers and candidate options the commands share are
  * cli_common.hpp, the BAM records and BGZF blocks of the host are bam_writer.hpp.
  *
- *   guidescan index  [--index PREFIX] [--store-sa] [--sdsl] [--device D] GENOME.fa
+ *   guidescan index  [--index PREFIX] [--store-sa] [--sdsl] [--device D] [--fasta host|gpu] [--verbose] GENOME.fa
  *       writes PREFIX.gs (chromosome names/lengths, src/genomics/seq_io.cxx:112-122) and
  *       PREFIX.dna (= the reference's <fasta>.forward.dna: upper-cased concatenated sequence,
  *       seq_io.cxx:57-63).  The FM-index itself is built on the GPU when `enumerate` starts
@@ -14,6 +14,10 @@
  *       --sdsl: builds the index on the GPU now and also writes PREFIX.forward / PREFIX.reverse, the reference's
  *       own index files (src/guidescan.cxx:168-175), byte for byte what its `index` command writes: the
  *       reference binary opens them, and so does `enumerate` here when PREFIX.dna is absent.
+ *       --fasta gpu: GENOME.fa is parsed on the device (gs_fasta_parse_file under GS_FASTA_INDEX_RULES); PREFIX.gs comes from
+ *       its record table and PREFIX.dna from the text copied back, byte for byte the files of --fasta host (the default).
+ *       GENOME.fa must then be a regular file (the device buffer is sized from its length): a pipe, which --fasta host
+ *       reads, is "cannot read".  --verbose: one line on stderr with the seconds of the FASTA read and of the two writes.
  *   guidescan kmers PREFIX -o KMERS.csv [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S] [--start]
  *       [--chromosomes a,b,...] [--device D]
  *       the kmers file of every candidate guide of the indexed genome, byte for byte what the reference's
@@ -33,7 +37,8 @@
  *       from a shared queue, output written in input order (src/guidescan.cxx:226-251 is the
  *       reference's fan-out over threads).  On every device the search of batch i+1 overlaps the text
  *       formatting of batch i.
- *   guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--bgzf host|gpu] DATABASE GENOME.fa
+ *   guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--bgzf host|gpu] [--fasta host|gpu]
+ *       DATABASE GENOME.fa
  *       the CSV scripts/decode_database.py prints for a SAM/BAM database, decoded on the device (decode_cmd.hpp);
  *       stdout unless -o.  SEQ of at most 32 symbols.  The table streams, so only -o is all or nothing: stdout has
  *       the header and the earlier batches' rows when a later record fails.
@@ -56,6 +61,7 @@
 #include "cli_common.hpp"
 #include "decode_cmd.hpp"
 #include "enumerate_cmd.hpp"
+#include "fasta_names.hpp"
 
 namespace {
 
@@ -75,8 +81,9 @@ bool parse_fasta(const std::string &path, std::string &text, genome_structure &g
   std::string line;
   while (std::getline(in, line)) {
     if (!line.empty() && line[0] == '>') {
-      const size_t sp = line.find(' ');
-      gs.names.push_back(line.substr(1, sp == std::string::npos ? std::string::npos : sp - 1));
+      size_t nb, nl;
+      fasta_names::index_name(line.data(), line.size(), &nb, &nl);
+      gs.names.push_back(line.substr(nb, nl));
       gs.lengths.push_back(0);
       continue;
     }
@@ -88,6 +95,33 @@ bool parse_fasta(const std::string &path, std::string &text, genome_structure &g
   return true;
 }
 
+/* --fasta gpu: the same two results from the device reader (GS_FASTA_INDEX_RULES); the text is the object's host copy */
+struct fasta_holder {
+  gs_fasta *fa = nullptr;
+  ~fasta_holder() { gs_fasta_free(fa); }
+};
+gs_status parse_fasta_gpu(const std::string &path, int device, fasta_holder &h, genome_structure &gs, const char **text, size_t *text_len,
+                          double *s_text_back) {
+  gs_status rc = gs_fasta_parse_file(device, path.c_str(), GS_FASTA_INDEX_RULES, &h.fa);
+  if (rc != GS_OK) return rc;
+  uint64_t n = 0, tl = 0, nb = 0;
+  gs_fasta_info(h.fa, &n, &tl, &nb);
+  std::vector<uint64_t> line_len(n), name_off(n + 1);
+  std::string names(nb, '\0');
+  gs_fasta_records(h.fa, nullptr, nullptr, nullptr, nullptr, line_len.data(), name_off.data(), nb ? &names[0] : nullptr);
+  for (uint64_t r = 0; r < n; r++) {
+    gs.names.push_back(names.substr(name_off[r], name_off[r + 1] - name_off[r]));
+    gs.lengths.push_back(line_len[r]);
+  }
+  const void *p = nullptr;
+  const double t0 = decode_cmd::now_s();
+  if ((rc = gs_fasta_text(h.fa, 0, &p)) != GS_OK) return rc;
+  *s_text_back = decode_cmd::now_s() - t0;
+  *text = (const char *)p;
+  *text_len = (size_t)tl;
+  return GS_OK;
+}
+
 bool write_gs(const std::string &path, const genome_structure &gs) {
   std::ofstream out(path);
   if (!out) return false;
@@ -96,7 +130,9 @@ bool write_gs(const std::string &path, const genome_structure &gs) {
 }
 
 int usage() {
-  std::cerr << "usage: guidescan index [--index PREFIX] [--store-sa] [--sdsl] [--device D] GENOME.fa\n"
+  std::cerr << "usage: guidescan index [--index PREFIX] [--store-sa] [--sdsl] [--device D] [--fasta host|gpu] [--verbose] GENOME.fa\n"
+               "                 --fasta gpu: GENOME.fa is parsed on the device; the files are those of --fasta host.  GENOME.fa\n"
+               "                 must then be a regular file (no pipe).\n"
                "       guidescan kmers PREFIX -o KMERS [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S]\n"
                "                 [--start] [--chromosomes a,b,...] [--device D]\n"
                "       guidescan enumerate PREFIX (-f KMERS | --all-candidates) -o OUT [-m N] [-a PAM]... [--format csv|sam|bam]\n"
@@ -106,8 +142,10 @@ int usage() {
                "                 with --all-candidates: [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S]\n"
                "                 [--chromosomes a,b,...]\n"
                "       guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--verbose]\n"
-               "                 [--bgzf host|gpu] DATABASE GENOME.fa\n"
+               "                 [--bgzf host|gpu] [--fasta host|gpu] DATABASE GENOME.fa\n"
                "                 --bgzf gpu (a BAM database only): the file is inflated and split into records on the device.\n"
+               "                 --fasta gpu: GENOME.fa is parsed on the device and its text stays there; same table and messages,\n"
+               "                 but GENOME.fa must be a regular file (a pipe, which --fasta host reads, is \"cannot read\").\n"
                "                 a stored guide (SEQ) may have at most 32 symbols.  The table streams: without -o the header\n"
                "                 and the rows of earlier batches are on stdout already when a later record fails (exit\n"
                "                 status 1); with -o a failure leaves no file.\n";
@@ -115,12 +153,14 @@ int usage() {
 }
 
 int do_index(int argc, char **argv) {
-  std::string fasta, prefix;
-  bool store_sa = false, sdsl = false;
+  std::string fasta, prefix, fasta_on = "host";
+  bool store_sa = false, sdsl = false, verbose = false;
   int device = 0;
   for (int i = 0; i < argc; i++) {
     const std::string a = argv[i];
-    if (a == "--index" && i + 1 < argc)
+    if (a == "--verbose")
+      verbose = true;
+    else if (a == "--index" && i + 1 < argc)
       prefix = argv[++i];
     else if (a == "--store-sa")
       store_sa = true;
@@ -128,31 +168,67 @@ int do_index(int argc, char **argv) {
       sdsl = true;
     else if (a == "--device" && i + 1 < argc)
       device = atoi(argv[++i]);
+    else if (a == "--fasta" && i + 1 < argc)
+      fasta_on = argv[++i];
     else if (!a.empty() && a[0] != '-')
       fasta = a;
     else
       return usage();
   }
-  if (fasta.empty()) return usage();
+  if (fasta.empty() || (fasta_on != "host" && fasta_on != "gpu")) return usage();
   if (prefix.empty()) prefix = fasta + ".index"; /* src/guidescan.cxx:112-117 */
-  std::string text;
+  std::string host_text;
   genome_structure gs;
-  if (!parse_fasta(fasta, text, gs)) {
-    std::cerr << "error: cannot read " << fasta << "\n";
-    return 1;
+  fasta_holder parsed; /* --fasta gpu: owns the text copied back */
+  const char *text_p = nullptr;
+  size_t text_n = 0;
+  double s_text_back = 0;
+  const double t_start = decode_cmd::now_s();
+  if (fasta_on == "gpu") {
+    const gs_status rc = parse_fasta_gpu(fasta, device, parsed, gs, &text_p, &text_n, &s_text_back);
+    if (rc != GS_OK) {
+      std::cerr << "error: " << (rc == GS_ERR_IO ? "cannot read " + fasta : std::string(gs_status_string(rc))) << "\n";
+      return 1;
+    }
+  } else {
+    if (!parse_fasta(fasta, host_text, gs)) {
+      std::cerr << "error: cannot read " << fasta << "\n";
+      return 1;
+    }
+    text_p = host_text.data();
+    text_n = host_text.size();
   }
+  struct text_view {
+    const char *p;
+    size_t n;
+    const char *data() const { return p; }
+    size_t size() const { return n; }
+  } const text{text_p, text_n};
+  const double t_read = decode_cmd::now_s();
   if (!write_gs(prefix + ".gs", gs)) {
     std::cerr << "error: cannot write " << prefix << ".gs\n";
     return 1;
   }
   std::ofstream dna(prefix + ".dna", std::ios::binary);
   dna.write(text.data(), (std::streamsize)text.size());
+  dna.close();
   if (!dna) {
     std::cerr << "error: cannot write " << prefix << ".dna\n";
     return 1;
   }
   std::cout << "Wrote " << prefix << ".gs and " << prefix << ".dna (" << text.size() << " bases, "
             << gs.names.size() << " sequences)\n";
+  if (verbose) { /* the two stages of this command; what the wall clock shows beyond them is the process's start and end */
+    fprintf(stderr, "Stages: FASTA read %.3f s, .gs and .dna writes %.3f s", t_read - t_start, decode_cmd::now_s() - t_read);
+    if (fasta_on == "gpu") {
+      double ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      gs_debug_fasta_ms(parsed.fa, ms);
+      fprintf(stderr, "; fasta gpu: file reads %.3f s, waits for the uploads %.3f s, device stage %.3f s (its five passes %.3f s), titles and names "
+                      "%.3f s, text back %.3f s",
+              1e-3 * ms[0], 1e-3 * ms[1], 1e-3 * ms[2], 1e-3 * (ms[4] + ms[5] + ms[6] + ms[7] + ms[8]), 1e-3 * ms[3], s_text_back);
+    }
+    fprintf(stderr, "\n");
+  }
   if (store_sa || sdsl) {
     /* the part of the index worth storing: both suffix arrays (built on the GPU now), so that
      * `enumerate` skips the sort; 8 bytes per base on disk (--store-sa) - or the reference's own

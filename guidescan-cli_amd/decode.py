@@ -223,10 +223,11 @@ def inflate_bgzf(data: bytes, device=0) -> bytes:
     return import_module("guidescan-cli_amd.api").inflate_bgzf(data, device=device)
 
 
-def decode_bam(db_path, fasta_path, mode="succinct", device=0, group_members=None) -> str:
+def decode_bam(db_path, fasta_path, mode="succinct", device=0, group_members=None, fasta="host") -> str:
     """the text `decode_database.py DB.bam FASTA --mode MODE` prints, with the BAM file inflated, split and decoded on the
     GPU (api.Decoder.decode_bam over gs_decode_bam).  The header is read on the host.  group_members: members per
-    call (None: the whole file in one); the text does not depend on it."""
+    call (None: the whole file in one); the text does not depend on it.  fasta="gpu": the FASTA is parsed on the device
+    too and its text never leaves HBM (api.DeviceFasta, gs_decoder_open_fasta)."""
     if mode not in ("succinct", "complete"):
         raise ValueError("mode is succinct or complete")
     data = Path(db_path).read_bytes()
@@ -242,13 +243,12 @@ def decode_bam(db_path, fasta_path, mode="succinct", device=0, group_members=Non
             at = sum(sizes[:n_head])
             head += gzip.decompress(data[at:at + sizes[n_head]])
             n_head += 1
-    fasta = parse_fasta_records(fasta_path)
     from importlib import import_module
     api = import_module("guidescan-cli_amd.api")
     complete = mode == "complete"
     step = group_members or len(sizes) or 1
     out, done, at, k = [], 0, 0, 0
-    with api.Decoder(sq, fasta, device=device) as dec:
+    with _open_decoder(api, sq, fasta_path, device, fasta) as dec:
         while k < len(sizes) or k == 0:
             take = max(step, n_head) if k == 0 else step
             nbytes = sum(sizes[k:k + take])
@@ -377,18 +377,31 @@ def decode_text(sq, records, fasta, mode="succinct", tables=None) -> str:
     return "\n".join([COMPLETE_HEADER if complete else SUCCINCT_HEADER] + rows) + "\n"
 
 
-def decode_database(db_path, fasta_path, mode="succinct", device=None, tables=None) -> str:
+def _open_decoder(api, sq, fasta_path, device, fasta):
+    """api.Decoder over the FASTA read here (fasta="host") or parsed on the device (fasta="gpu")"""
+    if fasta not in ("host", "gpu"):
+        raise ValueError("fasta is host or gpu")
+    if fasta == "host":
+        return api.Decoder(sq, parse_fasta_records(fasta_path), device=device)
+    with api.DeviceFasta.parse(fasta_path, "records", device) as fa:   # the decoder keeps its own copy in HBM
+        return api.Decoder(sq, fa, device=device)
+
+
+def decode_database(db_path, fasta_path, mode="succinct", device=None, tables=None, fasta="host") -> str:
     """the text `decode_database.py DB FASTA --mode MODE` prints.  device=None: this module; an int: that GPU
     (api.Decoder over gs_decode_records; the records are read here and handed over as arrays).  tables: cfd_tables()
-    of another source than the library's, for the model."""
+    of another source than the library's, for the model.  fasta="gpu" (with a device): as decode_bam."""
     if mode not in ("succinct", "complete"):
         raise ValueError("mode is succinct or complete")
+    if fasta not in ("host", "gpu"):
+        raise ValueError("fasta is host or gpu")
+    if fasta == "gpu" and device is None:
+        raise ValueError('fasta="gpu" needs a device')
     sq, records = read_database(db_path)
-    fasta = parse_fasta_records(fasta_path)
     if device is None:
-        return decode_text(sq, records, fasta, mode, tables)
+        return decode_text(sq, records, parse_fasta_records(fasta_path), mode, tables)
     from importlib import import_module
     api = import_module("guidescan-cli_amd.api")
-    with api.Decoder(sq, fasta, device=device) as dec:
+    with _open_decoder(api, sq, fasta_path, device, fasta) as dec:
         body = dec.decode_records(records, complete=mode == "complete")
     return (COMPLETE_HEADER if mode == "complete" else SUCCINCT_HEADER) + "\n" + body

@@ -786,6 +786,65 @@ gs_status gs_decode_bam_device(gs_decoder *dec, const void *bgzf, uint64_t len, 
  * ms[4] = milliseconds of inflate (with the upload), record starts, fields, the decoder's kernels. */
 gs_status gs_debug_decode_bam_last(gs_decoder *dec, uint64_t *counts, double *ms);
 
+/* ---- FASTA read on the device: the first step of `index` and of `decode` ------------------------------------ */
+
+typedef struct gs_fasta gs_fasta;
+
+/* Both rule sets split the file at '\n' only (a last line without a newline is a line; a newline at the end of the file
+ * starts none); a line is a title iff its first byte is '>'; blank = C-locale isspace.
+ * GS_FASTA_INDEX_RULES: what the reference's `index` reads (src/genomics/seq_io.cxx:47-63 the sequence, :74-110 the
+ *   structure).  A non-title line adds its bytes with the blanks at both ends removed (blanks inside stay), a-z folded to
+ *   upper case and every other byte as it is; lines ahead of the first title add to the text but to no record; a record's
+ *   line_len is the sum of its lines' untrimmed lengths (seq_io.cxx:100-104; a '\r' counts, the '\n' does not); the name
+ *   is the title without its '>' up to the first ' '.
+ * GS_FASTA_RECORD_RULES: Bio.SeqIO.to_dict as scripts/decode_database.py:223 calls it.  Lines ahead of the first title are
+ *   dropped; every blank of a non-title line is removed; case is left alone; the name is the first run of non-blank bytes
+ *   behind '>', leading blanks skipped; a name that occurs twice is GS_ERR_FORMAT, and gs_status_string(GS_ERR_FORMAT)
+ *   then reads "FASTA record 'NAME' occurs twice" (the first such title of the file). */
+#define GS_FASTA_INDEX_RULES 0u
+#define GS_FASTA_RECORD_RULES 1u
+
+/* A FASTA file's bytes -> the text and the record table, parsed in HBM (seq_io.cxx:47-63, :74-110 or SeqIO.to_dict, by
+ * `rules`).  raw: host memory, uploaded whole.  The object holds the text in HBM until gs_fasta_free.  Device memory that
+ * runs out: GS_ERR_NOMEM, nothing stays allocated. */
+gs_status gs_fasta_parse(int device, const uint8_t *raw, uint64_t len, uint32_t rules, gs_fasta **out);
+/* The same (seq_io.cxx:57-63 opens the file by name too) from a regular file, read in chunks into two page-locked
+ * buffers: a chunk is uploaded while the next is read.  GS_ERR_IO ("cannot read PATH") when it cannot be read - and for
+ * anything that is no regular file (a pipe, a process substitution): the device buffer is sized from the file's length. */
+gs_status gs_fasta_parse_file(int device, const char *path, uint32_t rules, gs_fasta **out);
+/* The same (seq_io.cxx:47-63, :74-110) with the raw bytes in HBM already; the kernels run on `stream`, the call returns
+ * when they are done.  d_raw is only read and stays the caller's. */
+gs_status gs_fasta_parse_device(int device, const void *d_raw, uint64_t len, uint32_t rules, void *stream, gs_fasta **out);
+/* records (title lines), bytes of the text, bytes of all names (genome_structure of seq_io.cxx:74-110) */
+gs_status gs_fasta_info(const gs_fasta *fa, uint64_t *n_records, uint64_t *text_len, uint64_t *names_bytes);
+/* Per record (any array may be NULL): where its title line begins in the file and its length without the newline; its
+ * symbols text[text_off, + text_len); line_len (seq_io.cxx:100-104, both rule sets); its name names[name_off[r],
+ * name_off[r + 1]) - name_off has n + 1 entries, names is not NUL terminated (a name may hold any byte). */
+gs_status gs_fasta_records(const gs_fasta *fa, uint64_t *title_off, uint64_t *title_len, uint64_t *text_off, uint64_t *text_len,
+                           uint64_t *line_len, uint64_t *name_off, char *names);
+/* The text (seq_io.cxx:57-63: the <fasta>.forward.dna bytes under the index rules): on_device as in gs_kmers_get - a
+ * pointer into HBM, or a host copy that the object makes on the first such call (under a lock of its own: any number of
+ * threads may ask) and owns (NUL terminated). */
+gs_status gs_fasta_text(const gs_fasta *fa, int on_device, const void **text);
+void gs_fasta_free(gs_fasta *fa);
+/* gs_decoder_open (scripts/decode_database.py:142-146, :223) from a GS_FASTA_RECORD_RULES object of the same device: sq's
+ * names are matched to the records, the text goes from the object to the decoder inside HBM, and the decoder is in the
+ * state gs_decoder_open reaches from the host reader's output.  A name without a record: chr_text_len = UINT64_MAX.
+ * The object is still the caller's to free, at any time afterwards. */
+gs_status gs_decoder_open_fasta(int device, const gs_fasta *fa, const gs_genome_structure *sq, gs_decoder **out);
+/* the bytes of a tile of the device passes */
+uint64_t gs_debug_fasta_tile_bytes(void);
+/* Host only: the summaries, their composition and the walk of the device passes (gs_fasta_scan.h), run one tile after the
+ * other with tiles of `tile_bytes` (any size from 1 up): the same text and table (seq_io.cxx:47-63, :74-110 / SeqIO.to_dict).
+ * The object has no device side: gs_fasta_text(.., 1, ..) is GS_ERR_ARG. */
+gs_status gs_debug_fasta_host(const uint8_t *raw, uint64_t len, uint32_t rules, uint64_t tile_bytes, gs_fasta **out);
+/* the bytes of a staging chunk of gs_fasta_parse_file (32 MB); set != 0 replaces it, for every later call of the process */
+uint64_t gs_debug_fasta_chunk_bytes(uint64_t set);
+/* ms[9] of the object's making.  Host clocks: the file's reads, waits for its uploads, the device stage (its allocations,
+ * the five passes and the waits for their results), the title gather with the names.  Then the passes alone, by events
+ * in the stream: tile summaries, their two scans, tile counts, the counts' scan, emit. */
+gs_status gs_debug_fasta_ms(const gs_fasta *fa, double *ms);
+
 const char *gs_status_string(gs_status s);
 const char *gs_version(void);
 
