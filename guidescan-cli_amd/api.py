@@ -79,6 +79,12 @@ class GsDecodeBatch(C.Structure):
                 ("hex", C.c_void_p), ("hex_off", C.c_void_p)]
 
 
+class GsKmersReport(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("L", C.c_uint64), ("P", C.c_uint64), ("n_lines", C.c_uint64),
+                ("bad_kind", C.c_uint32), ("pad", C.c_uint32), ("bad_line", C.c_uint64), ("bad_row", C.c_uint64),
+                ("bad_off", C.c_uint64), ("bad_len", C.c_uint64), ("bad_text", C.c_void_p), ("ms", C.c_double * 8)]
+
+
 def build_library():
     subprocess.run(["make", "-s", "-C", str(PKG / "csrc")], check=True, timeout=3600)
 
@@ -294,6 +300,18 @@ def lib():
     L.gs_debug_fasta_chunk_bytes.argtypes = [u64]
     L.gs_debug_fasta_ms.restype = i32
     L.gs_debug_fasta_ms.argtypes = [vp, vp]
+    L.gs_kmers_parse.restype = i32
+    L.gs_kmers_parse.argtypes = [i32, vp, u64, C.POINTER(vp), C.POINTER(GsKmersReport)]
+    L.gs_kmers_parse_file.restype = i32
+    L.gs_kmers_parse_file.argtypes = [i32, C.c_char_p, C.POINTER(vp), C.POINTER(GsKmersReport)]
+    L.gs_kmers_parse_device.restype = i32
+    L.gs_kmers_parse_device.argtypes = [i32, vp, u64, vp, C.POINTER(vp), C.POINTER(GsKmersReport)]
+    L.gs_debug_kmers_tile_bytes.restype = u64
+    L.gs_debug_kmers_tile_bytes.argtypes = []
+    L.gs_debug_kmers_chunk_bytes.restype = u64
+    L.gs_debug_kmers_chunk_bytes.argtypes = [u64]
+    L.gs_debug_kmers_host.restype = i32
+    L.gs_debug_kmers_host.argtypes = [vp, u64, u64, C.POINTER(vp), C.POINTER(GsKmersReport)]
     L.gs_status_string.restype = C.c_char_p
     L.gs_status_string.argtypes = [i32]
     L.gs_version.restype = C.c_char_p
@@ -324,7 +342,9 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_decode_bam", "gs_decode_bam_device", "gs_debug_decode_bam_last",
            "gs_fasta_parse", "gs_fasta_parse_file", "gs_fasta_parse_device", "gs_fasta_info", "gs_fasta_records", "gs_fasta_text",
            "gs_fasta_free", "gs_decoder_open_fasta", "gs_debug_fasta_tile_bytes", "gs_debug_fasta_host",
-           "gs_debug_fasta_chunk_bytes", "gs_debug_fasta_ms"]
+           "gs_debug_fasta_chunk_bytes", "gs_debug_fasta_ms",
+           "gs_kmers_parse", "gs_kmers_parse_file", "gs_kmers_parse_device", "gs_debug_kmers_tile_bytes",
+           "gs_debug_kmers_chunk_bytes", "gs_debug_kmers_host"]
 
 
 def _check(rc):
@@ -561,17 +581,54 @@ class DeviceKmers:
         self.n = int(n.value)
         self.seqs_ptr, self.pams_ptr, self.pos_ptr, self.sense_ptr = a.value, b.value, c.value, d.value
 
+    @classmethod
+    def parse(cls, src, device=0):
+        """The rows of a kmers file parsed on the GPU (gs_kmers_parse / gs_kmers_parse_file) under the rules of the
+        command's host reader.  src: a path (read in chunks through page-locked staging), or the file's bytes.  The
+        object carries the file's ids (ids_ptr, id_offsets_ptr, sense_positive_ptr) and no positions; .report holds
+        n, L, P, n_lines and ms.  Raises KmersFileError (status 6) where the host reader fails, GsError with status 3
+        for rows of several shapes."""
+        h, rep = C.c_void_p(), GsKmersReport()
+        if isinstance(src, (str, os.PathLike)):
+            rc = lib().gs_kmers_parse_file(device, os.fsencode(src), C.byref(h), C.byref(rep))
+        else:
+            raw = np.frombuffer(src, dtype=np.uint8) if isinstance(src, (bytes, bytearray, memoryview)) else np.ascontiguousarray(src, dtype=np.uint8)
+            rc = lib().gs_kmers_parse(device, raw.ctypes.data if raw.size else None, raw.size, C.byref(h), C.byref(rep))
+        return cls._parsed(rc, h, rep)
+
+    @classmethod
+    def parse_device(cls, d_raw_ptr, length, device=0, stream=None):
+        """the raw bytes are in HBM already (d_raw_ptr: a device address, at any alignment)"""
+        h, rep = C.c_void_p(), GsKmersReport()
+        rc = lib().gs_kmers_parse_device(device, d_raw_ptr if length else None, length, stream, C.byref(h), C.byref(rep))
+        return cls._parsed(rc, h, rep)
+
+    @classmethod
+    def _parsed(cls, rc, h, rep, on_device=True):
+        report = _kmers_report(rc, rep)
+        km = cls.__new__(cls)
+        km._h, km.k, km.P, km.n, km.report = h, report["L"], report["P"], report["n"], report
+        km.pos_ptr = None
+        if on_device:
+            a, b, d = C.c_void_p(), C.c_void_p(), C.c_void_p()
+            _check(lib().gs_kmers_get(h, 1, None, C.byref(a), C.byref(b), None, C.byref(d)))
+            km.seqs_ptr, km.pams_ptr, km.sense_ptr = a.value, b.value, d.value
+            _check(lib().gs_kmers_get_ids(h, 1, C.byref(a), C.byref(b), C.byref(d)))
+            km.ids_ptr, km.id_offsets_ptr, km.sense_positive_ptr = a.value, b.value, d.value
+        return km
+
     def to_host(self):
-        """-> (seqs uint8[n,k], pams uint8[n,P], positions uint32[n] 1-based, senses uint8[n])"""
+        """-> (seqs uint8[n,k], pams uint8[n,P], positions uint32[n] 1-based, senses uint8[n]); the positions are None
+        on the rows of a kmers file"""
         n, a, b, c, d = C.c_uint64(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         _check(lib().gs_kmers_get(self._h, 0, C.byref(n), C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         m = int(n.value)
         if m == 0:
-            return (np.empty((0, self.k), np.uint8), np.empty((0, self.P), np.uint8), np.empty(0, np.uint32),
-                    np.empty(0, np.uint8))
+            return (np.empty((0, self.k), np.uint8), np.empty((0, self.P), np.uint8),
+                    None if getattr(self, "report", None) else np.empty(0, np.uint32), np.empty(0, np.uint8))
         seqs = np.frombuffer(C.string_at(a, m * self.k), dtype=np.uint8).reshape(m, self.k).copy()
         pams = np.frombuffer(C.string_at(b, m * self.P), dtype=np.uint8).reshape(m, self.P).copy()
-        pos = np.frombuffer(C.string_at(c, 4 * m), dtype=np.uint32).copy()
+        pos = np.frombuffer(C.string_at(c, 4 * m), dtype=np.uint32).copy() if c.value else None
         sense = np.frombuffer(C.string_at(d, m), dtype=np.uint8).copy()
         return seqs, pams, pos, sense
 
@@ -610,6 +667,64 @@ class DeviceKmers:
             self.close()
         except Exception:
             pass
+
+
+class KmersFileError(GsError):
+    """a kmers file that the host reader refuses: .message is that reader's message; kind, line, row, offset and text as
+    in gs_kmers_report"""
+
+    def __init__(self, status, msg, report):
+        super().__init__(status, msg)
+        self.message = msg
+        self.kind, self.line, self.row = report["bad_kind"], report["bad_line"], report["bad_row"]
+        self.offset, self.text = report["bad_off"], report["bad_text"]
+
+
+def _kmers_report(rc, rep):
+    """gs_kmers_report -> dict; raises for rc != 0"""
+    text = C.string_at(rep.bad_text, rep.bad_len) if rep.bad_text else b""
+    if rep.bad_text:
+        lib().gs_free(rep.bad_text)
+    report = {k: int(getattr(rep, k)) for k in ("n", "L", "P", "n_lines", "bad_kind", "bad_line", "bad_row", "bad_off")}
+    report["bad_text"] = text
+    report["ms"] = dict(zip(("file_reads", "upload_waits", "device_stage", "summaries", "line_starts", "line_walk",
+                             "row_scan", "emit"), (float(x) for x in rep.ms)))
+    if rc != 0 and report["bad_kind"]:
+        what = ("", "kmers row with too few columns: ", "kmers position is not an integer: ", "empty kmers file",
+                "kmers file lacks column ")[report["bad_kind"]]
+        raise KmersFileError(rc, what + text.decode("latin-1"), report)
+    _check(rc)
+    return report
+
+
+def parse_kmers_model_tiles(raw: bytes, tile_bytes):
+    """the host model of the device reader with tiles of tile_bytes (gs_debug_kmers_host; no GPU) ->
+    dict(n, L, P, seqs bytes, pams bytes, ids bytes, id_off uint64[n+1], sense uint8[n], report)"""
+    h, rep = C.c_void_p(), GsKmersReport()
+    raw = bytes(raw)
+    rc = lib().gs_debug_kmers_host(raw if raw else None, len(raw), tile_bytes, C.byref(h), C.byref(rep))
+    km = DeviceKmers._parsed(rc, h, rep, on_device=False)
+    try:
+        return kmers_arrays(km)
+    finally:
+        km.close()
+
+
+def kmers_arrays(km):
+    """the host copies of a parsed DeviceKmers as parse_kmers_model_tiles returns them"""
+    seqs, pams, _, _ = km.to_host()
+    ids, off, sp = km.ids_to_host()
+    return {"n": km.n, "L": km.k, "P": km.P, "seqs": seqs.tobytes(), "pams": pams.tobytes(), "ids": ids, "id_off": off,
+            "sense": sp, "report": km.report}
+
+
+def kmers_tile_bytes() -> int:
+    return int(lib().gs_debug_kmers_tile_bytes())
+
+
+def kmers_chunk_bytes(set_to=0) -> int:
+    """the staging chunk of gs_kmers_parse_file; set_to != 0 replaces it for the process"""
+    return int(lib().gs_debug_kmers_chunk_bytes(set_to))
 
 
 def generate_kmers(chrm, pam="NGG", k=20, start=False, device=0, chrm_device_ptr=None, chrm_len=None):

@@ -25,26 +25,11 @@
  * offsets), so that a batch can hold the tail of one chromosome and the heads of the next ones.
  */
 #include "gs_common.h"
+#include "gs_kmers_obj.h"
 
 #include <rocprim/rocprim.hpp>
 
 #define KM_BLOCK 256
-
-struct gs_kmers {
-  int device = 0;
-  uint64_t n = 0;
-  uint32_t k = 0, P = 0;
-  void *d_seqs = nullptr, *d_pams = nullptr, *d_pos = nullptr, *d_sense = nullptr;
-  std::vector<uint8_t> h_seqs, h_pams, h_sense;
-  std::vector<uint32_t> h_pos;
-  bool have_host = false;
-  /* gs_kmers_encode_ids: the ids back to back, n + 1 offsets, the senses as 0 / 1 ("+") */
-  void *d_ids = nullptr, *d_id_off = nullptr, *d_sense01 = nullptr;
-  uint64_t id_bytes = 0;
-  bool have_ids = false, have_host_ids = false;
-  std::vector<uint8_t> h_ids, h_sense01;
-  std::vector<uint64_t> h_id_off;
-};
 
 struct gs_km_args {
   const uint8_t *chr;
@@ -316,6 +301,7 @@ extern "C" gs_status gs_kmers_get(gs_kmers *km, int on_device, uint64_t *n, cons
   if (!km) return GS_ERR_ARG;
   if (n) *n = km->n;
   if (on_device) {
+    if (km->device < 0) return GS_ERR_ARG;
     if (seqs) *seqs = km->d_seqs;
     if (pams) *pams = km->d_pams;
     if (positions) *positions = km->d_pos;
@@ -326,19 +312,19 @@ extern "C" gs_status gs_kmers_get(gs_kmers *km, int on_device, uint64_t *n, cons
     GS_HIP(hipSetDevice(km->device));
     km->h_seqs.resize((size_t)km->n * km->k);
     km->h_pams.resize((size_t)km->n * km->P);
-    km->h_pos.resize((size_t)km->n);
+    km->h_pos.resize(km->parsed ? 0 : (size_t)km->n);
     km->h_sense.resize((size_t)km->n);
     if (km->n) {
       GS_HIP(hipMemcpy(km->h_seqs.data(), km->d_seqs, km->h_seqs.size(), hipMemcpyDeviceToHost));
       GS_HIP(hipMemcpy(km->h_pams.data(), km->d_pams, km->h_pams.size(), hipMemcpyDeviceToHost));
-      GS_HIP(hipMemcpy(km->h_pos.data(), km->d_pos, 4 * km->h_pos.size(), hipMemcpyDeviceToHost));
+      if (!km->parsed) GS_HIP(hipMemcpy(km->h_pos.data(), km->d_pos, 4 * km->h_pos.size(), hipMemcpyDeviceToHost));
       GS_HIP(hipMemcpy(km->h_sense.data(), km->d_sense, km->h_sense.size(), hipMemcpyDeviceToHost));
     }
     km->have_host = true;
   }
   if (seqs) *seqs = km->h_seqs.data();
   if (pams) *pams = km->h_pams.data();
-  if (positions) *positions = km->h_pos.data();
+  if (positions) *positions = km->parsed ? nullptr : km->h_pos.data();
   if (senses) *senses = km->h_sense.data();
   return GS_OK;
 }
@@ -500,6 +486,10 @@ static gs_status km_encode(gs_kmers *km, const char *prefix, const char *chr_nam
 
 extern "C" gs_status gs_kmers_encode_ids(gs_kmers *km, const char *prefix, const char *chr_name, void *stream) {
   if (!km || !prefix || !chr_name) return GS_ERR_ARG;
+  if (km->parsed) {
+    gs_set_error("gs_kmers_encode_ids on the rows of a kmers file: the ids are the file's");
+    return GS_ERR_ARG;
+  }
   uint64_t bytes = 0;
   try {
     return km_encode(km, prefix, chr_name, false, (hipStream_t)stream, nullptr, nullptr, &bytes);
@@ -516,6 +506,7 @@ extern "C" gs_status gs_kmers_get_ids(gs_kmers *km, int on_device, const void **
     return GS_ERR_ARG;
   }
   if (on_device) {
+    if (km->device < 0) return GS_ERR_ARG;
     if (ids) *ids = km->d_ids;
     if (id_offsets) *id_offsets = km->d_id_off;
     if (sense_positive) *sense_positive = km->d_sense01;
@@ -543,6 +534,10 @@ extern "C" gs_status gs_kmers_get_ids(gs_kmers *km, int on_device, const void **
 
 extern "C" gs_status gs_kmers_csv(gs_kmers *km, const char *prefix, const char *chr_name, char **text, uint64_t *len) {
   if (!km || !prefix || !chr_name || !text || !len) return GS_ERR_ARG;
+  if (km->parsed) {
+    gs_set_error("gs_kmers_csv on the rows of a kmers file: they carry no positions");
+    return GS_ERR_ARG;
+  }
   *text = nullptr;
   *len = 0;
   void *d_text = nullptr;
@@ -566,8 +561,8 @@ extern "C" gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, g
     if (!parts[i]) return GS_ERR_ARG;
   for (uint32_t i = 0; i < n_parts; i++)
     if (parts[i]->device != parts[0]->device || parts[i]->k != parts[0]->k || parts[i]->P != parts[0]->P ||
-        parts[i]->have_ids != parts[0]->have_ids) {
-      gs_set_error("gs_kmers_concat: parts of different devices, kmer or PAM lengths, or ids on some of them only");
+        parts[i]->have_ids != parts[0]->have_ids || parts[i]->parsed != parts[0]->parsed || parts[i]->device < 0) {
+      gs_set_error("gs_kmers_concat: parts of different devices, kmer or PAM lengths or origins, or ids on some of them only");
       return GS_ERR_ARG;
     }
   gs_kmers *km = new (std::nothrow) gs_kmers();
@@ -580,6 +575,7 @@ extern "C" gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, g
   km->k = parts[0]->k;
   km->P = parts[0]->P;
   km->have_ids = parts[0]->have_ids;
+  km->parsed = parts[0]->parsed;
   for (uint32_t i = 0; i < n_parts; i++) {
     km->n += parts[i]->n;
     km->id_bytes += parts[i]->id_bytes;
@@ -597,7 +593,7 @@ extern "C" gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, g
   KM_HIP(hipSetDevice(km->device));
   KM_HIP(hipMalloc(&km->d_seqs, (size_t)km->n * k + 16));
   KM_HIP(hipMalloc(&km->d_pams, (size_t)km->n * P + 16));
-  KM_HIP(hipMalloc(&km->d_pos, 4 * (size_t)km->n + 16));
+  if (!km->parsed) KM_HIP(hipMalloc(&km->d_pos, 4 * (size_t)km->n + 16));
   KM_HIP(hipMalloc(&km->d_sense, (size_t)km->n + 16));
   if (km->have_ids) {
     KM_HIP(hipMalloc(&km->d_ids, (size_t)km->id_bytes + 16));
@@ -611,7 +607,7 @@ extern "C" gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, g
     if (p->n) {
       KM_HIP(hipMemcpyAsync((char *)km->d_seqs + at * k, p->d_seqs, (size_t)p->n * k, hipMemcpyDeviceToDevice, nullptr));
       KM_HIP(hipMemcpyAsync((char *)km->d_pams + at * P, p->d_pams, (size_t)p->n * P, hipMemcpyDeviceToDevice, nullptr));
-      KM_HIP(hipMemcpyAsync((char *)km->d_pos + at * 4, p->d_pos, (size_t)p->n * 4, hipMemcpyDeviceToDevice, nullptr));
+      if (!km->parsed) KM_HIP(hipMemcpyAsync((char *)km->d_pos + at * 4, p->d_pos, (size_t)p->n * 4, hipMemcpyDeviceToDevice, nullptr));
       KM_HIP(hipMemcpyAsync((char *)km->d_sense + at, p->d_sense, (size_t)p->n, hipMemcpyDeviceToDevice, nullptr));
     }
     if (km->have_ids) {

@@ -133,13 +133,8 @@ inline std::vector<std::string> split_csv(const std::string &line) {
   }
   return out;
 }
-/* src/genomics/kmer.cxx:9-25 */
-inline bool read_kmers(const std::string &path, std::vector<kmer_row> &rows, std::string &err) {
-  std::ifstream in(path);
-  if (!in) {
-    err = "cannot open kmers file";
-    return false;
-  }
+/* src/genomics/kmer.cxx:9-25, from an open stream */
+inline bool read_kmers(std::istream &in, std::vector<kmer_row> &rows, std::string &err) {
   std::string line;
   if (!std::getline(in, line)) {
     err = "empty kmers file";
@@ -181,6 +176,15 @@ inline bool read_kmers(const std::string &path, std::vector<kmer_row> &rows, std
     rows.push_back(std::move(r));
   }
   return true;
+}
+/* src/genomics/kmer.cxx:9-25 */
+inline bool read_kmers(const std::string &path, std::vector<kmer_row> &rows, std::string &err) {
+  std::ifstream in(path);
+  if (!in) {
+    err = "cannot open kmers file";
+    return false;
+  }
+  return read_kmers((std::istream &)in, rows, err);
 }
 
 /* the index handles of a command, one per device: closed when the command returns, whichever way */

@@ -2,7 +2,8 @@
  * enumerate_cmd.hpp -- `guidescan enumerate PREFIX (-f KMERS.csv | --all-candidates) -o OUT ...`: the off-target database
  * of a set of guides (src/guidescan.cxx:181-258), searched, scored and - where the batch allows it - encoded on the device
  * through the C-ABI.  Control plane only.  run() is a sequence of stages: options, genome text, guides (a kmers file or
- * the candidate scan), one index per device, the job, the output file, the batches, the pipeline, the report.
+ * the candidate scan; a kmers file under --kmers gpu is parsed on the device and then treated as a scan's candidates),
+ * one index per device, the job, the output file, the batches, the pipeline, the report.
  *
  * A batch takes one of three routes to its text: the device's text or BGZF members (--encoder gpu, --bgzf gpu: a batch
  * that is all fast path, from device pointers under --all-candidates on one device, else from host pointers), the fast
@@ -55,7 +56,8 @@ struct options {
   int device = 0, gpus = 1;
   size_t batch_size = 0;
   unsigned fmt_threads = 0;
-  bool all_candidates = false;
+  bool all_candidates = false, verbose = false;
+  std::string kmers; /* --kmers host|gpu: who reads the kmers file; empty: not given (host) */
   cli::candidate_opts co; /* co.start is --start, with or without --all-candidates */
 };
 
@@ -96,6 +98,8 @@ inline int parse_options(int argc, char **argv, int (*usage)(), options &o) {
     else if (a == "--batch-size") o.batch_size = (size_t)atoll(need("--batch-size"));
     else if (a == "--encoder") o.encoder = need("--encoder");
     else if (a == "--bgzf") o.bgzf = need("--bgzf");
+    else if (a == "--kmers") o.kmers = need("--kmers");
+    else if (a == "--verbose") o.verbose = true;
     else if (!a.empty() && a[0] != '-' && o.prefix.empty()) o.prefix = a;
     else return usage();
   }
@@ -105,6 +109,11 @@ inline int parse_options(int argc, char **argv, int (*usage)(), options &o) {
     return usage();
   }
   if (o.prefix.empty() || o.output.empty()) return usage();
+  if (!o.kmers.empty() && o.kmers != "host" && o.kmers != "gpu") return usage();
+  if (!o.kmers.empty() && o.kmers_file.empty()) {
+    std::cerr << "error: --kmers says who reads the kmers file of -f\n";
+    return usage();
+  }
   if (o.all_candidates && o.co.k < 1) return usage();
   if (!o.all_candidates && candidate_opts_given) {
     std::cerr << "error: --pam, --kmer-length, --min-chr-length, --prefix and --chromosomes describe the scan of --all-candidates; with -f the kmers file says what the guides are\n";
@@ -193,6 +202,7 @@ struct candidate_set {
   uint64_t n = 0;
   size_t n_chr = 0;
   uint32_t L = 0, P = 0;
+  bool from_file = false; /* --kmers gpu: the rows of the kmers file, parsed on the device */
   kmers_view d, h; /* h: once on_host */
   std::mutex mtx;
   bool on_host = false;
@@ -642,11 +652,53 @@ inline bool load_genome(const options &o, genome_structure &gs, std::string &tex
 /* -f: the guides are the rows of the kmers file */
 inline bool read_guides(const options &o, enumerate_job &job) {
   std::string err;
+  const auto t0 = std::chrono::steady_clock::now();
   if (!cli::read_kmers(o.kmers_file, job.kmers, err)) {
     std::cerr << "error: " << err << "\n";
     return false;
   }
+  if (o.verbose)
+    std::cout << "kmers host: read_kmers " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s\n";
   std::cout << "Read in " << job.kmers.size() << " kmer(s).\n";
+  return true;
+}
+
+/* -f --kmers gpu: the file is parsed on the first device (gs_kmers_parse_file) into a candidate set, and the command goes
+ * on as --all-candidates does from its scan.  The host reader's messages and status; a file the device reader does not
+ * take (rows of several shapes) is read by the host reader after all */
+inline bool read_guides_device(const options &o, enumerate_job &job, candidate_set &cand) {
+  gs_kmers_report rep;
+  gs_status rc = gs_kmers_parse_file(o.device, o.kmers_file.c_str(), &cand.all, &rep);
+  if (rc == GS_ERR_UNSUPPORTED) {
+    if (o.verbose) std::cout << "kmers gpu: rows of several shapes, the file is read on the host\n";
+    return read_guides(o, job);
+  }
+  if (rc == GS_ERR_FORMAT && rep.bad_kind >= GS_KMERS_BAD_FEW && rep.bad_kind <= GS_KMERS_BAD_LACKS) { /* cli::read_kmers' messages */
+    static const char *const what[5] = {"", "kmers row with too few columns: ", "kmers position is not an integer: ", "empty kmers file",
+                                        "kmers file lacks column "};
+    std::cerr << "error: " << what[rep.bad_kind] << std::string(rep.bad_text ? rep.bad_text : "", (size_t)rep.bad_len) << "\n";
+    gs_free(rep.bad_text);
+    return false;
+  }
+  if (rc == GS_ERR_IO) {
+    std::cerr << "error: cannot open kmers file\n";
+    return false;
+  }
+  if (rc == GS_OK) rc = view_kmers(cand.all, 1, &cand.n, cand.d);
+  if (rc != GS_OK) {
+    std::cerr << "error: kmers file on the device: " << gs_status_string(rc) << "\n";
+    return false;
+  }
+  cand.from_file = true;
+  cand.L = (uint32_t)rep.L;
+  cand.P = (uint32_t)rep.P;
+  job.cand = &cand;
+  /* as scan_candidates: one device, and a shape the fast path's key takes; every other batch takes the host route */
+  job.cand_device = (o.encoder == "gpu" || o.bgzf == "gpu") && o.gpus == 1 && cand.L <= 31 && 2 * cand.L + 3 * cand.P <= 59;
+  if (o.verbose)
+    std::cout << "kmers gpu: file reads " << rep.ms[0] / 1e3 << " s, waits for the uploads " << rep.ms[1] / 1e3 << " s, device stage "
+              << rep.ms[2] / 1e3 << " s\n";
+  std::cout << "Read in " << cand.n << " kmer(s).\n";
   return true;
 }
 
@@ -845,7 +897,9 @@ inline int report(const enumerate_job &job, const batch_pipeline::result &r, siz
   std::cout << "Processed " << n_guides << " kmers in " << secs << " seconds.\n";
   std::cout << "Stages (overlapping): device " << r.s_search << " s, text formatting " << r.s_format << " s, file writes " << r.s_write
             << " s\n";
-  if (job.cand)
+  if (job.cand && job.cand->from_file)
+    std::cout << "Kmers: " << job.cand->n << " row(s) parsed on the device in " << job.batches.size() << " batch(es)\n";
+  else if (job.cand)
     std::cout << "Candidates: " << job.cand->n << " guide(s) from " << job.cand->n_chr << " chromosome(s) in " << job.batches.size()
               << " batch(es)\n";
   if (job.encoder_gpu)
@@ -866,8 +920,9 @@ inline int run(int argc, char **argv, int (*usage)()) {
   bool from_sdsl = false;
   if (!load_genome(o, job.gs, text, from_sdsl)) return 1;
   candidate_set cand;
-  if (!(o.all_candidates ? scan_candidates(o, text, job, cand) : read_guides(o, job))) return 1;
-  const size_t n_guides = o.all_candidates ? (size_t)cand.n : job.kmers.size();
+  if (!(o.all_candidates ? scan_candidates(o, text, job, cand) : o.kmers == "gpu" ? read_guides_device(o, job, cand) : read_guides(o, job)))
+    return 1;
+  const size_t n_guides = job.cand ? (size_t)cand.n : job.kmers.size();
   cli::index_set idx((size_t)o.gpus);
   if (!build_indexes(o, text, from_sdsl, idx)) return 1;
   text = std::string();

@@ -30,6 +30,10 @@
  *       `enumerate -f` writes for that kmers file.  With --encoder gpu on one device the candidates, their ids and
  *       senses stay in HBM from the scan to the text (gs_enumerate_text_device); any other batch is copied to the
  *       host and takes the route of a kmers file's batch.
+ *       -f KMERS.csv --kmers gpu: the kmers file is parsed on the first device (gs_kmers_parse_file, the rules of
+ *       cli::read_kmers) and the command goes on as --all-candidates does from its scan: sequences, PAMs, ids and
+ *       senses stay in HBM where the batch allows it.  Same output, messages and exit status as --kmers host (the
+ *       default); a file whose rows differ in shape is read on the host after all.  --verbose: the reader's stage line.
  *       --format bam --bgzf gpu: batches that are all fast path leave the device as BGZF members (BAM records and
  *       deflate made in HBM: gs_enumerate_text with GS_TEXT_BAM | GS_TEXT_BGZF); any other batch, and every batch
  *       under the default --bgzf host, takes bam_writer.hpp's records and zlib.  Same records either way.
@@ -139,6 +143,8 @@ int usage() {
                "                 [--mode succinct|complete] [--max-off-targets N] [--start]\n"
                "                 [--rna-bulges N] [--dna-bulges N] [--bulge-form walk|seeded] [-t THRESHOLD] [-n FORMAT_THREADS]\n"
                "                 [--device D] [--gpus N] [--batch-size B] [--encoder host|gpu] [--bgzf host|gpu]\n"
+               "                 [--kmers host|gpu] [--verbose]\n"
+               "                 --kmers gpu (with -f): the kmers file is parsed on the first device; same output and messages\n"
                "                 with --all-candidates: [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S]\n"
                "                 [--chromosomes a,b,...]\n"
                "       guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--verbose]\n"

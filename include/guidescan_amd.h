@@ -669,6 +669,54 @@ gs_status gs_kmers_csv(gs_kmers *km, const char *prefix, const char *chr_name, c
 gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, gs_kmers **out);
 void gs_kmers_free(gs_kmers *km);
 
+/* ---- the kmers file read on the device: the guides of `enumerate -f` (src/genomics/kmer.cxx:9-25) ------------- */
+
+/* What a parse found.  bad_kind != 0: the call returned GS_ERR_FORMAT, made no object, and gs_status_string(GS_ERR_FORMAT)
+ * reads as cli::read_kmers' message. */
+#define GS_KMERS_BAD_FEW 1u      /* "kmers row with too few columns: LINE": bad_text is the line, its '\r' dropped */
+#define GS_KMERS_BAD_POSITION 2u /* "kmers position is not an integer: FIELD": bad_text is the trimmed field */
+#define GS_KMERS_BAD_EMPTY 3u    /* "empty kmers file" */
+#define GS_KMERS_BAD_LACKS 4u    /* "kmers file lacks column NAME": bad_text is NAME */
+typedef struct gs_kmers_report {
+  uint64_t n, L, P;  /* rows, and the symbols of every row's sequence and PAM */
+  uint64_t n_lines;  /* lines of the file, the header and the skipped ones included */
+  uint32_t bad_kind, pad;
+  /* the first failing row in file order: its line (0 = the header) and its number among the rows, from 0; where bad_text
+   * stands in the file and its bytes.  Only these bytes are copied back from the device. */
+  uint64_t bad_line, bad_row, bad_off, bad_len;
+  char *bad_text;    /* malloc'ed, NUL terminated behind bad_len bytes: release with gs_free.  NULL when bad_kind is 0 */
+  /* milliseconds.  Host clocks: the file's reads, waits for its uploads, the device stage (allocations, passes, waits for
+   * their results).  Then by events in the stream: tile summaries with their scan, line starts, the line walk, the scan
+   * of the rows and id lengths, the emit. */
+  double ms[8];
+} gs_kmers_report;
+
+/* The rows of a kmers file (src/genomics/kmer.cxx:9-25, under the rules of cli::read_kmers: gs_kmers_scan.h states them)
+ * as a gs_kmers object, parsed in HBM: sequences n*L, PAMs n*P, the ids back to back with n + 1 offsets and the senses
+ * as 0 / 1, bytes as they stand in the file.  raw: host memory, uploaded whole.  rep may be NULL.
+ * GS_ERR_FORMAT: the file fails as it fails on the host (rep->bad_*).  GS_ERR_UNSUPPORTED, no object: rows of several
+ * shapes, or a first row without a sequence - read the file on the host.  L > 31 or 2L + 3P > 59 still gives an object.
+ * On the object gs_kmers_get gives NULL for the positions and '+' / '-' for the senses; gs_kmers_get_ids, gs_kmers_concat
+ * (with other parsed objects) and the host copies work as for scanned ones; gs_kmers_encode_ids and gs_kmers_csv are
+ * GS_ERR_ARG.  Device memory at the peak: the raw bytes, the outputs, and 40 bytes per line plus 48 per 4,096 bytes for
+ * the passes; the raw bytes and the passes' arrays are freed before the call returns.  Out of it: GS_ERR_NOMEM, nothing
+ * stays allocated. */
+gs_status gs_kmers_parse(int device, const uint8_t *raw, uint64_t len, gs_kmers **out, gs_kmers_report *rep);
+/* The same (src/genomics/kmer.cxx:9-25 opens the file by name too) from a regular file, read in chunks into two
+ * page-locked buffers: a chunk is uploaded while the next is read.  GS_ERR_IO when it cannot be read or is no regular file. */
+gs_status gs_kmers_parse_file(int device, const char *path, gs_kmers **out, gs_kmers_report *rep);
+/* The same (src/genomics/kmer.cxx:9-25) with the raw bytes in HBM already, at any alignment; the kernels run on `stream`,
+ * the call returns when they are done.  d_raw is only read and stays the caller's. */
+gs_status gs_kmers_parse_device(int device, const void *d_raw, uint64_t len, void *stream, gs_kmers **out, gs_kmers_report *rep);
+/* the bytes of a tile of the device passes of gs_kmers_parse* (src/genomics/kmer.cxx:9-25) */
+uint64_t gs_debug_kmers_tile_bytes(void);
+/* the bytes of a staging chunk of gs_kmers_parse_file (src/genomics/kmer.cxx:9-25 from a file; 32 MB); set != 0 replaces it, for every later call of the process */
+uint64_t gs_debug_kmers_chunk_bytes(uint64_t set);
+/* Host only: the passes of the device reader (src/genomics/kmer.cxx:9-25 through gs_kmers_scan.h), run one after the other
+ * with tiles of `tile_bytes` and windows of min(tile_bytes, 16) bytes: the same arrays and report.  The object has no
+ * device side: gs_kmers_get / gs_kmers_get_ids with on_device != 0 are GS_ERR_ARG. */
+gs_status gs_debug_kmers_host(const uint8_t *raw, uint64_t len, uint64_t tile_bytes, gs_kmers **out, gs_kmers_report *rep);
+
 /* ---- SAM/BAM databases back to CSV on the device (scripts/decode_database.py) --------------------------------- */
 
 typedef struct gs_decoder gs_decoder;
