@@ -14,17 +14,15 @@
  */
 #include "gs_common.h"
 #include "gs_device.h"
+#include "gs_scratch.h"
+#include "gs_block_scan.h"
 #include "gs_decoder.h"
 #include "gs_fasta_scan.h"
 #include "host/fasta_names.hpp"
 
 #include <rocprim/rocprim.hpp>
 
-#include <sys/stat.h>
-
 #include <algorithm>
-#include <chrono>
-#include <cstdio>
 #include <cstdlib>
 #include <set>
 
@@ -73,25 +71,6 @@ struct fa_add {
   __host__ __device__ unsigned long long operator()(unsigned long long a, unsigned long long b) const { return a + b; }
 };
 
-/* Scan of one value per lane in LDS, the lane's value standing at index `at` (a permutation of 0..255): -> the
- * combination of the values at the indices below `at` (`none` at index 0); *total: of all 256.  lds is free again on return. */
-template <class T, class Op>
-__device__ __forceinline__ T fa_block_scan(T *lds, const T &v, uint32_t at, Op op, const T &none, T *total) {
-  lds[at] = v;
-  __syncthreads();
-  for (uint32_t d = 1; d < FA_THREADS; d <<= 1) {
-    T x = lds[at];
-    if (at >= d) x = op(lds[at - d], x);
-    __syncthreads();
-    lds[at] = x;
-    __syncthreads();
-  }
-  const T r = at ? lds[at - 1] : none;
-  if (total) *total = lds[FA_THREADS - 1];
-  __syncthreads();
-  return r;
-}
-
 struct fa_emitter {
   uint8_t *text;
   gs_fa_title *titles;
@@ -121,7 +100,7 @@ __global__ __launch_bounds__(FA_THREADS) void k_fa_tile(fa_args a) {
     /* each lane reads back its own bytes only: no barrier needed here, and the scans below begin with one */
     const gs_fa_sum s = gs_fa_summarize(mine, n);
     gs_fa_sum tile;
-    const gs_fa_sum left_in = fa_block_scan(s_scan, s, t, fa_fwd(), gs_fa_identity(), &tile);
+    const gs_fa_sum left_in = gs_block_scan<FA_THREADS>(s_scan, s, t, fa_fwd(), gs_fa_identity(), &tile);
     if (MODE == FA_SUM) {
       if (t == 0) {
         a.sums[k + 1] = tile;
@@ -129,13 +108,13 @@ __global__ __launch_bounds__(FA_THREADS) void k_fa_tile(fa_args a) {
       }
       continue;
     }
-    const gs_fa_sum right_in = fa_block_scan(s_scan, s, FA_THREADS - 1u - t, fa_rev(), gs_fa_identity(), (gs_fa_sum *)nullptr);
+    const gs_fa_sum right_in = gs_block_scan<FA_THREADS>(s_scan, s, FA_THREADS - 1u - t, fa_rev(), gs_fa_identity(), (gs_fa_sum *)nullptr);
     const gs_fa_sum left = gs_fa_compose(a.fwd[k], left_in), right = gs_fa_compose(right_in, a.bwd[a.n_tiles - 1 - k]);
     gs_fa_edge edge = gs_fa_edge_of(left, right, 0);
     gs_fa_count_only none;
     const unsigned long long mine_kept = gs_fa_walk(mine, n, at, a.rules, edge, none);
     unsigned long long tile_kept = 0;
-    const unsigned long long before = fa_block_scan((unsigned long long *)s_scan, mine_kept, t, fa_add(), 0ull, &tile_kept);
+    const unsigned long long before = gs_block_scan<FA_THREADS>((unsigned long long *)s_scan, mine_kept, t, fa_add(), 0ull, &tile_kept);
     if (MODE == FA_COUNT) {
       if (t == 0) a.counts[k] = tile_kept;
       continue;
@@ -156,42 +135,6 @@ __global__ __launch_bounds__(64) void k_fa_titles(const uint8_t *raw, const gs_f
     for (uint64_t i = threadIdx.x; i < len; i += 64u) dst[to + i] = raw[off + i];
   }
 }
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-/* plain allocations of the exact size, all released by the holder's destructor unless taken out */
-struct fa_mem {
-  std::vector<void *> p;
-  ~fa_mem() {
-    for (void *q : p)
-      if (q) (void)hipFree(q);
-  }
-  gs_status get(size_t bytes, void **out) {
-    *out = nullptr;
-    if (hipMalloc(out, bytes ? bytes : 16) != hipSuccess) {
-      (void)hipGetLastError();
-      *out = nullptr;
-      gs_set_error("out of device memory");
-      return GS_ERR_NOMEM;
-    }
-    p.push_back(*out);
-    return GS_OK;
-  }
-  void release(void *q) { /* the caller keeps q */
-    for (void *&x : p)
-      if (x == q) x = nullptr;
-  }
-};
-
-struct fa_events {
-  hipEvent_t e[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  ~fa_events() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
 
 /* the table and the title lines -> the arrays of gs_fasta_records; a name twice under the record rules: GS_ERR_FORMAT */
 gs_status fa_finish(gs_fasta *fa, const std::vector<gs_fa_title> &t, const std::vector<uint64_t> &line_off, const std::string &lines) {
@@ -226,18 +169,20 @@ gs_status fa_run(gs_fasta *fa, const uint8_t *d_raw, uint64_t len, hipStream_t s
   std::vector<uint64_t> line_off(1, 0);
   std::string lines;
   if (nt) {
-    fa_mem mem;
-    gs_status rc;
+    gs_scratch mem;
     size_t tb_f = 0, tb_r = 0, tb_c = 0;
     GS_HIP(rocprim::inclusive_scan(nullptr, tb_f, (gs_fa_sum *)nullptr, (gs_fa_sum *)nullptr, (size_t)nt + 1, fa_fwd(), st));
     GS_HIP(rocprim::inclusive_scan(nullptr, tb_r, (gs_fa_sum *)nullptr, (gs_fa_sum *)nullptr, (size_t)nt + 1, fa_rev(), st));
     GS_HIP(rocprim::exclusive_scan(nullptr, tb_c, (unsigned long long *)nullptr, (unsigned long long *)nullptr, 0ull, (size_t)nt + 1, fa_add(), st));
     const size_t sb = sizeof(gs_fa_sum) * ((size_t)nt + 1), cb = 8 * ((size_t)nt + 1);
     void *sums, *rsums, *fwd, *bwd, *counts, *koff, *tmp;
-    if ((rc = mem.get(sb, &sums)) != GS_OK || (rc = mem.get(sb, &rsums)) != GS_OK || (rc = mem.get(sb, &fwd)) != GS_OK ||
-        (rc = mem.get(sb, &bwd)) != GS_OK || (rc = mem.get(cb, &counts)) != GS_OK || (rc = mem.get(cb, &koff)) != GS_OK ||
-        (rc = mem.get(std::max(tb_f, std::max(tb_r, tb_c)) + 16, &tmp)) != GS_OK)
-      return rc;
+    GS_TRY(mem.get(sb, &sums));
+    GS_TRY(mem.get(sb, &rsums));
+    GS_TRY(mem.get(sb, &fwd));
+    GS_TRY(mem.get(sb, &bwd));
+    GS_TRY(mem.get(cb, &counts));
+    GS_TRY(mem.get(cb, &koff));
+    GS_TRY(mem.get(std::max(tb_f, std::max(tb_r, tb_c)), &tmp));
     fa_args a;
     memset(&a, 0, sizeof a);
     a.raw = d_raw;
@@ -256,8 +201,8 @@ gs_status fa_run(gs_fasta *fa, const uint8_t *d_raw, uint64_t len, hipStream_t s
     GS_HIP(hipMemcpyAsync(rsums, &none, sizeof none, hipMemcpyHostToDevice, st));
     GS_HIP(hipStreamSynchronize(st)); /* the two sources are on this frame */
     /* the passes are timed by events in the stream: nothing waits between them */
-    fa_events ev;
-    for (int i = 0; i < 7; i++) GS_HIP(hipEventCreate(&ev.e[i]));
+    gs_events<7> ev;
+    for (hipEvent_t &e : ev.e) GS_HIP(hipEventCreate(&e));
     GS_HIP(hipEventRecord(ev.e[0], st));
     hipLaunchKernelGGL(k_fa_tile<FA_SUM>, dim3(grid), dim3(FA_THREADS), 0, st, a);
     GS_HIP(hipEventRecord(ev.e[1], st));
@@ -279,7 +224,8 @@ gs_status fa_run(gs_fasta *fa, const uint8_t *d_raw, uint64_t len, hipStream_t s
     fa->file_nls = whole.n_nl;
     const uint64_t n = whole.n_titles;
     void *text, *tab;
-    if ((rc = mem.get(kept + 16, &text)) != GS_OK || (rc = mem.get(sizeof(gs_fa_title) * n, &tab)) != GS_OK) return rc;
+    GS_TRY(mem.get(kept, &text));
+    GS_TRY(mem.get(sizeof(gs_fa_title) * n, &tab));
     a.text = (uint8_t *)text;
     a.titles = (gs_fa_title *)tab;
     if (n) hipLaunchKernelGGL(k_fa_title_fill, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, a.titles, n, len);
@@ -289,12 +235,8 @@ gs_status fa_run(gs_fasta *fa, const uint8_t *d_raw, uint64_t len, hipStream_t s
     GS_HIP(hipStreamSynchronize(st));
     GS_HIP(hipGetLastError());
     static const int from[5] = {0, 1, 2, 3, 5};
-    for (int i = 0; i < 5; i++) {
-      float ms = 0;
-      GS_HIP(hipEventElapsedTime(&ms, ev.e[from[i]], ev.e[from[i] + 1]));
-      fa->ms[4 + i] = ms;
-    }
-    fa->ms[2] = ms_since(t0);
+    GS_TRY(ev.elapsed(from, 5, fa->ms + 4));
+    fa->ms[2] = gs_ms_since(t0);
     t0 = std::chrono::steady_clock::now();
     if (n) {
       titles.resize(n);
@@ -302,7 +244,8 @@ gs_status fa_run(gs_fasta *fa, const uint8_t *d_raw, uint64_t len, hipStream_t s
       line_off.resize(n + 1);
       for (uint64_t r = 0; r < n; r++) line_off[r + 1] = line_off[r] + (titles[r].end - titles[r].off);
       void *d_off, *d_lines;
-      if ((rc = mem.get(8 * (n + 1), &d_off)) != GS_OK || (rc = mem.get(line_off[n], &d_lines)) != GS_OK) return rc;
+      GS_TRY(mem.get(8 * (n + 1), &d_off));
+      GS_TRY(mem.get(line_off[n], &d_lines));
       GS_HIP(hipMemcpy(d_off, line_off.data(), 8 * (n + 1), hipMemcpyHostToDevice));
       hipLaunchKernelGGL(k_fa_titles, dim3((uint32_t)std::min<uint64_t>(n, 65536)), dim3(64), 0, st, d_raw, (const gs_fa_title *)tab,
                          (const uint64_t *)d_off, n, (uint8_t *)d_lines);
@@ -311,11 +254,11 @@ gs_status fa_run(gs_fasta *fa, const uint8_t *d_raw, uint64_t len, hipStream_t s
       lines.resize(line_off[n]);
       if (line_off[n]) GS_HIP(hipMemcpy(&lines[0], d_lines, line_off[n], hipMemcpyDeviceToHost));
     }
-    mem.release(text);
+    mem.keep(text);
     fa->d_text = text;
   }
   const gs_status rc = fa_finish(fa, titles, line_off, lines);
-  fa->ms[3] = nt ? ms_since(t0) : 0;
+  fa->ms[3] = nt ? gs_ms_since(t0) : 0;
   return rc;
 }
 
@@ -363,14 +306,13 @@ extern "C" gs_status gs_fasta_parse(int device, const uint8_t *raw, uint64_t len
   if (!out || (len && !raw) || rules > GS_FASTA_RECORD_RULES) return GS_ERR_ARG;
   *out = nullptr;
   GS_HIP(hipSetDevice(device));
-  fa_mem mem;
+  gs_scratch mem;
   void *d_raw = nullptr;
-  gs_status rc;
-  if ((rc = mem.get(len + 16, &d_raw)) != GS_OK) return rc;
+  GS_TRY(mem.get(len, &d_raw));
   const auto t0 = std::chrono::steady_clock::now();
   if (len) GS_HIP(hipMemcpy(d_raw, raw, len, hipMemcpyHostToDevice));
-  const double up = ms_since(t0);
-  rc = gs_fasta_parse_device(device, d_raw, len, rules, nullptr, out);
+  const double up = gs_ms_since(t0);
+  const gs_status rc = gs_fasta_parse_device(device, d_raw, len, rules, nullptr, out);
   if (rc == GS_OK) (*out)->ms[1] = up;
   return rc;
 }
@@ -383,74 +325,12 @@ extern "C" uint64_t gs_debug_fasta_chunk_bytes(uint64_t set) {
 extern "C" gs_status gs_fasta_parse_file(int device, const char *path, uint32_t rules, gs_fasta **out) {
   if (!out || !path || rules > GS_FASTA_RECORD_RULES) return GS_ERR_ARG;
   *out = nullptr;
-  FILE *f = fopen(path, "rb");
-  struct stat sb;
-  if (!f || fstat(fileno(f), &sb) != 0 || !S_ISREG(sb.st_mode)) {
-    if (f) fclose(f);
-    gs_set_error(std::string("cannot read ") + path);
-    return GS_ERR_IO;
-  }
-  const uint64_t size = (uint64_t)sb.st_size, chunk = g_chunk_bytes.load();
-  fa_mem mem;
-  void *d_raw = nullptr, *pin[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  hipStream_t st = nullptr;
-  double ms_read = 0, ms_wait = 0;
-  uint64_t at = 0;
-  /* two page-locked chunks: one is being read into while the other's copy to the device is under way */
-  auto body = [&]() -> gs_status {
-    GS_HIP(hipSetDevice(device));
-    gs_status rc;
-    if ((rc = mem.get(size + 16, &d_raw)) != GS_OK) return rc;
-    GS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) {
-      if (hipHostMalloc(&pin[i], (size_t)std::min<uint64_t>(chunk, size ? size : 1), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        pin[i] = nullptr;
-        gs_set_error("out of page-locked host memory");
-        return GS_ERR_NOMEM;
-      }
-      GS_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-    }
-    for (uint64_t c = 0; at < size; c++) {
-      const int b = (int)(c & 1);
-      auto t0 = std::chrono::steady_clock::now();
-      if (c >= 2) GS_HIP(hipEventSynchronize(ev[b]));
-      ms_wait += ms_since(t0);
-      t0 = std::chrono::steady_clock::now();
-      const size_t want = (size_t)std::min<uint64_t>(chunk, size - at), got = fread(pin[b], 1, want, f);
-      ms_read += ms_since(t0);
-      if (got != want) {
-        gs_set_error(std::string("cannot read ") + path);
-        return GS_ERR_IO;
-      }
-      GS_HIP(hipMemcpyAsync((uint8_t *)d_raw + at, pin[b], got, hipMemcpyHostToDevice, st));
-      GS_HIP(hipEventRecord(ev[b], st));
-      at += got;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    GS_HIP(hipStreamSynchronize(st));
-    ms_wait += ms_since(t0);
-    return gs_fasta_parse_device(device, d_raw, size, rules, st, out);
-  };
-  gs_status rc;
-  try {
-    rc = body();
-  } catch (const std::bad_alloc &) {
-    rc = GS_ERR_NOMEM;
-  }
-  fclose(f);
-  if (st) (void)hipStreamSynchronize(st);
-  for (int i = 0; i < 2; i++) {
-    if (ev[i]) (void)hipEventDestroy(ev[i]);
-    if (pin[i]) (void)hipHostFree(pin[i]);
-  }
-  if (st) (void)hipStreamDestroy(st);
-  if (rc == GS_OK) {
-    (*out)->ms[0] = ms_read;
-    (*out)->ms[1] = ms_wait;
-  }
-  return rc;
+  gs_staged_file f;
+  GS_TRY(f.open(device, path, g_chunk_bytes.load()));
+  GS_TRY(gs_fasta_parse_device(device, f.d_raw, f.size, rules, f.st, out));
+  (*out)->ms[0] = f.ms_read;
+  (*out)->ms[1] = f.ms_wait;
+  return GS_OK;
 }
 
 extern "C" gs_status gs_fasta_info(const gs_fasta *fa, uint64_t *n_records, uint64_t *text_len, uint64_t *names_bytes) {

@@ -17,6 +17,7 @@
  * refuses, per guide, so that no input of the reference aborts a batch.
  */
 #include "gs_device.h"
+#include "gs_scratch.h"
 #include "gs_bulge_step.h" /* the node, record and argument layouts both forms of the search share */
 
 #include <rocprim/rocprim.hpp>
@@ -318,12 +319,6 @@ struct gs_result_ex {
   std::vector<uint32_t> raw;
 };
 
-#define GS_TRY(expr)                 \
-  do {                               \
-    gs_status rc__ = (expr);         \
-    if (rc__ != GS_OK) return rc__;  \
-  } while (0)
-
 /* genomics::complement (src/genomics/sequences.cxx:14-26): bases and lower-case bases, anything else unchanged */
 static uint8_t gen_comp(uint8_t c) {
   switch (c) {
@@ -383,15 +378,10 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
     return GS_OK;
   }
   /* per-call device buffers (rare mode: no workspace reuse) */
-  struct dbuf {
-    void *p = nullptr;
-    ~dbuf() {
-      if (p) hipFree(p);
-    }
-    gs_status get(size_t b) { return hipMalloc(&p, b ? b : 16) == hipSuccess ? GS_OK : GS_ERR_NOMEM; }
-  };
-  dbuf d_g, d_cnt, d_misc, d_off, d_a, d_b, d_flag, d_pos, d_uq, d_c64, d_scan, d_nm, d_nh, d_first, d_frec, d_goff,
-      d_hits, d_tmp, d_gl;
+  gs_scratch mem;
+  void *d_g = nullptr, *d_cnt = nullptr, *d_misc = nullptr, *d_a = nullptr, *d_b = nullptr, *d_flag = nullptr, *d_pos = nullptr, *d_uq = nullptr,
+       *d_c64 = nullptr, *d_scan = nullptr, *d_nm = nullptr, *d_nh = nullptr, *d_first = nullptr, *d_frec = nullptr, *d_goff = nullptr,
+       *d_hits = nullptr, *d_tmp = nullptr, *d_gl = nullptr, *d_raw = nullptr;
   /* query = reverse_complement(sequence) consumed right to left == complement of the guide left to
    * right (process.hpp:63, index.hpp:218); with --start the guide itself right to left; PAMs likewise */
   std::vector<gs_gen_guide> hg(n);
@@ -416,18 +406,18 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
     sa.plen[P ? n_alt : 0u] = (uint8_t)P;
     sa.p_max = p_max;
   }
-  GS_TRY(d_g.get(sizeof(gs_gen_guide) * n));
-  GS_TRY(d_cnt.get(8 * n));
-  GS_TRY(d_misc.get(256)); /* the walk's 16 words, then the seeded form's 16 and its five 64-bit counters (gs_bsearch_args::bwork) */
-  GS_HIP(hipMemcpy(d_g.p, hg.data(), sizeof(gs_gen_guide) * n, hipMemcpyHostToDevice));
-  GS_HIP(hipMemset(d_misc.p, 0, 256));
+  GS_TRY(mem.get(sizeof(gs_gen_guide) * n, &d_g));
+  GS_TRY(mem.get(8 * n, &d_cnt));
+  GS_TRY(mem.get(256, &d_misc)); /* the walk's 16 words, then the seeded form's 16 and its five 64-bit counters (gs_bsearch_args::bwork) */
+  GS_HIP(hipMemcpy(d_g, hg.data(), sizeof(gs_gen_guide) * n, hipMemcpyHostToDevice));
+  GS_HIP(hipMemset(d_misc, 0, 256));
   sa.sd[0] = ix->strand[0].d;
   sa.sd[1] = ix->strand[1].d;
-  sa.guides = (const gs_gen_guide *)d_g.p;
+  sa.guides = (const gs_gen_guide *)d_g;
   sa.recs = nullptr;
   sa.slot_off = nullptr;
-  sa.counts = (uint32_t *)d_cnt.p;
-  sa.work = (uint32_t *)d_misc.p;
+  sa.counts = (uint32_t *)d_cnt;
+  sa.work = (uint32_t *)d_misc;
   sa.n_items = 2 * n32;
   sa.L = L;
   sa.P = P;
@@ -467,13 +457,13 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
           gl[n32 - 1u - (g - n_seed)] = g;
       }
       n_walk = n32 - n_seed;
-      GS_TRY(d_gl.get(4 * n));
-      GS_HIP(hipMemcpy(d_gl.p, gl.data(), 4 * n, hipMemcpyHostToDevice));
+      GS_TRY(mem.get(4 * n, &d_gl));
+      GS_HIP(hipMemcpy(d_gl, gl.data(), 4 * n, hipMemcpyHostToDevice));
     }
     bs.k = k;
     bs.rows = GS_BULGE_ROWS_DEFAULT;
     if (const char *e = gs_opt(ix, "GS_BULGE_ROWS")) bs.rows = (uint32_t)std::min(std::max(0ll, atoll(e)), 0x7FFFFFFFll);
-    bs.bwork = (uint32_t *)d_misc.p + 16;
+    bs.bwork = (uint32_t *)d_misc + 16;
   }
   uint32_t grid = 2 * n_walk;
   if (grid > grid_max) grid = grid_max;
@@ -497,31 +487,26 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
   }
   const uint64_t cap_first = cap;
   for (int attempt = 0; attempt < 2; attempt++) {
-    if (d_a.p) {
-      hipFree(d_a.p);
-      d_a.p = nullptr;
-    }
-    if (attempt == 0 && d_a.get(sizeof(gs_grec) * cap) != GS_OK) {
-      (void)hipGetLastError(); /* no room for the guess: count with a small pool, then allocate what the batch needs */
-      cap = 1u << 12;
-    }
-    if (!d_a.p) GS_TRY(d_a.get(sizeof(gs_grec) * cap));
-    GS_HIP(hipMemset(d_misc.p, 0, 256));
-    sa.recs = (gs_grec *)d_a.p;
+    mem.drop(d_a);
+    if (attempt == 0 && mem.get(sizeof(gs_grec) * cap, &d_a) == GS_ERR_NOMEM)
+      cap = 1u << 12; /* no room for the guess: count with a small pool, then allocate what the batch needs */
+    if (!d_a) GS_TRY(mem.get(sizeof(gs_grec) * cap, &d_a));
+    GS_HIP(hipMemset(d_misc, 0, 256));
+    sa.recs = (gs_grec *)d_a;
     sa.slot_off = nullptr;
-    sa.pool_next = (unsigned long long *)((char *)d_misc.p + 16);
+    sa.pool_next = (unsigned long long *)((char *)d_misc + 16);
     sa.pool_cap = cap;
     if (n_seed) { /* the eligible guides: the seeded form, into the same pool */
       bs.g = sa;
-      bs.g.glist = (const uint32_t *)d_gl.p;
+      bs.g.glist = (const uint32_t *)d_gl;
       bs.g.n_items = 2 * n_seed;
       GS_TRY(gs_bulge_launch(bs, grid_b, st));
-      sa.glist = (const uint32_t *)d_gl.p + n_seed;
+      sa.glist = (const uint32_t *)d_gl + n_seed;
       sa.n_items = 2 * n_walk;
     }
     if (n_walk) hipLaunchKernelGGL(k_search_general, dim3(grid), dim3(WAVE), 0, st, sa);
     uint32_t h_misc[64] = {0};
-    GS_HIP(hipMemcpy(h_misc, d_misc.p, 256, hipMemcpyDeviceToHost));
+    GS_HIP(hipMemcpy(h_misc, d_misc, 256, hipMemcpyDeviceToHost));
     {
       /* both reports of the pass, before anything can end the call: the two always speak of the same pass */
       unsigned long long c64[5];
@@ -560,51 +545,51 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
     *out = res;
     return GS_OK;
   }
-  GS_TRY(d_b.get(sizeof(gs_grec) * T));
+  GS_TRY(mem.get(sizeof(gs_grec) * T, &d_b));
   {
-    dbuf d_raw;
-    GS_TRY(d_raw.get(8 * n));
-    GS_HIP(hipMemsetAsync(d_raw.p, 0, 8 * n, st));
-    hipLaunchKernelGGL(k_gen_raw, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, (const gs_grec *)d_a.p, T,
-                       (unsigned long long *)d_raw.p);
+    GS_TRY(mem.get(8 * n, &d_raw));
+    GS_HIP(hipMemsetAsync(d_raw, 0, 8 * n, st));
+    hipLaunchKernelGGL(k_gen_raw, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, (const gs_grec *)d_a, T,
+                       (unsigned long long *)d_raw);
     std::vector<unsigned long long> hr(n);
-    GS_HIP(hipMemcpy(hr.data(), d_raw.p, 8 * n, hipMemcpyDeviceToHost));
+    GS_HIP(hipMemcpy(hr.data(), d_raw, 8 * n, hipMemcpyDeviceToHost));
     for (uint64_t g = 0; g < n; g++) res->raw[g] = hr[g] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)hr[g];
+    mem.drop(d_raw);
   }
   /* canonical order: (guide, distance, index, sequence, row) */
   size_t tb = 0, tb2 = 0, tb3 = 0;
-  GS_TRY(d_flag.get(4 * T));
-  GS_TRY(d_pos.get(4 * T));
-  GS_TRY(d_c64.get(8 * (T + 1)));
-  GS_TRY(d_scan.get(8 * (T + 1)));
-  GS_HIP(rocprim::merge_sort(nullptr, tb, (gs_grec *)d_a.p, (gs_grec *)d_b.p, (size_t)T, gs_grec_less(), st));
-  GS_HIP(rocprim::exclusive_scan(nullptr, tb2, (uint32_t *)d_flag.p, (uint32_t *)d_pos.p, 0u, (size_t)T,
+  GS_TRY(mem.get(4 * T, &d_flag));
+  GS_TRY(mem.get(4 * T, &d_pos));
+  GS_TRY(mem.get(8 * (T + 1), &d_c64));
+  GS_TRY(mem.get(8 * (T + 1), &d_scan));
+  GS_HIP(rocprim::merge_sort(nullptr, tb, (gs_grec *)d_a, (gs_grec *)d_b, (size_t)T, gs_grec_less(), st));
+  GS_HIP(rocprim::exclusive_scan(nullptr, tb2, (uint32_t *)d_flag, (uint32_t *)d_pos, 0u, (size_t)T,
                                  rocprim::plus<uint32_t>(), st));
-  GS_HIP(rocprim::exclusive_scan(nullptr, tb3, (unsigned long long *)d_c64.p, (unsigned long long *)d_scan.p,
+  GS_HIP(rocprim::exclusive_scan(nullptr, tb3, (unsigned long long *)d_c64, (unsigned long long *)d_scan,
                                  0ull, (size_t)T + 1, rocprim::plus<unsigned long long>(), st));
   if (tb2 > tb) tb = tb2;
   if (tb3 > tb) tb = tb3;
-  GS_TRY(d_tmp.get(tb + 16));
+  GS_TRY(mem.get(tb, &d_tmp));
   size_t tbs = tb;
-  GS_HIP(rocprim::merge_sort(d_tmp.p, tbs, (gs_grec *)d_a.p, (gs_grec *)d_b.p, (size_t)T, gs_grec_less(), st));
+  GS_HIP(rocprim::merge_sort(d_tmp, tbs, (gs_grec *)d_a, (gs_grec *)d_b, (size_t)T, gs_grec_less(), st));
   const unsigned gT = (unsigned)((T + 255) / 256);
-  hipLaunchKernelGGL(k_gen_flags, dim3(gT), dim3(256), 0, st, (const gs_grec *)d_b.p, T, (uint32_t *)d_flag.p);
+  hipLaunchKernelGGL(k_gen_flags, dim3(gT), dim3(256), 0, st, (const gs_grec *)d_b, T, (uint32_t *)d_flag);
   tbs = tb;
-  GS_HIP(rocprim::exclusive_scan(d_tmp.p, tbs, (uint32_t *)d_flag.p, (uint32_t *)d_pos.p, 0u, (size_t)T,
+  GS_HIP(rocprim::exclusive_scan(d_tmp, tbs, (uint32_t *)d_flag, (uint32_t *)d_pos, 0u, (size_t)T,
                                  rocprim::plus<uint32_t>(), st));
-  GS_TRY(d_uq.get(sizeof(gs_grec) * T));
-  GS_TRY(d_nm.get(4 * n));
-  GS_TRY(d_nh.get(8 * n));
-  GS_HIP(hipMemsetAsync(d_nm.p, 0, 4 * n, st));
-  GS_HIP(hipMemsetAsync(d_nh.p, 0, 8 * n, st));
-  GS_HIP(hipMemsetAsync(d_c64.p, 0, 8 * (T + 1), st));
-  hipLaunchKernelGGL(k_gen_compact, dim3(gT), dim3(256), 0, st, (const gs_grec *)d_b.p,
-                     (const uint32_t *)d_flag.p, (const uint32_t *)d_pos.p, T, (gs_grec *)d_uq.p,
-                     (unsigned long long *)d_c64.p, (uint32_t *)d_nm.p, (unsigned long long *)d_nh.p);
+  GS_TRY(mem.get(sizeof(gs_grec) * T, &d_uq));
+  GS_TRY(mem.get(4 * n, &d_nm));
+  GS_TRY(mem.get(8 * n, &d_nh));
+  GS_HIP(hipMemsetAsync(d_nm, 0, 4 * n, st));
+  GS_HIP(hipMemsetAsync(d_nh, 0, 8 * n, st));
+  GS_HIP(hipMemsetAsync(d_c64, 0, 8 * (T + 1), st));
+  hipLaunchKernelGGL(k_gen_compact, dim3(gT), dim3(256), 0, st, (const gs_grec *)d_b,
+                     (const uint32_t *)d_flag, (const uint32_t *)d_pos, T, (gs_grec *)d_uq,
+                     (unsigned long long *)d_c64, (uint32_t *)d_nm, (unsigned long long *)d_nh);
   std::vector<uint32_t> nm(n);
   std::vector<unsigned long long> nh(n);
-  GS_HIP(hipMemcpy(nm.data(), d_nm.p, 4 * n, hipMemcpyDeviceToHost));
-  GS_HIP(hipMemcpy(nh.data(), d_nh.p, 8 * n, hipMemcpyDeviceToHost));
+  GS_HIP(hipMemcpy(nm.data(), d_nm, 4 * n, hipMemcpyDeviceToHost));
+  GS_HIP(hipMemcpy(nh.data(), d_nh, 8 * n, hipMemcpyDeviceToHost));
   std::vector<uint64_t> first_rec(n + 1, 0);
   uint64_t nuq = 0;
   for (size_t g = 0; g < n; g++) {
@@ -615,30 +600,30 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
   first_rec[n] = nuq;
   const uint64_t H = res->offsets[n];
   tbs = tb;
-  GS_HIP(rocprim::exclusive_scan(d_tmp.p, tbs, (unsigned long long *)d_c64.p, (unsigned long long *)d_scan.p,
+  GS_HIP(rocprim::exclusive_scan(d_tmp, tbs, (unsigned long long *)d_c64, (unsigned long long *)d_scan,
                                  0ull, (size_t)nuq + 1, rocprim::plus<unsigned long long>(), st));
-  GS_TRY(d_frec.get(8 * (n + 1)));
-  GS_TRY(d_first.get(8 * n));
-  GS_TRY(d_goff.get(8 * (n + 1)));
-  GS_TRY(d_hits.get(sizeof(gs_hit_ex) * (H + 1)));
-  GS_HIP(hipMemcpy(d_frec.p, first_rec.data(), 8 * (n + 1), hipMemcpyHostToDevice));
-  GS_HIP(hipMemcpy(d_goff.p, res->offsets.data(), 8 * (n + 1), hipMemcpyHostToDevice));
+  GS_TRY(mem.get(8 * (n + 1), &d_frec));
+  GS_TRY(mem.get(8 * n, &d_first));
+  GS_TRY(mem.get(8 * (n + 1), &d_goff));
+  GS_TRY(mem.get(sizeof(gs_hit_ex) * (H + 1), &d_hits));
+  GS_HIP(hipMemcpy(d_frec, first_rec.data(), 8 * (n + 1), hipMemcpyHostToDevice));
+  GS_HIP(hipMemcpy(d_goff, res->offsets.data(), 8 * (n + 1), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_gen_first, dim3((n32 + 255) / 256), dim3(256), 0, st,
-                     (const unsigned long long *)d_scan.p, (const uint64_t *)d_frec.p, n32,
-                     (unsigned long long *)d_first.p);
+                     (const unsigned long long *)d_scan, (const uint64_t *)d_frec, n32,
+                     (unsigned long long *)d_first);
   gs_glocate_args la;
   la.sd[0] = ix->strand[0].d;
   la.sd[1] = ix->strand[1].d;
-  la.uq = (const gs_grec *)d_uq.p;
-  la.hit_scan = (const unsigned long long *)d_scan.p;
-  la.guide_first = (const unsigned long long *)d_first.p;
-  la.offsets = (const uint64_t *)d_goff.p;
-  la.hits = (gs_hit_ex *)d_hits.p;
+  la.uq = (const gs_grec *)d_uq;
+  la.hit_scan = (const unsigned long long *)d_scan;
+  la.guide_first = (const unsigned long long *)d_first;
+  la.offsets = (const uint64_t *)d_goff;
+  la.hits = (gs_hit_ex *)d_hits;
   la.genome_length = ix->genome_length;
   la.n_uq = (uint32_t)nuq;
   if (nuq) hipLaunchKernelGGL(k_gen_locate, dim3((unsigned)nuq), dim3(WAVE), 0, st, la);
   res->hits.resize(H);
-  if (H) GS_HIP(hipMemcpy(res->hits.data(), d_hits.p, sizeof(gs_hit_ex) * H, hipMemcpyDeviceToHost));
+  if (H) GS_HIP(hipMemcpy(res->hits.data(), d_hits, sizeof(gs_hit_ex) * H, hipMemcpyDeviceToHost));
   GS_HIP(hipDeviceSynchronize());
   GS_HIP(hipGetLastError());
   guard.p = nullptr;

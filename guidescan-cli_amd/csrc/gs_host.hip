@@ -3,10 +3,14 @@
  * decoding, CFD, status strings.  No kernels here.
  */
 #include "gs_common.h"
+#include "gs_scratch.h"
 #include "cfd_table.h"
+
+#include <sys/stat.h>
 
 #include <algorithm>
 #include <cctype>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -240,6 +244,109 @@ gs_status gs_text_to_host(const void *d_text, uint64_t tl, char **text) {
   out[tl] = 0;
   *text = out;
   return GS_OK;
+}
+
+/* ---- gs_scratch.h ---- */
+double gs_ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+gs_scratch::~gs_scratch() {
+  for (void *q : p) (void)hipFree(q);
+}
+gs_status gs_scratch::get(size_t bytes, void **out) {
+  *out = nullptr;
+  p.reserve(p.size() + 1);
+  const hipError_t e = hipMalloc(out, bytes + 16);
+  if (e != hipSuccess) {
+    *out = nullptr;
+    if (e != hipErrorOutOfMemory) {
+      gs_set_error(std::string("hipMalloc(out, bytes + 16): ") + hipGetErrorString(e));
+      return GS_ERR_DEVICE;
+    }
+    (void)hipGetLastError();
+    gs_set_error("out of device memory");
+    return GS_ERR_NOMEM;
+  }
+  p.push_back(*out);
+  return GS_OK;
+}
+void gs_scratch::keep(const void *q) { p.erase(std::remove(p.begin(), p.end(), q), p.end()); }
+
+gs_status gs_events_elapsed(const hipEvent_t *e, const int *from, int n, double *out) {
+  for (int i = 0; i < n; i++) {
+    float ms = 0;
+    GS_HIP(hipEventElapsedTime(&ms, e[from[i]], e[from[i] + 1]));
+    out[i] = ms;
+  }
+  return GS_OK;
+}
+
+gs_staged_file::~gs_staged_file() {
+  if (st) {
+    (void)hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+  }
+}
+gs_status gs_staged_file::open(int device, const char *path, uint64_t chunk) {
+  FILE *f = fopen(path, "rb");
+  struct stat sb;
+  if (!f || fstat(fileno(f), &sb) != 0 || !S_ISREG(sb.st_mode)) {
+    if (f) fclose(f);
+    gs_set_error(std::string("cannot read ") + path);
+    return GS_ERR_IO;
+  }
+  size = (uint64_t)sb.st_size;
+  void *pin[2] = {nullptr, nullptr};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  uint64_t at = 0;
+  auto body = [&]() -> gs_status {
+    GS_HIP(hipSetDevice(device));
+    GS_TRY(mem.get(size, &d_raw));
+    GS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    for (int i = 0; i < 2; i++) {
+      if (hipHostMalloc(&pin[i], (size_t)std::min<uint64_t>(chunk, size ? size : 1), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        pin[i] = nullptr;
+        gs_set_error("out of page-locked host memory");
+        return GS_ERR_NOMEM;
+      }
+      GS_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+    }
+    for (uint64_t c = 0; at < size; c++) {
+      const int b = (int)(c & 1);
+      auto t0 = std::chrono::steady_clock::now();
+      if (c >= 2) GS_HIP(hipEventSynchronize(ev[b]));
+      ms_wait += gs_ms_since(t0);
+      t0 = std::chrono::steady_clock::now();
+      const size_t want = (size_t)std::min<uint64_t>(chunk, size - at), got = fread(pin[b], 1, want, f);
+      ms_read += gs_ms_since(t0);
+      if (got != want) {
+        gs_set_error(std::string("cannot read ") + path);
+        return GS_ERR_IO;
+      }
+      GS_HIP(hipMemcpyAsync((uint8_t *)d_raw + at, pin[b], got, hipMemcpyHostToDevice, st));
+      GS_HIP(hipEventRecord(ev[b], st));
+      at += got;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    GS_HIP(hipStreamSynchronize(st));
+    ms_wait += gs_ms_since(t0);
+    return GS_OK;
+  };
+  gs_status rc;
+  try {
+    rc = body();
+  } catch (const std::bad_alloc &) {
+    rc = GS_ERR_NOMEM;
+  }
+  fclose(f);
+  if (st) (void)hipStreamSynchronize(st); /* a copy may still read a chunk when the loop ended early */
+  for (int i = 0; i < 2; i++) {
+    if (ev[i]) (void)hipEventDestroy(ev[i]);
+    if (pin[i]) (void)hipHostFree(pin[i]);
+  }
+  return rc;
 }
 
 /* search -> score -> encode on the device (gs_textdev.hip), then the text back to the host.  The guides come from the

@@ -8,6 +8,7 @@
  * Offline step, not on the enumerate hot path; rocPRIM is used for the plain sorts/scans.
  */
 #include "gs_common.h"
+#include "gs_scratch.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -160,10 +161,11 @@ gs_status gs_strand_from_device(const uint8_t *d_text, uint32_t *d_sa_owned, uin
   uint4 *blocks = nullptr;
   uint32_t *wcount = nullptr, *wscan = nullptr;
   unsigned long long *d_hist = nullptr;
-  GS_HIP(hipMalloc(&blocks, nblocks * 64));
-  GS_HIP(hipMalloc(&wcount, nwords * 16));
-  GS_HIP(hipMalloc(&wscan, nwords * 16));
-  GS_HIP(hipMalloc(&d_hist, 256 * 8));
+  gs_scratch mem; /* the temporaries, and the blocks until the strand has them */
+  GS_TRY(mem.get(nblocks * 64, &blocks));
+  GS_TRY(mem.get(nwords * 16, &wcount));
+  GS_TRY(mem.get(nwords * 16, &wscan));
+  GS_TRY(mem.get(256 * 8, &d_hist));
   GS_HIP(hipMemsetAsync(d_hist, 0, 256 * 8, st));
   hipLaunchKernelGGL(k_build_words, dim3(nblk(nwords, 256)), dim3(256), 0, st, d_text, d_sa_owned, n,
                      nwords, blocks, wcount);
@@ -172,12 +174,12 @@ gs_status gs_strand_from_device(const uint8_t *d_text, uint32_t *d_sa_owned, uin
     GS_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, wcount, wscan, 0u, nwords,
                                    rocprim::plus<uint32_t>(), st));
     void *tmp = nullptr;
-    GS_HIP(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
+    GS_TRY(mem.get(tmp_bytes, &tmp));
     for (int c = 0; c < 4; c++)
       GS_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, wcount + c * nwords, wscan + c * nwords, 0u,
                                      nwords, rocprim::plus<uint32_t>(), st));
     GS_HIP(hipStreamSynchronize(st));
-    hipFree(tmp);
+    mem.drop(tmp);
   }
   hipLaunchKernelGGL(k_write_headers, dim3(nblk(nblocks, 256)), dim3(256), 0, st, blocks, wscan,
                      nwords, nblocks);
@@ -185,9 +187,9 @@ gs_status gs_strand_from_device(const uint8_t *d_text, uint32_t *d_sa_owned, uin
   unsigned long long hist[256];
   GS_HIP(hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
-  hipFree(wcount);
-  hipFree(wscan);
-  hipFree(d_hist);
+  mem.drop(wcount);
+  mem.drop(wscan);
+  mem.drop(d_hist);
 
   /* byte_alphabet semantics: C[c] = number of text symbols smaller than c
    * (sdsl/lib/csa_alphabet_strategy.cpp:25-55) */
@@ -208,29 +210,27 @@ gs_status gs_strand_from_device(const uint8_t *d_text, uint32_t *d_sa_owned, uin
   std::vector<unsigned long long> xstarts;
   std::vector<uint32_t> xends;
   for (;;) {
-    GS_HIP(hipMalloc(&d_cnt, 8));
-    GS_HIP(hipMalloc(&d_starts, 8ull * cap));
-    GS_HIP(hipMalloc(&d_ends, 4ull * cap));
+    GS_TRY(mem.get(8, &d_cnt));
+    GS_TRY(mem.get(8ull * cap, &d_starts));
+    GS_TRY(mem.get(4ull * cap, &d_ends));
     GS_HIP(hipMemsetAsync(d_cnt, 0, 8, st));
     hipLaunchKernelGGL(k_x_runs, dim3(nblk(n, 256)), dim3(256), 0, st, d_text, d_sa_owned, n, d_starts,
                        d_ends, d_cnt, cap);
     uint32_t hc[2];
     GS_HIP(hipMemcpyAsync(hc, d_cnt, 8, hipMemcpyDeviceToHost, st));
     GS_HIP(hipStreamSynchronize(st));
-    if (hc[0] <= cap && hc[1] <= cap) {
+    const bool fits = hc[0] <= cap && hc[1] <= cap;
+    if (fits) {
       xstarts.resize(hc[0]);
       xends.resize(hc[1]);
       if (hc[0]) GS_HIP(hipMemcpy(xstarts.data(), d_starts, 8ull * hc[0], hipMemcpyDeviceToHost));
       if (hc[1]) GS_HIP(hipMemcpy(xends.data(), d_ends, 4ull * hc[1], hipMemcpyDeviceToHost));
-      hipFree(d_cnt);
-      hipFree(d_starts);
-      hipFree(d_ends);
-      break;
     }
+    mem.drop(d_cnt);
+    mem.drop(d_starts);
+    mem.drop(d_ends);
+    if (fits) break;
     cap = std::max(hc[0], hc[1]);
-    hipFree(d_cnt);
-    hipFree(d_starts);
-    hipFree(d_ends);
   }
   if (xstarts.size() != xends.size()) {
     gs_set_error("internal: run boundaries do not pair up");
@@ -284,6 +284,7 @@ gs_status gs_strand_from_device(const uint8_t *d_text, uint32_t *d_sa_owned, uin
     out->d.C256 = (const uint32_t *)out->C256;
   }
 
+  mem.keep(blocks);
   out->blocks = blocks;
   out->sa = d_sa_owned;
   out->n = n;
@@ -364,7 +365,8 @@ __global__ void k_sa_count_heads(const uint32_t *head, uint64_t n, unsigned long
 gs_status gs_device_suffix_array(const uint8_t *d_text, uint64_t n, uint32_t *d_sa, hipStream_t st) {
   /* dense alphabet */
   unsigned long long *d_hist = nullptr;
-  GS_HIP(hipMalloc(&d_hist, 256 * 8 + 8));
+  gs_scratch mem;
+  GS_TRY(mem.get(256 * 8 + 8, &d_hist)); /* the histogram, then the group count */
   GS_HIP(hipMemsetAsync(d_hist, 0, 256 * 8 + 8, st));
   hipLaunchKernelGGL(k_histogram, dim3(1024), dim3(256), 0, st, d_text, n, d_hist);
   unsigned long long hist[256];
@@ -383,13 +385,13 @@ gs_status gs_device_suffix_array(const uint8_t *d_text, uint64_t n, uint32_t *d_
   uint64_t *keys_a = nullptr, *keys_b = nullptr;
   uint32_t *idx_a = nullptr, *rank = nullptr, *head = nullptr;
   unsigned long long *d_cnt = d_hist + 256;
-  GS_HIP(hipMalloc(&d_dense, 256));
+  GS_TRY(mem.get(256, &d_dense));
   GS_HIP(hipMemcpy(d_dense, dense, 256, hipMemcpyHostToDevice));
-  GS_HIP(hipMalloc(&keys_a, 8 * n));
-  GS_HIP(hipMalloc(&keys_b, 8 * n));
-  GS_HIP(hipMalloc(&idx_a, 4 * n));
-  GS_HIP(hipMalloc(&rank, 4 * n));
-  GS_HIP(hipMalloc(&head, 4 * n));
+  GS_TRY(mem.get(8 * n, &keys_a));
+  GS_TRY(mem.get(8 * n, &keys_b));
+  GS_TRY(mem.get(4 * n, &idx_a));
+  GS_TRY(mem.get(4 * n, &rank));
+  GS_TRY(mem.get(4 * n, &head));
   const unsigned g = nblk(n, 256);
   hipLaunchKernelGGL(k_sa_init_keys, dim3(g), dim3(256), 0, st, d_text, n, d_dense, bits, k0, keys_a,
                      idx_a);
@@ -398,7 +400,7 @@ gs_status gs_device_suffix_array(const uint8_t *d_text, uint64_t n, uint32_t *d_
   GS_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, head, head, n, sa_flag_op(), st));
   void *tmp = nullptr;
   const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
-  GS_HIP(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
+  GS_TRY(mem.get(tmp_bytes, &tmp));
   size_t sb = tmp_bytes;
   GS_HIP(rocprim::radix_sort_pairs(tmp, sb, keys_a, keys_b, idx_a, d_sa, n, 0, bits * k0, st));
   gs_status rc = GS_OK;
@@ -425,14 +427,6 @@ gs_status gs_device_suffix_array(const uint8_t *d_text, uint64_t n, uint32_t *d_
     GS_HIP(rocprim::radix_sort_pairs(tmp, sb, keys_a, keys_b, idx_a, d_sa, n, 0, 2 * nbits, st));
   }
   GS_HIP(hipStreamSynchronize(st));
-  hipFree(tmp);
-  hipFree(d_dense);
-  hipFree(keys_a);
-  hipFree(keys_b);
-  hipFree(idx_a);
-  hipFree(rank);
-  hipFree(head);
-  hipFree(d_hist);
   return rc;
 }
 
@@ -551,7 +545,8 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
   const uint64_t entries = 1ull << (2 * k);
   const size_t bytes = sizeof(uint4) * entries;
   uint4 *tab = nullptr;
-  GS_HIP(hipMalloc(&tab, bytes));
+  gs_scratch mem; /* the temporaries, and each array until the strand has it */
+  GS_TRY(mem.get(bytes, &tab));
   GS_HIP(hipMemsetAsync(tab, 0, bytes, st));
   hipLaunchKernelGGL(k_ptab_build, dim3(nblk(s->n, 256)), dim3(256), 0, st, d_text,
                      (const uint32_t *)s->sa, s->n, k, tab);
@@ -559,8 +554,8 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
   uint32_t *ctx = nullptr;
   uint16_t *ctx16 = nullptr;
   if (!gs_opt(ix, "GS_NO_CTX")) {
-    GS_HIP(hipMalloc(&ctx, 4 * s->n + 16));
-    GS_HIP(hipMalloc(&ctx16, 2 * s->n + 32)); /* one row group of padding (k_search reads groups of eight) */
+    GS_TRY(mem.get(4 * s->n, &ctx));
+    GS_TRY(mem.get(2 * s->n + 32, &ctx16)); /* one row group of padding (k_search reads groups of eight) */
     /* pair positions of the context mask (gs_strand_dev::mask_off) */
     uint32_t off3 = k < 21 ? 21u - k : 6u;
     if (off3 < 6) off3 = 6;
@@ -579,23 +574,21 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
     uint32_t *d_cnt = nullptr, *d_er = nullptr;
     uint64_t *d_es = nullptr;
     uint32_t cap = 1u << 16, h_cnt = 0;
-    GS_HIP(hipMalloc(&d_cnt, 4));
+    GS_TRY(mem.get(4, &d_cnt));
     for (int pass = 0; pass < 2; pass++) {
-      GS_HIP(hipMalloc(&d_er, 4 * (size_t)cap));
-      GS_HIP(hipMalloc(&d_es, 8 * (size_t)cap));
+      GS_TRY(mem.get(4 * (size_t)cap, &d_er));
+      GS_TRY(mem.get(8 * (size_t)cap, &d_es));
       GS_HIP(hipMemsetAsync(d_cnt, 0, 4, st));
       hipLaunchKernelGGL(k_ctx_build, dim3(nblk(s->n, 256)), dim3(256), 0, st, d_text,
                          (const uint32_t *)s->sa, s->n, k, ctx, ctx16, tab, d_cnt, d_er, d_es, cap, mask_off);
       GS_HIP(hipMemcpyAsync(&h_cnt, d_cnt, 4, hipMemcpyDeviceToHost, st));
       GS_HIP(hipStreamSynchronize(st));
       if (h_cnt <= cap) break;
-      hipFree(d_er);
-      hipFree(d_es);
-      d_er = nullptr;
-      d_es = nullptr;
+      mem.drop(d_er);
+      mem.drop(d_es);
       cap = h_cnt; /* flags and masks are set by atomicOr: a second pass changes nothing there */
     }
-    hipFree(d_cnt);
+    mem.drop(d_cnt);
     if (h_cnt) {
       std::vector<uint32_t> er(h_cnt);
       std::vector<uint64_t> es(h_cnt);
@@ -612,6 +605,8 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
       }
       GS_HIP(hipMemcpy(d_er, er2.data(), 4 * (size_t)h_cnt, hipMemcpyHostToDevice));
       GS_HIP(hipMemcpy(d_es, es2.data(), 8 * (size_t)h_cnt, hipMemcpyHostToDevice));
+      mem.keep(d_er);
+      mem.keep(d_es);
       s->exc_row = d_er;
       s->exc_sym = d_es;
       s->d.exc_row = d_er;
@@ -619,8 +614,8 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
       s->d.n_exc = h_cnt;
       s->bytes += 12 * (size_t)h_cnt;
     } else {
-      hipFree(d_er);
-      hipFree(d_es);
+      mem.drop(d_er);
+      mem.drop(d_es);
     }
     s->bytes += 6 * s->n;
   } else {
@@ -644,12 +639,9 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
   const double rot_bytes = (double)bytes * nrot, isa_bytes = 4.0 * (double)s->n;
   uint32_t *isa = nullptr;
   if (ctx && !gs_opt(ix, "GS_NO_BIDIR") && !gs_opt(ix, "GS_NO_ISA") && base_bytes + isa_bytes <= budget) {
-    if (hipMalloc(&isa, 4 * s->n) == hipSuccess) {
+    if (mem.get(4 * s->n, &isa) == GS_OK) {
       hipLaunchKernelGGL(k_isa_build, dim3(nblk(s->n, 256)), dim3(256), 0, st, (const uint32_t *)s->sa, s->n, isa);
       s->bytes += 4 * s->n;
-    } else {
-      isa = nullptr;
-      (void)hipGetLastError();
     }
   }
   /* the rotated copies are derived data written in milliseconds: built by the first batch that reads them
@@ -659,6 +651,7 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
   s->rot_plan_n = (ctx && nrot && !gs_opt(ix, "GS_NO_ROT") && base_bytes + (isa ? isa_bytes : 0.0) + rot_bytes <= budget) ? nrot : 0;
   s->rot_k = k;
   GS_HIP(hipStreamSynchronize(st));
+  for (const void *q : {(const void *)isa, (const void *)tab, (const void *)ctx, (const void *)ctx16}) mem.keep(q);
   s->isa = isa;
   s->d.isa = isa;
   s->ptab_rot = nullptr;
@@ -762,22 +755,16 @@ static gs_status build_common(const uint8_t *text, uint64_t len, const uint32_t 
   gs_opts_from_env(ix);
   hipStream_t st = nullptr;
   uint8_t *d_fwd = nullptr, *d_rev = nullptr;
-  /* every early return below (GS_HIP) releases what was allocated so far */
-  struct cleanup_t {
-    gs_index *&ix;
-    uint8_t *&a, *&b;
-    uint32_t *sa = nullptr; /* a suffix array not yet owned by a strand */
-    bool armed = true;
-    ~cleanup_t() {
-      if (a) hipFree(a);
-      if (b) hipFree(b);
-      if (!armed) return;
-      if (sa) hipFree(sa);
+  /* every early return below releases what was allocated so far: the texts, a suffix array not yet owned by a strand, the handle */
+  gs_scratch mem;
+  struct closer_t {
+    gs_index *ix;
+    ~closer_t() {
       if (ix) gs_index_close(ix);
     }
-  } cleanup{ix, d_fwd, d_rev};
-  GS_HIP(hipMalloc(&d_fwd, n));
-  GS_HIP(hipMalloc(&d_rev, n));
+  } closer{ix};
+  GS_TRY(mem.get(n, &d_fwd));
+  GS_TRY(mem.get(n, &d_rev));
   GS_HIP(hipMemcpy(d_fwd, text, len, hipMemcpyHostToDevice));
   GS_HIP(hipMemset(d_fwd + len, 0, 1)); /* sentinel: sdsl/include/sdsl/construct.hpp:133-135 */
   hipLaunchKernelGGL(k_revcomp, dim3(nblk(len, 256)), dim3(256), 0, st, d_fwd, d_rev, len);
@@ -786,8 +773,7 @@ static gs_status build_common(const uint8_t *text, uint64_t len, const uint32_t 
   const uint32_t pk = choose_prefix_k(ix, n);
   for (int s = 0; s < 2 && rc == GS_OK; s++) {
     uint32_t *d_sa = nullptr;
-    GS_HIP(hipMalloc(&d_sa, 4 * n));
-    cleanup.sa = d_sa;
+    GS_TRY(mem.get(4 * n, &d_sa));
     const uint32_t *given = s == 0 ? sa_fwd : sa_rev;
     const uint8_t *d_t = s == 0 ? d_fwd : d_rev;
     if (given) {
@@ -807,13 +793,13 @@ static gs_status build_common(const uint8_t *text, uint64_t len, const uint32_t 
                                      : gs_device_suffix_array_discarding(d_t, n, d_sa, st, gs_opt(ix, "GS_DEBUG") != nullptr);
     }
     if (rc == GS_OK) rc = gs_strand_from_device(d_t, d_sa, n, &ix->strand[s], st);
-    if (ix->strand[s].sa == d_sa) cleanup.sa = nullptr; /* the strand owns it now (also when it failed later) */
+    if (ix->strand[s].sa == d_sa) mem.keep(d_sa); /* the strand owns it now (also when it failed later) */
     if (rc == GS_OK) rc = build_ptab(ix, d_t, &ix->strand[s], pk, st);
   }
   if (rc == GS_OK) ix->pt_k = pk; /* depth of the prefix interval tables; the seed recipes are written per batch shape (gs_search.hip) */
   if (rc == GS_OK) scan_n_runs(text, len, ix->nruns_text);
-  if (rc != GS_OK) return rc; /* cleanup releases everything */
-  cleanup.armed = false;
+  if (rc != GS_OK) return rc;
+  closer.ix = nullptr;
   *out = ix;
   return GS_OK;
 }

@@ -25,9 +25,12 @@
  * offsets), so that a batch can hold the tail of one chromosome and the heads of the next ones.
  */
 #include "gs_common.h"
+#include "gs_scratch.h"
 #include "gs_kmers_obj.h"
 
 #include <rocprim/rocprim.hpp>
+
+#include <memory>
 
 #define KM_BLOCK 256
 
@@ -143,6 +146,13 @@ __global__ __launch_bounds__(KM_BLOCK) void k_km_emit(gs_km_emit_args a) {
   a.sense[j] = minus ? '-' : '+';
 }
 
+/* an array of the object: km_release frees it */
+static gs_status km_alloc(size_t bytes, void **out) {
+  gs_scratch one;
+  GS_TRY(one.get(bytes, out));
+  one.keep(*out);
+  return GS_OK;
+}
 static void km_release(gs_kmers *km) {
   if (!km) return;
   bool any = false; /* an empty object never touched a device */
@@ -195,42 +205,30 @@ extern "C" gs_status gs_kmers_generate(int device, const uint8_t *chr, uint64_t 
 
   hipStream_t st = (hipStream_t)stream;
   GS_HIP(hipSetDevice(device));
-  gs_kmers *km = new gs_kmers();
+  std::unique_ptr<gs_kmers, void (*)(gs_kmers *)> own(new gs_kmers(), km_release);
+  gs_kmers *km = own.get();
   km->device = device;
   km->k = k;
   km->P = P;
   if (chr_len == 0) {
-    *out = km;
+    *out = own.release();
     return GS_OK;
   }
   const uint32_t nb = (uint32_t)((chr_len + KM_BLOCK - 1) / KM_BLOCK);
+  gs_scratch mem;
   void *d_chr_own = nullptr, *d_lut = nullptr, *d_cnt = nullptr, *d_off = nullptr, *d_keys = nullptr,
        *d_keys2 = nullptr, *d_tmp = nullptr;
-  auto cleanup = [&]() {
-    for (void *p : {d_chr_own, d_lut, d_cnt, d_off, d_keys, d_keys2, d_tmp})
-      if (p) hipFree(p);
-  };
-#define KM_HIP(expr)                                                        \
-  do {                                                                      \
-    hipError_t e__ = (expr);                                                \
-    if (e__ != hipSuccess) {                                                \
-      gs_set_error(std::string(#expr) + ": " + hipGetErrorString(e__));     \
-      cleanup();                                                            \
-      km_release(km);                                                       \
-      return GS_ERR_DEVICE;                                                 \
-    }                                                                       \
-  } while (0)
   const uint8_t *d_chr = chr;
   if (!chr_on_device) {
-    KM_HIP(hipMalloc(&d_chr_own, chr_len));
-    KM_HIP(hipMemcpyAsync(d_chr_own, chr, chr_len, hipMemcpyHostToDevice, st));
+    GS_TRY(mem.get(chr_len, &d_chr_own));
+    GS_HIP(hipMemcpyAsync(d_chr_own, chr, chr_len, hipMemcpyHostToDevice, st));
     d_chr = (const uint8_t *)d_chr_own;
   }
-  KM_HIP(hipMalloc(&d_lut, 2 * lut.size()));
-  KM_HIP(hipMemcpyAsync(d_lut, lut.data(), 2 * lut.size(), hipMemcpyHostToDevice, st));
-  KM_HIP(hipMalloc(&d_cnt, 4 * ((size_t)nb + 1)));
-  KM_HIP(hipMalloc(&d_off, 4 * ((size_t)nb + 1)));
-  KM_HIP(hipMemsetAsync(d_cnt, 0, 4 * ((size_t)nb + 1), st));
+  GS_TRY(mem.get(2 * lut.size(), &d_lut));
+  GS_HIP(hipMemcpyAsync(d_lut, lut.data(), 2 * lut.size(), hipMemcpyHostToDevice, st));
+  GS_TRY(mem.get(4 * ((size_t)nb + 1), &d_cnt));
+  GS_TRY(mem.get(4 * ((size_t)nb + 1), &d_off));
+  GS_HIP(hipMemsetAsync(d_cnt, 0, 4 * ((size_t)nb + 1), st));
   gs_km_args a;
   a.chr = d_chr;
   a.lut = (const uint16_t *)d_lut;
@@ -241,36 +239,35 @@ extern "C" gs_status gs_kmers_generate(int device, const uint8_t *chr, uint64_t 
   a.start = (flags & GS_FLAG_PAM_AT_START) ? 1u : 0u;
   hipLaunchKernelGGL(k_km_count, dim3(nb), dim3(KM_BLOCK), 0, st, a, (uint32_t *)d_cnt);
   size_t tb = 0;
-  KM_HIP(rocprim::exclusive_scan(nullptr, tb, (uint32_t *)d_cnt, (uint32_t *)d_off, 0u, (size_t)nb + 1,
+  GS_HIP(rocprim::exclusive_scan(nullptr, tb, (uint32_t *)d_cnt, (uint32_t *)d_off, 0u, (size_t)nb + 1,
                                  rocprim::plus<uint32_t>(), st));
-  KM_HIP(hipMalloc(&d_tmp, tb + 16));
-  KM_HIP(rocprim::exclusive_scan(d_tmp, tb, (uint32_t *)d_cnt, (uint32_t *)d_off, 0u, (size_t)nb + 1,
+  GS_TRY(mem.get(tb, &d_tmp));
+  GS_HIP(rocprim::exclusive_scan(d_tmp, tb, (uint32_t *)d_cnt, (uint32_t *)d_off, 0u, (size_t)nb + 1,
                                  rocprim::plus<uint32_t>(), st));
   uint32_t total = 0;
-  KM_HIP(hipMemcpyAsync(&total, (uint32_t *)d_off + nb, 4, hipMemcpyDeviceToHost, st));
-  KM_HIP(hipStreamSynchronize(st));
+  GS_HIP(hipMemcpyAsync(&total, (uint32_t *)d_off + nb, 4, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipStreamSynchronize(st));
   km->n = total;
   if (total) {
-    KM_HIP(hipMalloc(&d_keys, 8 * (size_t)total));
-    KM_HIP(hipMalloc(&d_keys2, 8 * (size_t)total));
+    GS_TRY(mem.get(8 * (size_t)total, &d_keys));
+    GS_TRY(mem.get(8 * (size_t)total, &d_keys2));
     hipLaunchKernelGGL(k_km_keys, dim3(nb), dim3(KM_BLOCK), 0, st, a, (const uint32_t *)d_off, (uint64_t *)d_keys);
     /* bucket (1 + 2*nn bits above bit 32), then position: the whole key, so the order does not
      * lean on the sort being stable */
     const unsigned end_bit = 32u + 1u + 2u * nn;
     size_t sb = 0;
-    KM_HIP(rocprim::radix_sort_keys(nullptr, sb, (uint64_t *)d_keys, (uint64_t *)d_keys2, (size_t)total, 0u,
+    GS_HIP(rocprim::radix_sort_keys(nullptr, sb, (uint64_t *)d_keys, (uint64_t *)d_keys2, (size_t)total, 0u,
                                     end_bit, st));
     if (sb > tb) {
-      hipFree(d_tmp);
-      d_tmp = nullptr;
-      KM_HIP(hipMalloc(&d_tmp, sb + 16));
+      mem.drop(d_tmp);
+      GS_TRY(mem.get(sb, &d_tmp));
     }
-    KM_HIP(rocprim::radix_sort_keys(d_tmp, sb, (uint64_t *)d_keys, (uint64_t *)d_keys2, (size_t)total, 0u,
+    GS_HIP(rocprim::radix_sort_keys(d_tmp, sb, (uint64_t *)d_keys, (uint64_t *)d_keys2, (size_t)total, 0u,
                                     end_bit, st));
-    KM_HIP(hipMalloc(&km->d_seqs, (size_t)total * k));
-    KM_HIP(hipMalloc(&km->d_pams, (size_t)total * P));
-    KM_HIP(hipMalloc(&km->d_pos, 4 * (size_t)total));
-    KM_HIP(hipMalloc(&km->d_sense, (size_t)total));
+    GS_TRY(km_alloc((size_t)total * k, &km->d_seqs));
+    GS_TRY(km_alloc((size_t)total * P, &km->d_pams));
+    GS_TRY(km_alloc(4 * (size_t)total, &km->d_pos));
+    GS_TRY(km_alloc((size_t)total, &km->d_sense));
     gs_km_emit_args ea;
     ea.chr = d_chr;
     ea.keys = (const uint64_t *)d_keys2;
@@ -288,11 +285,9 @@ extern "C" gs_status gs_kmers_generate(int device, const uint8_t *chr, uint64_t 
     hipLaunchKernelGGL(k_km_emit, dim3((unsigned)(((size_t)total + KM_BLOCK - 1) / KM_BLOCK)), dim3(KM_BLOCK), 0,
                        st, ea);
   }
-  KM_HIP(hipStreamSynchronize(st));
-  KM_HIP(hipGetLastError());
-#undef KM_HIP
-  cleanup();
-  *out = km;
+  GS_HIP(hipStreamSynchronize(st));
+  GS_HIP(hipGetLastError());
+  *out = own.release();
   return GS_OK;
 }
 
@@ -411,28 +406,13 @@ static gs_status km_encode(gs_kmers *km, const char *prefix, const char *chr_nam
   if (pl >= (1u << 20) || nl >= (1u << 20)) return GS_ERR_ARG;
   GS_HIP(hipSetDevice(km->device));
   const uint64_t n = km->n;
+  gs_scratch mem;
   void *d_names = nullptr, *d_lens = nullptr, *d_tmp = nullptr, *off = nullptr, *text = nullptr, *s01 = nullptr;
-  auto cleanup = [&](bool all) {
-    for (void *p : {d_names, d_lens, d_tmp})
-      if (p) hipFree(p);
-    if (all)
-      for (void *p : {off, text, s01})
-        if (p) hipFree(p);
-  };
-#define KM_HIP(expr)                                                    \
-  do {                                                                  \
-    hipError_t e__ = (expr);                                            \
-    if (e__ != hipSuccess) {                                            \
-      gs_set_error(std::string(#expr) + ": " + hipGetErrorString(e__)); \
-      cleanup(true);                                                    \
-      return GS_ERR_DEVICE;                                             \
-    }                                                                   \
-  } while (0)
   std::string names = std::string(prefix) + chr_name;
-  KM_HIP(hipMalloc(&d_names, names.size() + 16));
-  KM_HIP(hipMemcpyAsync(d_names, names.data(), names.size(), hipMemcpyHostToDevice, st));
-  KM_HIP(hipMalloc(&d_lens, 8 * (n + 1)));
-  KM_HIP(hipMalloc(&off, 8 * (n + 1)));
+  GS_TRY(mem.get(names.size(), &d_names));
+  GS_HIP(hipMemcpyAsync(d_names, names.data(), names.size(), hipMemcpyHostToDevice, st));
+  GS_TRY(mem.get(8 * (n + 1), &d_lens));
+  GS_TRY(mem.get(8 * (n + 1), &off));
   gs_km_text_args a;
   memset(&a, 0, sizeof a);
   a.seqs = (const uint8_t *)km->d_seqs;
@@ -451,25 +431,25 @@ static gs_status km_encode(gs_kmers *km, const char *prefix, const char *chr_nam
   const unsigned grid = (unsigned)((n + 1 + KM_BLOCK - 1) / KM_BLOCK);
   hipLaunchKernelGGL(k_km_text_len, dim3(grid), dim3(KM_BLOCK), 0, st, a);
   size_t tb = 0;
-  KM_HIP(rocprim::exclusive_scan(nullptr, tb, (uint64_t *)d_lens, (uint64_t *)off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
-  KM_HIP(hipMalloc(&d_tmp, tb + 16));
-  KM_HIP(rocprim::exclusive_scan(d_tmp, tb, (uint64_t *)d_lens, (uint64_t *)off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+  GS_HIP(rocprim::exclusive_scan(nullptr, tb, (uint64_t *)d_lens, (uint64_t *)off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+  GS_TRY(mem.get(tb, &d_tmp));
+  GS_HIP(rocprim::exclusive_scan(d_tmp, tb, (uint64_t *)d_lens, (uint64_t *)off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
   uint64_t total = 0;
-  KM_HIP(hipMemcpyAsync(&total, (uint64_t *)off + n, 8, hipMemcpyDeviceToHost, st));
-  KM_HIP(hipStreamSynchronize(st));
-  KM_HIP(hipMalloc(&text, total + 16));
-  if (!rows) KM_HIP(hipMalloc(&s01, n + 16));
+  GS_HIP(hipMemcpyAsync(&total, (uint64_t *)off + n, 8, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipStreamSynchronize(st));
+  GS_TRY(mem.get(total, &text));
+  if (!rows) GS_TRY(mem.get(n, &s01));
   a.text = (uint8_t *)text;
   a.sense01 = (uint8_t *)s01;
   if (n) hipLaunchKernelGGL(k_km_text_write, dim3((unsigned)((n + KM_BLOCK - 1) / KM_BLOCK)), dim3(KM_BLOCK), 0, st, a);
-  KM_HIP(hipStreamSynchronize(st));
-  KM_HIP(hipGetLastError());
-#undef KM_HIP
-  cleanup(false);
+  GS_HIP(hipStreamSynchronize(st));
+  GS_HIP(hipGetLastError());
+  mem.keep(text);
   if (rows) {
-    hipFree(off);
     *d_text = text;
   } else {
+    mem.keep(off);
+    mem.keep(s01);
     for (void *p : {km->d_ids, km->d_id_off, km->d_sense01})
       if (p) hipFree(p);
     km->d_ids = text;
@@ -565,10 +545,11 @@ extern "C" gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, g
       gs_set_error("gs_kmers_concat: parts of different devices, kmer or PAM lengths or origins, or ids on some of them only");
       return GS_ERR_ARG;
     }
-  gs_kmers *km = new (std::nothrow) gs_kmers();
+  std::unique_ptr<gs_kmers, void (*)(gs_kmers *)> own(new (std::nothrow) gs_kmers(), km_release);
+  gs_kmers *km = own.get();
   if (!km) return GS_ERR_NOMEM;
   if (n_parts == 0) {
-    *out = km;
+    *out = own.release();
     return GS_OK;
   }
   km->device = parts[0]->device;
@@ -581,38 +562,29 @@ extern "C" gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, g
     km->id_bytes += parts[i]->id_bytes;
   }
   const uint32_t k = km->k, P = km->P;
-#define KM_HIP(expr)                                                    \
-  do {                                                                  \
-    hipError_t e__ = (expr);                                            \
-    if (e__ != hipSuccess) {                                            \
-      gs_set_error(std::string(#expr) + ": " + hipGetErrorString(e__)); \
-      km_release(km);                                                   \
-      return GS_ERR_DEVICE;                                             \
-    }                                                                   \
-  } while (0)
-  KM_HIP(hipSetDevice(km->device));
-  KM_HIP(hipMalloc(&km->d_seqs, (size_t)km->n * k + 16));
-  KM_HIP(hipMalloc(&km->d_pams, (size_t)km->n * P + 16));
-  if (!km->parsed) KM_HIP(hipMalloc(&km->d_pos, 4 * (size_t)km->n + 16));
-  KM_HIP(hipMalloc(&km->d_sense, (size_t)km->n + 16));
+  GS_HIP(hipSetDevice(km->device));
+  GS_TRY(km_alloc((size_t)km->n * k, &km->d_seqs));
+  GS_TRY(km_alloc((size_t)km->n * P, &km->d_pams));
+  if (!km->parsed) GS_TRY(km_alloc(4 * (size_t)km->n, &km->d_pos));
+  GS_TRY(km_alloc((size_t)km->n, &km->d_sense));
   if (km->have_ids) {
-    KM_HIP(hipMalloc(&km->d_ids, (size_t)km->id_bytes + 16));
-    KM_HIP(hipMalloc(&km->d_id_off, 8 * ((size_t)km->n + 1)));
-    KM_HIP(hipMalloc(&km->d_sense01, (size_t)km->n + 16));
+    GS_TRY(km_alloc((size_t)km->id_bytes, &km->d_ids));
+    GS_TRY(km_alloc(8 * ((size_t)km->n + 1), &km->d_id_off));
+    GS_TRY(km_alloc((size_t)km->n, &km->d_sense01));
   }
   uint64_t at = 0, id_at = 0;
   for (uint32_t i = 0; i < n_parts; i++) {
     const gs_kmers *p = parts[i];
     const bool last = i + 1 == n_parts;
     if (p->n) {
-      KM_HIP(hipMemcpyAsync((char *)km->d_seqs + at * k, p->d_seqs, (size_t)p->n * k, hipMemcpyDeviceToDevice, nullptr));
-      KM_HIP(hipMemcpyAsync((char *)km->d_pams + at * P, p->d_pams, (size_t)p->n * P, hipMemcpyDeviceToDevice, nullptr));
-      if (!km->parsed) KM_HIP(hipMemcpyAsync((char *)km->d_pos + at * 4, p->d_pos, (size_t)p->n * 4, hipMemcpyDeviceToDevice, nullptr));
-      KM_HIP(hipMemcpyAsync((char *)km->d_sense + at, p->d_sense, (size_t)p->n, hipMemcpyDeviceToDevice, nullptr));
+      GS_HIP(hipMemcpyAsync((char *)km->d_seqs + at * k, p->d_seqs, (size_t)p->n * k, hipMemcpyDeviceToDevice, nullptr));
+      GS_HIP(hipMemcpyAsync((char *)km->d_pams + at * P, p->d_pams, (size_t)p->n * P, hipMemcpyDeviceToDevice, nullptr));
+      if (!km->parsed) GS_HIP(hipMemcpyAsync((char *)km->d_pos + at * 4, p->d_pos, (size_t)p->n * 4, hipMemcpyDeviceToDevice, nullptr));
+      GS_HIP(hipMemcpyAsync((char *)km->d_sense + at, p->d_sense, (size_t)p->n, hipMemcpyDeviceToDevice, nullptr));
     }
     if (km->have_ids) {
-      if (p->n) KM_HIP(hipMemcpyAsync((char *)km->d_sense01 + at, p->d_sense01, (size_t)p->n, hipMemcpyDeviceToDevice, nullptr));
-      if (p->id_bytes) KM_HIP(hipMemcpyAsync((char *)km->d_ids + id_at, p->d_ids, (size_t)p->id_bytes, hipMemcpyDeviceToDevice, nullptr));
+      if (p->n) GS_HIP(hipMemcpyAsync((char *)km->d_sense01 + at, p->d_sense01, (size_t)p->n, hipMemcpyDeviceToDevice, nullptr));
+      if (p->id_bytes) GS_HIP(hipMemcpyAsync((char *)km->d_ids + id_at, p->d_ids, (size_t)p->id_bytes, hipMemcpyDeviceToDevice, nullptr));
       const uint64_t cnt = p->n + (last ? 1u : 0u); /* the last part's closing offset closes the stream */
       if (cnt)
         hipLaunchKernelGGL(k_km_rebase, dim3((unsigned)((cnt + KM_BLOCK - 1) / KM_BLOCK)), dim3(KM_BLOCK), 0, nullptr,
@@ -621,10 +593,9 @@ extern "C" gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, g
     at += p->n;
     id_at += p->id_bytes;
   }
-  KM_HIP(hipStreamSynchronize(nullptr));
-  KM_HIP(hipGetLastError());
-#undef KM_HIP
-  *out = km;
+  GS_HIP(hipStreamSynchronize(nullptr));
+  GS_HIP(hipGetLastError());
+  *out = own.release();
   return GS_OK;
 }
 

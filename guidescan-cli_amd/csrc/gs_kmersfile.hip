@@ -18,16 +18,14 @@
  */
 #include "gs_common.h"
 #include "gs_device.h"
+#include "gs_scratch.h"
+#include "gs_block_scan.h"
 #include "gs_kmers_obj.h"
 #include "gs_kmers_scan.h"
 
 #include <rocprim/rocprim.hpp>
 
-#include <sys/stat.h>
-
 #include <algorithm>
-#include <chrono>
-#include <cstdio>
 #include <cstdlib>
 
 #define KF_THREADS 256u
@@ -78,23 +76,6 @@ struct kf_pair_add {
   __host__ __device__ kf_pair operator()(const kf_pair &a, const kf_pair &b) const { return kf_pair{a.rows + b.rows, a.ids + b.ids}; }
 };
 
-/* Scan of one summary per lane in LDS: -> the composition of the lanes below t; *total: of all 256 */
-__device__ __forceinline__ gs_km_sum kf_block_scan(gs_km_sum *lds, const gs_km_sum &v, uint32_t t, gs_km_sum *total) {
-  lds[t] = v;
-  __syncthreads();
-  for (uint32_t d = 1; d < KF_THREADS; d <<= 1) {
-    gs_km_sum x = lds[t];
-    if (t >= d) x = gs_km_compose(lds[t - d], x);
-    __syncthreads();
-    lds[t] = x;
-    __syncthreads();
-  }
-  const gs_km_sum r = t ? lds[t - 1] : gs_km_identity();
-  *total = lds[KF_THREADS - 1];
-  __syncthreads();
-  return r;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(KF_THREADS) void k_kf_tile(kf_args a) {
   __shared__ gs_km_sum s_scan[KF_THREADS];
@@ -113,7 +94,7 @@ __global__ __launch_bounds__(KF_THREADS) void k_kf_tile(kf_args a) {
     s.n_nl = (uint32_t)__builtin_popcount(nl);
     s.open = valid && !((nl >> (hi - 1u)) & 1u);
     gs_km_sum tile;
-    const gs_km_sum left_in = kf_block_scan(s_scan, s, t, &tile);
+    const gs_km_sum left_in = gs_block_scan<KF_THREADS>(s_scan, s, t, kf_compose(), gs_km_identity(), &tile);
     if (MODE == KF_SUM) {
       if (t == 0) a.sums[k + 1] = tile;
       continue;
@@ -198,41 +179,6 @@ __global__ __launch_bounds__(KF_THREADS) void k_kf_emit(kf_args a) {
   }
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-/* plain allocations of the exact size, all released by the holder's destructor unless taken out */
-struct kf_mem {
-  std::vector<void *> p;
-  ~kf_mem() {
-    for (void *q : p)
-      if (q) (void)hipFree(q);
-  }
-  gs_status get(size_t bytes, void **out) {
-    *out = nullptr;
-    if (hipMalloc(out, bytes + 16) != hipSuccess) {
-      (void)hipGetLastError();
-      *out = nullptr;
-      gs_set_error("out of device memory");
-      return GS_ERR_NOMEM;
-    }
-    p.push_back(*out);
-    return GS_OK;
-  }
-  void release(void *q) { /* the caller keeps q */
-    for (void *&x : p)
-      if (x == q) x = nullptr;
-  }
-};
-struct kf_events {
-  hipEvent_t e[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  ~kf_events() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
-
 void kf_report_clear(gs_kmers_report *rep) {
   if (rep) memset(rep, 0, sizeof *rep);
 }
@@ -262,8 +208,7 @@ gs_status kf_unsupported(gs_kmers_report *rep, uint64_t n) {
 gs_status kf_run(int device, const uint8_t *d_raw, uint64_t len, hipStream_t st, gs_kmers *km, gs_kmers_report *rep) {
   const auto t0 = std::chrono::steady_clock::now();
   if (len == 0) return kf_report_bad(rep, GS_KM_EMPTY, 0, 0, 0, "");
-  kf_mem mem;
-  gs_status rc;
+  gs_scratch mem;
   kf_args a;
   memset(&a, 0, sizeof a);
   a.raw = d_raw;
@@ -274,16 +219,17 @@ gs_status kf_run(int device, const uint8_t *d_raw, uint64_t len, hipStream_t st,
   size_t tb_s = 0, tb_p = 0;
   GS_HIP(rocprim::inclusive_scan(nullptr, tb_s, (gs_km_sum *)nullptr, (gs_km_sum *)nullptr, (size_t)nt + 1, kf_compose(), st));
   void *sums, *fwd, *tmp, *red;
-  if ((rc = mem.get(sizeof(gs_km_sum) * (nt + 1), &sums)) != GS_OK || (rc = mem.get(sizeof(gs_km_sum) * (nt + 1), &fwd)) != GS_OK ||
-      (rc = mem.get(tb_s, &tmp)) != GS_OK || (rc = mem.get(sizeof(kf_red), &red)) != GS_OK)
-    return rc;
+  GS_TRY(mem.get(sizeof(gs_km_sum) * (nt + 1), &sums));
+  GS_TRY(mem.get(sizeof(gs_km_sum) * (nt + 1), &fwd));
+  GS_TRY(mem.get(tb_s, &tmp));
+  GS_TRY(mem.get(sizeof(kf_red), &red));
   a.sums = (gs_km_sum *)sums;
   a.fwd = (const gs_km_sum *)fwd;
   a.red = (kf_red *)red;
   const uint32_t cus = (uint32_t)gs_num_cus(device);
   const uint32_t tile_grid = (uint32_t)std::min<uint64_t>(nt, (uint64_t)cus * 64u);
-  kf_events ev;
-  for (int i = 0; i < 8; i++) GS_HIP(hipEventCreate(&ev.e[i]));
+  gs_events<8> ev;
+  for (hipEvent_t &e : ev.e) GS_HIP(hipEventCreate(&e));
   /* a. */
   GS_HIP(hipMemsetAsync(sums, 0, sizeof(gs_km_sum), st)); /* gs_km_identity() */
   GS_HIP(hipEventRecord(ev.e[0], st));
@@ -296,7 +242,7 @@ gs_status kf_run(int device, const uint8_t *d_raw, uint64_t len, hipStream_t st,
   const uint64_t n_lines = gs_km_lines(whole); /* >= 1: the file has bytes */
   a.n_lines = n_lines;
   void *starts;
-  if ((rc = mem.get(8 * (n_lines + 1), &starts)) != GS_OK) return rc;
+  GS_TRY(mem.get(8 * (n_lines + 1), &starts));
   a.starts = (uint64_t *)starts;
   const uint64_t first = 0, past = len + 1;
   GS_HIP(hipMemcpyAsync(starts, &first, 8, hipMemcpyHostToDevice, st));
@@ -318,9 +264,9 @@ gs_status kf_run(int device, const uint8_t *d_raw, uint64_t len, hipStream_t st,
   GS_HIP(rocprim::exclusive_scan(nullptr, tb_p, rocprim::make_transform_iterator((const kf_rec *)nullptr, kf_to_pair()), (kf_pair *)nullptr,
                                  kf_pair{0, 0}, (size_t)n_lines + 1, kf_pair_add(), st));
   void *recs, *before, *tmp_p;
-  if ((rc = mem.get(sizeof(kf_rec) * (n_lines + 1), &recs)) != GS_OK || (rc = mem.get(sizeof(kf_pair) * (n_lines + 1), &before)) != GS_OK ||
-      (rc = mem.get(tb_p, &tmp_p)) != GS_OK)
-    return rc;
+  GS_TRY(mem.get(sizeof(kf_rec) * (n_lines + 1), &recs));
+  GS_TRY(mem.get(sizeof(kf_pair) * (n_lines + 1), &before));
+  GS_TRY(mem.get(tb_p, &tmp_p));
   a.recs = (kf_rec *)recs;
   a.before = (const kf_pair *)before;
   const kf_red none{~0ull, ~0u, 0u, ~0u, 0u, 0u, 0u};
@@ -363,10 +309,12 @@ gs_status kf_run(int device, const uint8_t *d_raw, uint64_t len, hipStream_t st,
   km->P = a.P = n ? got.min_P : 0u;
   /* d. */
   void *seqs, *pams, *ids, *id_off, *s01, *sense;
-  if ((rc = mem.get((size_t)n * a.L, &seqs)) != GS_OK || (rc = mem.get((size_t)n * a.P, &pams)) != GS_OK ||
-      (rc = mem.get((size_t)all.ids, &ids)) != GS_OK || (rc = mem.get(8 * (n + 1), &id_off)) != GS_OK || (rc = mem.get((size_t)n, &s01)) != GS_OK ||
-      (rc = mem.get((size_t)n, &sense)) != GS_OK)
-    return rc;
+  GS_TRY(mem.get((size_t)n * a.L, &seqs));
+  GS_TRY(mem.get((size_t)n * a.P, &pams));
+  GS_TRY(mem.get((size_t)all.ids, &ids));
+  GS_TRY(mem.get(8 * (n + 1), &id_off));
+  GS_TRY(mem.get((size_t)n, &s01));
+  GS_TRY(mem.get((size_t)n, &sense));
   a.seqs = (uint8_t *)seqs, a.pams = (uint8_t *)pams, a.ids = (uint8_t *)ids, a.id_off = (uint64_t *)id_off;
   a.sense01 = (uint8_t *)s01, a.sense = (uint8_t *)sense;
   GS_HIP(hipEventRecord(ev.e[6], st));
@@ -374,17 +322,13 @@ gs_status kf_run(int device, const uint8_t *d_raw, uint64_t len, hipStream_t st,
   GS_HIP(hipEventRecord(ev.e[7], st));
   GS_HIP(hipStreamSynchronize(st));
   GS_HIP(hipGetLastError());
-  for (void *q : {seqs, pams, ids, id_off, s01, sense}) mem.release(q);
+  for (void *q : {seqs, pams, ids, id_off, s01, sense}) mem.keep(q);
   km->d_seqs = seqs, km->d_pams = pams, km->d_ids = ids, km->d_id_off = id_off, km->d_sense01 = s01, km->d_sense = sense;
   if (rep) {
     rep->n = n, rep->L = a.L, rep->P = a.P;
     static const int from[5] = {0, 1, 3, 4, 6}; /* 0 -> 1 holds the wait for the line count and the allocation too */
-    for (int i = 0; i < 5; i++) {
-      float ms = 0;
-      GS_HIP(hipEventElapsedTime(&ms, ev.e[from[i]], ev.e[from[i] + 1]));
-      rep->ms[3 + i] = ms;
-    }
-    rep->ms[2] = ms_since(t0);
+    GS_TRY(ev.elapsed(from, 5, rep->ms + 3));
+    rep->ms[2] = gs_ms_since(t0);
   }
   return GS_OK;
 }
@@ -427,14 +371,13 @@ extern "C" gs_status gs_kmers_parse(int device, const uint8_t *raw, uint64_t len
   if (!out || (len && !raw)) return GS_ERR_ARG;
   *out = nullptr;
   GS_HIP(hipSetDevice(device));
-  kf_mem mem;
+  gs_scratch mem;
   void *d_raw = nullptr;
-  gs_status rc;
-  if ((rc = mem.get(len, &d_raw)) != GS_OK) return rc;
+  GS_TRY(mem.get(len, &d_raw));
   const auto t0 = std::chrono::steady_clock::now();
   if (len) GS_HIP(hipMemcpy(d_raw, raw, len, hipMemcpyHostToDevice));
-  const double up = ms_since(t0);
-  rc = gs_kmers_parse_device(device, d_raw, len, nullptr, out, rep);
+  const double up = gs_ms_since(t0);
+  const gs_status rc = gs_kmers_parse_device(device, d_raw, len, nullptr, out, rep);
   if (rep) rep->ms[1] = up;
   return rc;
 }
@@ -444,77 +387,16 @@ extern "C" uint64_t gs_debug_kmers_chunk_bytes(uint64_t set) {
   return g_chunk_bytes.load();
 }
 
-/* the staging loop of gs_fasta_parse_file, a second time: that one ends in its own parse and keeps its own clocks */
 extern "C" gs_status gs_kmers_parse_file(int device, const char *path, gs_kmers **out, gs_kmers_report *rep) {
   kf_report_clear(rep);
   if (!out || !path) return GS_ERR_ARG;
   *out = nullptr;
-  FILE *f = fopen(path, "rb");
-  struct stat sb;
-  if (!f || fstat(fileno(f), &sb) != 0 || !S_ISREG(sb.st_mode)) {
-    if (f) fclose(f);
-    gs_set_error(std::string("cannot read ") + path);
-    return GS_ERR_IO;
-  }
-  const uint64_t size = (uint64_t)sb.st_size, chunk = g_chunk_bytes.load();
-  kf_mem mem;
-  void *d_raw = nullptr, *pin[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  hipStream_t st = nullptr;
-  double ms_read = 0, ms_wait = 0;
-  uint64_t at = 0;
-  /* two page-locked chunks: one is being read into while the other's copy to the device is under way */
-  auto body = [&]() -> gs_status {
-    GS_HIP(hipSetDevice(device));
-    gs_status rc;
-    if ((rc = mem.get(size, &d_raw)) != GS_OK) return rc;
-    GS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) {
-      if (hipHostMalloc(&pin[i], (size_t)std::min<uint64_t>(chunk, size ? size : 1), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        pin[i] = nullptr;
-        gs_set_error("out of page-locked host memory");
-        return GS_ERR_NOMEM;
-      }
-      GS_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-    }
-    for (uint64_t c = 0; at < size; c++) {
-      const int b = (int)(c & 1);
-      auto t0 = std::chrono::steady_clock::now();
-      if (c >= 2) GS_HIP(hipEventSynchronize(ev[b]));
-      ms_wait += ms_since(t0);
-      t0 = std::chrono::steady_clock::now();
-      const size_t want = (size_t)std::min<uint64_t>(chunk, size - at), got = fread(pin[b], 1, want, f);
-      ms_read += ms_since(t0);
-      if (got != want) {
-        gs_set_error(std::string("cannot read ") + path);
-        return GS_ERR_IO;
-      }
-      GS_HIP(hipMemcpyAsync((uint8_t *)d_raw + at, pin[b], got, hipMemcpyHostToDevice, st));
-      GS_HIP(hipEventRecord(ev[b], st));
-      at += got;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    GS_HIP(hipStreamSynchronize(st));
-    ms_wait += ms_since(t0);
-    return gs_kmers_parse_device(device, d_raw, size, st, out, rep);
-  };
-  gs_status rc;
-  try {
-    rc = body();
-  } catch (const std::bad_alloc &) {
-    rc = GS_ERR_NOMEM;
-  }
-  fclose(f);
-  if (st) (void)hipStreamSynchronize(st);
-  for (int i = 0; i < 2; i++) {
-    if (ev[i]) (void)hipEventDestroy(ev[i]);
-    if (pin[i]) (void)hipHostFree(pin[i]);
-  }
-  if (st) (void)hipStreamDestroy(st);
-  if (rep) {
-    rep->ms[0] = ms_read;
-    rep->ms[1] = ms_wait;
+  gs_staged_file f;
+  gs_status rc = f.open(device, path, g_chunk_bytes.load());
+  if (rc == GS_OK) rc = gs_kmers_parse_device(device, f.d_raw, f.size, f.st, out, rep);
+  if (rep) { /* also of a file that did not parse */
+    rep->ms[0] = f.ms_read;
+    rep->ms[1] = f.ms_wait;
   }
   return rc;
 }

@@ -9,6 +9,7 @@
  * normal GPU builder - the device layout is derived from the text, never from SDSL's layout.
  */
 #include "gs_common.h"
+#include "gs_scratch.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -449,29 +450,6 @@ __global__ __launch_bounds__(256) void k_imp_cmp_revcomp(const uint8_t *fwd, con
   if ((threadIdx.x & 63u) == 0u && v) atomicAdd(diff, v);
 }
 
-namespace {
-struct dbuf { /* a device allocation that frees itself */
-  void *p = nullptr;
-  ~dbuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t get(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  void *release() {
-    void *q = p;
-    p = nullptr;
-    return q;
-  }
-};
-}  // namespace
-#define IMP_HIP(expr)                                                         \
-  do {                                                                        \
-    hipError_t e__ = (expr);                                                  \
-    if (e__ != hipSuccess) {                                                  \
-      gs_set_error(std::string(#expr) + ": " + hipGetErrorString(e__));       \
-      return e__ == hipErrorOutOfMemory ? GS_ERR_NOMEM : GS_ERR_DEVICE;       \
-    }                                                                         \
-  } while (0)
-
 /* one strand's file -> its text (n bytes: the genome and the sentinel) and suffix array (n rows) in device memory.
  * GS_ERR_UNSUPPORTED: a file this path does not take (more than 16 distinct symbols, 2^32 rows) - the caller uses the host path */
 static gs_status sdsl_strand_on_device(const char *path, uint8_t **d_text_out, uint32_t **d_sa_out, uint64_t *n_out) {
@@ -510,23 +488,24 @@ static gs_status sdsl_strand_on_device(const char *path, uint8_t **d_text_out, u
     gs_set_error("bad SA sample width");
     return GS_ERR_FORMAT;
   }
-  dbuf d_words, d_ones, d_bwt, d_hist;
-  IMP_HIP(d_words.get(8 * (nw + 2)));
-  IMP_HIP(d_ones.get(8 * (nw + 2)));
-  IMP_HIP(d_bwt.get(nb * 64 + 64)); /* whole chunks, zero beyond the last row */
-  IMP_HIP(d_hist.get(256 * 8));
-  IMP_HIP(hipMemset(d_words.p, 0, 8 * (nw + 2)));
-  IMP_HIP(hipMemcpy(d_words.p, P.bv.words, 8 * nw, hipMemcpyHostToDevice));
-  IMP_HIP(hipMemcpy(d_ones.p, P.ones_before.data(), 8 * (nw + 1), hipMemcpyHostToDevice));
-  IMP_HIP(hipMemset(d_bwt.p, 0, nb * 64 + 64));
-  IMP_HIP(hipMemset(d_hist.p, 0, 256 * 8));
+  gs_scratch mem;
+  void *d_words = nullptr, *d_ones = nullptr, *d_bwt = nullptr, *d_hist = nullptr;
+  GS_TRY(mem.get(8 * (nw + 2), &d_words));
+  GS_TRY(mem.get(8 * (nw + 2), &d_ones));
+  GS_TRY(mem.get(nb * 64 + 64, &d_bwt)); /* whole chunks, zero beyond the last row */
+  GS_TRY(mem.get(256 * 8, &d_hist));
+  GS_HIP(hipMemset(d_words, 0, 8 * (nw + 2)));
+  GS_HIP(hipMemcpy(d_words, P.bv.words, 8 * nw, hipMemcpyHostToDevice));
+  GS_HIP(hipMemcpy(d_ones, P.ones_before.data(), 8 * (nw + 1), hipMemcpyHostToDevice));
+  GS_HIP(hipMemset(d_bwt, 0, nb * 64 + 64));
+  GS_HIP(hipMemset(d_hist, 0, 256 * 8));
   const unsigned grid = 256u * 32u;
-  hipLaunchKernelGGL(k_imp_access, dim3(grid), dim3(256), 0, 0, (const uint64_t *)d_words.p, (const uint64_t *)d_ones.p, T, n, (uint8_t *)d_bwt.p);
-  hipLaunchKernelGGL(k_imp_hist, dim3(grid), dim3(256), 0, 0, (const uint8_t *)d_bwt.p, n, (unsigned long long *)d_hist.p);
+  hipLaunchKernelGGL(k_imp_access, dim3(grid), dim3(256), 0, 0, (const uint64_t *)d_words, (const uint64_t *)d_ones, T, n, (uint8_t *)d_bwt);
+  hipLaunchKernelGGL(k_imp_hist, dim3(grid), dim3(256), 0, 0, (const uint8_t *)d_bwt, n, (unsigned long long *)d_hist);
   unsigned long long hist[256];
-  IMP_HIP(hipMemcpy(hist, d_hist.p, sizeof(hist), hipMemcpyDeviceToHost));
-  (void)hipFree(d_words.release());
-  (void)hipFree(d_ones.release());
+  GS_HIP(hipMemcpy(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost));
+  mem.drop(d_words);
+  mem.drop(d_ones);
   imp_lf L;
   memset(&L, 0, sizeof(L));
   memset(L.D.of, 0xFF, sizeof(L.D.of));
@@ -544,63 +523,65 @@ static gs_status sdsl_strand_on_device(const char *path, uint8_t **d_text_out, u
     return GS_ERR_FORMAT;
   }
   /* rows of each symbol before every chunk of 64 */
-  dbuf d_cnt, d_ck, d_tmp;
-  IMP_HIP(d_cnt.get(4 * (size_t)sigma * nb));
-  IMP_HIP(d_ck.get(4 * (size_t)sigma * nb));
-  hipLaunchKernelGGL(k_imp_chunks, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, 0, (const uint8_t *)d_bwt.p, n, L.D, sigma, nb, (uint32_t *)d_cnt.p);
+  void *d_cnt = nullptr, *d_ck = nullptr, *d_tmp = nullptr;
+  GS_TRY(mem.get(4 * (size_t)sigma * nb, &d_cnt));
+  GS_TRY(mem.get(4 * (size_t)sigma * nb, &d_ck));
+  hipLaunchKernelGGL(k_imp_chunks, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, 0, (const uint8_t *)d_bwt, n, L.D, sigma, nb, (uint32_t *)d_cnt);
   size_t tb = 0;
-  IMP_HIP(rocprim::exclusive_scan(nullptr, tb, (uint32_t *)d_cnt.p, (uint32_t *)d_ck.p, 0u, (size_t)nb, rocprim::plus<uint32_t>(), 0));
-  IMP_HIP(d_tmp.get(tb + 16));
+  GS_HIP(rocprim::exclusive_scan(nullptr, tb, (uint32_t *)d_cnt, (uint32_t *)d_ck, 0u, (size_t)nb, rocprim::plus<uint32_t>(), 0));
+  GS_TRY(mem.get(tb, &d_tmp));
   for (uint32_t d = 0; d < sigma; d++) {
     size_t t2 = tb;
-    IMP_HIP(rocprim::exclusive_scan(d_tmp.p, t2, (uint32_t *)d_cnt.p + (size_t)d * nb, (uint32_t *)d_ck.p + (size_t)d * nb, 0u, (size_t)nb,
+    GS_HIP(rocprim::exclusive_scan(d_tmp, t2, (uint32_t *)d_cnt + (size_t)d * nb, (uint32_t *)d_ck + (size_t)d * nb, 0u, (size_t)nb,
                                     rocprim::plus<uint32_t>(), 0));
   }
-  (void)hipFree(d_cnt.release());
+  mem.drop(d_cnt);
   /* the samples by text position */
-  dbuf d_packed, d_pos, d_idx, d_pos2, d_idx2, d_sorttmp;
+  void *d_packed = nullptr, *d_pos = nullptr, *d_idx = nullptr, *d_pos2 = nullptr, *d_idx2 = nullptr, *d_sorttmp = nullptr;
   const uint64_t pw = (P.sa_samples.bits + 63) >> 6;
-  IMP_HIP(d_packed.get(8 * (pw + 2)));
-  IMP_HIP(hipMemset(d_packed.p, 0, 8 * (pw + 2)));
-  IMP_HIP(hipMemcpy(d_packed.p, P.sa_samples.words, 8 * pw, hipMemcpyHostToDevice));
-  IMP_HIP(d_pos.get(4 * ns));
-  IMP_HIP(d_idx.get(4 * ns));
-  IMP_HIP(d_pos2.get(4 * ns));
-  IMP_HIP(d_idx2.get(4 * ns));
-  hipLaunchKernelGGL(k_imp_samples, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, 0, (const uint64_t *)d_packed.p, width, ns, (uint32_t *)d_pos.p,
-                     (uint32_t *)d_idx.p);
+  GS_TRY(mem.get(8 * (pw + 2), &d_packed));
+  GS_HIP(hipMemset(d_packed, 0, 8 * (pw + 2)));
+  GS_HIP(hipMemcpy(d_packed, P.sa_samples.words, 8 * pw, hipMemcpyHostToDevice));
+  GS_TRY(mem.get(4 * ns, &d_pos));
+  GS_TRY(mem.get(4 * ns, &d_idx));
+  GS_TRY(mem.get(4 * ns, &d_pos2));
+  GS_TRY(mem.get(4 * ns, &d_idx2));
+  hipLaunchKernelGGL(k_imp_samples, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, 0, (const uint64_t *)d_packed, width, ns, (uint32_t *)d_pos,
+                     (uint32_t *)d_idx);
   size_t sb = 0;
-  IMP_HIP(rocprim::radix_sort_pairs(nullptr, sb, (uint32_t *)d_pos.p, (uint32_t *)d_pos2.p, (uint32_t *)d_idx.p, (uint32_t *)d_idx2.p, (size_t)ns, 0, 32, 0));
-  IMP_HIP(d_sorttmp.get(sb + 16));
-  IMP_HIP(rocprim::radix_sort_pairs(d_sorttmp.p, sb, (uint32_t *)d_pos.p, (uint32_t *)d_pos2.p, (uint32_t *)d_idx.p, (uint32_t *)d_idx2.p, (size_t)ns, 0, 32, 0));
+  GS_HIP(rocprim::radix_sort_pairs(nullptr, sb, (uint32_t *)d_pos, (uint32_t *)d_pos2, (uint32_t *)d_idx, (uint32_t *)d_idx2, (size_t)ns, 0, 32, 0));
+  GS_TRY(mem.get(sb, &d_sorttmp));
+  GS_HIP(rocprim::radix_sort_pairs(d_sorttmp, sb, (uint32_t *)d_pos, (uint32_t *)d_pos2, (uint32_t *)d_idx, (uint32_t *)d_idx2, (size_t)ns, 0, 32, 0));
   uint32_t last = 0;
-  IMP_HIP(hipMemcpy(&last, (uint32_t *)d_pos2.p + (ns - 1), 4, hipMemcpyDeviceToHost));
+  GS_HIP(hipMemcpy(&last, (uint32_t *)d_pos2 + (ns - 1), 4, hipMemcpyDeviceToHost));
   if ((uint64_t)last != n - 1) { /* row 0 (the sentinel suffix) is always sampled */
     gs_set_error("SA samples lack the sentinel suffix");
     return GS_ERR_FORMAT;
   }
   /* the walks */
-  dbuf d_text, d_sa, d_bad;
-  IMP_HIP(d_text.get(n + 64));
-  IMP_HIP(d_sa.get(4 * (n + 64)));
-  IMP_HIP(d_bad.get(16));
-  IMP_HIP(hipMemset(d_text.p, 0, n + 64));
-  IMP_HIP(hipMemset(d_sa.p, 0xFF, 4 * (n + 64)));
-  IMP_HIP(hipMemset(d_bad.p, 0, 16));
-  L.bwt = (const uint8_t *)d_bwt.p;
-  L.ck = (const uint32_t *)d_ck.p;
+  void *d_text = nullptr, *d_sa = nullptr, *d_bad = nullptr;
+  GS_TRY(mem.get(n + 64, &d_text));
+  GS_TRY(mem.get(4 * (n + 64), &d_sa));
+  GS_TRY(mem.get(16, &d_bad));
+  GS_HIP(hipMemset(d_text, 0, n + 64));
+  GS_HIP(hipMemset(d_sa, 0xFF, 4 * (n + 64)));
+  GS_HIP(hipMemset(d_bad, 0, 16));
+  L.bwt = (const uint8_t *)d_bwt;
+  L.ck = (const uint32_t *)d_ck;
   L.nb = nb;
-  hipLaunchKernelGGL(k_imp_invert, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, 0, L, (const uint32_t *)d_pos2.p, (const uint32_t *)d_idx2.p, ns,
-                     (uint8_t *)d_text.p, (uint32_t *)d_sa.p, (uint32_t *)d_bad.p);
+  hipLaunchKernelGGL(k_imp_invert, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, 0, L, (const uint32_t *)d_pos2, (const uint32_t *)d_idx2, ns,
+                     (uint8_t *)d_text, (uint32_t *)d_sa, (uint32_t *)d_bad);
   uint32_t bad = 0;
-  IMP_HIP(hipMemcpy(&bad, d_bad.p, 4, hipMemcpyDeviceToHost));
-  IMP_HIP(hipGetLastError());
+  GS_HIP(hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost));
+  GS_HIP(hipGetLastError());
   if (bad) {
     gs_set_error(bad & 1u ? "BWT inversion met the sentinel inside the text" : "two SA samples at one text position");
     return GS_ERR_FORMAT;
   }
-  *d_text_out = (uint8_t *)d_text.release();
-  *d_sa_out = (uint32_t *)d_sa.release();
+  mem.keep(d_text);
+  mem.keep(d_sa);
+  *d_text_out = (uint8_t *)d_text;
+  *d_sa_out = (uint32_t *)d_sa;
   *n_out = n;
   return GS_OK;
 }
@@ -614,7 +595,7 @@ static gs_status open_sdsl_on_device(const char *prefix, int device, gs_index **
     gs_set_error("no such HIP device");
     return GS_ERR_DEVICE;
   }
-  IMP_HIP(hipSetDevice(device));
+  GS_HIP(hipSetDevice(device));
   struct strand_t {
     uint8_t *text = nullptr;
     uint32_t *sa = nullptr;
@@ -634,12 +615,13 @@ static gs_status open_sdsl_on_device(const char *prefix, int device, gs_index **
   }
   /* the reverse index is the FM-index of reverse_complement(forward text) (src/guidescan.cxx:146-157): it must be */
   const uint64_t len = f.n - 1;
-  dbuf d_diff;
-  IMP_HIP(d_diff.get(16));
-  IMP_HIP(hipMemset(d_diff.p, 0, 16));
-  hipLaunchKernelGGL(k_imp_cmp_revcomp, dim3(256u * 16u), dim3(256), 0, 0, (const uint8_t *)f.text, (const uint8_t *)r.text, len, (unsigned long long *)d_diff.p);
+  gs_scratch mem;
+  void *d_diff = nullptr;
+  GS_TRY(mem.get(16, &d_diff));
+  GS_HIP(hipMemset(d_diff, 0, 16));
+  hipLaunchKernelGGL(k_imp_cmp_revcomp, dim3(256u * 16u), dim3(256), 0, 0, (const uint8_t *)f.text, (const uint8_t *)r.text, len, (unsigned long long *)d_diff);
   unsigned long long diff = 0;
-  IMP_HIP(hipMemcpy(&diff, d_diff.p, 8, hipMemcpyDeviceToHost));
+  GS_HIP(hipMemcpy(&diff, d_diff, 8, hipMemcpyDeviceToHost));
   if (diff) {
     gs_set_error(".reverse is not the index of the reverse complement of .forward's text");
     return GS_ERR_FORMAT;
@@ -647,7 +629,7 @@ static gs_status open_sdsl_on_device(const char *prefix, int device, gs_index **
   (void)hipFree(r.text);
   r.text = nullptr;
   std::vector<uint8_t> text(len);
-  IMP_HIP(hipMemcpy(text.data(), f.text, len, hipMemcpyDeviceToHost));
+  GS_HIP(hipMemcpy(text.data(), f.text, len, hipMemcpyDeviceToHost));
   (void)hipFree(f.text);
   f.text = nullptr;
   rc = gs_build_from_device_sa(text.data(), len, f.sa, r.sa, device, out);

@@ -21,6 +21,7 @@
  * plain sorts and scans.
  */
 #include "gs_common.h"
+#include "gs_scratch.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -98,39 +99,11 @@ __global__ void k_sx_apply(const uint32_t *vals, const uint32_t *ngrp, const uin
   rank[s] = ngrp[j];
 }
 
-namespace {
-struct sx_buffers { /* everything the builder allocates: released on every way out */
-  void *p[16] = {nullptr};
-  int n = 0;
-  template <typename T>
-  hipError_t get(T **out, size_t bytes) {
-    void *q = nullptr;
-    *out = nullptr;
-    if (n >= 16) return hipErrorOutOfMemory; /* (the list is sized for what the builder allocates: 13 at most) */
-    const hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-    if (e == hipSuccess) p[n++] = q;
-    *out = (T *)q;
-    return e;
-  }
-  void drop(void *q) {
-    for (int i = 0; i < n; i++)
-      if (p[i] == q) {
-        hipFree(q);
-        p[i] = p[--n];
-        return;
-      }
-  }
-  ~sx_buffers() {
-    for (int i = 0; i < n; i++) hipFree(p[i]);
-  }
-};
-}  // namespace
-
 gs_status gs_device_suffix_array_discarding(const uint8_t *d_text, uint64_t n, uint32_t *d_sa, hipStream_t st, bool debug) {
-  sx_buffers B;
+  gs_scratch B; /* everything the builder allocates: released on every way out */
   /* dense alphabet: as many symbols per first key as 64 bits hold */
   unsigned long long *d_hist = nullptr;
-  GS_HIP(B.get(&d_hist, 256 * 8));
+  GS_TRY(B.get(256 * 8, &d_hist));
   GS_HIP(hipMemsetAsync(d_hist, 0, 256 * 8, st));
   hipLaunchKernelGGL(k_sx_histogram, dim3(1024), dim3(256), 0, st, d_text, n, d_hist);
   unsigned long long hist[256];
@@ -148,13 +121,13 @@ gs_status gs_device_suffix_array_discarding(const uint8_t *d_text, uint64_t n, u
   uint8_t *d_dense = nullptr;
   uint64_t *keys_a = nullptr, *keys_b = nullptr;
   uint32_t *idx_a = nullptr, *rank = nullptr, *head = nullptr;
-  GS_HIP(B.get(&d_dense, 256));
+  GS_TRY(B.get(256, &d_dense));
   GS_HIP(hipMemcpy(d_dense, dense, 256, hipMemcpyHostToDevice));
-  GS_HIP(B.get(&keys_a, 8 * n));
-  GS_HIP(B.get(&keys_b, 8 * n));
-  GS_HIP(B.get(&idx_a, 4 * n));
-  GS_HIP(B.get(&rank, 4 * n));
-  GS_HIP(B.get(&head, 4 * n));
+  GS_TRY(B.get(8 * n, &keys_a));
+  GS_TRY(B.get(8 * n, &keys_b));
+  GS_TRY(B.get(4 * n, &idx_a));
+  GS_TRY(B.get(4 * n, &rank));
+  GS_TRY(B.get(4 * n, &head));
   const unsigned g = sx_blk(n, 256);
   hipLaunchKernelGGL(k_sx_init_keys, dim3(g), dim3(256), 0, st, d_text, n, d_dense, bits, k0, keys_a, idx_a);
   size_t sort_bytes = 0, scan_bytes = 0, xscan_bytes = 0;
@@ -163,7 +136,7 @@ gs_status gs_device_suffix_array_discarding(const uint8_t *d_text, uint64_t n, u
   GS_HIP(rocprim::exclusive_scan(nullptr, xscan_bytes, head, head, 0u, n, rocprim::plus<uint32_t>(), st));
   void *tmp = nullptr;
   const size_t tmp_bytes = std::max(sort_bytes, std::max(scan_bytes, xscan_bytes));
-  GS_HIP(B.get(&tmp, tmp_bytes));
+  GS_TRY(B.get(tmp_bytes, &tmp));
   size_t sb = tmp_bytes;
   /* round 0, all rows: sort by the first k0 symbols; groups, ranks */
   GS_HIP(rocprim::radix_sort_pairs(tmp, sb, keys_a, keys_b, idx_a, d_sa, n, 0, bits * k0, st));
@@ -184,7 +157,7 @@ gs_status gs_device_suffix_array_discarding(const uint8_t *d_text, uint64_t n, u
   if (debug) fprintf(stderr, "[gs] suffix array: %llu rows, %u symbols per first key, %llu rows in groups with company\n", (unsigned long long)n, k0, (unsigned long long)n_act);
   if (n_act == 0) return GS_OK;
   uint32_t *pos = nullptr, *pos2 = nullptr;
-  GS_HIP(B.get(&pos, 4 * n_act));
+  GS_TRY(B.get(4 * n_act, &pos));
   hipLaunchKernelGGL(k_sx_compact, dim3(g), dim3(256), 0, st, flag, place, (const uint32_t *)nullptr, n, pos);
   GS_HIP(hipStreamSynchronize(st));
   /* the arrays of the rows in play take the place of the arrays of all rows */
@@ -194,14 +167,14 @@ gs_status gs_device_suffix_array_discarding(const uint8_t *d_text, uint64_t n, u
   B.drop(head);
   uint64_t *keys = nullptr, *keys2 = nullptr;
   uint32_t *vals = nullptr, *vals2 = nullptr, *ngrp = nullptr, *cflag = nullptr, *cplace = nullptr;
-  GS_HIP(B.get(&keys, 8 * n_act));
-  GS_HIP(B.get(&keys2, 8 * n_act));
-  GS_HIP(B.get(&vals, 4 * n_act));
-  GS_HIP(B.get(&vals2, 4 * n_act));
-  GS_HIP(B.get(&ngrp, 4 * n_act));
-  GS_HIP(B.get(&cflag, 4 * n_act));
-  GS_HIP(B.get(&cplace, 4 * n_act));
-  GS_HIP(B.get(&pos2, 4 * n_act));
+  GS_TRY(B.get(8 * n_act, &keys));
+  GS_TRY(B.get(8 * n_act, &keys2));
+  GS_TRY(B.get(4 * n_act, &vals));
+  GS_TRY(B.get(4 * n_act, &vals2));
+  GS_TRY(B.get(4 * n_act, &ngrp));
+  GS_TRY(B.get(4 * n_act, &cflag));
+  GS_TRY(B.get(4 * n_act, &cplace));
+  GS_TRY(B.get(4 * n_act, &pos2));
   uint32_t rounds = 0;
   for (uint64_t h = k0; n_act != 0; h *= 2) {
     if (h >= 2 * n) {

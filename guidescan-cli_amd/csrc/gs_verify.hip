@@ -11,6 +11,7 @@
  * divsufsort), checked there by sdsl/test/csa_byte_test.cpp on small texts.
  */
 #include "gs_device.h"
+#include "gs_scratch.h"
 
 #include <algorithm>
 
@@ -63,27 +64,17 @@ __device__ __forceinline__ uint64_t v_run_left(const gs_vrun *runs, uint32_t nru
  * What a suffix array that did not come from this library's own sort is put through before any table is
  * derived from it (gs_index_open_sa, gs_index_build_with_sa): the builders read text[sa[r] - j] unchecked. */
 gs_status gs_count_bad_sa_rows(const uint32_t *d_sa, uint64_t n, hipStream_t st, uint64_t *bad) {
+  gs_scratch mem;
   uint32_t *bitmap = nullptr;
-  unsigned long long *d_bad = nullptr;
   const size_t words = (size_t)((n + 31) / 32);
-  if (hipMalloc(&bitmap, 4 * words + 16) != hipSuccess) { /* the bitmap, then the 8-byte aligned counter */
-    (void)hipGetLastError();
-    return GS_ERR_NOMEM;
-  }
-  d_bad = (unsigned long long *)(bitmap + ((words + 1) & ~(size_t)1));
-  hipError_t e = hipMemsetAsync(bitmap, 0, 4 * words + 16, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_v_permutation, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_sa, n, bitmap, d_bad);
-    unsigned long long h = 0;
-    e = hipMemcpyAsync(&h, d_bad, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    *bad = h;
-  }
-  hipFree(bitmap);
-  if (e != hipSuccess) {
-    gs_set_error(std::string("suffix-array check: ") + hipGetErrorString(e));
-    return GS_ERR_DEVICE;
-  }
+  GS_TRY(mem.get(4 * words + 16, &bitmap)); /* the bitmap, then the 8-byte aligned counter */
+  unsigned long long *d_bad = (unsigned long long *)(bitmap + ((words + 1) & ~(size_t)1));
+  GS_HIP(hipMemsetAsync(bitmap, 0, 4 * words + 16, st));
+  hipLaunchKernelGGL(k_v_permutation, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_sa, n, bitmap, d_bad);
+  unsigned long long h = 0;
+  GS_HIP(hipMemcpyAsync(&h, d_bad, 8, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipStreamSynchronize(st));
+  *bad = h;
   return GS_OK;
 }
 
@@ -198,22 +189,20 @@ extern "C" gs_status gs_index_verify_sa(gs_index *ix, int strand, const uint8_t 
   const uint64_t n = s.n;
   memset(rep, 0, sizeof(*rep));
   rep->rows = n;
-  struct dbuf {
-    void *p = nullptr;
-    ~dbuf() {
-      if (p) hipFree(p);
-    }
-  } d_text, d_tmp, d_bitmap, d_out, d_runs;
-  GS_HIP(hipMalloc(&d_text.p, n));
+  gs_scratch mem;
+  uint8_t *d_text = nullptr, *d_tmp = nullptr;
+  gs_vrun *d_runs = nullptr;
+  uint32_t *d_bitmap = nullptr;
+  unsigned long long *out = nullptr;
+  GS_TRY(mem.get(n, &d_text));
   if (strand == 0) {
-    GS_HIP(hipMemcpy(d_text.p, text, len, hipMemcpyHostToDevice));
+    GS_HIP(hipMemcpy(d_text, text, len, hipMemcpyHostToDevice));
   } else {
-    GS_HIP(hipMalloc(&d_tmp.p, len));
-    GS_HIP(hipMemcpy(d_tmp.p, text, len, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_v_revcomp, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, 0, (const uint8_t *)d_tmp.p,
-                       (uint8_t *)d_text.p, len);
+    GS_TRY(mem.get(len, &d_tmp));
+    GS_HIP(hipMemcpy(d_tmp, text, len, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_v_revcomp, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, 0, (const uint8_t *)d_tmp, d_text, len);
   }
-  GS_HIP(hipMemset((uint8_t *)d_text.p + len, 0, 1));
+  GS_HIP(hipMemset(d_text + len, 0, 1));
   /* N runs of this strand's text: the forward runs, mirrored for the reverse strand */
   std::vector<gs_vrun> runs;
   for (const gs_nrun &r : ix->nruns_text) {
@@ -229,24 +218,22 @@ extern "C" gs_status gs_index_verify_sa(gs_index *ix, int strand, const uint8_t 
   }
   std::sort(runs.begin(), runs.end(), [](const gs_vrun &a, const gs_vrun &b) { return a.start < b.start; });
   if (!runs.empty()) {
-    GS_HIP(hipMalloc(&d_runs.p, sizeof(gs_vrun) * runs.size()));
-    GS_HIP(hipMemcpy(d_runs.p, runs.data(), sizeof(gs_vrun) * runs.size(), hipMemcpyHostToDevice));
+    GS_TRY(mem.get(sizeof(gs_vrun) * runs.size(), &d_runs));
+    GS_HIP(hipMemcpy(d_runs, runs.data(), sizeof(gs_vrun) * runs.size(), hipMemcpyHostToDevice));
   }
   const size_t words = (size_t)((n + 31) / 32);
-  GS_HIP(hipMalloc(&d_bitmap.p, 4 * words));
-  GS_HIP(hipMemset(d_bitmap.p, 0, 4 * words));
-  GS_HIP(hipMalloc(&d_out.p, 64));
-  GS_HIP(hipMemset(d_out.p, 0, 64));
-  unsigned long long *out = (unsigned long long *)d_out.p;
-  hipLaunchKernelGGL(k_v_permutation, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const uint32_t *)s.sa, n,
-                     (uint32_t *)d_bitmap.p, out + 3);
+  GS_TRY(mem.get(4 * words, &d_bitmap));
+  GS_HIP(hipMemset(d_bitmap, 0, 4 * words));
+  GS_TRY(mem.get(64, &out));
+  GS_HIP(hipMemset(out, 0, 64));
+  hipLaunchKernelGGL(k_v_permutation, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const uint32_t *)s.sa, n, d_bitmap, out + 3);
   if (n_samples == GS_VERIFY_ALL_ROWS) {
     if (!s.isa) {
       gs_set_error("gs_index_verify_sa: the check of every row reads the inverse suffix array, which this index was built without");
       return GS_ERR_UNSUPPORTED;
     }
     gs_vfull_args a;
-    a.text = (const uint8_t *)d_text.p;
+    a.text = d_text;
     a.sa = (const uint32_t *)s.sa;
     a.isa = (const uint32_t *)s.isa;
     a.blocks = (const uint4 *)s.blocks;
@@ -267,10 +254,10 @@ extern "C" gs_status gs_index_verify_sa(gs_index *ix, int strand, const uint8_t 
   if (n_samples > n - 1) n_samples = n - 1;
   if (n_samples) {
     gs_vorder_args a;
-    a.text = (const uint8_t *)d_text.p;
+    a.text = d_text;
     a.sa = (const uint32_t *)s.sa;
     a.blocks = (const uint4 *)s.blocks;
-    a.runs = (const gs_vrun *)d_runs.p;
+    a.runs = d_runs;
     a.out = out;
     a.n = n;
     a.samples = n_samples;
