@@ -336,6 +336,7 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_kmers_concat", "gs_decoder_open", "gs_decoder_close", "gs_decode_records", "gs_decode_records_device",
            "gs_decode_sam", "gs_debug_repr_doubles", "gs_debug_decode_tables",
            "gs_index_last_spaced", "gs_debug_seed_recipes_a8", "gs_debug_spaced_rows",
+           "gs_debug_seed_probes", "gs_debug_seed_path", "gs_debug_rot_index",
            "gs_debug_bulge_last", "gs_debug_bulge_seeds", "gs_debug_bulge_verify",
            "gs_bgzf_compress_device", "gs_bgzf_compress", "gs_debug_huffman_lengths", "gs_debug_sp_float",
            "gs_bgzf_inflate", "gs_bgzf_inflate_device", "gs_bgzf_inflate_base", "gs_debug_inflate_member", "gs_debug_bgzf_members",
@@ -433,6 +434,44 @@ def seed_recipes_a8(k, m, n_x, astar, trimmed=False):
     out = np.zeros(int(n.value), dtype=np.uint64)
     _check(L_.gs_debug_seed_recipes_a8(k, m, n_x, a, 1 if trimmed else 0, out.ctypes.data, out.shape[0], C.byref(n)))
     return out
+
+
+def seed_probes(k, L, P, m, n_x, astar, side, rot_first=31):
+    """the probe list the seeding launches read beside a batch shape's recipes (gs_debug_seed_probes; host only), an (n, 2)
+    uint32 array in the recipes' order.  side 0: the other strand's share (deep tables; the order of seed_recipes(...,
+    deep=True)[2]); side 1 / 2: this strand's, whole / trimmed (the order of seed_recipes_a8), through a PAM-pair table whose
+    rotated copies start at step rot_first (31: none)"""
+    L_ = lib()
+    L_.gs_debug_seed_probes.restype = C.c_int
+    L_.gs_debug_seed_probes.argtypes = [C.c_uint32] * 5 + [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    a = (C.c_uint32 * 8)(*(list(astar) + [15] * 8)[:8])
+    n = C.c_uint64()
+    _check(L_.gs_debug_seed_probes(k, L, P, m, n_x, a, side, rot_first, None, 0, C.byref(n)))
+    out = np.zeros((int(n.value), 2), dtype=np.uint32)
+    _check(L_.gs_debug_seed_probes(k, L, P, m, n_x, a, side, rot_first, out.ctypes.data, out.shape[0], C.byref(n)))
+    return out
+
+
+def seed_path(q: int, word: int, L: int, P: int, nst: int, side_b: bool = False, sid: int = 0, pams=(0, 0, 0, 0)):
+    """what the seeding launches make of one recipe word for the packed guide q (gs_debug_seed_path; host only):
+    (the seed's path word, the recipe's xor on a table index of nst symbols)"""
+    L_ = lib()
+    L_.gs_debug_seed_path.restype = C.c_int
+    L_.gs_debug_seed_path.argtypes = [C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_uint32] * 5 + [C.c_void_p]
+    pam = (C.c_uint32 * 4)(*(list(pams) + [0] * 4)[:4])
+    out = (C.c_uint64 * 2)()
+    _check(L_.gs_debug_seed_path(q, pam, int(word), sid, 1 if side_b else 0, L, P, nst, out))
+    return int(out[0]), int(out[1])
+
+
+def rot_index(pidx: int, k: int, rs: int) -> int:
+    """index pidx of a depth-k table as the copy rotated at consumption step rs holds it (gs_debug_rot_index; host only)"""
+    L_ = lib()
+    L_.gs_debug_rot_index.restype = C.c_int
+    L_.gs_debug_rot_index.argtypes = [C.c_uint32] * 3 + [C.c_void_p]
+    out = C.c_uint32()
+    _check(L_.gs_debug_rot_index(pidx, k, rs, C.byref(out)))
+    return int(out.value)
 
 
 def guide_descriptor(q: int, pams, L: int, P: int, k: int, x_len: int, codes=(0, 0xFFFFFFFF), n_pt: int = 1, valid: bool = True):

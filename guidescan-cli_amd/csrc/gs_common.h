@@ -162,6 +162,16 @@ struct gs_recipe_set {
   uint32_t n_full = 0, n_a = 0, n_b = 0, n_a8 = 0; /* full | a | b | a as read through PAM-pair tables */
   uint32_t n_a8s = 0; /* | the same without the class (no substitution in X, the whole budget in O): the spaced tables' share */
   uint32_t a_rot_first = 31; /* lowest consumption step whose rotated copy the PAM-pair list reads (31: none) */
+  /* the seeding launches' probe lists (gs_kernels.h: gs_probe_b, gs_probe_a), eight bytes per recipe: prb_b beside the b
+   * share; prb_a[] beside both a8 lists, one per value of a PAM-pair table's rot_first the set has met (two table slots:
+   * two values at a time).  host_ba: the b | a8 | trimmed a8 words they are built from */
+  gs_buffer prb_b;
+  struct {
+    gs_buffer buf;
+    uint32_t rot_first = 31;
+    bool valid = false;
+  } prb_a[2];
+  std::vector<uint64_t> host_ba;
 };
 
 struct gs_index {

@@ -901,6 +901,7 @@ static gs_status launch_search(batch &b, const search_pass &p, gs_search_args &s
        * a piece of a table are then in flight together */
       sb.seed_opt = b.sw.seed_opt;
       sb.take = b.sw.seed_take;
+      if (r2 == GS_OK) r2 = gs_probes_attach(ix, sb, st); /* the probe lists of the recipes, for the copies sb.pt[] hold */
       if (r2 == GS_OK) r2 = gs_seed_launch(sb, k.seed_grid, b.count_req, st);
       if (r2 != GS_OK) return r2;
     } else if (k.spec)
@@ -1071,7 +1072,7 @@ static gs_status run_search(batch &b, const search_pass &p, unsigned long long h
   const uint32_t *d_shctl = sa.shq_ctl;
   k.seed_grid = 0;
   if (k.f.seed_form) {
-    const size_t lds_seed = sizeof(uint4) * (VQ_CAP + 32 + 24 + 6) * SEARCH_WAVES;
+    const size_t lds_seed = sizeof(uint4) * SEED_LDS * SEARCH_WAVES;
     k.seed_grid = (uint32_t)b.cus * std::min<uint32_t>((uint32_t)(160u * 1024u / lds_seed), GS_WAVES_EU_SEED);
     if (k.seed_grid > need) k.seed_grid = need;
   }

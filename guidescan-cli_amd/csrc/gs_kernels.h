@@ -103,6 +103,10 @@ struct gs_search_args {
    * variant are one 128-byte block, so the class with one substitution left needs no rotated copy) */
   const uint2 *rec_a8;
   uint32_t n_rec_a8;
+  /* the seeding launches' probe lists (gs_recipes.hip: gs_probes_attach), eight bytes per recipe in the order of rec_b /
+   * rec_a8: what a probe of that recipe needs, for every guide alike (gs_probe_b, gs_probe_a).  prb_a[slot]: the list for
+   * the rotated copies that PAM-pair table slot holds */
+  const uint2 *prb_b, *prb_a[2];
   /* PAM-pair tables (gs_pairtab.hip): this strand's seeds of an item whose PAM patterns all end (in
    * consumption order) in one of these pairs of concrete bases are looked up among the rows that
    * have that pair in place - a sixteenth of the genome's rows - instead of all of them */
@@ -231,6 +235,77 @@ __device__ __forceinline__ uint4 ld16_agent(const uint4 *p) {
 }
 #define DSC_LO 27u  /* descriptor.y bits 29:27: fewest substitutions allowed among the remaining guide symbols */
 #define DSC_EXC 30u /* descriptor.y bit 30: the interval holds exception rows (gs_strand_dev::exc_row) */
+
+/* ---- the seeding launches (gs_seed.hip) read a recipe's digit d at a step whose guide symbol is qc as "the base
+ * qc ^ (d + 1)" (k_search_body: "the d-th other base counted from qc").  Under this rule what a substitution does to a
+ * table index, ((d + 1) & 3) << (2 x its place), does not depend on the guide, so a recipe's whole effect on the index is one
+ * constant: its DELTA.  The recipe lists enumerate all three digits at every substituted step, whatever else a recipe
+ * says depends on its steps only: both rules name the same set of seeds per item.  One function each for the device and
+ * the host (gs_recipes.hip builds the probe lists with them, tests/test_seed_probes.py pins them). ---- */
+#define SEED_VQ VQ_CAP
+#define SEED_COPIES 16u /* copy table of an item: the plain PAM-pair table + its rotated copies (steps rot_first .. k-3, k <= 16) */
+#define SEED_LDS (SEED_VQ + 32 + SEED_COPIES + 6) /* uint4 per wave: queue, owner markers, copy table, state (24 words) */
+#define SEED_PB 7u
+#define SEED_PSG (50u + SEED_PB) /* path bit of guide symbol 0's code; symbol t: SEED_PSG - 2 t */
+#define SEED_PSP (49u + SEED_PB) /* the PAM's codes lie below the guide's: symbol u at SEED_PSP - 2 L - 3 u */
+/* a recipe's delta on an index of nst symbols whose step s lies at bits 2 (nst - 1 - s): unused fields hold "step 0, digit 3" = 0 */
+__host__ __device__ inline uint32_t gs_recipe_delta(const uint64_t w, const uint32_t nst) {
+  uint32_t delta = 0;
+  uint64_t f = w >> 12;
+  for (uint32_t i = 0; i < 7u; ++i) {
+    const uint32_t fld = (uint32_t)f & 127u, s = fld >> 2, d = fld & 3u;
+    f >>= 7;
+    if (s < nst) delta ^= ((d + 1u) & 3u) << (2u * (nst - 1u - s));
+  }
+  return delta;
+}
+/* the index of k-mer `pidx` in the copy rotated at step rs: that step's symbol and everything after it swap places.  A
+ * permutation of the index bits, hence linear over xor: gs_rot_index(a ^ b) = gs_rot_index(a) ^ gs_rot_index(b) */
+__host__ __device__ inline uint32_t gs_rot_index(const uint32_t pidx, const uint32_t k, const uint32_t rs) {
+  const uint32_t sh = 2u * (k - 1u - rs);
+  const uint32_t top = sh + 2u >= 32u ? 0u : (pidx >> (sh + 2u)) << (sh + 2u);
+  return top | ((pidx & ((1u << sh) - 1u)) << 2) | ((pidx >> sh) & 3u);
+}
+/* the probe of recipe w on the other strand's side (deep tables, nst = L - x_len index symbols):
+ * {delta on pidxg, the queue meta the recipe alone decides: substitutions << 14 | lo << DSC_LO, and the substitutions again in bits 2:0} */
+__host__ __device__ inline uint2 gs_probe_b(const uint64_t w, const uint32_t nst) {
+  const uint32_t jb = (uint32_t)w & 7u, lo = (uint32_t)(w >> 3) & 7u;
+  return make_uint2(gs_recipe_delta(w, nst), (jb << 14) | (lo << DSC_LO) | jb);
+}
+/* ... and on this strand's side, through a PAM-pair table whose rotated copies start at step rot_first (31: none): copy c = 0
+ * is the plain table, c >= 1 the copy of step rot_first + c - 1.  {delta as copy c indexes it, substitutions << 14 | c << 4 |
+ * substitutions}: bits 11:4 are the byte offset of the copy's entry in the item's copy table */
+__host__ __device__ inline uint2 gs_probe_a(const uint64_t w, const uint32_t k, const uint32_t rot_first) {
+  const uint32_t kk = (uint32_t)w & 7u, rs = (uint32_t)(w >> 7) & 31u;
+  const bool rot = ((uint32_t)w & 64u) != 0u && rs >= rot_first && rs + 2u < k;
+  const uint32_t delta = gs_recipe_delta(w, k);
+  return make_uint2(rot ? gs_rot_index(delta, k, rs) : delta, (kk << 14) | ((rot ? rs - rot_first + 1u : 0u) << 4) | kk);
+}
+/* the path of a seed: the substitutions of its recipe as codes at their guide positions (index.hpp:230-247: the text
+ * base's place among the three other bases), on the other strand's side (side_b; sid carries the base under the N in bits
+ * 25:24 and the pattern in 27:26) also the pattern's fixed PAM symbols and the base the deep table's entry stands for */
+__host__ __device__ inline uint64_t gs_seed_path(const uint64_t w, const uint32_t sid, const bool side_b, const uint64_t q, const uint32_t L,
+                                                 const uint32_t P, const uint32_t pam0, const uint32_t pam1, const uint32_t pam2,
+                                                 const uint32_t pam3) {
+  const uint32_t n = (uint32_t)w & 7u;
+  uint64_t f = w >> 12;
+  uint64_t path = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t fld = (uint32_t)f & 127u, s = fld >> 2, d = fld & 3u;
+    f >>= 7;
+    const uint32_t t = side_b ? L - 1u - s : s;
+    const uint32_t qc = (uint32_t)(q >> (2u * t)) & 3u;
+    const uint32_t sym = qc ^ ((d + 1u) & 3u);
+    path |= (uint64_t)(1u + sym - (sym > qc ? 1u : 0u)) << (SEED_PSG - 2u * t);
+  }
+  if (side_b) {
+    const uint32_t bx = (sid >> 24) & 3u, pj = (sid >> 26) & 3u;
+    const uint32_t pw = pj == 0 ? pam0 : pj == 1 ? pam1 : pj == 2 ? pam2 : pam3;
+    path |= (uint64_t)(bx != 0u ? 3u - bx : 4u) << (SEED_PSP - 2u * L);
+    for (uint32_t u = 1; u < P; ++u) path |= (uint64_t)(((pw >> (3u * u)) & 7u) < 3u ? ((pw >> (3u * u)) & 7u) : 4u) << (SEED_PSP - 2u * L - 3u * u);
+  }
+  return path;
+}
 
 #define VERIFY_MAX_DEFAULT 1023u
 #define DTAB 88u /* per-item substitution table: 4 entries per step of this strand's k-mer (k <= 16) or per
@@ -472,3 +547,6 @@ void gs_choose_astar(uint32_t m, uint32_t nX, uint32_t nO, uint32_t nR, double e
                      double verify_b = 1.9);
 gs_status gs_recipes_for(gs_index *ix, uint32_t L, uint32_t P, uint32_t m, uint32_t v_rem, const uint32_t *astar, bool deep,
                          hipStream_t st);
+/* the probe lists of the current recipe set for the seeding launches of `sa` (sa.prb_b, sa.prb_a[]): this strand's per
+ * table slot, for the rotated copies sa.pt[slot] holds - built and kept the first time a set meets that value */
+gs_status gs_probes_attach(gs_index *ix, gs_search_args &sa, hipStream_t st);

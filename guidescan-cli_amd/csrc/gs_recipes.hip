@@ -262,6 +262,17 @@ gs_status gs_recipes_for(gs_index *ix, uint32_t L, uint32_t P, uint32_t m, uint3
   R.a_rot_first = 31; /* of the list read through PAM-pair tables */
   for (size_t i = n_full + n_a + n_b; i < n_full + n_a + n_b + n_a8; i++)
     if (all[i] & 64u) R.a_rot_first = std::min(R.a_rot_first, (uint32_t)(all[i] >> 7) & 31u);
+  /* the probe lists of the seeding launches: the other strand's here, this strand's when a batch attaches them (they depend
+   * on the rotated copies its PAM-pair tables hold) */
+  R.host_ba.assign(all.begin() + (n_full + n_a), all.end());
+  for (auto &pa : R.prb_a) pa.valid = false;
+  if (n_b) {
+    std::vector<uint2> pb(n_b);
+    for (size_t i = 0; i < n_b; i++) pb[i] = gs_probe_b(R.host_ba[i], L - v_rem);
+    if ((rc = gs_reserve(R.prb_b, 8 * n_b + 64)) != GS_OK) return rc;
+    GS_HIP(hipMemcpyAsync(R.prb_b.p, pb.data(), 8 * n_b, hipMemcpyHostToDevice, st));
+    GS_HIP(hipStreamSynchronize(st)); /* `pb` is a local */
+  }
   R.key[0] = key[0];
   R.key[1] = key[1];
   R.valid = true;
@@ -271,3 +282,77 @@ gs_status gs_recipes_for(gs_index *ix, uint32_t L, uint32_t P, uint32_t m, uint3
   return GS_OK;
 }
 
+gs_status gs_probes_attach(gs_index *ix, gs_search_args &sa, hipStream_t st) {
+  gs_recipe_set &R = ix->rec[ix->rec_cur];
+  sa.prb_b = nullptr;
+  sa.prb_a[0] = sa.prb_a[1] = nullptr;
+  if (!R.valid || !sa.bidir || R.host_ba.size() != (size_t)R.n_b + R.n_a8 + R.n_a8s) return GS_ERR_ARG;
+  const uint2 *a8 = (const uint2 *)R.buf.p + R.n_full + R.n_a + R.n_b;
+  const size_t off = sa.rec_a8 == a8 ? 0 : R.n_a8; /* (run_search: the list without the spaced tables' class lies behind the whole one) */
+  if (sa.rec_a8 != a8 + off || sa.rec_b != a8 - R.n_b) return GS_ERR_ARG;
+  sa.prb_b = (const uint2 *)R.prb_b.p;
+  const size_t n_a = (size_t)R.n_a8 + R.n_a8s;
+  int used = -1;
+  for (uint32_t i = 0; i < sa.n_pt && i < 2u; i++) {
+    const uint32_t rf = sa.pt[i][0].rot_first;
+    if (sa.pt[i][1].rot_first != rf) return GS_ERR_ARG; /* (gs_pairtab_ensure builds both strands' tables alike) */
+    int e = -1;
+    for (int j = 0; j < 2; j++)
+      if (R.prb_a[j].valid && R.prb_a[j].rot_first == rf) e = j;
+    if (e < 0) {
+      e = used == 0 ? 1 : used == 1 ? 0 : !R.prb_a[0].valid ? 0 : !R.prb_a[1].valid ? 1 : 0;
+      std::vector<uint2> pa(n_a);
+      for (size_t r = 0; r < n_a; r++) pa[r] = gs_probe_a(R.host_ba[R.n_b + r], sa.pt_k, rf);
+      R.prb_a[e].valid = false;
+      const gs_status rc = gs_reserve(R.prb_a[e].buf, 8 * n_a + 64);
+      if (rc != GS_OK) return rc;
+      GS_HIP(hipMemcpyAsync(R.prb_a[e].buf.p, pa.data(), 8 * n_a, hipMemcpyHostToDevice, st));
+      GS_HIP(hipStreamSynchronize(st)); /* `pa` is a local */
+      R.prb_a[e].rot_first = rf;
+      R.prb_a[e].valid = true;
+    }
+    used = e;
+    sa.prb_a[i] = (const uint2 *)R.prb_a[e].buf.p + off;
+  }
+  return GS_OK;
+}
+
+/* host only: the probe list of a batch shape's recipes - side 0: the other strand's (deep tables), side 1 / 2: this strand's
+ * through PAM-pair tables whose rotated copies start at step rot_first, whole / without the spaced tables' class - as pairs of
+ * words, in the order of gs_debug_seed_recipes' third list / gs_debug_seed_recipes_a8's */
+extern "C" gs_status gs_debug_seed_probes(uint32_t k, uint32_t L, uint32_t P, uint32_t m, uint32_t n_x, const uint32_t *astar, uint32_t side,
+                                          uint32_t rot_first, uint32_t *out, uint64_t cap, uint64_t *count) {
+  if (k < 4 || k > 16 || L < k || L > 31 || m > 7 || n_x + 1 > k || !astar || !count || side > 2) return GS_ERR_ARG;
+  try {
+    std::vector<uint64_t> all;
+    if (side == 0)
+      build_recipes_b(all, k, L, P, m, n_x, astar, true, true);
+    else
+      build_recipes_a(all, k, m, n_x, astar, true, true, side == 2);
+    *count = all.size();
+    for (uint64_t i = 0; i < all.size() && i < cap && out; i++) {
+      const uint2 p = side == 0 ? gs_probe_b(all[i], L - n_x) : gs_probe_a(all[i], k, rot_first);
+      out[2 * i] = p.x;
+      out[2 * i + 1] = p.y;
+    }
+  } catch (const std::bad_alloc &) {
+    return GS_ERR_NOMEM;
+  }
+  return GS_OK;
+}
+/* host only: what the seeding launches make of one recipe word for one packed guide - out[0] the seed's path (sid: the
+ * recipe's number, on the other strand's side with the base under the N in bits 25:24 and the pattern in 27:26), out[1]
+ * the recipe's delta on an index of nst symbols */
+extern "C" gs_status gs_debug_seed_path(uint64_t q, const uint32_t pam[4], uint64_t word, uint32_t sid, uint32_t side_b, uint32_t L, uint32_t P,
+                                        uint32_t nst, uint64_t out[2]) {
+  if (!pam || !out || L < 1 || L > 31 || P > 8 || nst < 1 || nst > 16) return GS_ERR_ARG;
+  out[0] = gs_seed_path(word, sid, side_b != 0, q, L, P, pam[0], pam[1], pam[2], pam[3]);
+  out[1] = gs_recipe_delta(word, nst);
+  return GS_OK;
+}
+/* host only: index `pidx` of a depth-k table as the copy rotated at step rs holds it */
+extern "C" gs_status gs_debug_rot_index(uint32_t pidx, uint32_t k, uint32_t rs, uint32_t *out) {
+  if (!out || k < 2 || k > 16 || rs + 1 > k) return GS_ERR_ARG;
+  *out = gs_rot_index(pidx, k, rs);
+  return GS_OK;
+}

@@ -29,9 +29,6 @@
  */
 #include "gs_kernels.h"
 
-#define SEED_VQ VQ_CAP
-#define SEED_LDS (SEED_VQ + 32 + 24 + 6) /* uint4 per wave: queue, owner markers, substitution table (96 words), state (24 words) */
-
 __device__ __forceinline__ uint32_t seed_xcc_id() {
   /* HW_REG_XCC_ID (20), bits 3:0: the XCD this wave runs on (MI355X_MICROARCH.md, workgroup dispatch) */
   return (uint32_t)__builtin_amdgcn_s_getreg(20 | (0 << 6) | ((4 - 1) << 11)) & 7u;
@@ -256,14 +253,14 @@ gs_status gs_estimate_heavy(gs_index *ix, const gs_guide_rec *guides, uint32_t n
 template <bool CNT, int SIDE>
 __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds) {
   constexpr bool modeB = SIDE == 0;
-  constexpr uint32_t PB = 7u, KSH = 61u, PSG = 50u + PB, PSP = 49u + PB;
+  constexpr uint32_t PB = SEED_PB, KSH = 61u, PSG = SEED_PSG, PSP = SEED_PSP;
   constexpr uint64_t PMASK = (1ull << (52u + PB)) - 1ull;
   const uint32_t lane = lane_id();
   uint4 *const vq = lds;                                   /* queued seeds: {first row, meta, seed number, -} */
   uint2 *const own2 = (uint2 *)(vq + SEED_VQ);              /* owner markers of a pass, two per lane */
   uint32_t *const own = (uint32_t *)own2;
-  uint32_t *const dtab = (uint32_t *)(vq + SEED_VQ + 32);   /* substitution table: entry 4 step + digit = its xor on the table index */
-  uint32_t *const wmisc = dtab + 96;                        /* [0..2] overflow chunks {taken, last, the one before}, [4..11] matches per class, [16..18] chunk reserve */
+  uint4 *const ctab = vq + SEED_VQ + 32;                    /* SIDE 1: the copies of the PAM-pair table in hand: {entries (64-bit address), the item's index as the copy holds it, -} */
+  uint32_t *const wmisc = (uint32_t *)(ctab + SEED_COPIES); /* [0..2] overflow chunks {taken, last, the one before}, [4..11] matches per class, [16..18] chunk reserve */
   const uint32_t L = a.L, P = a.P, m = a.m, k = a.pt_k, sx = a.x_len;
   const bool k_arena = a.arena != nullptr;
   const bool k_append = modeB ? a.append != 0u : true;
@@ -435,24 +432,7 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
      * pattern's fixed PAM symbols and the base the deep table's entry stands for under the N */
     auto seed_path = [&](const uint32_t sid) __attribute__((always_inline)) -> uint64_t {
       const uint2 rc = recs[sid & 0xFFFFFFu];
-      const uint32_t n = rc.x & 7u;
-      uint64_t f = (((uint64_t)rc.y << 32) | rc.x) >> 12;
-      uint64_t path = 0;
-      for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t fld = (uint32_t)f & 127u, s = fld >> 2, d = fld & 3u;
-        f >>= 7;
-        const uint32_t t = modeB ? L - 1u - s : s;
-        const uint32_t qc = (uint32_t)(gr_q >> (2u * t)) & 3u;
-        const uint32_t sym = (qc + 1u + d) & 3u;
-        path |= (uint64_t)(1u + sym - (sym > qc ? 1u : 0u)) << (PSG - 2u * t);
-      }
-      if (modeB) {
-        const uint32_t bx = (sid >> 24) & 3u, pj = (sid >> 26) & 3u;
-        const uint32_t pw = pj == 0 ? gr_pam0 : pj == 1 ? gr_pam1 : pj == 2 ? gr_pam2 : gr_pam3;
-        path |= (uint64_t)(bx != 0u ? 3u - bx : 4u) << (PSP - 2u * L);
-        for (uint32_t u = 1; u < P; ++u) path |= (uint64_t)(((pw >> (3u * u)) & 7u) < 3u ? ((pw >> (3u * u)) & 7u) : 4u) << (PSP - 2u * L - 3u * u);
-      }
-      return path;
+      return gs_seed_path(((uint64_t)rc.y << 32) | rc.x, sid, modeB, gr_q, L, P, gr_pam0, gr_pam1, gr_pam2, gr_pam3);
     };
 
     /* what the rows of this side's seeds are verified against */
@@ -669,31 +649,6 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
         break;
       }
     };
-    /* entry 4 step + digit: what substituting the digit-th other base at that step does to the table index (3: nothing) */
-    auto fill_dtab = [&]() __attribute__((always_inline)) {
-      const uint32_t nst = modeB ? L - sx : k;
-      for (uint32_t e = lane; e < 4u * nst; e += WAVE) {
-        const uint32_t s = e >> 2, d = e & 3u;
-        const uint32_t t = modeB ? L - 1u - s : s;
-        const uint32_t qc = (uint32_t)(gr_q >> (2u * t)) & 3u;
-        const uint32_t sym = (qc + 1u + d) & 3u;
-        dtab[e] = d == 3u ? 0u : (qc ^ sym) << (2u * (nst - 1u - s)); /* (the other strand's k-mer holds the complements: the xor stays) */
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    /* the recipe's substitutions applied to the exact index.  A recipe's unused fields hold 3 = "step 0, digit 3" = nothing
-     * (gs_recipes.hip: recipe_word), so the first three fields are read whatever the recipe's count, side by side; the other
-     * four only by a batch whose budget allows more than three substitutions, in a round some lane needs */
-    auto apply_recipe = [&](const uint2 rc, uint32_t pidx) __attribute__((always_inline)) -> uint32_t {
-      const uint32_t w0 = __builtin_amdgcn_alignbit(rc.y, rc.x, 12); /* fields 0..2: bits 12..32 of the word */
-      pidx ^= dtab[w0 & 127u] ^ dtab[(w0 >> 7) & 127u] ^ dtab[(w0 >> 14) & 127u];
-      if (m > 3u && __ballot((rc.x & 7u) > 3u) != 0ull) {
-        const uint32_t w1 = rc.y >> 1; /* fields 3..6: bits 33..60 */
-        pidx ^= dtab[w1 & 127u] ^ dtab[(w1 >> 7) & 127u] ^ dtab[(w1 >> 14) & 127u] ^ dtab[(w1 >> 21) & 127u];
-      }
-      return pidx;
-    };
     const uint32_t keep = (a.dbg_skip & 3u) ? 0u : 0xFFFFFFFFu; /* (timing experiments: GS_DBG_SKIP = 1, 2 keep no seed) */
 
     if constexpr (modeB) {
@@ -750,9 +705,10 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
        * four entries of one deep-table line ---- */
       const uint32_t pidxg = dp[8], bsel_z = dp[10], bsel_w = dp[11], n_bpairs = (meta >> 5) & 7u;
       const uint32_t nlanes = 4u * nrec;
-      fill_dtab();
+      /* a step: the recipe's probe {xor on the item's index, what the queue keeps of the recipe} (gs_probe_b; a hit reads the recipe itself) */
+      const uint2 *const prb = seed_sgprs(a.prb_b);
       uint2 rc_next = make_uint2(0u, 0u);
-      if (lane < nlanes) rc_next = recs[lane >> 2];
+      if (lane < nlanes) rc_next = prb[lane >> 2];
       for (uint32_t bpj = 0; bpj < npams && !bailed; ++bpj) {
         const uint32_t bslot = (meta >> (8u + bpj)) & 1u, bxset = (meta >> (12u + 4u * bpj)) & 15u;
         const uint4 *bdeep = seed_sgprs(a.pt[bslot][strand ^ 1u].deep);
@@ -763,11 +719,11 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
           {
             const uint32_t nidx = (bc0 + WAVE >= nlanes ? 0u : bc0 + WAVE) + lane;
             rc_next = make_uint2(0u, 0u);
-            if (nidx < nlanes) rc_next = recs[nidx >> 2];
+            if (nidx < nlanes) rc_next = prb[nidx >> 2];
           }
-          count_lines(c_rec, idx < nlanes, recs + ri);
-          const uint32_t jb = rc.x & 7u, lo = (rc.x >> 3) & 7u;
-          const uint32_t pidx = apply_recipe(rc, pidxg);
+          count_lines(c_rec, idx < nlanes, prb + ri);
+          const uint32_t jb = rc.y & 7u;
+          const uint32_t pidx = pidxg ^ rc.x;
           const uint4 *ep = bdeep + ((size_t)pidx << 2) + bx;
           uint4 ent = make_uint4(0u, 0u, 0u, 0u);
           if (act) ent = *ep;
@@ -777,7 +733,7 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
           const uint32_t need = n_bpairs > m - jb ? n_bpairs - (m - jb) : 0u;
           const uint32_t intact = (uint32_t)__popc(ent.z & bsel_z) + (uint32_t)__popc(ent.w & bsel_w);
           const uint32_t y = ((int32_t)ent.y < 0 || intact >= need) ? ent.y & keep : 0u;
-          queue_step(y & 0x7FFFFFFFu, ent.x, (jb << 14) | (lo << DSC_LO) | ((y >> 31) << DSC_EXC), ri | (bx << 24) | (bpj << 26),
+          queue_step(y & 0x7FFFFFFFu, ent.x, (rc.y & ~7u) | ((y >> 31) << DSC_EXC), ri | (bx << 24) | (bpj << 26),
                      bc0 + WAVE >= nlanes && bpj + 1u == npams);
           if (bailed) break;
         }
@@ -804,44 +760,71 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
         }
         if constexpr (CNT) c_tab += (pslots & 1u) + (pslots >> 1);
       }
-      fill_dtab();
-      uint2 rc_ahead = make_uint2(0u, 0u);
-      if (lane < nrec) rc_ahead = recs[lane];
+      /* a step reads entry[copy].index ^ the probe's word of the copy the probe names (gs_probe_a): cheap enough to ask for the
+       * NEXT step's entries before this step's are looked at (their probes two steps ahead) - two table reads in flight per wave */
+      auto step_after = [&](const uint32_t p0) __attribute__((always_inline)) -> uint32_t { return p0 + WAVE >= nrec ? 0u : p0 + WAVE; };
+      auto probe_of = [&](const uint2 *const list, const uint32_t p0) __attribute__((always_inline)) -> uint2 {
+        uint2 r = make_uint2(0u, 0u); /* (lanes beyond the list hold zeros: they load nothing) */
+        if (p0 + lane < nrec) r = list[p0 + lane];
+        return r;
+      };
+      uint2 rc_n1, rc_n2; /* the probes of the step to come and of the one behind it */
+      {
+        const uint2 *const first_list = seed_sgprs(a.prb_a[(pslots & 1u) ? 0u : 1u]);
+        rc_n1 = probe_of(first_list, 0u);
+        rc_n2 = probe_of(nrec > WAVE || pslots != 3u ? first_list : seed_sgprs(a.prb_a[1]), step_after(0u));
+      }
       while (pslots != 0u && !bailed) {
         const uint32_t s = (pslots & 1u) ? 0u : 1u;
         pslots &= ~(1u << s);
         const gs_pairtab_dev &p = a.pt[s][strand];
-        const uint2 *atab8 = seed_sgprs(p.tab), *arot8 = seed_sgprs(p.rot);
-        const uint32_t arot_first = p.rot_first;
+        /* the probe list of this table's copies, and of the table whose pass comes next */
+        const uint2 *const prb = seed_sgprs(a.prb_a[s]);
+        const uint2 *const prb_after = pslots != 0u ? seed_sgprs(a.prb_a[1]) : prb;
+        {
+          /* the copy table: entry c = where copy c's entries lie and the item's own k-mer as that copy indexes it; a probe is
+           * then entry[its copy].index ^ its delta, whatever the copy (rotation is linear over xor) */
+          const uint32_t arot_first = p.rot_first;
+          const uint32_t ncopy = arot_first + 2u < k ? k - 1u - arot_first : 1u;
+          if (lane < ncopy && lane < SEED_COPIES) {
+            const uint2 *base = p.tab;
+            uint32_t pi = pidx0;
+            if (lane != 0u) {
+              base = p.rot + ((size_t)(lane - 1u) << (2u * k));
+              pi = gs_rot_index(pidx0, k, arot_first + lane - 1u);
+            }
+            ctab[lane] = make_uint4((uint32_t)(uintptr_t)base, (uint32_t)((uintptr_t)base >> 32), pi, 0u);
+          }
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
         v16 = seed_sgprs(p.c16);
         vctx = seed_sgprs(p.ctx);
         arow = seed_sgprs(p.rowid);
-        for (uint32_t spos = 0; spos < nrec; spos += WAVE) {
-          const uint32_t l = spos + lane;
-          const bool act = l < nrec;
-          const uint2 rc = rc_ahead; /* (lanes beyond the list hold zeros: they load nothing) */
-          {
-            const uint32_t nl = (spos + WAVE >= nrec ? 0u : spos + WAVE) + lane; /* past the end: the next table's pass */
-            rc_ahead = make_uint2(0u, 0u);
-            if (nl < nrec) rc_ahead = recs[nl];
-          }
-          count_lines(c_rec, act, recs + l);
-          const uint32_t kk = rc.x & 7u;
-          const uint32_t pidx = apply_recipe(rc, pidx0);
-          const uint2 *ep = atab8 + pidx;
-          const uint32_t rs = (rc.x >> 7) & 31u;
-          const bool rot = (rc.x & 64u) != 0u && rs >= arot_first;
-          if (__ballot(rot) != 0ull) {
-            if (rot) {
-              /* the copy rotated at step rs: that step's symbol and everything after it swap places */
-              const uint32_t sh = 2u * (k - 1u - rs);
-              const uint32_t ridx = ((pidx >> (sh + 2u)) << (sh + 2u)) | ((pidx & ((1u << sh) - 1u)) << 2) | ((pidx >> sh) & 3u);
-              ep = arot8 + (((size_t)(rs - arot_first) << (2u * k)) + ridx);
-            }
-          }
+        auto entry_of = [&](const uint32_t p0, const uint2 pr) __attribute__((always_inline)) -> uint2 {
+          const bool act = p0 + lane < nrec;
+          const uint4 cp = *(const uint4 *)((const char *)ctab + (pr.y & 0xF0u));
+          /* (an address that came through LDS: said to be global memory's, or the entry is read with a flat load) */
+          const uint2 *ep = (const uint2 *)(const uint2 __attribute__((address_space(1))) *)(((uint64_t)cp.y << 32) | cp.x) + (cp.z ^ pr.x);
           uint2 e8 = make_uint2(0u, 0u);
           if (act) e8 = *ep;
           count_lines(c_tab, act, ep);
+          return e8;
+        };
+        uint2 e8_n1 = entry_of(0u, rc_n1); /* (a pass's first entries wait for nothing but themselves) */
+        for (uint32_t spos = 0; spos < nrec; spos += WAVE) {
+          const uint32_t l = spos + lane;
+          const bool act = l < nrec, last = spos + WAVE >= nrec;
+          const uint32_t ry = rc_n1.y;
+          const uint2 e8 = e8_n1;
+          rc_n1 = rc_n2; /* (behind a pass's last step: step 0 of the next table's pass) */
+          if (!last) e8_n1 = entry_of(spos + WAVE, rc_n1);
+          {
+            const uint32_t s1 = step_after(spos), s2 = step_after(s1);
+            rc_n2 = probe_of(last || s2 < s1 ? prb_after : prb, s2);
+          }
+          count_lines(c_rec, act, prb + l);
+          const uint32_t kk = ry & 7u;
           uint32_t first = e8.x, ecnt = e8.y & 63u;
           const uint32_t filt = e8.y >> 6, bl = m - kk;
           /* one row: its own context symbols against the query's; several: a query symbol none of the rows shows at its
@@ -857,7 +840,7 @@ __device__ __forceinline__ void k_seed_body(const gs_search_args &a, uint4 *lds)
             if constexpr (CNT) c_isa += (uint32_t)__popcll(__ballot(true));
           }
           const uint32_t rem = hopeless ? 0u : ecnt & keep;
-          queue_step(rem, first, kk << 14, l, spos + WAVE >= nrec);
+          queue_step(rem, first, ry & (7u << 14), l, last);
           if (bailed) break;
         }
       }

@@ -304,6 +304,20 @@ void gs_debug_choose_thresholds(uint32_t m, uint32_t n_x, uint32_t n_o, uint32_t
  * the class "no substitution in X, all m in O", which a spaced table's lookup finds instead. */
 gs_status gs_debug_seed_recipes_a8(uint32_t k, uint32_t m, uint32_t n_x, const uint32_t *astar, uint32_t trimmed, uint64_t *out,
                                    uint64_t cap, uint64_t *count);
+/* The probe lists the two seeding launches read beside those recipes (host only), two words per recipe in the recipes' order.
+ * side 0: the other strand's share through deep tables - {xor on the item's index, substitutions << 14 | lo << 27 |
+ * substitutions}; side 1 / 2: this strand's share, whole / trimmed, through a PAM-pair table whose rotated copies start at
+ * step rot_first (31: none) - {xor on the index as the copy it reads holds it, substitutions << 14 | copy << 4 |
+ * substitutions}, copy 0 = the plain table, copy c = the copy of step rot_first + c - 1. */
+gs_status gs_debug_seed_probes(uint32_t k, uint32_t L, uint32_t P, uint32_t m, uint32_t n_x, const uint32_t *astar, uint32_t side,
+                               uint32_t rot_first, uint32_t *out, uint64_t cap, uint64_t *count);
+/* What the seeding launches make of one recipe word for the packed guide q (host only): out[0] = the seed's path word
+ * (guide symbol t's code at bit 57 - 2 t; on the other strand's side, side_b != 0, sid carries the base under the PAM's N in
+ * bits 25:24 and the pattern's number in 27:26), out[1] = the recipe's xor on a table index of nst symbols. */
+gs_status gs_debug_seed_path(uint64_t q, const uint32_t pam[4], uint64_t word, uint32_t sid, uint32_t side_b, uint32_t L, uint32_t P,
+                             uint32_t nst, uint64_t out[2]);
+/* Index pidx of a depth-k table as the copy rotated at consumption step rs holds it (host only). */
+gs_status gs_debug_rot_index(uint32_t pidx, uint32_t k, uint32_t rs, uint32_t *out);
 /* The rows under `key` (X symbols << 2 |R| | R symbols, both in consumption order) in the spaced table of a PAM-pair table
  * slot and strand, four words per row: {row in the table's row arrays, its O symbols, its row in the strand's suffix array,
  * its context word}; *n = rows under the key (out holds the first cap); info = {1 = the slot has spaced tables, pair code,
