@@ -335,7 +335,7 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_format_device_ids", "gs_enumerate_text_device", "gs_kmers_encode_ids", "gs_kmers_get_ids", "gs_kmers_csv",
            "gs_kmers_concat", "gs_decoder_open", "gs_decoder_close", "gs_decode_records", "gs_decode_records_device",
            "gs_decode_sam", "gs_debug_repr_doubles", "gs_debug_decode_tables",
-           "gs_index_last_spaced", "gs_debug_seed_recipes_a8", "gs_debug_spaced_rows",
+           "gs_index_last_spaced", "gs_debug_seed_recipes_a8", "gs_debug_spaced_rows", "gs_debug_resident",
            "gs_debug_seed_probes", "gs_debug_seed_path", "gs_debug_rot_index",
            "gs_debug_bulge_last", "gs_debug_bulge_seeds", "gs_debug_bulge_verify",
            "gs_bgzf_compress_device", "gs_bgzf_compress", "gs_debug_huffman_lengths", "gs_debug_sp_float",
@@ -1595,6 +1595,15 @@ class GenomeIndex:
                     items_pair_tables=v[7] >> 8, recipe_lines=v[3],
                     slots_per_item=v[13], matches_sum=v[14], matches_max_per_item=v[15],
                     table_lines=v[8], ctx16_lines=v[9], ctx_words=v[10], sa_isa_gathers=v[11], occ_lines=v[12])
+
+    def resident(self):
+        """the arrays the handle keeps on the device and the bytes they count for (gs_debug_resident)"""
+        L_ = lib()
+        L_.gs_debug_resident.restype = C.c_int
+        L_.gs_debug_resident.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_uint64 * 4)()
+        _check(L_.gs_debug_resident(self._h, out))
+        return dict(zip(("strand_arrays", "strand_bytes", "pairtab_arrays", "pairtab_bytes"), (int(x) for x in out)))
 
     def spaced_rows(self, slot, strand, key, cap=4096):
         """the rows under `key` in a slot's spaced table (gs_debug_spaced_rows) -> (rows uint32[n, 4], n under the key, info)"""

@@ -115,15 +115,59 @@ struct gs_strand_dev {
   const uint32_t *C256;
 };
 
+struct gs_buffer {
+  void *p = nullptr;
+  size_t cap = 0;
+};
+
+/* The device arrays a handle keeps between calls (a strand's, a PAM-pair slot's): each with the bytes it counts for in
+ * gs_index_device_bytes - what the fit estimates reckon with, not the allocation's size.  Frees them when it goes.
+ * take(): the array leaves the scratch it was built in (gs_scratch.h), its address goes into `field` of the gs_strand_dev /
+ * gs_pairtab_dev; a null array is no entry.  release(): frees the array `field` names, nulls it, returns its bytes. */
+struct gs_scratch;
+struct gs_resident {
+  gs_resident() = default;
+  gs_resident(gs_resident &&o) noexcept { v.swap(o.v); } /* (moves only: no copies) */
+  gs_resident &operator=(gs_resident &&o) noexcept {
+    clear();
+    v.swap(o.v);
+    return *this;
+  }
+  ~gs_resident() { clear(); }
+  template <class T>
+  void take(gs_scratch &from, const T *&field, const void *q, uint64_t bytes) {
+    adopt(from, q, bytes);
+    field = (const T *)q;
+  }
+  template <class T>
+  uint64_t release(const T *&field) {
+    const uint64_t b = drop(field);
+    field = nullptr;
+    return b;
+  }
+  void clear();
+  uint64_t bytes() const;
+  uint64_t bytes_of(const void *q) const; /* 0: not one of its arrays */
+  uint64_t count() const { return v.size(); }
+
+ private:
+  struct item {
+    const void *p;
+    uint64_t bytes;
+  };
+  std::vector<item> v;
+  void adopt(gs_scratch &from, const void *q, uint64_t bytes);
+  uint64_t drop(const void *q);
+};
+
 struct gs_strand {
-  gs_strand_dev d{};
-  void *blocks = nullptr, *sa = nullptr, *run_start = nullptr, *run_cum = nullptr, *ptab = nullptr, *ctx = nullptr, *ctx16 = nullptr, *ptab_rot = nullptr, *isa = nullptr, *exc_row = nullptr, *exc_sym = nullptr, *xr_start = nullptr, *xr_cum = nullptr, *xr_seg = nullptr, *C256 = nullptr;
+  gs_strand_dev d{}; /* the one record of the arrays' addresses */
+  gs_resident own;   /* ... of who frees them and what they count for */
   bool has_sym[256] = {false}; /* bytes present in this strand's text */
   /* the rotated table copies this strand may hold (gs_strand_rot_ensure builds them on first use): first step, count (0: none), table depth */
   uint32_t rot_plan_first = 31, rot_plan_n = 0, rot_k = 0;
   uint64_t n = 0;
   uint64_t C_acgtn[5] = {0, 0, 0, 0, 0};
-  uint64_t bytes = 0;
 };
 
 /* a maximal run of 'N' bytes in the forward text with the bytes around it (host side; used per
@@ -135,24 +179,20 @@ struct gs_nrun {
   uint8_t right[GS_NRUN_FLANK]; /* text[start+len .. start+len+40) */
 };
 
-struct gs_buffer {
-  void *p = nullptr;
-  size_t cap = 0;
-};
-
 struct gs_pairtab_host {
   bool valid = false;
   uint32_t v_rem = 0, code = 0, rot_first = 31;
   gs_pairtab_dev d[2]{};
-  void *mem[2][8] = {{nullptr}, {nullptr}};
+  gs_resident own;
   bool deep = false;               /* both strands' deep tables exist (PAM length deep_P) */
   uint32_t deep_P = 0, deep_kb = 0;
   bool spaced = false;             /* both strands' spaced tables exist, keyed by the first sp_x and the last sp_g guide symbols */
   uint32_t sp_x = 0, sp_g = 0;
-  uint64_t sp_bytes = 0, sp_rows[2] = {0, 0};
+  uint64_t sp_rows[2] = {0, 0};
+  uint64_t sp_bytes() const { return own.bytes_of(d[0].sp_off) + own.bytes_of(d[0].sp_rows) + own.bytes_of(d[1].sp_off) + own.bytes_of(d[1].sp_rows); }
   uint64_t n_slots[2] = {0, 0};    /* slots of each strand's row arrays (rows + the big entries' header slots) */
   double sp_build_ms = 0;
-  uint64_t bytes = 0, used = 0;
+  uint64_t used = 0;
 };
 
 struct gs_recipe_set {
@@ -340,9 +380,9 @@ size_t gs_buffer_free(gs_buffer &b);
 
 /* GPU suffix array: d_text (n bytes incl. sentinel) -> d_sa (n uint32) */
 gs_status gs_device_suffix_array(const uint8_t *d_text, uint64_t n, uint32_t *d_sa, hipStream_t st);
-/* build the device layout of one strand from device-resident text and SA */
-gs_status gs_strand_from_device(const uint8_t *d_text, uint32_t *d_sa_owned, uint64_t n,
-                                gs_strand *out, hipStream_t st);
+/* build the device layout of one strand from device-resident text and SA; when it succeeds the strand has taken the
+ * suffix array out of sa_mem, otherwise the strand holds nothing */
+gs_status gs_strand_from_device(const uint8_t *d_text, gs_scratch &sa_mem, uint32_t *d_sa, uint64_t n, gs_strand *out, hipStream_t st);
 void gs_strand_free(gs_strand *s);
 /* gs_verify.hip: rows of a device-resident suffix array that are out of range or repeat a value */
 gs_status gs_count_bad_sa_rows(const uint32_t *d_sa, uint64_t n, hipStream_t st, uint64_t *bad);

@@ -5,6 +5,7 @@
  * (and its host side), gs_tileorder.hip.
  */
 #include "gs_kernels.h"
+#include "gs_scratch.h"
 
 /* gs_seed.hip (launched here behind k_prepare; gs_estimate_heavy is its stand-alone form) */
 __global__ void k_estimate_heavy(const gs_guide_rec *guides, uint32_t n, const uint4 *ptab0, const uint4 *ptab1, uint32_t k,
@@ -377,11 +378,11 @@ static gs_status launch_prepare(batch &b) {
    * costing the step a host round trip of their own (25-70 us on this pool's hosts).  Not when the main pass cannot
    * share: the back-off is counted down before it is tested, so from 2 on */
   const uint32_t smin = b.sw.share_min;
-  if (b.n_chunks == 1 && smin != 0 && ix->share_backoff <= 1 && ix->pt_k && ix->strand[0].ptab && ix->strand[1].ptab &&
+  if (b.n_chunks == 1 && smin != 0 && ix->share_backoff <= 1 && ix->pt_k && ix->strand[0].d.ptab && ix->strand[1].d.ptab &&
       !b.sw.no_form_estimate) {
     b.pre_est_ran = true;
     hipLaunchKernelGGL(k_estimate_heavy, dim3((b.n32 + 255) / 256), dim3(256), 0, st, (const gs_guide_rec *)ix->w_grec.p, b.n32,
-                       (const uint4 *)ix->strand[0].ptab, (const uint4 *)ix->strand[1].ptab, ix->pt_k, estimate_thresh(smin),
+                       ix->strand[0].d.ptab, ix->strand[1].d.ptab, ix->pt_k, estimate_thresh(smin),
                        b.d_work + WK_SCRATCH2);
   }
   /* guides the fast path does not encode get empty hit lists and a flag; the batch goes on */
@@ -457,8 +458,8 @@ static gs_status place_pair_tables(batch &b, const uint32_t want[2], uint32_t ma
     GS_HIP(hipMemGetInfo(&free_b, &total_b));
     double reserve = b.sw.pairtab_reserve;
     if (reserve > 0.25 * (double)total_b) reserve = 0.25 * (double)total_b;
-    double room = (double)free_b + (double)ix->pairtab[0].bytes + (double)ix->pairtab[1].bytes - reserve;
-    if (b.sw.has_index_budget) room = std::min(room, b.sw.index_budget - (double)(ix->strand[0].bytes + ix->strand[1].bytes));
+    double room = (double)free_b + (double)ix->pairtab[0].own.bytes() + (double)ix->pairtab[1].own.bytes() - reserve;
+    if (b.sw.has_index_budget) room = std::min(room, b.sw.index_budget - (double)(ix->strand[0].own.bytes() + ix->strand[1].own.bytes()));
     const double one = 2.0 * 8.0 * (double)(1ull << (2 * ix->pt_k)) + 10.0 * 1.5 * ((double)ix->strand[0].n + (double)ix->strand[1].n) / 16.0 +
                        8.0 * (double)(1ull << (2 * ix->pt_k)) + 64e6;
     if (2.0 * one > room) {
@@ -501,8 +502,8 @@ static gs_status seeding_plan(batch &b) {
   gs_status rc;
   const uint32_t L = b.L, P = b.P;
   /* context verification is possible when what remains after the table depth fits ctx[] */
-  if (ix->pt_k >= 4 && ix->pt_k + 1 <= L && !(b.flags & GS_FLAG_FAITHFUL_WALK) && ix->strand[0].ctx &&
-      ix->strand[1].ctx && ix->strand[0].ctx16 && ix->strand[1].ctx16 && L + P - ix->pt_k <= 16)
+  if (ix->pt_k >= 4 && ix->pt_k + 1 <= L && !(b.flags & GS_FLAG_FAITHFUL_WALK) && ix->strand[0].d.ctx &&
+      ix->strand[1].d.ctx && ix->strand[0].d.ctx16 && ix->strand[1].d.ctx16 && L + P - ix->pt_k <= 16)
     b.v_rem = L + P - ix->pt_k;
   if (b.wide_key && b.v_rem == 0) {
     gs_set_error("match sequences beyond 52 key bits (2L+3P > 52) need the table-seeded search: this index's prefix table is too "
@@ -514,7 +515,7 @@ static gs_status seeding_plan(batch &b) {
    * both inverse suffix arrays exist */
   b.table_seeding = ix->pt_k >= 4 && ix->pt_k + 1 <= L && !(b.flags & GS_FLAG_FAITHFUL_WALK);
   const bool two_ok = b.v_rem != 0 && b.m >= 1 && b.v_rem + 1 <= ix->pt_k && P + 1 <= ix->pt_k && ix->pt_k - P <= 21 &&
-                      L <= 31 && ix->strand[0].isa && ix->strand[1].isa && !b.sw.no_bidir;
+                      L <= 31 && ix->strand[0].d.isa && ix->strand[1].d.isa && !b.sw.no_bidir;
   /* the pairs of bases the batch's patterns end in (k_prepare's tally), most frequent first */
   uint32_t want[2] = {16, 16};
   for (uint32_t c = 0; c < 16; c++) {
@@ -1080,7 +1081,7 @@ static gs_status run_search(batch &b, const search_pass &p, unsigned long long h
   if (p.with_arena) { /* (gs_index_last_launch: what the main pass is launched with) */
     const bool seed_launches = k.f.seed_form != 0u && !k.walk && sa.shq == nullptr; /* (launch_search's branch) */
     const unsigned long long ll[8] = {k.walk ? 1u : 0u, k.spec ? 1u : 0u, sa.bdeep, sa.take, seed_launches ? b.sw.seed_take : 0u, sa.n_pt, sa.x_len,
-                                      ix->strand[0].ptab_rot ? ix->strand[0].rot_plan_n : 0u};
+                                      ix->strand[0].d.ptab_rot ? ix->strand[0].rot_plan_n : 0u};
     memcpy(ix->last_launch, ll, sizeof(ll));
   }
   bool spaced = b.spaced_wanted && k.f.seed_form != 0u && !k.walk && sa.shq == nullptr; /* (launch_search's branch: the two seeding launches) */
@@ -1819,14 +1820,13 @@ extern "C" gs_status gs_rank_bwt4(gs_index *ix, int strand, const uint64_t *rows
   GS_HIP(hipSetDevice(ix->device));
   uint64_t *d_rows = nullptr, *d_out = nullptr;
   if (n == 0) return GS_OK;
-  GS_HIP(hipMalloc(&d_rows, 8 * n));
-  GS_HIP(hipMalloc(&d_out, 32 * n));
+  gs_scratch mem;
+  GS_TRY(mem.get(8 * n, &d_rows));
+  GS_TRY(mem.get(32 * n, &d_out));
   GS_HIP(hipMemcpy(d_rows, rows, 8 * n, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_rank4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ix->strand[strand].d,
                      d_rows, n, d_out);
   GS_HIP(hipMemcpy(out, d_out, 32 * n, hipMemcpyDeviceToHost));
-  hipFree(d_rows);
-  hipFree(d_out);
   return GS_OK;
 }
 
@@ -1839,14 +1839,13 @@ extern "C" gs_status gs_resolve(gs_index *ix, int strand, const uint64_t *rows, 
   GS_HIP(hipSetDevice(ix->device));
   uint64_t *d_rows = nullptr, *d_out = nullptr;
   if (n == 0) return GS_OK;
-  GS_HIP(hipMalloc(&d_rows, 8 * n));
-  GS_HIP(hipMalloc(&d_out, 8 * n));
+  gs_scratch mem;
+  GS_TRY(mem.get(8 * n, &d_rows));
+  GS_TRY(mem.get(8 * n, &d_out));
   GS_HIP(hipMemcpy(d_rows, rows, 8 * n, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0,
                      ix->strand[strand].d, d_rows, n, d_out);
   GS_HIP(hipMemcpy(out, d_out, 8 * n, hipMemcpyDeviceToHost));
-  hipFree(d_rows);
-  hipFree(d_out);
   return GS_OK;
 }
 
@@ -1869,12 +1868,9 @@ extern "C" gs_status gs_index_prepare(gs_index *ix, uint64_t n, uint32_t L, cons
   if (n == 0) return GS_OK;
   GS_HIP(hipSetDevice(ix->device));
   uint8_t *d_g = nullptr, *d_p = nullptr;
-  GS_HIP(hipMalloc(&d_g, n * L));
-  if (hipMalloc(&d_p, n * (P ? P : 1u)) != hipSuccess) {
-    (void)hipFree(d_g);
-    (void)hipGetLastError();
-    return GS_ERR_NOMEM;
-  }
+  gs_scratch mem;
+  GS_TRY(mem.get(n * L, &d_g));
+  GS_TRY(mem.get(n * P, &d_p));
   uint4 pat = make_uint4(0u, 0u, 0u, 0u);
   for (uint32_t u = 0; u < P; ++u) (u < 4u ? pat.x : pat.y) |= (uint32_t)(uint8_t)pam[u] << (8u * (u & 3u));
   hipLaunchKernelGGL(k_prepare_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_g, d_p, n, L, P, pat);
@@ -1889,7 +1885,5 @@ extern "C" gs_status gs_index_prepare(gs_index *ix, uint64_t n, uint32_t L, cons
   ix->seen = s_seen;
   ix->shq_packages = s_pk;
   (void)hipDeviceSynchronize();
-  (void)hipFree(d_g);
-  (void)hipFree(d_p);
   return rc;
 }

@@ -354,7 +354,7 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
                  "L+dna_bulges+P<=32");
     return GS_ERR_UNSUPPORTED;
   }
-  if (!ix->strand[0].xr_seg || !ix->strand[1].xr_seg) {
+  if (!ix->strand[0].d.xr_seg || !ix->strand[1].d.xr_seg) {
     gs_set_error("index lacks the per-symbol run lists");
     return GS_ERR_UNSUPPORTED;
   }

@@ -273,6 +273,35 @@ gs_status gs_scratch::get(size_t bytes, void **out) {
 }
 void gs_scratch::keep(const void *q) { p.erase(std::remove(p.begin(), p.end(), q), p.end()); }
 
+/* ---- gs_common.h: gs_resident ---- */
+void gs_resident::adopt(gs_scratch &from, const void *q, uint64_t bytes) {
+  if (!q) return;
+  v.push_back({q, bytes}); /* (before keep: a push_back that throws leaves the array with the scratch) */
+  from.keep(q);
+}
+uint64_t gs_resident::drop(const void *q) {
+  const auto it = std::find_if(v.begin(), v.end(), [&](const item &i) { return i.p == q; });
+  if (it == v.end()) return 0;
+  const uint64_t b = it->bytes;
+  (void)hipFree((void *)q);
+  v.erase(it);
+  return b;
+}
+uint64_t gs_resident::bytes_of(const void *q) const {
+  for (const item &i : v)
+    if (i.p == q) return i.bytes;
+  return 0;
+}
+void gs_resident::clear() {
+  for (const item &i : v) (void)hipFree((void *)i.p);
+  v.clear();
+}
+uint64_t gs_resident::bytes() const {
+  uint64_t b = 0;
+  for (const item &i : v) b += i.bytes;
+  return b;
+}
+
 gs_status gs_events_elapsed(const hipEvent_t *e, const int *from, int n, double *out) {
   for (int i = 0; i < n; i++) {
     float ms = 0;

@@ -132,26 +132,11 @@ __global__ void k_revcomp(const uint8_t *in, uint8_t *out, uint64_t len) {
 static inline unsigned nblk(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 void gs_strand_free(gs_strand *s) {
-  if (s->blocks) hipFree(s->blocks);
-  if (s->sa) hipFree(s->sa);
-  if (s->run_start) hipFree(s->run_start);
-  if (s->run_cum) hipFree(s->run_cum);
-  if (s->ptab) hipFree(s->ptab);
-  if (s->ctx) hipFree(s->ctx);
-  if (s->ctx16) hipFree(s->ctx16);
-  if (s->ptab_rot) hipFree(s->ptab_rot);
-  if (s->isa) hipFree(s->isa);
-  if (s->exc_row) hipFree(s->exc_row);
-  if (s->exc_sym) hipFree(s->exc_sym);
-  if (s->xr_start) hipFree(s->xr_start);
-  if (s->xr_cum) hipFree(s->xr_cum);
-  if (s->xr_seg) hipFree(s->xr_seg);
-  if (s->C256) hipFree(s->C256);
+  s->own.clear();
   *s = gs_strand();
 }
 
-gs_status gs_strand_from_device(const uint8_t *d_text, uint32_t *d_sa_owned, uint64_t n,
-                                gs_strand *out, hipStream_t st) {
+gs_status gs_strand_from_device(const uint8_t *d_text, gs_scratch &sa_mem, uint32_t *d_sa_owned, uint64_t n, gs_strand *out, hipStream_t st) {
   if (n < 2 || n >= (1ull << 32) - 256) {
     gs_set_error("text length must be in [1, 2^32-258]");
     return GS_ERR_UNSUPPORTED;
@@ -161,7 +146,7 @@ gs_status gs_strand_from_device(const uint8_t *d_text, uint32_t *d_sa_owned, uin
   uint4 *blocks = nullptr;
   uint32_t *wcount = nullptr, *wscan = nullptr;
   unsigned long long *d_hist = nullptr;
-  gs_scratch mem; /* the temporaries, and the blocks until the strand has them */
+  gs_scratch mem; /* the temporaries, and every array until the strand has it */
   GS_TRY(mem.get(nblocks * 64, &blocks));
   GS_TRY(mem.get(nwords * 16, &wcount));
   GS_TRY(mem.get(nwords * 16, &wscan));
@@ -251,6 +236,15 @@ gs_status gs_strand_from_device(const uint8_t *d_text, uint32_t *d_sa_owned, uin
   }
   std::vector<uint32_t> cum(starts.size() + 1, 0);
   for (size_t r = 0; r < starts.size(); r++) cum[r + 1] = cum[r] + (ends[r] - starts[r]);
+  /* a host vector's copy in HBM, or nullptr for an empty one */
+  auto upload = [&](const void *h, size_t bytes, void **q) -> gs_status {
+    *q = nullptr;
+    if (!bytes) return GS_OK;
+    GS_TRY(mem.get(bytes, q));
+    GS_HIP(hipMemcpy(*q, h, bytes, hipMemcpyHostToDevice));
+    return GS_OK;
+  };
+  void *xr_seg = nullptr, *C256 = nullptr, *xr_start = nullptr, *xr_cum = nullptr, *run_start = nullptr, *run_cum = nullptr;
   {
     std::vector<uint32_t> xs, xc, c256(256, 0);
     std::vector<uint2> seg(256, make_uint2(0u, 0u));
@@ -268,38 +262,26 @@ gs_status gs_strand_from_device(const uint8_t *d_text, uint32_t *d_sa_owned, uin
       xs.push_back(0xFFFFFFFFu); /* keeps xr_cum[i + 1] valid for the symbol's last run */
       xc.push_back(acc);
     }
-    GS_HIP(hipMalloc(&out->xr_seg, sizeof(uint2) * 256));
-    GS_HIP(hipMalloc(&out->C256, 4 * 256));
-    GS_HIP(hipMemcpy(out->xr_seg, seg.data(), sizeof(uint2) * 256, hipMemcpyHostToDevice));
-    GS_HIP(hipMemcpy(out->C256, c256.data(), 4 * 256, hipMemcpyHostToDevice));
-    if (!xs.empty()) {
-      GS_HIP(hipMalloc(&out->xr_start, 4 * xs.size()));
-      GS_HIP(hipMalloc(&out->xr_cum, 4 * xc.size()));
-      GS_HIP(hipMemcpy(out->xr_start, xs.data(), 4 * xs.size(), hipMemcpyHostToDevice));
-      GS_HIP(hipMemcpy(out->xr_cum, xc.data(), 4 * xc.size(), hipMemcpyHostToDevice));
-    }
-    out->d.xr_start = (const uint32_t *)out->xr_start;
-    out->d.xr_cum = (const uint32_t *)out->xr_cum;
-    out->d.xr_seg = (const uint2 *)out->xr_seg;
-    out->d.C256 = (const uint32_t *)out->C256;
+    GS_TRY(upload(seg.data(), sizeof(uint2) * 256, &xr_seg));
+    GS_TRY(upload(c256.data(), 4 * 256, &C256));
+    GS_TRY(upload(xs.data(), 4 * xs.size(), &xr_start));
+    GS_TRY(upload(xc.data(), 4 * xc.size(), &xr_cum));
   }
-
-  mem.keep(blocks);
-  out->blocks = blocks;
-  out->sa = d_sa_owned;
-  out->n = n;
-  out->bytes = nblocks * 64 + n * 4;
   if (!starts.empty()) {
-    GS_HIP(hipMalloc(&out->run_start, 4 * starts.size()));
-    GS_HIP(hipMalloc(&out->run_cum, 4 * cum.size()));
-    GS_HIP(hipMemcpy(out->run_start, starts.data(), 4 * starts.size(), hipMemcpyHostToDevice));
-    GS_HIP(hipMemcpy(out->run_cum, cum.data(), 4 * cum.size(), hipMemcpyHostToDevice));
+    GS_TRY(upload(starts.data(), 4 * starts.size(), &run_start));
+    GS_TRY(upload(cum.data(), 4 * cum.size(), &run_cum));
   }
+  /* nothing fails from here on: the strand takes the arrays, the suffix array among them */
+  out->n = n;
   gs_strand_dev &d = out->d;
-  d.blocks = blocks;
-  d.sa = d_sa_owned;
-  d.run_start = (const uint32_t *)out->run_start;
-  d.run_cum = (const uint32_t *)out->run_cum;
+  out->own.take(mem, d.blocks, blocks, nblocks * 64);
+  out->own.take(sa_mem, d.sa, d_sa_owned, n * 4);
+  out->own.take(mem, d.xr_seg, xr_seg, 0);
+  out->own.take(mem, d.C256, C256, 0);
+  out->own.take(mem, d.xr_start, xr_start, 0);
+  out->own.take(mem, d.xr_cum, xr_cum, 0);
+  out->own.take(mem, d.run_start, run_start, 0);
+  out->own.take(mem, d.run_cum, run_cum, 0);
   d.n = (uint32_t)n;
   d.nruns = (uint32_t)starts.size();
   for (int k = 0; k < 4; k++) d.C[k] = (uint32_t)Cc[(uint8_t)bases[k]];
@@ -549,10 +531,12 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
   GS_TRY(mem.get(bytes, &tab));
   GS_HIP(hipMemsetAsync(tab, 0, bytes, st));
   hipLaunchKernelGGL(k_ptab_build, dim3(nblk(s->n, 256)), dim3(256), 0, st, d_text,
-                     (const uint32_t *)s->sa, s->n, k, tab);
+                     s->d.sa, s->n, k, tab);
   hipLaunchKernelGGL(k_ptab_finish, dim3(nblk(entries, 256)), dim3(256), 0, st, tab, entries);
-  uint32_t *ctx = nullptr;
+  uint32_t *ctx = nullptr, *d_er = nullptr;
   uint16_t *ctx16 = nullptr;
+  uint64_t *d_es = nullptr;
+  uint32_t h_cnt = 0; /* exception rows */
   if (!gs_opt(ix, "GS_NO_CTX")) {
     GS_TRY(mem.get(4 * s->n, &ctx));
     GS_TRY(mem.get(2 * s->n + 32, &ctx16)); /* one row group of padding (k_search reads groups of eight) */
@@ -571,16 +555,15 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
     }
     s->d.mask_off = mask_off;
     /* exception rows: counted in a first pass when the first guess is too small */
-    uint32_t *d_cnt = nullptr, *d_er = nullptr;
-    uint64_t *d_es = nullptr;
-    uint32_t cap = 1u << 16, h_cnt = 0;
+    uint32_t *d_cnt = nullptr;
+    uint32_t cap = 1u << 16;
     GS_TRY(mem.get(4, &d_cnt));
     for (int pass = 0; pass < 2; pass++) {
       GS_TRY(mem.get(4 * (size_t)cap, &d_er));
       GS_TRY(mem.get(8 * (size_t)cap, &d_es));
       GS_HIP(hipMemsetAsync(d_cnt, 0, 4, st));
       hipLaunchKernelGGL(k_ctx_build, dim3(nblk(s->n, 256)), dim3(256), 0, st, d_text,
-                         (const uint32_t *)s->sa, s->n, k, ctx, ctx16, tab, d_cnt, d_er, d_es, cap, mask_off);
+                         s->d.sa, s->n, k, ctx, ctx16, tab, d_cnt, d_er, d_es, cap, mask_off);
       GS_HIP(hipMemcpyAsync(&h_cnt, d_cnt, 4, hipMemcpyDeviceToHost, st));
       GS_HIP(hipStreamSynchronize(st));
       if (h_cnt <= cap) break;
@@ -605,19 +588,10 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
       }
       GS_HIP(hipMemcpy(d_er, er2.data(), 4 * (size_t)h_cnt, hipMemcpyHostToDevice));
       GS_HIP(hipMemcpy(d_es, es2.data(), 8 * (size_t)h_cnt, hipMemcpyHostToDevice));
-      mem.keep(d_er);
-      mem.keep(d_es);
-      s->exc_row = d_er;
-      s->exc_sym = d_es;
-      s->d.exc_row = d_er;
-      s->d.exc_sym = d_es;
-      s->d.n_exc = h_cnt;
-      s->bytes += 12 * (size_t)h_cnt;
     } else {
       mem.drop(d_er);
       mem.drop(d_es);
     }
-    s->bytes += 6 * s->n;
   } else {
     /* No context arrays: k_ctx_build, which computes the entries' context masks (z, w), does not run, and the table-seeded
      * walk tests its seeds against them all the same.  Every pair set: no seed is dropped by a mask nobody computed.
@@ -632,7 +606,8 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
    * the copies go first, then the inverse suffix array; an allocation that fails is skipped too. */
   double budget = 1e30;
   if (const char *e = gs_opt(ix, "GS_INDEX_BUDGET_GB")) budget = atof(e) * 1e9 / 2.0; /* per strand */
-  const double base_bytes = (double)s->bytes + (double)bytes; /* blocks, SA, context arrays, table */
+  const uint64_t ctx_bytes = ctx ? 6 * s->n + 12 * (uint64_t)h_cnt : 0; /* ctx, ctx16, exception rows */
+  const double base_bytes = (double)(s->own.bytes() + ctx_bytes) + (double)bytes; /* blocks, SA, context arrays, table */
   uint32_t rot_first = 3; /* see gs_strand_dev::rot_first */
   if (const char *e = gs_opt(ix, "GS_ROT_FIRST")) rot_first = (uint32_t)atoi(e);
   const uint32_t nrot = k >= 4 && rot_first + 1 < k ? k - 1 - rot_first : 0;
@@ -640,8 +615,7 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
   uint32_t *isa = nullptr;
   if (ctx && !gs_opt(ix, "GS_NO_BIDIR") && !gs_opt(ix, "GS_NO_ISA") && base_bytes + isa_bytes <= budget) {
     if (mem.get(4 * s->n, &isa) == GS_OK) {
-      hipLaunchKernelGGL(k_isa_build, dim3(nblk(s->n, 256)), dim3(256), 0, st, (const uint32_t *)s->sa, s->n, isa);
-      s->bytes += 4 * s->n;
+      hipLaunchKernelGGL(k_isa_build, dim3(nblk(s->n, 256)), dim3(256), 0, st, s->d.sa, s->n, isa);
     }
   }
   /* the rotated copies are derived data written in milliseconds: built by the first batch that reads them
@@ -651,19 +625,15 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
   s->rot_plan_n = (ctx && nrot && !gs_opt(ix, "GS_NO_ROT") && base_bytes + (isa ? isa_bytes : 0.0) + rot_bytes <= budget) ? nrot : 0;
   s->rot_k = k;
   GS_HIP(hipStreamSynchronize(st));
-  for (const void *q : {(const void *)isa, (const void *)tab, (const void *)ctx, (const void *)ctx16}) mem.keep(q);
-  s->isa = isa;
-  s->d.isa = isa;
-  s->ptab_rot = nullptr;
+  s->own.take(mem, s->d.ptab, tab, bytes);
+  s->own.take(mem, s->d.ctx, ctx, 4 * s->n);
+  s->own.take(mem, s->d.ctx16, ctx16, 2 * s->n);
+  s->own.take(mem, s->d.exc_row, d_er, 4 * (uint64_t)h_cnt);
+  s->own.take(mem, s->d.exc_sym, d_es, 8 * (uint64_t)h_cnt);
+  s->d.n_exc = h_cnt;
+  s->own.take(mem, s->d.isa, isa, 4 * s->n);
   s->d.ptab_rot = nullptr;
   s->d.rot_first = 31u;
-  s->ptab = tab;
-  s->d.ptab = tab;
-  s->ctx = ctx;
-  s->d.ctx = ctx;
-  s->ctx16 = ctx16;
-  s->d.ctx16 = ctx16;
-  s->bytes += bytes;
   return GS_OK;
 }
 
@@ -675,7 +645,7 @@ static gs_status build_ptab(const gs_index *ix, const uint8_t *d_text, gs_strand
 gs_status gs_strand_rot_ensure(gs_index *ix, hipStream_t st) {
   for (int s = 0; s < 2; s++) {
     gs_strand &S = ix->strand[s];
-    if (S.ptab_rot || !S.rot_plan_n || !S.ptab || ix->rot_off) continue;
+    if (S.d.ptab_rot || !S.rot_plan_n || !S.d.ptab || ix->rot_off) continue;
     const uint64_t entries = 1ull << (2 * S.rot_k);
     const size_t bytes = sizeof(uint4) * entries * S.rot_plan_n;
     size_t free_b = 0, total_b = 0;
@@ -684,18 +654,13 @@ gs_status gs_strand_rot_ensure(gs_index *ix, hipStream_t st) {
     if (reserve > 0.125 * (double)total_b) reserve = 0.125 * (double)total_b;
     if (const char *e = gs_opt(ix, "GS_ROT_RESERVE_GB")) reserve = atof(e) * 1e9; /* (tests: no rung by what other processes hold) */
     uint4 *rot = nullptr;
-    if ((double)bytes + reserve > (double)free_b || hipMalloc(&rot, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      continue;
-    }
+    gs_scratch mem;
+    if ((double)bytes + reserve > (double)free_b || mem.get(bytes, &rot) != GS_OK) continue;
     for (uint32_t p = 0; p < S.rot_plan_n; p++)
-      hipLaunchKernelGGL(k_rot_copy, dim3(nblk(entries, 256)), dim3(256), 0, st, (const uint4 *)S.ptab, rot, S.rot_k,
-                         S.rot_plan_first + p, p);
+      hipLaunchKernelGGL(k_rot_copy, dim3(nblk(entries, 256)), dim3(256), 0, st, S.d.ptab, rot, S.rot_k, S.rot_plan_first + p, p);
     GS_HIP(hipStreamSynchronize(st));
-    S.ptab_rot = rot;
-    S.d.ptab_rot = rot;
+    S.own.take(mem, S.d.ptab_rot, rot, bytes);
     S.d.rot_first = S.rot_plan_first;
-    S.bytes += bytes;
     if (gs_opt(ix, "GS_DEBUG"))
       fprintf(stderr, "[gs] strand %d: %u rotated table copies built (%.1f GB)\n", s, S.rot_plan_n, 1e-9 * (double)bytes);
   }
@@ -705,11 +670,8 @@ bool gs_strand_rot_release(gs_index *ix) {
   bool any = false;
   for (int s = 0; s < 2; s++) {
     gs_strand &S = ix->strand[s];
-    if (!S.ptab_rot) continue;
-    hipFree(S.ptab_rot);
-    S.bytes -= sizeof(uint4) * (1ull << (2 * S.rot_k)) * S.rot_plan_n;
-    S.ptab_rot = nullptr;
-    S.d.ptab_rot = nullptr;
+    if (!S.d.ptab_rot) continue;
+    S.own.release(S.d.ptab_rot);
     S.d.rot_first = 31u;
     any = true;
   }
@@ -792,8 +754,7 @@ static gs_status build_common(const uint8_t *text, uint64_t len, const uint32_t 
       rc = gs_opt(ix, "GS_SA_PLAIN") ? gs_device_suffix_array(d_t, n, d_sa, st)
                                      : gs_device_suffix_array_discarding(d_t, n, d_sa, st, gs_opt(ix, "GS_DEBUG") != nullptr);
     }
-    if (rc == GS_OK) rc = gs_strand_from_device(d_t, d_sa, n, &ix->strand[s], st);
-    if (ix->strand[s].sa == d_sa) mem.keep(d_sa); /* the strand owns it now (also when it failed later) */
+    if (rc == GS_OK) rc = gs_strand_from_device(d_t, mem, d_sa, n, &ix->strand[s], st);
     if (rc == GS_OK) rc = build_ptab(ix, d_t, &ix->strand[s], pk, st);
   }
   if (rc == GS_OK) ix->pt_k = pk; /* depth of the prefix interval tables; the seed recipes are written per batch shape (gs_search.hip) */
@@ -894,7 +855,7 @@ extern "C" gs_status gs_index_save_sa(gs_index *ix, const uint8_t *text, uint64_
   for (int s = 0; s < 2 && ok; s++)
     for (uint64_t at = 0; at < h.n && ok; at += chunk) {
       const size_t m = (size_t)std::min<uint64_t>(chunk, h.n - at);
-      if (hipMemcpy(buf.data(), (const uint32_t *)ix->strand[s].sa + at, 4 * m, hipMemcpyDeviceToHost) != hipSuccess) {
+      if (hipMemcpy(buf.data(), ix->strand[s].d.sa + at, 4 * m, hipMemcpyDeviceToHost) != hipSuccess) {
         fclose(f);
         gs_set_error("copying the suffix array back failed");
         return GS_ERR_DEVICE;
@@ -1027,13 +988,22 @@ extern "C" gs_status gs_index_last_spaced(const gs_index *ix, uint64_t out[6]) {
   GS_HANDLE_LOCK(ix);
   if (!ix || !out) return GS_ERR_ARG;
   for (int i = 0; i < 4; i++) out[i] = ix->last_spaced[i];
-  out[4] = ix->pairtab[0].sp_bytes + ix->pairtab[1].sp_bytes;
+  out[4] = ix->pairtab[0].sp_bytes() + ix->pairtab[1].sp_bytes();
   out[5] = (uint64_t)(1e3 * (ix->pairtab[0].sp_build_ms + ix->pairtab[1].sp_build_ms));
   return GS_OK;
 }
 extern "C" uint64_t gs_index_genome_length(const gs_index *ix) { return ix ? ix->genome_length : 0; }
 extern "C" uint64_t gs_index_device_bytes(const gs_index *ix) {
-  return ix ? ix->strand[0].bytes + ix->strand[1].bytes + ix->pairtab[0].bytes + ix->pairtab[1].bytes : 0;
+  return ix ? ix->strand[0].own.bytes() + ix->strand[1].own.bytes() + ix->pairtab[0].own.bytes() + ix->pairtab[1].own.bytes() : 0;
+}
+extern "C" gs_status gs_debug_resident(gs_index *ix, uint64_t out[4]) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !out) return GS_ERR_ARG;
+  out[0] = ix->strand[0].own.count() + ix->strand[1].own.count();
+  out[1] = ix->strand[0].own.bytes() + ix->strand[1].own.bytes();
+  out[2] = ix->pairtab[0].own.count() + ix->pairtab[1].own.count();
+  out[3] = ix->pairtab[0].own.bytes() + ix->pairtab[1].own.bytes();
+  return GS_OK;
 }
 extern "C" gs_status gs_index_meta(const gs_index *ix, int strand, uint64_t C_acgtn[5],
                                    uint64_t *size) {
@@ -1047,7 +1017,7 @@ extern "C" gs_status gs_index_copy_sa(gs_index *ix, int strand, uint32_t *out) {
   GS_HANDLE_LOCK(ix);
   if (!ix || strand < 0 || strand > 1 || !out) return GS_ERR_ARG;
   GS_HIP(hipSetDevice(ix->device));
-  GS_HIP(hipMemcpy(out, ix->strand[strand].sa, 4 * ix->strand[strand].n, hipMemcpyDeviceToHost));
+  GS_HIP(hipMemcpy(out, ix->strand[strand].d.sa, 4 * ix->strand[strand].n, hipMemcpyDeviceToHost));
   return GS_OK;
 }
 

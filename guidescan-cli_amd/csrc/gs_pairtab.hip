@@ -21,6 +21,7 @@
  * answers what C(|O|, m) 3^m seeds of the class (no substitution in X, m in O) ask one table entry each.
  */
 #include "gs_device.h"
+#include "gs_scratch.h"
 
 #include <algorithm>
 #include <rocprim/rocprim.hpp>
@@ -170,18 +171,29 @@ __global__ void k_pb_build(pb_args a) {
 
 void gs_pairtab_free(gs_index *ix, uint32_t slot) {
   gs_pairtab_host &p = ix->pairtab[slot];
-  for (int s = 0; s < 2; s++)
-    for (int j = 0; j < 8; j++) {
-      if (p.mem[s][j]) hipFree(p.mem[s][j]);
-      p.mem[s][j] = nullptr;
-    }
+  p.own.clear();
   p.valid = false;
   p.deep = false;
   p.spaced = false;
-  p.sp_bytes = 0;
   p.d[0] = gs_pairtab_dev{};
   p.d[1] = gs_pairtab_dev{};
-  p.bytes = 0;
+}
+
+/* start[] = the exclusive sums of count[] over `entries` entries (the scan's temporary comes from mem and goes back);
+ * *total = their sum */
+static gs_status scan_counts(gs_scratch &mem, uint32_t *count, uint32_t *start, uint64_t entries, hipStream_t st, uint64_t *total) {
+  size_t tmp_bytes = 0;
+  void *tmp = nullptr;
+  GS_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, count, start, 0u, entries, rocprim::plus<uint32_t>(), st));
+  GS_TRY(mem.get(tmp_bytes, &tmp));
+  GS_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, count, start, 0u, entries, rocprim::plus<uint32_t>(), st));
+  uint32_t last_start = 0, last_count = 0;
+  GS_HIP(hipMemcpyAsync(&last_start, start + entries - 1, 4, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipMemcpyAsync(&last_count, count + entries - 1, 4, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipStreamSynchronize(st));
+  mem.drop(tmp);
+  *total = (uint64_t)last_start + last_count;
+  return GS_OK;
 }
 
 static gs_status build_one(gs_index *ix, gs_pairtab_host &p, int s, uint32_t k, uint32_t rot_from, hipStream_t st) {
@@ -189,8 +201,8 @@ static gs_status build_one(gs_index *ix, gs_pairtab_host &p, int s, uint32_t k, 
   const uint64_t entries = 1ull << (2 * k);
   pt_args a;
   memset(&a, 0, sizeof(a));
-  a.tab = (const uint4 *)S.ptab;
-  a.ctx = (const uint32_t *)S.ctx;
+  a.tab = S.d.ptab;
+  a.ctx = S.d.ctx;
   a.exc_row = S.d.exc_row;
   a.exc_sym = S.d.exc_sym;
   a.n_exc = S.d.n_exc;
@@ -198,64 +210,43 @@ static gs_status build_one(gs_index *ix, gs_pairtab_host &p, int s, uint32_t k, 
   a.code = p.code;
   a.mask_off = S.d.mask_off;
   a.entries = entries;
+  gs_scratch mem; /* the temporaries, and each array until the slot has it */
   uint32_t *d_count = nullptr, *d_start = nullptr;
-  void *d_tmp = nullptr;
-  struct cleanup_t {
-    uint32_t *&c, *&s;
-    void *&t;
-    ~cleanup_t() {
-      if (c) hipFree(c);
-      if (s) hipFree(s);
-      if (t) hipFree(t);
-    }
-  } cleanup{d_count, d_start, d_tmp};
-  if (hipMalloc(&d_count, 4 * entries) != hipSuccess || hipMalloc(&d_start, 4 * entries) != hipSuccess) {
-    (void)hipGetLastError();
-    return GS_ERR_NOMEM;
-  }
+  GS_TRY(mem.get(4 * entries, &d_count));
+  GS_TRY(mem.get(4 * entries, &d_start));
   a.count = d_count;
   const uint32_t nb = (uint32_t)((entries + 255) / 256);
   hipLaunchKernelGGL(k_pt_count, dim3(nb), dim3(256), 0, st, a);
-  size_t tmp_bytes = 0;
-  GS_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_count, d_start, 0u, entries, rocprim::plus<uint32_t>(), st));
-  if (hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16) != hipSuccess) {
-    (void)hipGetLastError();
-    return GS_ERR_NOMEM;
-  }
-  GS_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_count, d_start, 0u, entries, rocprim::plus<uint32_t>(), st));
-  uint32_t last_start = 0, last_count = 0;
-  GS_HIP(hipMemcpyAsync(&last_start, d_start + entries - 1, 4, hipMemcpyDeviceToHost, st));
-  GS_HIP(hipMemcpyAsync(&last_count, d_count + entries - 1, 4, hipMemcpyDeviceToHost, st));
-  GS_HIP(hipStreamSynchronize(st));
-  const uint64_t rows = (uint64_t)last_start + last_count;
-  void **m = p.mem[s];
+  uint64_t rows = 0;
+  GS_TRY(scan_counts(mem, d_count, d_start, entries, st, &rows));
   const uint32_t nrot = rot_from + 2 < k ? k - 2 - rot_from : 0; /* steps rot_from .. k-3 (step k-2's variants sit in the plain table's 128-byte blocks) */
-  if (hipMalloc(&m[0], sizeof(uint2) * entries) != hipSuccess || hipMalloc(&m[2], 2 * rows + 64) != hipSuccess ||
-      hipMalloc(&m[3], 4 * rows + 16) != hipSuccess || hipMalloc(&m[4], 4 * rows + 16) != hipSuccess ||
-      (nrot && hipMalloc(&m[1], sizeof(uint2) * entries * nrot) != hipSuccess)) {
-    (void)hipGetLastError();
-    return GS_ERR_NOMEM;
-  }
-  GS_HIP(hipMemsetAsync(m[2], 0, 2 * rows + 64, st)); /* k_search reads whole groups of eight */
+  uint2 *tab = nullptr, *rot = nullptr;
+  uint16_t *c16 = nullptr;
+  uint32_t *octx = nullptr, *rowid = nullptr;
+  GS_TRY(mem.get(sizeof(uint2) * entries, &tab));
+  GS_TRY(mem.get(2 * rows + 64, &c16));
+  GS_TRY(mem.get(4 * rows, &octx));
+  GS_TRY(mem.get(4 * rows, &rowid));
+  if (nrot) GS_TRY(mem.get(sizeof(uint2) * entries * nrot, &rot));
+  GS_HIP(hipMemsetAsync(c16, 0, 2 * rows + 64, st)); /* k_search reads whole groups of eight */
   a.start = d_start;
-  a.out = (uint2 *)m[0];
-  a.c16 = (uint16_t *)m[2];
-  a.octx = (uint32_t *)m[3];
-  a.rowid = (uint32_t *)m[4];
+  a.out = tab;
+  a.c16 = c16;
+  a.octx = octx;
+  a.rowid = rowid;
   hipLaunchKernelGGL(k_pt_fill, dim3(nb), dim3(256), 0, st, a);
   for (uint32_t j = 0; j < nrot; j++)
-    hipLaunchKernelGGL(k_pt_rot, dim3(nb), dim3(256), 0, st, (const uint2 *)m[0], (uint2 *)m[1], k, rot_from + j, j);
+    hipLaunchKernelGGL(k_pt_rot, dim3(nb), dim3(256), 0, st, (const uint2 *)tab, rot, k, rot_from + j, j);
   GS_HIP(hipStreamSynchronize(st));
   GS_HIP(hipGetLastError());
   gs_pairtab_dev &d = p.d[s];
-  d.tab = (const uint2 *)m[0];
-  d.rot = (const uint2 *)m[1];
-  d.c16 = (const uint16_t *)m[2];
-  d.ctx = (const uint32_t *)m[3];
-  d.rowid = (const uint32_t *)m[4];
+  p.own.take(mem, d.tab, tab, sizeof(uint2) * entries);
+  p.own.take(mem, d.rot, rot, sizeof(uint2) * entries * nrot);
+  p.own.take(mem, d.c16, c16, 2 * rows);
+  p.own.take(mem, d.ctx, octx, 4 * rows);
+  p.own.take(mem, d.rowid, rowid, 4 * rows);
   d.rot_first = nrot ? rot_from : 31u;
   d.code = p.code;
-  p.bytes += sizeof(uint2) * entries * (1 + nrot) + 10 * rows;
   p.n_slots[s] = rows;
   if (gs_opt(ix, "GS_DEBUG"))
     fprintf(stderr, "[gs] PAM-pair table: strand %d, pair %u at context depth %u: %llu of %llu rows, %u rotated copies, %.2f GB\n",
@@ -268,11 +259,9 @@ static gs_status build_one(gs_index *ix, gs_pairtab_host &p, int s, uint32_t k, 
 static gs_status build_deep(gs_index *ix, gs_pairtab_host &p, int s, uint32_t k, uint32_t P, uint32_t kb, hipStream_t st) {
   const gs_strand &S = ix->strand[s];
   const uint64_t entries = 1ull << (2 * kb);
-  void **m = p.mem[s];
-  if (hipMalloc(&m[5], 64 * entries) != hipSuccess) {
-    (void)hipGetLastError();
-    return GS_ERR_NOMEM;
-  }
+  gs_scratch mem;
+  uint4 *deep = nullptr;
+  GS_TRY(mem.get(64 * entries, &deep));
   pb_args a;
   memset(&a, 0, sizeof(a));
   a.sd = S.d;
@@ -281,12 +270,11 @@ static gs_status build_deep(gs_index *ix, gs_pairtab_host &p, int s, uint32_t k,
   a.kb = kb;
   a.code = p.code;
   a.entries = entries;
-  a.out = (uint4 *)m[5];
+  a.out = deep;
   hipLaunchKernelGGL(k_pb_build, dim3((uint32_t)((entries + 255) / 256)), dim3(256), 0, st, a);
   GS_HIP(hipStreamSynchronize(st));
   GS_HIP(hipGetLastError());
-  p.d[s].deep = (const uint4 *)m[5];
-  p.bytes += 64 * entries;
+  p.own.take(mem, p.d[s].deep, deep, 64 * entries);
   if (gs_opt(ix, "GS_DEBUG"))
     fprintf(stderr, "[gs] deep table: strand %d, pair %u: %llu lines of four entries, %.2f GB\n", s, p.code,
             (unsigned long long)entries, 1e-9 * (double)(64 * entries));
@@ -301,7 +289,7 @@ gs_status gs_pairtab_ensure(gs_index *ix, uint32_t slot, uint32_t v_rem, uint32_
   const uint32_t rot_wanted = rot_first;
   if (p.valid && p.v_rem == v_rem && p.code == code && p.rot_first <= rot_wanted) return GS_OK;
   gs_pairtab_free(ix, slot);
-  if (!k || v_rem < 2 || v_rem > 16 || !ix->strand[0].ctx || !ix->strand[1].ctx) return GS_OK;
+  if (!k || v_rem < 2 || v_rem > 16 || !ix->strand[0].d.ctx || !ix->strand[1].d.ctx) return GS_OK;
   /* fit into what is free, keeping room for the batch workspace: drop rotated copies first */
   size_t free_b = 0, total_b = 0;
   GS_HIP(hipMemGetInfo(&free_b, &total_b));
@@ -350,11 +338,7 @@ gs_status gs_pairtab_ensure_deep(gs_index *ix, uint32_t slot, uint32_t P, uint32
   if (!p.valid || P != 3 || k < 6 || kb + P < k || kb > 14) return GS_OK;
   if (p.deep && p.deep_P == P && p.deep_kb == kb) return GS_OK;
   auto drop = [&]() {
-    for (int s = 0; s < 2; s++) {
-      if (p.mem[s][5]) hipFree(p.mem[s][5]);
-      p.mem[s][5] = nullptr;
-      p.d[s].deep = nullptr;
-    }
+    for (int s = 0; s < 2; s++) p.own.release(p.d[s].deep);
     p.deep = false;
   };
   drop();
@@ -448,19 +432,11 @@ bool gs_pairtab_free_spaced(gs_index *ix, uint32_t slot) {
   gs_pairtab_host &p = ix->pairtab[slot];
   bool any = false;
   for (int s = 0; s < 2; s++) {
-    for (int j = 6; j < 8; j++) {
-      if (p.mem[s][j]) {
-        hipFree(p.mem[s][j]);
-        any = true;
-      }
-      p.mem[s][j] = nullptr;
-    }
-    p.d[s].sp_off = nullptr;
-    p.d[s].sp_rows = nullptr;
+    any |= p.d[s].sp_off || p.d[s].sp_rows;
+    p.own.release(p.d[s].sp_off);
+    p.own.release(p.d[s].sp_rows);
     p.d[s].sp_rem = 0;
   }
-  p.bytes -= p.sp_bytes;
-  p.sp_bytes = 0;
   p.spaced = false;
   return any;
 }
@@ -479,22 +455,11 @@ static uint32_t sp_direct_bits(uint64_t rows, uint32_t key_bits, uint32_t obits)
 static gs_status build_spaced(gs_index *ix, gs_pairtab_host &p, int s, uint32_t k, uint32_t x_len, uint32_t g, hipStream_t st) {
   const uint64_t entries = 1ull << (2 * k);
   const uint32_t key_bits = 2u * (x_len + g), obits = 2u * (k - x_len);
-  void **m = p.mem[s];
-  uint32_t *d_count = nullptr, *d_start = nullptr, *d_keys = nullptr, *d_keys2 = nullptr;
-  uint64_t *d_vals = nullptr;
-  void *d_tmp = nullptr;
-  struct cleanup_t {
-    void *const *v[6];
-    ~cleanup_t() {
-      for (void *const *q : v)
-        if (*q) hipFree(*q);
-    }
-  } cleanup{{(void **)&d_count, (void **)&d_start, (void **)&d_keys, (void **)&d_keys2, (void **)&d_vals, &d_tmp}};
-  auto nomem = [&]() {
-    (void)hipGetLastError();
-    return GS_ERR_NOMEM;
-  };
-  if (hipMalloc(&d_count, 4 * entries) != hipSuccess || hipMalloc(&d_start, 4 * entries) != hipSuccess) return nomem();
+  gs_scratch mem; /* the temporaries, and both arrays until the slot has them */
+  uint32_t *d_count = nullptr, *d_start = nullptr, *d_keys = nullptr, *d_keys2 = nullptr, *sp_off = nullptr;
+  uint64_t *d_vals = nullptr, *sp_rows = nullptr;
+  GS_TRY(mem.get(4 * entries, &d_count));
+  GS_TRY(mem.get(4 * entries, &d_start));
   sp_args a;
   memset(&a, 0, sizeof(a));
   a.tab = p.d[s].tab;
@@ -507,50 +472,41 @@ static gs_status build_spaced(gs_index *ix, gs_pairtab_host &p, int s, uint32_t 
   a.count = d_count;
   const uint32_t nb = (uint32_t)((entries + 255) / 256);
   hipLaunchKernelGGL(k_sp_count, dim3(nb), dim3(256), 0, st, a);
-  size_t tmp_bytes = 0;
-  GS_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_count, d_start, 0u, entries, rocprim::plus<uint32_t>(), st));
-  if (hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16) != hipSuccess) return nomem();
-  GS_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_count, d_start, 0u, entries, rocprim::plus<uint32_t>(), st));
-  uint32_t last_start = 0, last_count = 0;
-  GS_HIP(hipMemcpyAsync(&last_start, d_start + entries - 1, 4, hipMemcpyDeviceToHost, st));
-  GS_HIP(hipMemcpyAsync(&last_count, d_count + entries - 1, 4, hipMemcpyDeviceToHost, st));
-  GS_HIP(hipStreamSynchronize(st));
-  (void)hipFree(d_tmp);
-  d_tmp = nullptr;
   /* the rows are the slots of the pair table's row arrays without the header slots: the builder's own count bounds them, so
-   * the 32-bit scan above cannot have wrapped unseen */
-  const uint64_t rows = (uint64_t)last_start + last_count;
+   * the 32-bit scan cannot have wrapped unseen */
+  uint64_t rows = 0;
+  GS_TRY(scan_counts(mem, d_count, d_start, entries, st, &rows));
   if (p.n_slots[s] >= 0xFFFFFFFFull || rows > p.n_slots[s]) return GS_ERR_UNSUPPORTED;
   const uint32_t d = sp_direct_bits(rows, key_bits, obits);
   if (!d) return GS_ERR_UNSUPPORTED;
   const uint32_t rem = key_bits - d;
-  if (hipMalloc(&d_keys, 4 * rows + 16) != hipSuccess || hipMalloc(&d_keys2, 4 * rows + 16) != hipSuccess ||
-      hipMalloc(&d_vals, 8 * rows + 16) != hipSuccess || hipMalloc(&m[7], 8 * rows + 16) != hipSuccess ||
-      hipMalloc(&m[6], 4 * ((1ull << d) + 1)) != hipSuccess)
-    return nomem();
+  GS_TRY(mem.get(4 * rows, &d_keys));
+  GS_TRY(mem.get(4 * rows, &d_keys2));
+  GS_TRY(mem.get(8 * rows, &d_vals));
+  GS_TRY(mem.get(8 * rows, &sp_rows));
+  GS_TRY(mem.get(4 * ((1ull << d) + 1), &sp_off));
   a.start = d_start;
   a.rem = rem;
   a.keys = d_keys;
   a.vals = d_vals;
   hipLaunchKernelGGL(k_sp_fill, dim3(nb), dim3(256), 0, st, a);
   if (rows) {
-    tmp_bytes = 0;
-    GS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys, d_keys2, d_vals, (uint64_t *)m[7], rows, 0, key_bits, st));
-    if (hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16) != hipSuccess) return nomem();
-    GS_HIP(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_vals, (uint64_t *)m[7], rows, 0, key_bits, st));
+    size_t tmp_bytes = 0;
+    void *d_tmp = nullptr;
+    GS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys, d_keys2, d_vals, sp_rows, rows, 0, key_bits, st));
+    GS_TRY(mem.get(tmp_bytes, &d_tmp));
+    GS_HIP(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_vals, sp_rows, rows, 0, key_bits, st));
   }
   hipLaunchKernelGGL(k_sp_offsets, dim3((uint32_t)((rows + 1 + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_keys2, (uint32_t)rows, rem, d,
-                     (uint32_t *)m[6]);
+                     sp_off);
   GS_HIP(hipStreamSynchronize(st));
   GS_HIP(hipGetLastError());
   gs_pairtab_dev &dv = p.d[s];
-  dv.sp_off = (const uint32_t *)m[6];
-  dv.sp_rows = (const uint2 *)m[7];
+  p.own.take(mem, dv.sp_off, sp_off, 4 * ((1ull << d) + 1));
+  p.own.take(mem, dv.sp_rows, sp_rows, 8 * rows + 16);
   dv.sp_rem = rem;
   p.sp_rows[s] = rows;
   const uint64_t bytes = 8 * rows + 16 + 4 * ((1ull << d) + 1);
-  p.sp_bytes += bytes;
-  p.bytes += bytes;
   if (gs_opt(ix, "GS_DEBUG"))
     fprintf(stderr, "[gs] spaced table: strand %d, pair %u: %llu rows by %u key bits (|X|=%u, |R|=%u), %u direct, %.2f GB\n", s, p.code,
             (unsigned long long)rows, key_bits, x_len, g, d, 1e-9 * (double)bytes);
@@ -604,7 +560,7 @@ gs_status gs_pairtab_ensure_spaced(gs_index *ix, uint32_t slot, uint32_t x_len, 
   p.spaced = true;
   p.sp_x = x_len;
   p.sp_g = g;
-  if (gs_opt(ix, "GS_DEBUG")) fprintf(stderr, "[gs] spaced tables of pair %u: %.2f GB, built in %.1f ms\n", p.code, 1e-9 * (double)p.sp_bytes, p.sp_build_ms);
+  if (gs_opt(ix, "GS_DEBUG")) fprintf(stderr, "[gs] spaced tables of pair %u: %.2f GB, built in %.1f ms\n", p.code, 1e-9 * (double)p.sp_bytes(), p.sp_build_ms);
   return GS_OK;
 }
 

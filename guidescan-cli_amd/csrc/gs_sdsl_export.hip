@@ -484,7 +484,7 @@ struct exp_parts {
 static gs_status export_strand_device(gs_index *ix, int strand, const uint8_t *text, uint64_t len, exp_parts &X) {
   hipStream_t st = nullptr; /* the stream the handle's builders use */
   const uint64_t n = len + 1;
-  const uint32_t *d_sa = ix->strand[strand].sa ? (const uint32_t *)ix->strand[strand].sa : nullptr;
+  const uint32_t *d_sa = ix->strand[strand].d.sa;
   if (!d_sa) {
     gs_set_error("the handle holds no suffix array");
     return GS_ERR_ARG;

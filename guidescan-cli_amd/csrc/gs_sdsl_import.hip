@@ -450,9 +450,9 @@ __global__ __launch_bounds__(256) void k_imp_cmp_revcomp(const uint8_t *fwd, con
   if ((threadIdx.x & 63u) == 0u && v) atomicAdd(diff, v);
 }
 
-/* one strand's file -> its text (n bytes: the genome and the sentinel) and suffix array (n rows) in device memory.
+/* one strand's file -> its text (n bytes: the genome and the sentinel) and suffix array (n rows) in device memory, both `keep`'s.
  * GS_ERR_UNSUPPORTED: a file this path does not take (more than 16 distinct symbols, 2^32 rows) - the caller uses the host path */
-static gs_status sdsl_strand_on_device(const char *path, uint8_t **d_text_out, uint32_t **d_sa_out, uint64_t *n_out) {
+static gs_status sdsl_strand_on_device(const char *path, gs_scratch &keep, uint8_t **d_text_out, uint32_t **d_sa_out, uint64_t *n_out) {
   std::vector<uint8_t> buf;
   parsed P;
   gs_status rc = parse_index_file(path, buf, P, true);
@@ -560,8 +560,8 @@ static gs_status sdsl_strand_on_device(const char *path, uint8_t **d_text_out, u
   }
   /* the walks */
   void *d_text = nullptr, *d_sa = nullptr, *d_bad = nullptr;
-  GS_TRY(mem.get(n + 64, &d_text));
-  GS_TRY(mem.get(4 * (n + 64), &d_sa));
+  GS_TRY(keep.get(n + 64, &d_text));
+  GS_TRY(keep.get(4 * (n + 64), &d_sa));
   GS_TRY(mem.get(16, &d_bad));
   GS_HIP(hipMemset(d_text, 0, n + 64));
   GS_HIP(hipMemset(d_sa, 0xFF, 4 * (n + 64)));
@@ -578,8 +578,6 @@ static gs_status sdsl_strand_on_device(const char *path, uint8_t **d_text_out, u
     gs_set_error(bad & 1u ? "BWT inversion met the sentinel inside the text" : "two SA samples at one text position");
     return GS_ERR_FORMAT;
   }
-  mem.keep(d_text);
-  mem.keep(d_sa);
   *d_text_out = (uint8_t *)d_text;
   *d_sa_out = (uint32_t *)d_sa;
   *n_out = n;
@@ -600,14 +598,11 @@ static gs_status open_sdsl_on_device(const char *prefix, int device, gs_index **
     uint8_t *text = nullptr;
     uint32_t *sa = nullptr;
     uint64_t n = 0;
-    ~strand_t() {
-      if (text) (void)hipFree(text);
-      if (sa) (void)hipFree(sa);
-    }
   } f, r;
-  gs_status rc = sdsl_strand_on_device((std::string(prefix) + ".forward").c_str(), &f.text, &f.sa, &f.n);
+  gs_scratch mem; /* both strands' texts and suffix arrays, until the index has its own */
+  gs_status rc = sdsl_strand_on_device((std::string(prefix) + ".forward").c_str(), mem, &f.text, &f.sa, &f.n);
   if (rc != GS_OK) return rc;
-  rc = sdsl_strand_on_device((std::string(prefix) + ".reverse").c_str(), &r.text, &r.sa, &r.n);
+  rc = sdsl_strand_on_device((std::string(prefix) + ".reverse").c_str(), mem, &r.text, &r.sa, &r.n);
   if (rc != GS_OK) return rc == GS_ERR_IO ? GS_ERR_UNSUPPORTED : rc; /* (no .reverse file: the host path rebuilds that strand from the text) */
   if (r.n != f.n) {
     gs_set_error(".forward and .reverse hold texts of different lengths");
@@ -615,7 +610,6 @@ static gs_status open_sdsl_on_device(const char *prefix, int device, gs_index **
   }
   /* the reverse index is the FM-index of reverse_complement(forward text) (src/guidescan.cxx:146-157): it must be */
   const uint64_t len = f.n - 1;
-  gs_scratch mem;
   void *d_diff = nullptr;
   GS_TRY(mem.get(16, &d_diff));
   GS_HIP(hipMemset(d_diff, 0, 16));
@@ -626,12 +620,10 @@ static gs_status open_sdsl_on_device(const char *prefix, int device, gs_index **
     gs_set_error(".reverse is not the index of the reverse complement of .forward's text");
     return GS_ERR_FORMAT;
   }
-  (void)hipFree(r.text);
-  r.text = nullptr;
+  mem.drop(r.text);
   std::vector<uint8_t> text(len);
   GS_HIP(hipMemcpy(text.data(), f.text, len, hipMemcpyDeviceToHost));
-  (void)hipFree(f.text);
-  f.text = nullptr;
+  mem.drop(f.text);
   rc = gs_build_from_device_sa(text.data(), len, f.sa, r.sa, device, out);
   if (rc != GS_OK) return rc;
   /* the arrays came from the file's samples, not from a sort of this text.  A damaged sample value moves its whole walk
@@ -642,7 +634,7 @@ static gs_status open_sdsl_on_device(const char *prefix, int device, gs_index **
    * rows are compared by their suffixes at 2^16 places per strand, which from some 2^22 rows on MISSES most such damage */
   for (int strand = 0; strand < 2; strand++) {
     gs_sa_report rep;
-    if ((*out)->strand[strand].isa)
+    if ((*out)->strand[strand].d.isa)
       rc = gs_index_verify_sa(*out, strand, text.data(), len, GS_VERIFY_ALL_ROWS, 0, &rep);
     else
       rc = gs_index_verify_sa(*out, strand, text.data(), len, 65536, 0x5D51ull + (uint64_t)strand, &rep);

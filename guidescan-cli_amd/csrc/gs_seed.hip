@@ -239,10 +239,10 @@ __global__ void k_estimate_heavy(const gs_guide_rec *guides, uint32_t n, const u
 gs_status gs_estimate_heavy(gs_index *ix, const gs_guide_rec *guides, uint32_t n, uint32_t thresh, uint32_t *d_out, hipStream_t st,
                             uint32_t n_heavy[2]) {
   n_heavy[0] = n_heavy[1] = 0;
-  if (!ix->pt_k || !ix->strand[0].ptab || !ix->strand[1].ptab || !n) return GS_OK;
+  if (!ix->pt_k || !ix->strand[0].d.ptab || !ix->strand[1].d.ptab || !n) return GS_OK;
   GS_HIP(hipMemsetAsync(d_out, 0, 8, st));
-  hipLaunchKernelGGL(k_estimate_heavy, dim3((n + 255) / 256), dim3(256), 0, st, guides, n, (const uint4 *)ix->strand[0].ptab,
-                     (const uint4 *)ix->strand[1].ptab, ix->pt_k, thresh, d_out);
+  hipLaunchKernelGGL(k_estimate_heavy, dim3((n + 255) / 256), dim3(256), 0, st, guides, n, ix->strand[0].d.ptab,
+                     ix->strand[1].d.ptab, ix->pt_k, thresh, d_out);
   GS_HIP(hipMemcpyAsync(n_heavy, d_out, 8, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   return GS_OK;

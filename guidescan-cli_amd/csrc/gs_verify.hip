@@ -226,17 +226,17 @@ extern "C" gs_status gs_index_verify_sa(gs_index *ix, int strand, const uint8_t 
   GS_HIP(hipMemset(d_bitmap, 0, 4 * words));
   GS_TRY(mem.get(64, &out));
   GS_HIP(hipMemset(out, 0, 64));
-  hipLaunchKernelGGL(k_v_permutation, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const uint32_t *)s.sa, n, d_bitmap, out + 3);
+  hipLaunchKernelGGL(k_v_permutation, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, s.d.sa, n, d_bitmap, out + 3);
   if (n_samples == GS_VERIFY_ALL_ROWS) {
-    if (!s.isa) {
+    if (!s.d.isa) {
       gs_set_error("gs_index_verify_sa: the check of every row reads the inverse suffix array, which this index was built without");
       return GS_ERR_UNSUPPORTED;
     }
     gs_vfull_args a;
     a.text = d_text;
-    a.sa = (const uint32_t *)s.sa;
-    a.isa = (const uint32_t *)s.isa;
-    a.blocks = (const uint4 *)s.blocks;
+    a.sa = s.d.sa;
+    a.isa = s.d.isa;
+    a.blocks = s.d.blocks;
     a.out = out;
     a.n = n;
     hipLaunchKernelGGL(k_v_full, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, a);
@@ -255,8 +255,8 @@ extern "C" gs_status gs_index_verify_sa(gs_index *ix, int strand, const uint8_t 
   if (n_samples) {
     gs_vorder_args a;
     a.text = d_text;
-    a.sa = (const uint32_t *)s.sa;
-    a.blocks = (const uint4 *)s.blocks;
+    a.sa = s.d.sa;
+    a.blocks = s.d.blocks;
     a.runs = d_runs;
     a.out = out;
     a.n = n;

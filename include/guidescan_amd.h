@@ -318,6 +318,10 @@ gs_status gs_debug_seed_path(uint64_t q, const uint32_t pam[4], uint64_t word, u
                              uint32_t nst, uint64_t out[2]);
 /* Index pidx of a depth-k table as the copy rotated at consumption step rs holds it (host only). */
 gs_status gs_debug_rot_index(uint32_t pidx, uint32_t k, uint32_t rs, uint32_t *out);
+/* The device arrays the handle keeps between calls and the bytes they count for in gs_index_device_bytes: [0] arrays and
+ * [1] bytes of the two strands (Occ blocks, suffix array, tables, context and inverse arrays, rotated copies), [2] arrays and
+ * [3] bytes of the PAM-pair table slots (pair, deep and spaced tables).  [1] + [3] = gs_index_device_bytes.  Tests only. */
+gs_status gs_debug_resident(gs_index *ix, uint64_t out[4]);
 /* The rows under `key` (X symbols << 2 |R| | R symbols, both in consumption order) in the spaced table of a PAM-pair table
  * slot and strand, four words per row: {row in the table's row arrays, its O symbols, its row in the strand's suffix array,
  * its context word}; *n = rows under the key (out holds the first cap); info = {1 = the slot has spaced tables, pair code,
