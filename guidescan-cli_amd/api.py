@@ -336,6 +336,7 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_kmers_concat", "gs_decoder_open", "gs_decoder_close", "gs_decode_records", "gs_decode_records_device",
            "gs_decode_sam", "gs_debug_repr_doubles", "gs_debug_decode_tables",
            "gs_index_last_spaced", "gs_debug_seed_recipes_a8", "gs_debug_spaced_rows", "gs_debug_resident",
+           "gs_debug_buffers_live", "gs_debug_workspace",
            "gs_debug_seed_probes", "gs_debug_seed_path", "gs_debug_rot_index",
            "gs_debug_bulge_last", "gs_debug_bulge_seeds", "gs_debug_bulge_verify",
            "gs_bgzf_compress_device", "gs_bgzf_compress", "gs_debug_huffman_lengths", "gs_debug_sp_float",
@@ -351,6 +352,19 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
 def _check(rc):
     if rc != 0:
         raise GsError(rc, lib().gs_status_string(rc).decode())
+
+
+def buffers_live():
+    """(allocations, bytes) of the workspace buffers alive in the process (gs_debug_buffers_live)"""
+    L_ = lib()
+    L_.gs_debug_buffers_live.restype = C.c_int
+    L_.gs_debug_buffers_live.argtypes = [C.c_void_p]
+    out = (C.c_uint64 * 2)()
+    _check(L_.gs_debug_buffers_live(out))
+    return int(out[0]), int(out[1])
+
+
+WORKSPACE_GROUPS = ("batch", "big", "tile", "score", "text", "bgzf")
 
 
 BULGE_SEED_DTYPE = np.dtype([("index", "<u4"), ("state", "<u4"), ("seq", "S32")])
@@ -1604,6 +1618,17 @@ class GenomeIndex:
         out = (C.c_uint64 * 4)()
         _check(L_.gs_debug_resident(self._h, out))
         return dict(zip(("strand_arrays", "strand_bytes", "pairtab_arrays", "pairtab_bytes"), (int(x) for x in out)))
+
+    def workspace(self):
+        """per group of the handle's workspace (WORKSPACE_GROUPS): buffers held, bytes held, bytes an out-of-memory
+        recovery would release (gs_debug_workspace)"""
+        L_ = lib()
+        L_.gs_debug_workspace.restype = C.c_int
+        L_.gs_debug_workspace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        out = (C.c_uint64 * (3 * len(WORKSPACE_GROUPS)))()
+        _check(L_.gs_debug_workspace(self._h, out, len(WORKSPACE_GROUPS)))
+        return {g: dict(buffers=int(out[3 * i]), bytes=int(out[3 * i + 1]), releasable=int(out[3 * i + 2]))
+                for i, g in enumerate(WORKSPACE_GROUPS)}
 
     def spaced_rows(self, slot, strand, key, cap=4096):
         """the rows under `key` in a slot's spaced table (gs_debug_spaced_rows) -> (rows uint32[n, 4], n under the key, info)"""

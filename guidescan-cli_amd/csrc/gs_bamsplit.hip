@@ -23,6 +23,7 @@
  */
 #include "gs_device.h"
 #include "gs_decoder.h"
+#include "gs_scratch.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -298,7 +299,7 @@ gs_status decode_bam_device(gs_decoder *d, const void *bgzf, uint64_t len, uint6
   /* the starts are sized by the bytes (36 a record at least), everything per record by the records found */
   bump tm;
   const size_t t_res = tm.take(64), t_ref = tm.take(4 * (size_t)n_ref), t_starts = tm.take(8 * cap);
-  if ((rc = gs_reserve(d->w_bs_tmp, tm.at + 16)) != GS_OK) return rc;
+  GS_TRY(gs_reserve(d->w_bs_tmp, tm.at + 16));
   char *tmp = (char *)d->w_bs_tmp.p;
   unsigned long long *res = (unsigned long long *)(tmp + t_res);
   d->bam_tail = 0; /* the kept bytes are in front of these now: a call that fails from here on leaves no tail */
@@ -332,7 +333,7 @@ gs_status decode_bam_device(gs_decoder *d, const void *bgzf, uint64_t len, uint6
                  t_oid = tr.take(8 * (n + 1)), t_osq = tr.take(8 * (n + 1)), t_ohx = tr.take(8 * (n + 1)), t_hsrc = tr.take(8 * n),
                  t_pos = tr.take(8 * n), t_chr = tr.take(4 * n), t_rev = tr.take(n), t_scan = tr.take(tb);
     t_ow = tr.take(8 * (n + 1));
-    if ((rc = gs_reserve(d->w_bs_rec, tr.at + 16)) != GS_OK) return rc;
+    GS_TRY(gs_reserve(d->w_bs_rec, tr.at + 16));
     rec = (char *)d->w_bs_rec.p;
     a.d = (const uint8_t *)d_bytes;
     a.starts = (const uint64_t *)(tmp + t_starts);
@@ -359,7 +360,9 @@ gs_status decode_bam_device(gs_decoder *d, const void *bgzf, uint64_t len, uint6
     uint64_t *lens[4] = {a.len_id, a.len_seq, a.len_hex, a.len_word};
     const size_t offs[4] = {t_oid, t_osq, t_ohx, t_ow};
     for (int k = 0; k < 4; k++) {
-      GS_HIP(rocprim::exclusive_scan(rec + t_scan, tb, lens[k], (uint64_t *)(rec + offs[k]), 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+      GS_TRY(gs_prim_carved("gs_decode_bam: scan of the records' sizes", rec + t_scan, tb, [&](void *t, size_t &b) {
+        return rocprim::exclusive_scan(t, b, lens[k], (uint64_t *)(rec + offs[k]), 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st);
+      }));
       GS_HIP(hipMemcpyAsync(&totals[k], (uint64_t *)(rec + offs[k]) + n, 8, hipMemcpyDeviceToHost, st));
     }
     unsigned long long ferr = ~0ull;
@@ -373,7 +376,7 @@ gs_status decode_bam_device(gs_decoder *d, const void *bgzf, uint64_t len, uint6
   if (n) {
     bump in;
     const size_t i_ids = in.take(totals[0]), i_seqs = in.take(totals[1]), i_hex = in.take(totals[2]);
-    if ((rc = gs_reserve(d->w_in, in.at + 16)) != GS_OK) return rc;
+    GS_TRY(gs_reserve(d->w_in, in.at + 16));
     a.ids = (uint8_t *)d->w_in.p + i_ids;
     a.seqs = (uint8_t *)d->w_in.p + i_seqs;
     a.hex = (uint8_t *)d->w_in.p + i_hex;

@@ -25,6 +25,7 @@
 #include "gs_device.h"
 #include "gs_bgzf_huff.h"
 #include "gs_bgzf_crc.h"
+#include "gs_scratch.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -280,7 +281,6 @@ extern "C" gs_status gs_bgzf_compress_device(gs_index *ix, const void *d_raw, ui
   const uint32_t n_pieces = (uint32_t)np64;
   hipStream_t st = (hipStream_t)stream;
   GS_HIP(hipSetDevice(ix->device));
-  gs_status rc;
   const uint32_t grid = std::min(n_pieces, BZ_MAX_GRID);
   size_t tb = 0;
   GS_HIP(rocprim::exclusive_scan(nullptr, tb, (uint64_t *)nullptr, (uint64_t *)nullptr, 0ull, (size_t)n_pieces + 1, rocprim::plus<uint64_t>(), st));
@@ -288,14 +288,16 @@ extern "C" gs_status gs_bgzf_compress_device(gs_index *ix, const void *d_raw, ui
   const size_t t_tok = 0, t_meta = t_tok + up(4 * (size_t)grid * BZ_PIECE), t_size = t_meta + up(sizeof(bz_meta) * (size_t)n_pieces),
                t_off = t_size + up(8 * ((size_t)n_pieces + 1)), t_scan = t_off + up(8 * ((size_t)n_pieces + 1)), t_stage = t_scan + up(tb),
                t_end = t_stage + (size_t)n_pieces * BZ_STAGE;
-  if ((rc = gs_reserve(ix->w_bgzf_tmp, t_end + 16)) != GS_OK) return rc;
-  char *tmp = (char *)ix->w_bgzf_tmp.p;
+  GS_TRY(gs_reserve(ix->w_bgzf.tmp, t_end + 16));
+  char *tmp = (char *)ix->w_bgzf.tmp.p;
   bz_meta *meta = (bz_meta *)(tmp + t_meta);
   uint64_t *sizes = (uint64_t *)(tmp + t_size), *off = (uint64_t *)(tmp + t_off);
   hipLaunchKernelGGL(k_bgzf_piece, dim3(grid), dim3(WAVE), 0, st, (const uint8_t *)d_raw, raw_len, n_pieces, (uint32_t *)(tmp + t_tok),
                      (uint8_t *)(tmp + t_stage), meta);
   hipLaunchKernelGGL(k_bgzf_sizes, dim3(n_pieces / 256 + 1), dim3(256), 0, st, (const bz_meta *)meta, n_pieces, sizes);
-  GS_HIP(rocprim::exclusive_scan(tmp + t_scan, tb, sizes, off, 0ull, (size_t)n_pieces + 1, rocprim::plus<uint64_t>(), st));
+  GS_TRY(gs_prim_carved("gs_bgzf_compress: scan of the pieces' sizes", tmp + t_scan, tb, [&](void *t, size_t &b) {
+    return rocprim::exclusive_scan(t, b, sizes, off, 0ull, (size_t)n_pieces + 1, rocprim::plus<uint64_t>(), st);
+  }));
   uint64_t total = 0;
   GS_HIP(hipMemcpyAsync(&total, off + n_pieces, 8, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
@@ -304,12 +306,12 @@ extern "C" gs_status gs_bgzf_compress_device(gs_index *ix, const void *d_raw, ui
     gs_set_error("gs_bgzf_compress_device: internal: the members' sizes do not add up");
     return GS_ERR_DEVICE;
   }
-  if ((rc = gs_reserve(ix->w_bgzf_out, total + 16)) != GS_OK) return rc;
+  GS_TRY(gs_reserve(ix->w_bgzf.out, total + 16));
   hipLaunchKernelGGL(k_bgzf_pack, dim3(n_pieces), dim3(256), 0, st, (const uint8_t *)d_raw, raw_len, (const uint8_t *)(tmp + t_stage),
-                     (const bz_meta *)meta, (const uint64_t *)off, (uint8_t *)ix->w_bgzf_out.p);
+                     (const bz_meta *)meta, (const uint64_t *)off, (uint8_t *)ix->w_bgzf.out.p);
   GS_HIP(hipStreamSynchronize(st));
   GS_HIP(hipGetLastError());
-  *d_out = ix->w_bgzf_out.p;
+  *d_out = ix->w_bgzf.out.p;
   *out_len = total;
   return GS_OK;
 }
@@ -322,11 +324,11 @@ extern "C" gs_status gs_bgzf_compress(gs_index *ix, const void *raw, uint64_t ra
   if (raw_len == 0) return GS_OK;
   GS_HIP(hipSetDevice(ix->device));
   gs_status rc;
-  if ((rc = gs_reserve(ix->w_bgzf_in, raw_len + 16)) != GS_OK) return rc;
-  GS_HIP(hipMemcpy(ix->w_bgzf_in.p, raw, raw_len, hipMemcpyHostToDevice));
+  GS_TRY(gs_reserve(ix->w_bgzf.in, raw_len + 16));
+  GS_HIP(hipMemcpy(ix->w_bgzf.in.p, raw, raw_len, hipMemcpyHostToDevice));
   const void *d_out = nullptr;
   uint64_t n = 0;
-  if ((rc = gs_bgzf_compress_device(ix, ix->w_bgzf_in.p, raw_len, nullptr, &d_out, &n)) != GS_OK) return rc;
+  if ((rc = gs_bgzf_compress_device(ix, ix->w_bgzf.in.p, raw_len, nullptr, &d_out, &n)) != GS_OK) return rc;
   uint8_t *o = (uint8_t *)malloc(n ? n : 1);
   if (!o) return GS_ERR_NOMEM;
   if (hipMemcpy(o, d_out, n, hipMemcpyDeviceToHost) != hipSuccess) {

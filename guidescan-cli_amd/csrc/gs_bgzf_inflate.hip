@@ -154,17 +154,17 @@ gs_status bi_run(const char *who, int device, gs_buffer &w_in, gs_buffer &w_tmp,
   std::vector<bi_member> tab;
   std::vector<uint64_t> file_off;
   uint64_t total = 0;
-  gs_status rc = bi_table(who, bgzf, len, keep, base_member, base_byte, tab, file_off, &total);
-  if (rc != GS_OK) return rc;
+  GS_TRY(bi_table(who, bgzf, len, keep, base_member, base_byte, tab, file_off, &total));
   if (tab.size() >= (1ull << 31)) return GS_ERR_UNSUPPORTED;
   const uint32_t n = (uint32_t)tab.size();
   hipStream_t st = nullptr;
   GS_HIP(hipSetDevice(device));
-  if ((rc = gs_reserve(w_out, keep + total + 16)) != GS_OK) return rc;
+  GS_TRY(gs_reserve(w_out, keep + total + 16));
   if (keep) GS_HIP(hipMemcpyAsync(w_out.p, d_keep, keep, hipMemcpyDeviceToDevice, st));
   if (n) {
     const size_t t_bytes = sizeof(bi_member) * (size_t)n, t_reason = (t_bytes + 255) & ~(size_t)255;
-    if ((rc = gs_reserve(w_in, len + BI_PAD)) != GS_OK || (rc = gs_reserve(w_tmp, t_reason + 4 * (size_t)n + 16)) != GS_OK) return rc;
+    GS_TRY(gs_reserve(w_in, len + BI_PAD));
+    GS_TRY(gs_reserve(w_tmp, t_reason + 4 * (size_t)n + 16));
     uint32_t *d_reason = (uint32_t *)((char *)w_tmp.p + t_reason);
     GS_HIP(hipMemcpyAsync(w_in.p, bgzf, len, hipMemcpyHostToDevice, st));
     GS_HIP(hipMemsetAsync((char *)w_in.p + len, 0, BI_PAD, st));
@@ -226,7 +226,7 @@ extern "C" gs_status gs_bgzf_inflate(int device, const void *bgzf, uint64_t len,
   if (!out || !out_len || (len && !bgzf)) return GS_ERR_ARG;
   *out = nullptr;
   *out_len = 0;
-  gs_buffer w_in, w_tmp, w_out;
+  gs_buffer w_in, w_tmp, w_out; /* freed on every way out */
   gs_status rc;
   uint64_t n = 0;
   uint8_t *o = nullptr;
@@ -240,9 +240,6 @@ extern "C" gs_status gs_bgzf_inflate(int device, const void *bgzf, uint64_t len,
     gs_set_error("gs_bgzf_inflate: copying the bytes back failed");
     rc = GS_ERR_DEVICE;
   }
-  gs_buffer_free(w_in);
-  gs_buffer_free(w_tmp);
-  gs_buffer_free(w_out);
   if (rc != GS_OK) {
     free(o);
     return rc;

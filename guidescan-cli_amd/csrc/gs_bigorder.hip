@@ -4,6 +4,7 @@
  * the batch pipeline in gs_enumerate.hip).
  */
 #include "gs_kernels.h"
+#include "gs_scratch.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -399,7 +400,7 @@ bool gs_bigorder_fits(uint32_t L, uint32_t P, uint32_t m, uint32_t n_set) {
   return guide_bits(n_set) + 4 + rbits <= 64;
 }
 gs_status gs_add_matches(gs_index *ix, unsigned long long add) {
-  unsigned long long *d = gs_misc_stats(ix->w_misc.p) + ST_MATCHES, cur = 0;
+  unsigned long long *d = gs_misc_stats(ix->w_batch.misc.p) + ST_MATCHES, cur = 0;
   GS_HIP(hipMemcpy(&cur, d, 8, hipMemcpyDeviceToHost));
   cur += add;
   GS_HIP(hipMemcpy(d, &cur, 8, hipMemcpyHostToDevice));
@@ -409,12 +410,11 @@ gs_status gs_add_matches(gs_index *ix, unsigned long long add) {
 /* compaction, sorts and flags of the T records: out.s2 holds them in final order, out.wfinal their sort words */
 static gs_status big2_sort(gs_index *ix, const gs_bigorder_in &in, hipStream_t st, gs_big2_compact_args &ca, uint64_t T,
                            uint32_t wbits, gs_bigorder_out &out) {
-  gs_status r2;
-  unsigned long long *W = ca.W, *Wb = (unsigned long long *)ix->w_b_w0b.p;
-  uint32_t *idx = ca.idx, *idxb = (uint32_t *)ix->w_b_idxb.p;
-  uint32_t *rk = ca.rowkey, *rkb = (uint32_t *)ix->w_b_keeps.p;
+  unsigned long long *W = ca.W, *Wb = (unsigned long long *)ix->w_big.w0b.p;
+  uint32_t *idx = ca.idx, *idxb = (uint32_t *)ix->w_big.idxb.p;
+  uint32_t *rk = ca.rowkey, *rkb = (uint32_t *)ix->w_big.keeps.p;
   uint4 *recs = ca.recs, *S2 = (uint4 *)out.s2;
-  uint32_t *d_scratch = gs_misc_work(ix->w_misc.p) + WK_BIG_SCRATCH;
+  uint32_t *d_scratch = gs_misc_work(ix->w_batch.misc.p) + WK_BIG_SCRATCH;
   /* Long runs of one sequence (a repeat-rich genome; the handle remembers having seen one): ONE sort by
    * (word << b | low b bits of the first row), b = what 64 bits leave, instead of a sort by row and a
    * stable one by word; the runs it leaves out of order (k_big2_wraps) are put right one by one
@@ -434,11 +434,12 @@ static gs_status big2_sort(gs_index *ix, const gs_bigorder_in &in, hipStream_t s
   ca.row_bits = rowb;
   ca.row_off = gs_opt(ix, "GS_BIG2_ROWOFF") ? (uint32_t)atol(gs_opt(ix, "GS_BIG2_ROWOFF")) : 0u;
   hipLaunchKernelGGL(k_big2_compact, dim3(ca.n_items + (in.from_arena ? in.n_used : 0u)), dim3(256), 0, st, ca);
-  size_t s1 = 0, s2 = 0, s3 = 0, tbs = 0;
-  GS_HIP(rocprim::radix_sort_pairs(nullptr, s1, rk, rkb, idx, idxb, (size_t)T, 0, 32, st));
-  GS_HIP(rocprim::radix_sort_pairs(nullptr, s2, Wb, W, idxb, idx, (size_t)T, 0, wbits, st));
-  GS_HIP(rocprim::radix_sort_pairs(nullptr, s3, Wb, W, idxb, idx, (size_t)T, 0, 64, st));
-  if ((r2 = gs_reserve(ix->w_h_tmp, std::max(std::max(s1, s2), s3) + 16)) != GS_OK) return r2;
+  /* a stable sort of T (key, index) pairs by the key's low `key_bits` bits */
+  auto sort = [&](auto *k_in, auto *k_out, uint32_t *v_in, uint32_t *v_out, unsigned key_bits) {
+    return gs_prim("device-wide ordering: sort", ix->w_batch.h_tmp, [&](void *t, size_t &tb) {
+      return rocprim::radix_sort_pairs(t, tb, k_in, k_out, v_in, v_out, (size_t)T, 0, key_bits, st);
+    });
+  };
   const unsigned gT = (unsigned)((T + 255) / 256);
   const unsigned long long *W_final = nullptr;
   const uint32_t *idx_final = nullptr;
@@ -450,8 +451,7 @@ static gs_status big2_sort(gs_index *ix, const gs_bigorder_in &in, hipStream_t s
   uint32_t short_max = 32;
   if (const char *e = gs_opt(ix, "GS_BIG2_SHORT")) short_max = (uint32_t)std::max(1l, atol(e));
   if (!two_from_start) {
-    tbs = ix->w_h_tmp.cap;
-    GS_HIP(rocprim::radix_sort_pairs(ix->w_h_tmp.p, tbs, W, Wb, idx, idxb, (size_t)T, 0, wbits, st));
+    GS_TRY(sort(W, Wb, idx, idxb, wbits));
     GS_HIP(hipMemsetAsync(d_scratch, 0, 4, st));
     hipLaunchKernelGGL(k_big2_runs, dim3(gT), dim3(256), 0, st, (const unsigned long long *)Wb, (const uint32_t *)idxb,
                        (const uint4 *)recs, T, short_max, idx, d_scratch);
@@ -474,19 +474,16 @@ static gs_status big2_sort(gs_index *ix, const gs_bigorder_in &in, hipStream_t s
   }
   if (!W_final && rowb) {
     unsigned long long *src = comp_in_wb ? Wb : W, *dst = comp_in_wb ? W : Wb;
-    tbs = ix->w_h_tmp.cap;
-    GS_HIP(rocprim::radix_sort_pairs(ix->w_h_tmp.p, tbs, src, dst, idx, idxb, (size_t)T, 0, wbits + rowb, st));
+    GS_TRY(sort(src, dst, idx, idxb, wbits + rowb));
     W_final = dst;
     idx_final = idxb;
     wshift = rowb;
     out.comp = true;
   }
   if (!W_final) {
-    tbs = ix->w_h_tmp.cap;
-    GS_HIP(rocprim::radix_sort_pairs(ix->w_h_tmp.p, tbs, rk, rkb, idx, idxb, (size_t)T, 0, 32, st));
+    GS_TRY(sort(rk, rkb, idx, idxb, 32));
     hipLaunchKernelGGL(k_big2_gather_w, dim3(gT), dim3(256), 0, st, (const unsigned long long *)W, (const uint32_t *)idxb, T, Wb);
-    tbs = ix->w_h_tmp.cap;
-    GS_HIP(rocprim::radix_sort_pairs(ix->w_h_tmp.p, tbs, Wb, W, idxb, idx, (size_t)T, 0, wbits, st));
+    GS_TRY(sort(Wb, W, idxb, idx, wbits));
     W_final = W;
     idx_final = idx;
   }
@@ -497,15 +494,15 @@ static gs_status big2_sort(gs_index *ix, const gs_bigorder_in &in, hipStream_t s
   if (wshift && (wshift < 32 || ca.row_off != 0)) {
     /* the descents go into the array the flags' row counts are written to afterwards, the claims into the
      * flags' own; each run that shows one is put in order through the unordered records' array */
-    uint32_t h_n = 0, *list = (uint32_t *)ix->w_b_rows.p;
+    uint32_t h_n = 0, *list = (uint32_t *)ix->w_big.rows.p;
     GS_HIP(hipMemsetAsync(d_scratch, 0, 4, st));
     hipLaunchKernelGGL(k_big2_wraps, dim3(gT), dim3(256), 0, st, (const uint4 *)S2, W_final, T, wshift, list, d_scratch);
     GS_HIP(hipMemcpyAsync(&h_n, d_scratch, 4, hipMemcpyDeviceToHost, st));
     GS_HIP(hipStreamSynchronize(st));
     if (h_n) {
-      GS_HIP(hipMemsetAsync(ix->w_b_keep.p, 0, 4 * (size_t)(T + 1), st));
+      GS_HIP(hipMemsetAsync(ix->w_big.keep.p, 0, 4 * (size_t)(T + 1), st));
       hipLaunchKernelGGL(k_big2_fixruns, dim3(std::min<uint32_t>(h_n, 8192u)), dim3(256), 0, st, S2, recs, W_final, T, wshift,
-                         ca.row_off, (const uint32_t *)list, h_n, (uint32_t *)ix->w_b_keep.p);
+                         ca.row_off, (const uint32_t *)list, h_n, (uint32_t *)ix->w_big.keep.p);
     }
     out.fixed += h_n;
     if (gs_opt(ix, "GS_DEBUG"))
@@ -513,34 +510,28 @@ static gs_status big2_sort(gs_index *ix, const gs_bigorder_in &in, hipStream_t s
               (unsigned long long)T, wbits, wshift, h_n);
   }
   hipLaunchKernelGGL(k_big2_flags, dim3(gT), dim3(256), 0, st, (const uint4 *)S2, W_final, T,
-                     (uint32_t *)ix->w_b_keep.p, (unsigned long long *)ix->w_b_rows.p, wshift);
+                     (uint32_t *)ix->w_big.keep.p, (unsigned long long *)ix->w_big.rows.p, wshift);
   return GS_OK;
 }
 
 gs_status gs_bigorder_run(gs_index *ix, const gs_bigorder_in &in, hipStream_t st, gs_bigorder_out &out) {
-  gs_status r2;
   const uint32_t n_it = 2 * in.n_set;
-  if ((r2 = gs_reserve(ix->w_b_src, sizeof(gs_big_src) * ((size_t)n_it + 1))) != GS_OK) return r2;
-  if ((r2 = gs_reserve(ix->w_b_cnt, 8 * ((size_t)n_it + 2))) != GS_OK) return r2;
-  if ((r2 = gs_reserve(ix->w_b_prefix, 8 * ((size_t)n_it + 2))) != GS_OK) return r2;
+  GS_TRY(gs_reserve(ix->w_big.src, sizeof(gs_big_src) * ((size_t)n_it + 1)));
+  GS_TRY(gs_reserve(ix->w_big.cnt, 8 * ((size_t)n_it + 2)));
+  GS_TRY(gs_reserve(ix->w_big.prefix, 8 * ((size_t)n_it + 2)));
   if (in.from_arena)
-    hipLaunchKernelGGL(k_big2_counts, dim3((n_it + 255) / 256), dim3(256), 0, st, (const uint32_t *)ix->w_counts.p, in.arena_list,
-                       n_it, (unsigned long long *)ix->w_b_cnt.p);
+    hipLaunchKernelGGL(k_big2_counts, dim3((n_it + 255) / 256), dim3(256), 0, st, (const uint32_t *)ix->w_batch.counts.p, in.arena_list,
+                       n_it, (unsigned long long *)ix->w_big.cnt.p);
   else
     hipLaunchKernelGGL(k_big_sources, dim3((n_it + 255) / 256), dim3(256), 0, st, in.counts_main, in.redo_pos, in.slot_off2,
-                       in.counts2, n_it, in.cap_main, (gs_big_src *)ix->w_b_src.p, (unsigned long long *)ix->w_b_cnt.p);
-  GS_HIP(hipMemsetAsync((unsigned long long *)ix->w_b_cnt.p + n_it, 0, 8, st));
-  size_t tb = 0;
-  GS_HIP(rocprim::exclusive_scan(nullptr, tb, (unsigned long long *)ix->w_b_cnt.p,
-                                 (unsigned long long *)ix->w_b_prefix.p, 0ull, (size_t)n_it + 1,
-                                 rocprim::plus<unsigned long long>(), st));
-  if ((r2 = gs_reserve(ix->w_h_tmp, tb + 16)) != GS_OK) return r2;
-  size_t tbs = ix->w_h_tmp.cap;
-  GS_HIP(rocprim::exclusive_scan(ix->w_h_tmp.p, tbs, (unsigned long long *)ix->w_b_cnt.p,
-                                 (unsigned long long *)ix->w_b_prefix.p, 0ull, (size_t)n_it + 1,
-                                 rocprim::plus<unsigned long long>(), st));
+                       in.counts2, n_it, in.cap_main, (gs_big_src *)ix->w_big.src.p, (unsigned long long *)ix->w_big.cnt.p);
+  GS_HIP(hipMemsetAsync((unsigned long long *)ix->w_big.cnt.p + n_it, 0, 8, st));
+  GS_TRY(gs_prim("device-wide ordering: scan of the items' records", ix->w_batch.h_tmp, [&](void *t, size_t &tb) {
+    return rocprim::exclusive_scan(t, tb, (unsigned long long *)ix->w_big.cnt.p, (unsigned long long *)ix->w_big.prefix.p, 0ull,
+                                   (size_t)n_it + 1, rocprim::plus<unsigned long long>(), st);
+  }));
   unsigned long long T = 0;
-  GS_HIP(hipMemcpyAsync(&T, (unsigned long long *)ix->w_b_prefix.p + n_it, 8, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipMemcpyAsync(&T, (unsigned long long *)ix->w_big.prefix.p + n_it, 8, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   if (T >= (1ull << 32) - 2) {
     gs_set_error("more than 2^32 match records in one batch: use smaller batches at this mismatch budget");
@@ -556,78 +547,70 @@ gs_status gs_bigorder_run(gs_index *ix, const gs_bigorder_in &in, hipStream_t st
     gs_set_error("the device-wide ordering's sort word (guide, class, sequence rank) does not fit 64 bits: use smaller batches");
     return GS_ERR_UNSUPPORTED;
   }
-  if ((r2 = gs_reserve(ix->w_b_recs, 16 * (T + 1))) != GS_OK) return r2;
-  if ((r2 = gs_reserve(ix->w_b_w0, 8 * (T + 1))) != GS_OK) return r2;
-  if ((r2 = gs_reserve(ix->w_b_w0b, 8 * (T + 1))) != GS_OK) return r2;
-  if ((r2 = gs_reserve(ix->w_b_idx, 4 * (T + 1))) != GS_OK) return r2;
-  if ((r2 = gs_reserve(ix->w_b_idxb, 4 * (T + 1))) != GS_OK) return r2;
-  if ((r2 = gs_reserve(ix->w_b_keep, 4 * (T + 2))) != GS_OK) return r2;
-  if ((r2 = gs_reserve(ix->w_b_keeps, 4 * (T + 2))) != GS_OK) return r2;
-  if ((r2 = gs_reserve(ix->w_b_rows, 8 * (T + 2))) != GS_OK) return r2;
-  if ((r2 = gs_reserve(ix->w_b_rowss, 8 * (T + 2))) != GS_OK) return r2;
+  GS_TRY(gs_reserve(ix->w_big.recs, 16 * (T + 1)));
+  GS_TRY(gs_reserve(ix->w_big.w0, 8 * (T + 1)));
+  GS_TRY(gs_reserve(ix->w_big.w0b, 8 * (T + 1)));
+  GS_TRY(gs_reserve(ix->w_big.idx, 4 * (T + 1)));
+  GS_TRY(gs_reserve(ix->w_big.idxb, 4 * (T + 1)));
+  GS_TRY(gs_reserve(ix->w_big.keep, 4 * (T + 2)));
+  GS_TRY(gs_reserve(ix->w_big.keeps, 4 * (T + 2)));
+  GS_TRY(gs_reserve(ix->w_big.rows, 8 * (T + 2)));
+  GS_TRY(gs_reserve(ix->w_big.rowss, 8 * (T + 2)));
   out.gshift = 4 + rbits;
   if (T) {
     /* the records in final order go where the arena's chunks were (read for the last time by the
      * compaction) when they fit there: 16 bytes per record less next to a 220 GB index */
-    const bool s2_in_arena = in.from_arena && ix->w_arena.cap >= 16 * (T + 1);
-    if (!s2_in_arena && (r2 = gs_reserve(ix->w_b_s, 16 * (T + 1))) != GS_OK) return r2;
-    out.s2 = s2_in_arena ? ix->w_arena.p : ix->w_b_s.p;
-    if ((r2 = gs_reserve(ix->w_b_tab, sizeof(gs_big2_tab))) != GS_OK) return r2;
-    GS_HIP(hipMemcpy(ix->w_b_tab.p, &tab, sizeof(tab), hipMemcpyHostToDevice));
+    const bool s2_in_arena = in.from_arena && ix->w_batch.arena.cap >= 16 * (T + 1);
+    if (!s2_in_arena) GS_TRY(gs_reserve(ix->w_big.s, 16 * (T + 1)));
+    out.s2 = s2_in_arena ? ix->w_batch.arena.p : ix->w_big.s.p;
+    GS_TRY(gs_reserve(ix->w_big.tab, sizeof(gs_big2_tab)));
+    GS_HIP(hipMemcpy(ix->w_big.tab.p, &tab, sizeof(tab), hipMemcpyHostToDevice));
     gs_big2_compact_args ca;
     memset(&ca, 0, sizeof(ca));
-    ca.slots_main = (const uint4 *)ix->w_slots.p;
-    ca.slots_alt = (const uint4 *)ix->w_slots2.p;
-    ca.src = (const gs_big_src *)ix->w_b_src.p;
+    ca.slots_main = (const uint4 *)ix->w_batch.slots.p;
+    ca.slots_alt = (const uint4 *)ix->w_batch.slots2.p;
+    ca.src = (const gs_big_src *)ix->w_big.src.p;
     if (in.from_arena) {
       ca.from_arena = 1;
-      ca.arena = (const uint4 *)ix->w_arena.p;
-      ca.chunk_item = (const uint32_t *)ix->w_arena_meta.p;
+      ca.arena = (const uint4 *)ix->w_batch.arena.p;
+      ca.chunk_item = (const uint32_t *)ix->w_batch.arena_meta.p;
       ca.chunk_seq = ca.chunk_item + in.arena_chunks;
-      ca.counts = (const uint32_t *)ix->w_counts.p;
+      ca.counts = (const uint32_t *)ix->w_batch.counts.p;
       ca.list = in.arena_list;
-      ca.redo_pos = in.arena_redo_pos ? in.arena_redo_pos : (const uint32_t *)ix->w_b_redo_pos.p;
+      ca.redo_pos = in.arena_redo_pos ? in.arena_redo_pos : (const uint32_t *)ix->w_big.redo_pos.p;
       ca.cap = in.cap;
       ca.n_used = in.n_used;
     }
-    ca.prefix = (const unsigned long long *)ix->w_b_prefix.p;
-    ca.tab = (const gs_big2_tab *)ix->w_b_tab.p;
-    ca.recs = (uint4 *)ix->w_b_recs.p;
-    ca.W = (unsigned long long *)ix->w_b_w0.p;
-    ca.rowkey = (uint32_t *)ix->w_b_keep.p; /* free until the flags are written */
-    ca.idx = (uint32_t *)ix->w_b_idx.p;
+    ca.prefix = (const unsigned long long *)ix->w_big.prefix.p;
+    ca.tab = (const gs_big2_tab *)ix->w_big.tab.p;
+    ca.recs = (uint4 *)ix->w_big.recs.p;
+    ca.W = (unsigned long long *)ix->w_big.w0.p;
+    ca.rowkey = (uint32_t *)ix->w_big.keep.p; /* free until the flags are written */
+    ca.idx = (uint32_t *)ix->w_big.idx.p;
     ca.pam_mul = pam_mul;
     ca.n_items = n_it;
     ca.L = in.L;
     ca.P = in.P;
     ca.rbits = rbits;
-    if ((r2 = big2_sort(ix, in, st, ca, T, gbits + 4 + rbits, out)) != GS_OK) return r2;
+    GS_TRY(big2_sort(ix, in, st, ca, T, gbits + 4 + rbits, out));
   }
-  GS_HIP(hipMemsetAsync((uint32_t *)ix->w_b_keep.p + T, 0, 4, st));
-  GS_HIP(hipMemsetAsync((unsigned long long *)ix->w_b_rows.p + T, 0, 8, st));
-  {
-    size_t s3 = 0, s4 = 0;
-    GS_HIP(rocprim::exclusive_scan(nullptr, s3, (uint32_t *)ix->w_b_keep.p, (uint32_t *)ix->w_b_keeps.p, 0u,
-                                   (size_t)T + 1, rocprim::plus<uint32_t>(), st));
-    GS_HIP(rocprim::exclusive_scan(nullptr, s4, (unsigned long long *)ix->w_b_rows.p,
-                                   (unsigned long long *)ix->w_b_rowss.p, 0ull, (size_t)T + 1,
-                                   rocprim::plus<unsigned long long>(), st));
-    if ((r2 = gs_reserve(ix->w_h_tmp, (s3 > s4 ? s3 : s4) + 16)) != GS_OK) return r2;
-    tbs = ix->w_h_tmp.cap;
-    GS_HIP(rocprim::exclusive_scan(ix->w_h_tmp.p, tbs, (uint32_t *)ix->w_b_keep.p, (uint32_t *)ix->w_b_keeps.p,
-                                   0u, (size_t)T + 1, rocprim::plus<uint32_t>(), st));
-    tbs = ix->w_h_tmp.cap;
-    GS_HIP(rocprim::exclusive_scan(ix->w_h_tmp.p, tbs, (unsigned long long *)ix->w_b_rows.p,
-                                   (unsigned long long *)ix->w_b_rowss.p, 0ull, (size_t)T + 1,
-                                   rocprim::plus<unsigned long long>(), st));
-  }
-  uint32_t *d_err = gs_misc_work(ix->w_misc.p) + WK_BIG_ERR;
+  GS_HIP(hipMemsetAsync((uint32_t *)ix->w_big.keep.p + T, 0, 4, st));
+  GS_HIP(hipMemsetAsync((unsigned long long *)ix->w_big.rows.p + T, 0, 8, st));
+  GS_TRY(gs_prim("device-wide ordering: scan of the kept records", ix->w_batch.h_tmp, [&](void *t, size_t &tb) {
+    return rocprim::exclusive_scan(t, tb, (uint32_t *)ix->w_big.keep.p, (uint32_t *)ix->w_big.keeps.p, 0u, (size_t)T + 1,
+                                   rocprim::plus<uint32_t>(), st);
+  }));
+  GS_TRY(gs_prim("device-wide ordering: scan of the rows", ix->w_batch.h_tmp, [&](void *t, size_t &tb) {
+    return rocprim::exclusive_scan(t, tb, (unsigned long long *)ix->w_big.rows.p, (unsigned long long *)ix->w_big.rowss.p, 0ull,
+                                   (size_t)T + 1, rocprim::plus<unsigned long long>(), st);
+  }));
+  uint32_t *d_err = gs_misc_work(ix->w_batch.misc.p) + WK_BIG_ERR;
   hipLaunchKernelGGL(k_big_totals, dim3((in.n_set + 255) / 256), dim3(256), 0, st,
-                     (const unsigned long long *)ix->w_b_prefix.p, (const uint32_t *)ix->w_b_keeps.p,
-                     (const unsigned long long *)ix->w_b_rowss.p, in.n_set, in.nmatch, in.nhits, d_err);
+                     (const unsigned long long *)ix->w_big.prefix.p, (const uint32_t *)ix->w_big.keeps.p,
+                     (const unsigned long long *)ix->w_big.rowss.p, in.n_set, in.nmatch, in.nhits, d_err);
   uint32_t h_err = 0, h_uq = 0;
   GS_HIP(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
-  GS_HIP(hipMemcpyAsync(&h_uq, (uint32_t *)ix->w_b_keeps.p + T, 4, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipMemcpyAsync(&h_uq, (uint32_t *)ix->w_big.keeps.p + T, 4, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   if (h_err) {
     gs_set_error("more than 2^32 hits for one guide");
@@ -643,12 +626,12 @@ void gs_bigorder_locate(gs_index *ix, const gs_bigorder_out &o, const uint32_t *
   la.sd[1] = ix->strand[1].d;
   la.S2 = (const uint4 *)o.s2;
   la.W = o.wfinal;
-  la.keep = (const uint32_t *)ix->w_b_keep.p;
-  la.row_scan = (const unsigned long long *)ix->w_b_rowss.p;
-  la.prefix = (const unsigned long long *)ix->w_b_prefix.p;
+  la.keep = (const uint32_t *)ix->w_big.keep.p;
+  la.row_scan = (const unsigned long long *)ix->w_big.rowss.p;
+  la.prefix = (const unsigned long long *)ix->w_big.prefix.p;
   la.gmap = gmap;
-  la.offsets = (const uint64_t *)ix->w_offsets.p;
-  la.hits = (gs_hit *)ix->w_hits.p;
+  la.offsets = (const uint64_t *)ix->w_batch.offsets.p;
+  la.hits = (gs_hit *)ix->w_batch.hits.p;
   la.genome_length = ix->genome_length;
   la.T = o.T;
   la.v_rem = v_rem;

@@ -115,10 +115,112 @@ struct gs_strand_dev {
   const uint32_t *C256;
 };
 
+/* A device allocation that grows on demand (gs_reserve) and is kept from call to call: a handle's or a decoder's
+ * workspace.  Frees itself; moves only.  (The owner sets its device before it lets one go.) */
 struct gs_buffer {
   void *p = nullptr;
   size_t cap = 0;
+  gs_buffer() = default;
+  gs_buffer(gs_buffer &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  gs_buffer &operator=(gs_buffer &&o) noexcept;
+  ~gs_buffer();
 };
+gs_status gs_reserve(gs_buffer &b, size_t bytes);
+/* frees the buffer (if any) and leaves it empty; returns the bytes it held */
+size_t gs_buffer_free(gs_buffer &b);
+
+/* ---- the handle's per-batch workspace, grown on demand and reused across calls: one group per unit that reserves it.
+ * each(f) names the group's buffers, f(buffer, bulk); bulk: sized by the records of a batch, so release() frees it when a
+ * batch runs out of device memory (gs_enumerate.hip: recover_release_workspace) and returns the bytes - the rest, a few
+ * words per guide or per tile, stays.  Nothing here decides what is freed with the handle: every gs_buffer frees itself. */
+template <class G>
+static inline size_t gs_ws_release(G &g) {
+  size_t freed = 0;
+  g.each([&](gs_buffer &b, bool bulk) { freed += bulk ? gs_buffer_free(b) : 0; });
+  return freed;
+}
+/* out[0..2] += buffers held, bytes held, bytes release() would free */
+template <class G>
+static inline void gs_ws_report(G &g, uint64_t *out) {
+  g.each([&](gs_buffer &b, bool bulk) {
+    if (!b.p) return;
+    out[0]++;
+    out[1] += b.cap;
+    out[2] += bulk ? b.cap : 0;
+  });
+}
+/* gs_enumerate.hip, the batch pipeline's own (its kernels: gs_search.hip, gs_seed.hip, gs_order.hip) */
+struct gs_ws_batch {
+  gs_buffer guides, slots, counts, nmatch, nhits, offsets, hits, misc, blocksums, grec, flags, raw, ovf_list, grec2, slots2,
+      counts2, nmatch2, nhits2, h_off, h_tmp,
+      /* overflow arena of k_search (gs_search.hip): records, chunk owners + sequence numbers, chunks per item */
+      arena, arena_meta, nchunk,
+      /* heavy items shared among waves (gs_search_args::shq): the package queue; counters, flags, shared-item list, sums, directory bases */
+      shq, sh_meta,
+      cls,         /* k_search's per-class counts (read by gs_tileorder.hip's plan) */
+      desc, sched, /* gs_seed.hip: descriptors per guide; work counters, histograms, the two schedules */
+      cand;        /* literal-N candidate windows: kept from batch to batch of one shape */
+  template <class F>
+  void each(F f) {
+    for (gs_buffer *b : {&slots, &hits, &slots2, &h_tmp, &arena, &shq}) f(*b, true);
+    for (gs_buffer *b : {&guides, &counts, &nmatch, &nhits, &offsets, &misc, &blocksums, &grec, &flags, &raw, &ovf_list, &grec2,
+                         &counts2, &nmatch2, &nhits2, &h_off, &arena_meta, &nchunk, &sh_meta, &cls, &desc, &sched, &cand})
+      f(*b, false);
+  }
+  size_t release() { return gs_ws_release(*this); }
+};
+/* gs_bigorder.hip: device-wide ordering of guides with more matches than an LDS sort holds */
+struct gs_ws_big {
+  gs_buffer src, cnt, prefix, recs, w0, w0b, idx, idxb, keep, keeps, rows, rowss, s, redo_pos, redo_pos2, tab;
+  template <class F>
+  void each(F f) {
+    for (gs_buffer *b : {&src, &cnt, &prefix, &recs, &w0, &w0b, &idx, &idxb, &keep, &keeps, &rows, &rowss, &s}) f(*b, true);
+    for (gs_buffer *b : {&redo_pos, &redo_pos2, &tab}) f(*b, false);
+  }
+  size_t release() { return gs_ws_release(*this); }
+};
+/* gs_tileorder.hip: per-guide ordering in LDS tiles - the plan's scans, tile descriptors, bucket space, chunk index,
+ * partitioned items, class starts, rank tables + flags, the guides beyond the tiles' reach, the spill list */
+struct gs_ws_tile {
+  gs_buffer plan, tiles, buckets, chunkof, big, rel, tab, excl, spill;
+  template <class F>
+  void each(F f) {
+    for (gs_buffer *b : {&buckets, &tiles, &chunkof, &big}) f(*b, true);
+    for (gs_buffer *b : {&plan, &rel, &tab, &excl, &spill}) f(*b, false);
+  }
+  size_t release() { return gs_ws_release(*this); }
+};
+/* gs_score.hip: score tables + chromosome prefix sums; host-pointer staging; scratch */
+struct gs_ws_score {
+  gs_buffer tab, io, tmp;
+  template <class F>
+  void each(F f) {
+    for (gs_buffer *b : {&tmp, &io}) f(*b, true);
+    f(tab, false);
+  }
+  size_t release() { return gs_ws_release(*this); }
+};
+/* gs_textdev.hip: what gs_format_device uploads, its scratch, the of:H: fields, the text it returns; gs_enumerate_text's
+ * specificities (gs_host.hip); per-guide text offsets */
+struct gs_ws_text {
+  gs_buffer in, tmp, hex, text, spec, goff;
+  template <class F>
+  void each(F f) {
+    for (gs_buffer *b : {&tmp, &hex, &text}) f(*b, true);
+    for (gs_buffer *b : {&in, &spec, &goff}) f(*b, false);
+  }
+  size_t release() { return gs_ws_release(*this); }
+};
+/* gs_bgzf.hip: what gs_bgzf_compress uploads; token lists, sizes and the pieces' streams; the members it returns */
+struct gs_ws_bgzf {
+  gs_buffer in, tmp, out;
+  template <class F>
+  void each(F f) {
+    for (gs_buffer *b : {&in, &tmp, &out}) f(*b, false);
+  }
+  size_t release() { return gs_ws_release(*this); }
+};
+#define GS_WS_GROUPS 6
 
 /* The device arrays a handle keeps between calls (a strand's, a PAM-pair slot's): each with the bytes it counts for in
  * gs_index_device_bytes - what the fit estimates reckon with, not the allocation's size.  Frees them when it goes.
@@ -228,25 +330,13 @@ struct gs_index {
   int device = 0;
   uint64_t genome_length = 0;
   gs_strand strand[2];
-  /* per-handle workspace, grown on demand, reused across calls */
-  gs_buffer w_guides, w_slots, w_counts, w_nmatch, w_nhits, w_offsets, w_hits, w_misc, w_blocksums,
-      w_grec, w_flags, w_raw, w_ovf_list, w_grec2, w_slots2, w_counts2, w_nmatch2, w_nhits2, w_h_off, w_h_tmp,
-      /* device-wide ordering of guides with more matches than an LDS sort holds (gs_search.hip) */
-      w_b_src, w_b_cnt, w_b_prefix, w_b_recs, w_b_w0, w_b_w0b, w_b_idx, w_b_idxb, w_b_keep, w_b_keeps,
-      w_b_rows, w_b_rowss, w_b_redo_pos, w_b_s, w_b_tab,
-      w_score, w_score_io, w_score_tmp, /* gs_score.hip: score tables + chromosome prefix sums; host-pointer staging */
-      /* overflow arena of k_search (gs_search.hip): records, chunk owners + sequence numbers, chunks per item */
-      w_arena, w_arena_meta, w_nchunk,
-      /* heavy items shared among waves (gs_search_args::shq): the package queue; counters, flags, shared-item list, sums, directory bases */
-      w_shq, w_sh_meta,
-      /* per-guide ordering in LDS tiles (gs_tileorder.hip): k_search's per-class counts, the plan's scans, tile
-       * descriptors, bucket space, chunk index, partitioned items, class starts, rank tables + flags */
-      w_cls, w_desc, w_sched, /* gs_seed.hip: descriptors per guide; work counters, histograms, the two schedules */
-      w_t_plan, w_t_tiles, w_t_buckets, w_t_chunkof, w_t_big, w_t_rel, w_t_tab, w_t_excl, w_t_spill, w_b_redo_pos2,
-      /* gs_textdev.hip: what gs_format_device uploads, its scratch, the of:H: fields, the text it returns; gs_enumerate_text's specificities */
-      w_text_in, w_text_tmp, w_text_hex, w_text, w_text_spec, w_text_goff /* per-guide text offsets */,
-      /* gs_bgzf.hip: what gs_bgzf_compress uploads; token lists, sizes and the pieces' streams; the members it returns */
-      w_bgzf_in, w_bgzf_tmp, w_bgzf_out;
+  /* per-handle workspace (above), grown on demand, reused across calls */
+  gs_ws_batch w_batch;
+  gs_ws_big w_big;
+  gs_ws_tile w_tile;
+  gs_ws_score w_score;
+  gs_ws_text w_text;
+  gs_ws_bgzf w_bgzf;
   uint32_t share_backoff = 0; /* batches this handle still runs without sharing after a sharing launch was not resident as a whole */
   bool share_timed_out = false; /* a helping wave gave up waiting for a package (k_search_body): the call fails, gs_enumerate_device redoes the batch without sharing */
   uint32_t opt_share_min = 512, opt_share_max = 2048; /* groups of eight rows: a verification pass of share_min or more is handed out, in packages of at most share_max (0: items are never shared) */
@@ -260,8 +350,8 @@ struct gs_index {
     uint64_t key = 0;
   };
   std::array<seen_t, 8> seen;
-  bool last_raw_valid = false;   /* w_raw holds the raw hit counts of the last batch (GS_FLAG_RAW_COUNTS) */
-  uint64_t last_unsupported = 0; /* guides of the last batch flagged GS_GUIDE_NEEDS_GENERAL (w_flags) */
+  bool last_raw_valid = false;   /* w_batch.raw holds the raw hit counts of the last batch (GS_FLAG_RAW_COUNTS) */
+  uint64_t last_unsupported = 0; /* guides of the last batch flagged GS_GUIDE_NEEDS_GENERAL (w_batch.flags) */
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_tile = nullptr;  /* gs_tileorder_run: behind the copy of the slow-tile counts */
   hipStream_t st_help = nullptr; /* lowest priority: the launch that runs published packages next to the search launch (run_search) */
@@ -281,8 +371,7 @@ struct gs_index {
    * walked, seeds looked up, seeds with an empty interval, row nodes made, interval nodes made, exception-row lookups, largest stack */
   unsigned long long last_bulge[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   std::vector<gs_nrun> nruns_text; /* 'N' runs of the forward text */
-  gs_buffer w_cand;                /* literal-N candidate windows (device): kept from batch to batch of one shape */
-  uint64_t cand_key = ~0ull;       /* (L, P, bucketed or not) w_cand was made for; ~0: nothing kept */
+  uint64_t cand_key = ~0ull;       /* (L, P, bucketed or not) w_batch.cand was made for; ~0: nothing kept */
   uint32_t cand_n[2] = {0, 0};     /* windows per strand */
   size_t cand_bidx[2] = {0, 0};    /* words of each strand's bucket index behind them */
   /* seed recipes of the last two (budget, geometry, thresholds) - the CLI's --threshold pass alternates two
@@ -301,8 +390,8 @@ struct gs_index {
   uint32_t dbg_nomem = 0;   /* GS_DBG_NOMEM (tests of those recoveries): passes of a batch that still end as if out of device memory */
   bool tile_order_off = false; /* a batch had interval records or one sequence at one row twice: the per-guide tile ordering is not tried again for that shape */
   uint64_t tile_order_off_key = 0;
-  uint64_t tx_n = 0; /* gs_textdev.hip: guides of the last gs_format_device, whose per-guide text offsets w_text_goff holds (0: none) */
-  bool big_long_runs = false; /* a batch showed long runs of one sequence (repeat-rich genome): the device-wide ordering sorts by row, then by word (gs_search.hip) */
+  uint64_t tx_n = 0; /* gs_textdev.hip: guides of the last gs_format_device, whose per-guide text offsets w_text.goff holds (0: none) */
+  bool big_long_runs = false; /* a batch showed long runs of one sequence (repeat-rich genome): the device-wide ordering sorts by row, then by word (gs_bigorder.hip) */
 };
 
 /* make sure slot `slot` holds the tables of pair `code` at context depth v_rem with rotated copies from
@@ -342,7 +431,7 @@ struct gs_tileorder_in {
 struct gs_tileorder_state {
   uint32_t n_it = 0, n_tiles = 0, n_btiles = 0, n_chunks = 0, n_big = 0, n_deal = 0;
   uint32_t spill_units = 0, spill_cap = 0; /* bucket units kept for the buckets that outgrow their slots; records the spill list holds */
-  uint32_t n_excl = 0; /* guides with an item beyond the tiles' reach (ix->w_t_excl lists them): ordered device-wide by the caller */
+  uint32_t n_excl = 0; /* guides with an item beyond the tiles' reach (ix->w_tile.excl lists them): ordered device-wide by the caller */
   uint64_t n_records = 0; /* records of the set (set by gs_tileorder_run) */
 };
 /* does the sort word (class base + rank of the sequence, then the row) fit 64 bits? */
@@ -367,16 +456,19 @@ gs_status gs_tileorder_run(gs_index *ix, const gs_tileorder_in &in, gs_tileorder
     }                                                                             \
   } while (0)
 
+#define GS_TRY(expr)                 \
+  do {                               \
+    gs_status rc__ = (expr);         \
+    if (rc__ != GS_OK) return rc__;  \
+  } while (0)
+
 void gs_set_error(const std::string &s);
 /* value of switch `key` on this handle, or nullptr (gs_index::opts) */
 const char *gs_opt(const gs_index *ix, const char *key);
 void gs_opts_from_env(gs_index *ix);
 extern std::atomic<int> gs_debug_any; /* some handle has GS_DEBUG set: the allocator reports large growth */
-gs_status gs_reserve(gs_buffer &b, size_t bytes);
 /* gs_host.hip: tl bytes of text in HBM -> *text, malloc'ed and NUL terminated, through page-locked staging */
 gs_status gs_text_to_host(const void *d_text, uint64_t tl, char **text);
-/* frees the buffer (if any) and leaves it empty; returns the bytes it held */
-size_t gs_buffer_free(gs_buffer &b);
 
 /* GPU suffix array: d_text (n bytes incl. sentinel) -> d_sa (n uint32) */
 gs_status gs_device_suffix_array(const uint8_t *d_text, uint64_t n, uint32_t *d_sa, hipStream_t st);

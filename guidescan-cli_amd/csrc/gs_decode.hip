@@ -37,6 +37,7 @@
 #include "gs_pow5_table.h"
 #include "gs_repr.h"
 #include "gs_decoder.h"
+#include "gs_scratch.h"
 
 #define DC_WAVES 4
 #define DC_LDS 12288u         /* bytes of a wave's slice */
@@ -604,17 +605,6 @@ gs_status gs_decoder_open_text(int device, const uint8_t *text, uint64_t len, in
 extern "C" void gs_decoder_close(gs_decoder *d) {
   if (!d) return;
   (void)hipSetDevice(d->device);
-  gs_buffer_free(d->text);
-  gs_buffer_free(d->tabs);
-  gs_buffer_free(d->w_in);
-  gs_buffer_free(d->w_tmp);
-  gs_buffer_free(d->w_text);
-  gs_buffer_free(d->w_bi_in);
-  gs_buffer_free(d->w_bi_tmp);
-  gs_buffer_free(d->w_inf[0]);
-  gs_buffer_free(d->w_inf[1]);
-  gs_buffer_free(d->w_bs_tmp);
-  gs_buffer_free(d->w_bs_rec);
   delete d;
 }
 
@@ -628,7 +618,6 @@ static gs_status decode_device(gs_decoder *d, const gs_decode_batch *b, uint32_t
   if (n >= (1ull << 31)) return GS_ERR_UNSUPPORTED;
   hipStream_t st = nullptr;
   GS_HIP(hipSetDevice(d->device));
-  gs_status rc;
   /* the words of each record: whole groups of 16 digits (what is left over fails on the device, with the record) */
   std::vector<uint64_t> word_off(n + 1, 0);
   for (uint64_t r = 0; r < n; r++) {
@@ -661,7 +650,7 @@ static gs_status decode_device(gs_decoder *d, const gs_decode_batch *b, uint32_t
     if (idb) memcpy(host.data() + i_ids, b->ids + id0, idb);
     if (sqb) memcpy(host.data() + i_seqs, b->seqs + sq0, sqb);
   }
-  if ((rc = gs_reserve(d->w_in, in.at + 16)) != GS_OK) return rc;
+  GS_TRY(gs_reserve(d->w_in, in.at + 16));
   uint8_t *din = (uint8_t *)d->w_in.p;
   GS_HIP(hipMemcpyAsync(din, host.data(), i_hex, hipMemcpyHostToDevice, st));
   if (hxb) GS_HIP(hipMemcpyAsync(din + i_hex, b->hex + hx0, hxb, hipMemcpyHostToDevice, st));
@@ -694,7 +683,6 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
   }
   hipStream_t st = nullptr;
   GS_HIP(hipSetDevice(d->device));
-  gs_status rc;
   const bool complete = (flags & GS_TEXT_COMPLETE) != 0;
   const uint64_t slots = complete ? nw : n;
   const uint32_t n_tiles = (uint32_t)((slots + WAVE - 1) / WAVE);
@@ -707,8 +695,8 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
   const size_t t_err = tm.take(16), t_words = tm.take(8 * nw), t_cfd = tm.take(8 * nw), t_rec = tm.take(4 * nw), t_mark = tm.take(4 * nw),
                t_next = tm.take(4 * nw), t_ispos = tm.take(4 * (nw + 1)), t_rank = tm.take(4 * (nw + 1)), t_lens = tm.take(4 * slots),
                t_cnt = tm.take(complete ? 0 : 16 * n), t_spec = tm.take(complete ? 0 : 8 * n), t_tsum = tm.take(8 * ((size_t)n_tiles + 1)),
-               t_toff = tm.take(8 * ((size_t)n_tiles + 1)), t_scan = tm.take(std::max(tb_next, std::max(tb_rank, tb_tiles)));
-  if ((rc = gs_reserve(d->w_tmp, tm.at + 16)) != GS_OK) return rc;
+               t_toff = tm.take(8 * ((size_t)n_tiles + 1)), tb_scan = std::max(tb_next, std::max(tb_rank, tb_tiles)), t_scan = tm.take(tb_scan);
+  GS_TRY(gs_reserve(d->w_tmp, tm.at + 16));
   char *tmp = (char *)d->w_tmp.p;
 
   dc_args a;
@@ -758,17 +746,23 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
   GS_HIP(hipMemsetAsync(a.tile_sum + n_tiles, 0, 8, st));
   if (nw) {
     hipLaunchKernelGGL(k_dc_hex, dim3(gw), dim3(256), 0, st, a);
-    GS_HIP(rocprim::inclusive_scan(tmp + t_scan, tb_next, a.mark, a.next, (size_t)nw, dc_min(), st));
+    GS_TRY(gs_prim_carved("gs_decode: scan of the marks", tmp + t_scan, tb_scan, [&](void *t, size_t &tb) {
+      return rocprim::inclusive_scan(t, tb, a.mark, a.next, (size_t)nw, dc_min(), st);
+    }));
   }
   hipLaunchKernelGGL(k_dc_rec, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_dc_eval, dim3(gw), dim3(256), 0, st, a);
-  GS_HIP(rocprim::exclusive_scan(tmp + t_scan, tb_rank, a.ispos, a.rank, 0u, (size_t)nw + 1, rocprim::plus<uint32_t>(), st));
+  GS_TRY(gs_prim_carved("gs_decode: scan of the positions", tmp + t_scan, tb_scan, [&](void *t, size_t &tb) {
+    return rocprim::exclusive_scan(t, tb, a.ispos, a.rank, 0u, (size_t)nw + 1, rocprim::plus<uint32_t>(), st);
+  }));
   if (!complete) {
     const uint32_t gf = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + DC_WAVES - 1) / DC_WAVES, (uint64_t)cus * 32u));
     hipLaunchKernelGGL(k_dc_fold, dim3(gf), dim3(WAVE * DC_WAVES), 0, st, a);
   }
   if (n_tiles) hipLaunchKernelGGL(k_dc_len, dim3(grid), dim3(WAVE * DC_WAVES), 0, st, a, n_tiles);
-  GS_HIP(rocprim::exclusive_scan(tmp + t_scan, tb_tiles, a.tile_sum, a.tile_off, 0ull, (size_t)n_tiles + 1, rocprim::plus<uint64_t>(), st));
+  GS_TRY(gs_prim_carved("gs_decode: scan of the tiles", tmp + t_scan, tb_scan, [&](void *t, size_t &tb) {
+    return rocprim::exclusive_scan(t, tb, a.tile_sum, a.tile_off, 0ull, (size_t)n_tiles + 1, rocprim::plus<uint64_t>(), st);
+  }));
   /* the length, the rows and the device's verdict come back together */
   uint64_t total = 0;
   unsigned long long err = 0;
@@ -794,7 +788,7 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
     gs_set_error("gs_decode: record " + std::to_string(first_record + r) + " (" + id + "): " + dc_reasons[reason < 9 ? reason : 0]);
     return GS_ERR_FORMAT;
   }
-  if ((rc = gs_reserve(d->w_text, total + 16)) != GS_OK) return rc;
+  GS_TRY(gs_reserve(d->w_text, total + 16));
   a.out = (char *)d->w_text.p;
   if (total) hipLaunchKernelGGL(k_dc_write, dim3(grid), dim3(WAVE * DC_WAVES), 0, st, a, n_tiles);
   GS_HIP(hipStreamSynchronize(st));

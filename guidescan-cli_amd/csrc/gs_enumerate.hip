@@ -300,8 +300,7 @@ static const uint32_t LDS_CAP_MAX = 4096; /* k_order_wg: 2 * cap records of 16 b
 
 /* redo_pos[g] = place of guide g on `list` (0xFFFFFFFF: not on it) */
 static gs_status mark_list(batch &b, gs_buffer &redo_pos, const uint32_t *list, uint32_t n_list) {
-  gs_status rc;
-  if ((rc = gs_reserve(redo_pos, 4 * ((size_t)b.n + 1))) != GS_OK) return rc;
+  GS_TRY(gs_reserve(redo_pos, 4 * ((size_t)b.n + 1)));
   hipLaunchKernelGGL(k_fill_u32, dim3((b.n32 + 255) / 256), dim3(256), 0, b.st, (uint32_t *)redo_pos.p, 0xFFFFFFFFu, b.n32);
   hipLaunchKernelGGL(k_mark_redo, dim3((n_list + 255) / 256), dim3(256), 0, b.st, list, n_list, (uint32_t *)redo_pos.p);
   return GS_OK;
@@ -310,9 +309,8 @@ static gs_status mark_list(batch &b, gs_buffer &redo_pos, const uint32_t *list, 
 /* ---- prepare: the alt-PAM filter, the workspace, k_prepare and the form estimate behind it, one readback ---- */
 static gs_status prepare_workspace(batch &b, const char *alt_pams, uint32_t n_alt) {
   gs_index *ix = b.ix;
-  gs_status rc;
   b.cap = choose_cap(ix, b.sw, b.m, b.L, b.P, b.P ? n_alt : 0, b.flags);
-  if ((rc = gs_reserve(ix->w_misc, 512)) != GS_OK) return rc;
+  GS_TRY(gs_reserve(ix->w_batch.misc, 512));
   /* PAM list = alt PAMs ++ the guide's own (process.hpp:51-56).  An alt PAM with a symbol outside
    * A,C,G,T,N is a literal (index.hpp:130-137): it can only match if the genome holds that symbol -
    * then the whole batch belongs to the general path - and is dropped otherwise. */
@@ -335,24 +333,24 @@ static gs_status prepare_workspace(batch &b, const char *alt_pams, uint32_t n_al
    * same match slots (k_order merges them and drops sequences found twice, as the std::set does) */
   b.n_chunks = (b.n_alt + 1 + 3) / 4;
   const uint64_t n = b.n;
-  if ((rc = gs_reserve(ix->w_grec, sizeof(gs_guide_rec) * (n + 1) * b.n_chunks)) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_flags, n + 16)) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_counts, sizeof(uint32_t) * (2 * n + 2))) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_nmatch, sizeof(uint32_t) * (n + 1))) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_nhits, sizeof(uint32_t) * (n + 1))) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_offsets, sizeof(uint64_t) * (n + 2))) != GS_OK) return rc;
+  GS_TRY(gs_reserve(ix->w_batch.grec, sizeof(gs_guide_rec) * (n + 1) * b.n_chunks));
+  GS_TRY(gs_reserve(ix->w_batch.flags, n + 16));
+  GS_TRY(gs_reserve(ix->w_batch.counts, sizeof(uint32_t) * (2 * n + 2)));
+  GS_TRY(gs_reserve(ix->w_batch.nmatch, sizeof(uint32_t) * (n + 1)));
+  GS_TRY(gs_reserve(ix->w_batch.nhits, sizeof(uint32_t) * (n + 1)));
+  GS_TRY(gs_reserve(ix->w_batch.offsets, sizeof(uint64_t) * (n + 2)));
   b.nb = (b.n32 + SCAN_BLOCK - 1) / SCAN_BLOCK;
-  if ((rc = gs_reserve(ix->w_blocksums, sizeof(uint64_t) * (b.nb + 2))) != GS_OK) return rc;
-  b.d_stats = gs_misc_stats(ix->w_misc.p);
-  b.d_work = gs_misc_work(ix->w_misc.p);
+  GS_TRY(gs_reserve(ix->w_batch.blocksums, sizeof(uint64_t) * (b.nb + 2)));
+  b.d_stats = gs_misc_stats(ix->w_batch.misc.p);
+  b.d_work = gs_misc_work(ix->w_batch.misc.p);
   GS_HIP(hipEventRecord(ix->ev[0], b.st));
-  GS_HIP(hipMemsetAsync(ix->w_misc.p, 0, 512, b.st));
+  GS_HIP(hipMemsetAsync(ix->w_batch.misc.p, 0, 512, b.st));
   return GS_OK;
 }
 static gs_status launch_prepare(batch &b) {
   gs_index *ix = b.ix;
   hipStream_t st = b.st;
-  uint32_t *pair_hist = (uint32_t *)((char *)ix->w_misc.p + MISC_PAIR_HIST);
+  uint32_t *pair_hist = (uint32_t *)((char *)ix->w_batch.misc.p + MISC_PAIR_HIST);
   for (uint32_t c = 0; c < b.n_chunks; c++) {
     gs_prep_args pa;
     memset(&pa, 0, sizeof(pa));
@@ -360,9 +358,9 @@ static gs_status launch_prepare(batch &b) {
     pa.guide_pams = (const uint8_t *)b.d_guide_pams;
     for (uint32_t j = 0; j < b.n_alt; j++)
       for (uint32_t u = 0; u < b.P; u++) pa.alt[j][u] = (uint8_t)b.alt_kept[j * b.P + u];
-    pa.out = (gs_guide_rec *)ix->w_grec.p + (size_t)c * b.n;
+    pa.out = (gs_guide_rec *)ix->w_batch.grec.p + (size_t)c * b.n;
     pa.n_invalid = b.d_work + WK_INVALID;
-    pa.flags = (uint8_t *)ix->w_flags.p;
+    pa.flags = (uint8_t *)ix->w_batch.flags.p;
     pa.n = b.n32;
     pa.L = b.L;
     pa.P = b.P;
@@ -381,7 +379,7 @@ static gs_status launch_prepare(batch &b) {
   if (b.n_chunks == 1 && smin != 0 && ix->share_backoff <= 1 && ix->pt_k && ix->strand[0].d.ptab && ix->strand[1].d.ptab &&
       !b.sw.no_form_estimate) {
     b.pre_est_ran = true;
-    hipLaunchKernelGGL(k_estimate_heavy, dim3((b.n32 + 255) / 256), dim3(256), 0, st, (const gs_guide_rec *)ix->w_grec.p, b.n32,
+    hipLaunchKernelGGL(k_estimate_heavy, dim3((b.n32 + 255) / 256), dim3(256), 0, st, (const gs_guide_rec *)ix->w_batch.grec.p, b.n32,
                        ix->strand[0].d.ptab, ix->strand[1].d.ptab, ix->pt_k, estimate_thresh(smin),
                        b.d_work + WK_SCRATCH2);
   }
@@ -653,11 +651,10 @@ static void window_buckets(const std::vector<uint4> &cand, std::vector<uint32_t>
  * pass over the runs and three blocking copies were 0.1 ms of every 17 ms step). */
 static gs_status upload_windows(batch &b) {
   gs_index *ix = b.ix;
-  gs_status rc;
   const bool cand_buckets_ok = !(b.m > 3 || b.L < 20 || b.sw.no_cand_buckets);
   const uint64_t cand_key = (uint64_t)b.L | ((uint64_t)b.P << 8) | ((uint64_t)(cand_buckets_ok ? 1u : 0u) << 16) |
                             ((uint64_t)b.sw.cand_from << 32);
-  const bool cand_hit = ix->cand_key == cand_key && ix->w_cand.p != nullptr;
+  const bool cand_hit = ix->cand_key == cand_key && ix->w_batch.cand.p != nullptr;
   std::vector<uint4> cand[2];
   std::vector<uint32_t> bidx[2];
   size_t n_bidx[2] = {0, 0};
@@ -678,15 +675,15 @@ static gs_status upload_windows(batch &b) {
   }
   if (b.n_cand[0] + b.n_cand[1]) {
     const size_t b_w = 16 * (size_t)(b.n_cand[0] + b.n_cand[1]);
-    if (!cand_hit && (rc = gs_reserve(ix->w_cand, b_w + 4 * (n_bidx[0] + n_bidx[1]) + 16)) != GS_OK) return rc;
-    uint4 *dc = (uint4 *)ix->w_cand.p;
+    if (!cand_hit) GS_TRY(gs_reserve(ix->w_batch.cand, b_w + 4 * (n_bidx[0] + n_bidx[1]) + 16));
+    uint4 *dc = (uint4 *)ix->w_batch.cand.p;
     if (!cand_hit) {
       if (b.n_cand[0]) GS_HIP(hipMemcpy(dc, cand[0].data(), 16 * (size_t)b.n_cand[0], hipMemcpyHostToDevice));
       if (b.n_cand[1]) GS_HIP(hipMemcpy(dc + b.n_cand[0], cand[1].data(), 16 * (size_t)b.n_cand[1], hipMemcpyHostToDevice));
     }
     b.d_cand[0] = dc;
     b.d_cand[1] = dc + b.n_cand[0];
-    uint32_t *di = (uint32_t *)((char *)ix->w_cand.p + b_w);
+    uint32_t *di = (uint32_t *)((char *)ix->w_batch.cand.p + b_w);
     for (uint32_t s = 0; s < 2; s++) {
       if (n_bidx[s] == 0) continue;
       if (!cand_hit) GS_HIP(hipMemcpy(di, bidx[s].data(), 4 * n_bidx[s], hipMemcpyHostToDevice));
@@ -719,16 +716,16 @@ static void reserve_arena(batch &b) {
   if (b.sw.no_arena) want = 0;
   if (want > (1ull << 21)) want = 1ull << 21; /* 32 GB of records */
   auto reserve = [&]() {
-    return gs_reserve(ix->w_arena, sizeof(uint4) * (want << ARENA_SHIFT)) == GS_OK &&
-           gs_reserve(ix->w_arena_meta, 16 * want + 64) == GS_OK && gs_reserve(ix->w_nchunk, sizeof(uint2) * (2 * b.n + 2)) == GS_OK &&
-           gs_reserve(ix->w_cls, 32 * (2 * b.n + 2)) == GS_OK;
+    return gs_reserve(ix->w_batch.arena, sizeof(uint4) * (want << ARENA_SHIFT)) == GS_OK &&
+           gs_reserve(ix->w_batch.arena_meta, 16 * want + 64) == GS_OK && gs_reserve(ix->w_batch.nchunk, sizeof(uint2) * (2 * b.n + 2)) == GS_OK &&
+           gs_reserve(ix->w_batch.cls, 32 * (2 * b.n + 2)) == GS_OK;
   };
   if (want && !reserve()) {
     /* no room: give back what only the paths without the arena use (the exact-size array of a second
      * pass, the ordered copy that otherwise lives in the arena, the raw-key sort word) and try again */
     (void)hipGetLastError();
-    gs_buffer_free(ix->w_slots2);
-    gs_buffer_free(ix->w_b_s);
+    gs_buffer_free(ix->w_batch.slots2);
+    gs_buffer_free(ix->w_big.s);
     if (!reserve()) {
       (void)hipGetLastError();
       want = 0; /* the second pass serves the overflowing guides */
@@ -763,12 +760,12 @@ static void fill_search_args(const batch &b, const search_pass &p, gs_search_arg
   sa.m = b.m;
   sa.cap = p.cap;
   if (p.with_arena) {
-    sa.arena = (uint4 *)ix->w_arena.p;
+    sa.arena = (uint4 *)ix->w_batch.arena.p;
     sa.arena_next = b.d_work + WK_ARENA_NEXT;
-    sa.chunk_item = (uint32_t *)ix->w_arena_meta.p;
+    sa.chunk_item = (uint32_t *)ix->w_batch.arena_meta.p;
     sa.chunk_seq = sa.chunk_item + b.arena_chunks;
-    sa.nchunk = (uint2 *)ix->w_nchunk.p;
-    sa.cls = (uint32_t *)ix->w_cls.p;
+    sa.nchunk = (uint2 *)ix->w_batch.nchunk.p;
+    sa.cls = (uint32_t *)ix->w_batch.cls.p;
     sa.arena_chunks = b.arena_chunks;
     sa.chunk_fill = sa.chunk_item + 2 * (size_t)b.arena_chunks;
   }
@@ -956,12 +953,12 @@ static gs_status reserve_share_queue(batch &b, const search_pass &p, gs_search_a
   if (qcap > (1ull << 20)) qcap = 1ull << 20; /* 1.2 GB of packages */
   const uint32_t sh_max = std::min<uint32_t>(2 * p.ng, 1u << 18);
   const size_t meta = 512 + 4 * (size_t)qcap + 4 * (size_t)sh_max + 64 * (size_t)sh_max;
-  if (gs_reserve(ix->w_shq, 16 * (size_t)SHQ_PKG * qcap) != GS_OK || gs_reserve(ix->w_sh_meta, meta + 4 * ((size_t)sh_max + 2)) != GS_OK) {
+  if (gs_reserve(ix->w_batch.shq, 16 * (size_t)SHQ_PKG * qcap) != GS_OK || gs_reserve(ix->w_batch.sh_meta, meta + 4 * ((size_t)sh_max + 2)) != GS_OK) {
     (void)hipGetLastError(); /* no room for the queue: every item stays with its wave */
     return GS_OK;
   }
-  uint32_t *d_shctl = (uint32_t *)ix->w_sh_meta.p;
-  sa.shq = (uint4 *)ix->w_shq.p;
+  uint32_t *d_shctl = (uint32_t *)ix->w_batch.sh_meta.p;
+  sa.shq = (uint4 *)ix->w_batch.shq.p;
   sa.shq_ctl = d_shctl;
   sa.shq_ready = d_shctl + 128;
   sa.sh_list = sa.shq_ready + qcap;
@@ -1018,7 +1015,7 @@ static gs_status pick_form(batch &b, const search_pass &p, bool walk, bool spec,
 static gs_status run_search(batch &b, const search_pass &p, unsigned long long h_stats[2]) {
   gs_index *ix = b.ix;
   hipStream_t st = b.st;
-  GS_HIP(hipMemsetAsync(ix->w_misc.p, 0, 16, st));            /* n_ext, overflow items */
+  GS_HIP(hipMemsetAsync(ix->w_batch.misc.p, 0, 16, st));            /* n_ext, overflow items */
   GS_HIP(hipMemsetAsync(b.d_stats + ST_ARENA_FAIL, 0, 8, st)); /* items the arena failed */
   GS_HIP(hipMemsetAsync(b.d_work + WK_ITEMS, 0, 4, st));
   GS_HIP(hipMemsetAsync(b.d_work + WK_SEARCH_ERR, 0, 4, st));
@@ -1027,8 +1024,8 @@ static gs_status run_search(batch &b, const search_pass &p, unsigned long long h
   if (p.with_arena) {
     GS_HIP(hipMemsetAsync(b.d_work + WK_ARENA_NEXT, 0, 4, st));
     /* every chunk empty until a wave says whose it is: waves reserve several per visit to the counter (k_search) */
-    GS_HIP(hipMemsetAsync((uint32_t *)ix->w_arena_meta.p + b.arena_chunks, 0xFF, 4 * (size_t)b.arena_chunks, st));
-    GS_HIP(hipMemsetAsync(ix->w_arena_meta.p, 0, 4 * (size_t)b.arena_chunks, st));
+    GS_HIP(hipMemsetAsync((uint32_t *)ix->w_batch.arena_meta.p + b.arena_chunks, 0xFF, 4 * (size_t)b.arena_chunks, st));
+    GS_HIP(hipMemsetAsync(ix->w_batch.arena_meta.p, 0, 4 * (size_t)b.arena_chunks, st));
     for (int i = 0; i < 7; i++) ix->last_share[i] = 0; /* (of the main pass: a redo shares nothing) */
   }
   gs_search_args sa;
@@ -1210,9 +1207,9 @@ static void run_locate(const batch &b, const uint4 *matches, const uint32_t *nma
   la.sd[1] = ix->strand[1].d;
   la.matches = matches;
   la.nmatch = nmatch;
-  la.offsets = (const uint64_t *)ix->w_offsets.p;
+  la.offsets = (const uint64_t *)ix->w_batch.offsets.p;
   la.gmap = gmap;
-  la.hits = (gs_hit *)ix->w_hits.p;
+  la.hits = (gs_hit *)ix->w_batch.hits.p;
   la.genome_length = ix->genome_length;
   la.n = ng;
   la.cap = cap_;
@@ -1227,8 +1224,8 @@ static gs_status main_pass(batch &b) {
   gs_index *ix = b.ix;
   hipStream_t st = b.st;
   gs_status rc;
-  if ((rc = gs_reserve(ix->w_slots, sizeof(uint4) * (size_t)b.cap * 2 * b.n)) != GS_OK) return rc;
-  const search_pass p = {(const gs_guide_rec *)ix->w_grec.p, b.n32, (uint4 *)ix->w_slots.p, (uint32_t *)ix->w_counts.p, b.cap,
+  GS_TRY(gs_reserve(ix->w_batch.slots, sizeof(uint4) * (size_t)b.cap * 2 * b.n));
+  const search_pass p = {(const gs_guide_rec *)ix->w_batch.grec.p, b.n32, (uint4 *)ix->w_batch.slots.p, (uint32_t *)ix->w_batch.counts.p, b.cap,
                          nullptr, b.arena_chunks != 0};
   if ((rc = run_search(b, p, b.h_stats)) != GS_OK) return rc;
   if (b.arena_chunks == 0 || b.arena_fail == 0 || b.sw.has_arena_chunks || b.n_chunks != 1) return GS_OK;
@@ -1241,13 +1238,13 @@ static gs_status main_pass(batch &b) {
   uint32_t *d_need = b.d_work + WK_SCRATCH2, h_need = 0;
   GS_HIP(hipMemsetAsync(d_need, 0, 4, st));
   hipLaunchKernelGGL(k_need_chunks, dim3(std::min<uint32_t>((2 * b.n32 + 255) / 256, 1024u)), dim3(256), 0, st,
-                     (const uint32_t *)ix->w_counts.p, 2 * b.n32, b.cap, d_need);
+                     (const uint32_t *)ix->w_batch.counts.p, 2 * b.n32, b.cap, d_need);
   GS_HIP(hipMemcpyAsync(&h_need, d_need, 4, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   uint64_t want = (uint64_t)h_need + h_need / 4 + (uint64_t)b.cus * 32u * 16u + 64; /* (+ the waves' reserves) */
   if (want > (1ull << 21)) want = 1ull << 21;
-  if (want > b.arena_chunks && gs_reserve(ix->w_arena, sizeof(uint4) * (want << ARENA_SHIFT)) == GS_OK &&
-      gs_reserve(ix->w_arena_meta, 16 * want + 64) == GS_OK) {
+  if (want > b.arena_chunks && gs_reserve(ix->w_batch.arena, sizeof(uint4) * (want << ARENA_SHIFT)) == GS_OK &&
+      gs_reserve(ix->w_batch.arena_meta, 16 * want + 64) == GS_OK) {
     if (b.sw.debug)
       fprintf(stderr, "[gs] the arena ran out (%u chunks, %u needed): main pass run again with %llu\n", b.arena_chunks, h_need, (unsigned long long)want);
     b.arena_chunks = (uint32_t)want;
@@ -1264,21 +1261,20 @@ static gs_status main_pass(batch &b) {
 static gs_status order_items(batch &b) {
   gs_index *ix = b.ix;
   hipStream_t st = b.st;
-  gs_status rc;
   GS_HIP(hipMemsetAsync(b.d_stats + ST_MATCHES, 0, 8, st)); /* match counter */
   unsigned long long h_cstat[2] = {0, 0}; /* sum and maximum of this batch's exact per-item counts */
   GS_HIP(hipMemsetAsync(b.d_stats + ST_COUNT_SUM, 0, 16, st));
   hipLaunchKernelGGL(k_count_stats, dim3(std::min<uint32_t>((2 * b.n32 + 1023) / 1024, 256u)), dim3(256), 0, st,
-                     (const uint32_t *)ix->w_counts.p, 2 * b.n32, b.d_stats + ST_COUNT_SUM);
+                     (const uint32_t *)ix->w_batch.counts.p, 2 * b.n32, b.d_stats + ST_COUNT_SUM);
   if (b.cap > 128) { /* sizes k_order_wg's LDS; the small-slot path does not wait for it */
     GS_HIP(hipMemcpyAsync(h_cstat, b.d_stats + ST_COUNT_SUM, 16, hipMemcpyDeviceToHost, st));
     GS_HIP(hipStreamSynchronize(st));
   }
   ix->last_raw_valid = false;
   if (b.flags & GS_FLAG_RAW_COUNTS) { /* before k_order replaces the raw records by the unique ones */
-    if ((rc = gs_reserve(ix->w_raw, 4 * ((size_t)b.n + 1))) != GS_OK) return rc;
-    hipLaunchKernelGGL(k_raw_counts, dim3((b.n32 + 3) / 4), dim3(256), 0, st, (const uint4 *)ix->w_slots.p,
-                       (const uint32_t *)ix->w_counts.p, b.n32, b.cap, (uint32_t *)ix->w_raw.p);
+    GS_TRY(gs_reserve(ix->w_batch.raw, 4 * ((size_t)b.n + 1)));
+    hipLaunchKernelGGL(k_raw_counts, dim3((b.n32 + 3) / 4), dim3(256), 0, st, (const uint4 *)ix->w_batch.slots.p,
+                       (const uint32_t *)ix->w_batch.counts.p, b.n32, b.cap, (uint32_t *)ix->w_batch.raw.p);
     ix->last_raw_valid = true;
   }
   /* every guide through the device-wide sort: slots beyond what LDS orders, and - measured at hg38 size,
@@ -1287,20 +1283,19 @@ static gs_status order_items(batch &b) {
   b.big_batch = b.cap > LDS_CAP_MAX || (b.cap >= b.sw.wide_from && (b.wide_key ? gs_tileorder_fits(b.L, b.P, b.m)
                                                                                 : gs_bigorder_fits(b.L, b.P, b.m, b.n32)));
   if (b.big_batch) return GS_OK;
-  return run_order(b, (uint4 *)ix->w_slots.p, (const uint32_t *)ix->w_counts.p, (uint32_t *)ix->w_nmatch.p, (uint32_t *)ix->w_nhits.p,
+  return run_order(b, (uint4 *)ix->w_batch.slots.p, (const uint32_t *)ix->w_batch.counts.p, (uint32_t *)ix->w_batch.nmatch.p, (uint32_t *)ix->w_batch.nhits.p,
                    b.n32, b.cap, (uint32_t)(h_cstat[1] < b.cap ? h_cstat[1] : b.cap));
 }
 
 /* ---- the guides whose matches did not fit their slots ---- */
-/* the exact-size array of the overflowing guides' items (counts c2): its item offsets go to w_h_off */
+/* the exact-size array of the overflowing guides' items (counts c2): its item offsets go to w_batch.h_off */
 static gs_status upload_exact_offsets(batch &b, const std::vector<uint32_t> &c2) {
   gs_index *ix = b.ix;
-  gs_status rc;
   std::vector<uint64_t> h_slot_off(2 * (size_t)b.n_o + 1, 0);
   for (size_t i = 0; i < 2 * (size_t)b.n_o; i++) h_slot_off[i + 1] = h_slot_off[i] + c2[i];
-  if ((rc = gs_reserve(ix->w_slots2, sizeof(uint4) * (h_slot_off.back() + 1))) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_h_off, 8 * h_slot_off.size())) != GS_OK) return rc;
-  GS_HIP(hipMemcpyAsync(ix->w_h_off.p, h_slot_off.data(), 8 * h_slot_off.size(), hipMemcpyHostToDevice, b.st));
+  GS_TRY(gs_reserve(ix->w_batch.slots2, sizeof(uint4) * (h_slot_off.back() + 1)));
+  GS_TRY(gs_reserve(ix->w_batch.h_off, 8 * h_slot_off.size()));
+  GS_HIP(hipMemcpyAsync(ix->w_batch.h_off.p, h_slot_off.data(), 8 * h_slot_off.size(), hipMemcpyHostToDevice, b.st));
   GS_HIP(hipStreamSynchronize(b.st)); /* h_slot_off is a local */
   return GS_OK;
 }
@@ -1308,15 +1303,15 @@ static gs_status upload_exact_offsets(batch &b, const std::vector<uint32_t> &c2)
 static void arena_gather(const batch &b, const uint64_t *dst_off, uint32_t cap2) {
   const gs_index *ix = b.ix;
   gs_agather_args ga;
-  ga.slots = (const uint4 *)ix->w_slots.p;
-  ga.arena = (const uint4 *)ix->w_arena.p;
-  ga.counts = (const uint32_t *)ix->w_counts.p;
-  ga.chunk_item = (const uint32_t *)ix->w_arena_meta.p;
+  ga.slots = (const uint4 *)ix->w_batch.slots.p;
+  ga.arena = (const uint4 *)ix->w_batch.arena.p;
+  ga.counts = (const uint32_t *)ix->w_batch.counts.p;
+  ga.chunk_item = (const uint32_t *)ix->w_batch.arena_meta.p;
   ga.chunk_seq = ga.chunk_item + b.arena_chunks;
-  ga.list = (const uint32_t *)ix->w_ovf_list.p;
-  ga.redo_pos = (const uint32_t *)ix->w_b_redo_pos.p;
+  ga.list = (const uint32_t *)ix->w_batch.ovf_list.p;
+  ga.redo_pos = (const uint32_t *)ix->w_big.redo_pos.p;
   ga.dst_off = dst_off;
-  ga.dst = (uint4 *)ix->w_slots2.p;
+  ga.dst = (uint4 *)ix->w_batch.slots2.p;
   ga.n_o = b.n_o;
   ga.cap = b.cap;
   ga.cap2 = cap2;
@@ -1328,11 +1323,11 @@ static gs_status redo_exact(batch &b) {
   gs_index *ix = b.ix;
   gs_status rc;
   std::vector<uint32_t> c2(2 * (size_t)b.n_o);
-  GS_HIP(hipMemcpy(c2.data(), ix->w_counts2.p, 8 * (size_t)b.n_o, hipMemcpyDeviceToHost));
+  GS_HIP(hipMemcpy(c2.data(), ix->w_batch.counts2.p, 8 * (size_t)b.n_o, hipMemcpyDeviceToHost));
   if ((rc = upload_exact_offsets(b, c2)) != GS_OK) return rc;
   unsigned long long h2[2] = {0, 0};
-  const search_pass p = {(const gs_guide_rec *)ix->w_grec2.p, b.n_o, (uint4 *)ix->w_slots2.p, (uint32_t *)ix->w_counts2.p, 0,
-                         (const uint64_t *)ix->w_h_off.p, false};
+  const search_pass p = {(const gs_guide_rec *)ix->w_batch.grec2.p, b.n_o, (uint4 *)ix->w_batch.slots2.p, (uint32_t *)ix->w_batch.counts2.p, 0,
+                         (const uint64_t *)ix->w_batch.h_off.p, false};
   if ((rc = run_search(b, p, h2)) != GS_OK) return rc;
   if (h2[1] != 0) {
     gs_set_error("internal: exact-size redo overflowed");
@@ -1349,29 +1344,29 @@ static gs_status overflow_redo(batch &b) {
   b.cap2 = cap;
   if (b.h_stats[1] == 0) return GS_OK;
   uint32_t *d_nlist = b.d_work + WK_NLIST;
-  if ((rc = gs_reserve(ix->w_ovf_list, sizeof(uint32_t) * (n + 1))) != GS_OK) return rc;
+  GS_TRY(gs_reserve(ix->w_batch.ovf_list, sizeof(uint32_t) * (n + 1)));
   GS_HIP(hipMemsetAsync(d_nlist, 0, 4, st));
   hipLaunchKernelGGL(k_collect_overflow, dim3((n32 + 255) / 256), dim3(256), 0, st,
-                     (const uint32_t *)ix->w_counts.p, n32, cap, (uint32_t *)ix->w_ovf_list.p, d_nlist);
+                     (const uint32_t *)ix->w_batch.counts.p, n32, cap, (uint32_t *)ix->w_batch.ovf_list.p, d_nlist);
   GS_HIP(hipMemcpyAsync(&b.n_o, d_nlist, 4, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   const uint32_t n_o = b.n_o;
-  if ((rc = gs_reserve(ix->w_grec2, sizeof(gs_guide_rec) * (size_t)n_o * b.n_chunks)) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_counts2, sizeof(uint32_t) * 2 * (size_t)n_o)) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_nmatch2, sizeof(uint32_t) * (size_t)n_o)) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_nhits2, sizeof(uint32_t) * (size_t)n_o)) != GS_OK) return rc;
+  GS_TRY(gs_reserve(ix->w_batch.grec2, sizeof(gs_guide_rec) * (size_t)n_o * b.n_chunks));
+  GS_TRY(gs_reserve(ix->w_batch.counts2, sizeof(uint32_t) * 2 * (size_t)n_o));
+  GS_TRY(gs_reserve(ix->w_batch.nmatch2, sizeof(uint32_t) * (size_t)n_o));
+  GS_TRY(gs_reserve(ix->w_batch.nhits2, sizeof(uint32_t) * (size_t)n_o));
   for (uint32_t c = 0; c < b.n_chunks; c++)
     hipLaunchKernelGGL(k_gather_guides, dim3((n_o + 255) / 256), dim3(256), 0, st,
-                       (const gs_guide_rec *)ix->w_grec.p + (size_t)c * n, (const uint32_t *)ix->w_ovf_list.p, n_o,
-                       (gs_guide_rec *)ix->w_grec2.p + (size_t)c * n_o);
+                       (const gs_guide_rec *)ix->w_batch.grec.p + (size_t)c * n, (const uint32_t *)ix->w_batch.ovf_list.p, n_o,
+                       (gs_guide_rec *)ix->w_batch.grec2.p + (size_t)c * n_o);
   /* the main pass counted every item's matches exactly, also beyond its slots */
   hipLaunchKernelGGL(k_gather_counts, dim3((n_o + 255) / 256), dim3(256), 0, st,
-                     (const uint32_t *)ix->w_counts.p, (const uint32_t *)ix->w_ovf_list.p, n_o,
-                     (uint32_t *)ix->w_counts2.p);
+                     (const uint32_t *)ix->w_batch.counts.p, (const uint32_t *)ix->w_batch.ovf_list.p, n_o,
+                     (uint32_t *)ix->w_batch.counts2.p);
   uint32_t need_cap = 0;
   uint64_t need_chunks = 0;
   std::vector<uint32_t> c2(2 * (size_t)n_o);
-  GS_HIP(hipMemcpyAsync(c2.data(), ix->w_counts2.p, 8 * (size_t)n_o, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipMemcpyAsync(c2.data(), ix->w_batch.counts2.p, 8 * (size_t)n_o, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   for (uint32_t c : c2) {
     need_cap = c > need_cap ? c : need_cap;
@@ -1386,7 +1381,7 @@ static gs_status overflow_redo(batch &b) {
     ix->arena_chunks = need_chunks + need_chunks / 4 + 64;
   if (arena_ok) {
     GS_HIP(hipMemcpyAsync(&b.n_used, b.d_work + WK_ARENA_NEXT, 4, hipMemcpyDeviceToHost, st));
-    if ((rc = mark_list(b, ix->w_b_redo_pos, (const uint32_t *)ix->w_ovf_list.p, n_o)) != GS_OK) return rc;
+    if ((rc = mark_list(b, ix->w_big.redo_pos, (const uint32_t *)ix->w_batch.ovf_list.p, n_o)) != GS_OK) return rc;
     GS_HIP(hipStreamSynchronize(st));
     if (b.n_used > b.arena_chunks) b.n_used = b.arena_chunks;
   }
@@ -1395,12 +1390,12 @@ static gs_status overflow_redo(batch &b) {
     /* slots every one of these guides fits, ordered in LDS */
     b.cap2 = 128;
     while (b.cap2 < need_cap) b.cap2 <<= 1;
-    if ((rc = gs_reserve(ix->w_slots2, sizeof(uint4) * (size_t)b.cap2 * 2 * n_o)) != GS_OK) return rc;
+    GS_TRY(gs_reserve(ix->w_batch.slots2, sizeof(uint4) * (size_t)b.cap2 * 2 * n_o));
     if (arena_ok) {
       arena_gather(b, nullptr, b.cap2);
     } else {
       unsigned long long h2[2] = {0, 0};
-      const search_pass p = {(const gs_guide_rec *)ix->w_grec2.p, n_o, (uint4 *)ix->w_slots2.p, (uint32_t *)ix->w_counts2.p,
+      const search_pass p = {(const gs_guide_rec *)ix->w_batch.grec2.p, n_o, (uint4 *)ix->w_batch.slots2.p, (uint32_t *)ix->w_batch.counts2.p,
                              b.cap2, nullptr, false};
       if ((rc = run_search(b, p, h2)) != GS_OK) return rc;
       if (h2[1] != 0) {
@@ -1408,12 +1403,12 @@ static gs_status overflow_redo(batch &b) {
         return GS_ERR_DEVICE;
       }
     }
-    if ((rc = run_order(b, (uint4 *)ix->w_slots2.p, (const uint32_t *)ix->w_counts2.p, (uint32_t *)ix->w_nmatch2.p,
-                        (uint32_t *)ix->w_nhits2.p, n_o, b.cap2, need_cap)) != GS_OK)
+    if ((rc = run_order(b, (uint4 *)ix->w_batch.slots2.p, (const uint32_t *)ix->w_batch.counts2.p, (uint32_t *)ix->w_batch.nmatch2.p,
+                        (uint32_t *)ix->w_batch.nhits2.p, n_o, b.cap2, need_cap)) != GS_OK)
       return rc;
     hipLaunchKernelGGL(k_patch_overflow, dim3((n_o + 255) / 256), dim3(256), 0, st,
-                       (const uint32_t *)ix->w_ovf_list.p, n_o, (const uint32_t *)ix->w_nhits2.p,
-                       (uint32_t *)ix->w_nhits.p);
+                       (const uint32_t *)ix->w_batch.ovf_list.p, n_o, (const uint32_t *)ix->w_batch.nhits2.p,
+                       (uint32_t *)ix->w_batch.nhits.p);
   }
   b.ovf_arena_ok = arena_ok;
   b.ovf_c2.swap(c2);
@@ -1438,19 +1433,19 @@ static uint64_t tile_key(const batch &b) {
 static gs_status plan_tiles(batch &b, gs_tileorder_in &ti, gs_tileorder_state &ts, bool *usable) {
   gs_index *ix = b.ix;
   gs_status rc;
-  if (b.n_o && (rc = mark_list(b, ix->w_b_redo_pos, (const uint32_t *)ix->w_ovf_list.p, b.n_o)) != GS_OK) return rc;
+  if (b.n_o && (rc = mark_list(b, ix->w_big.redo_pos, (const uint32_t *)ix->w_batch.ovf_list.p, b.n_o)) != GS_OK) return rc;
   ti.n_set = b.big_batch ? b.n32 : b.n_o;
-  ti.list = b.big_batch ? nullptr : (const uint32_t *)ix->w_ovf_list.p;
-  ti.redo_pos = (const uint32_t *)ix->w_b_redo_pos.p;
-  ti.counts = (const uint32_t *)ix->w_counts.p;
-  ti.cls = (const uint32_t *)ix->w_cls.p;
-  ti.slots = (const uint4 *)ix->w_slots.p;
+  ti.list = b.big_batch ? nullptr : (const uint32_t *)ix->w_batch.ovf_list.p;
+  ti.redo_pos = (const uint32_t *)ix->w_big.redo_pos.p;
+  ti.counts = (const uint32_t *)ix->w_batch.counts.p;
+  ti.cls = (const uint32_t *)ix->w_batch.cls.p;
+  ti.slots = (const uint4 *)ix->w_batch.slots.p;
   ti.cap = b.cap;
-  ti.arena = (const uint4 *)ix->w_arena.p;
-  ti.chunk_item = (const uint32_t *)ix->w_arena_meta.p;
+  ti.arena = (const uint4 *)ix->w_batch.arena.p;
+  ti.chunk_item = (const uint32_t *)ix->w_batch.arena_meta.p;
   ti.chunk_seq = ti.chunk_item + b.arena_chunks;
   ti.n_used = b.n_used;
-  ti.nhits = (uint32_t *)ix->w_nhits.p;
+  ti.nhits = (uint32_t *)ix->w_batch.nhits.p;
   ti.L = b.L;
   ti.P = b.P;
   ti.m = b.m;
@@ -1474,58 +1469,57 @@ static gs_status order_device_wide(batch &b) {
   gs_index *ix = b.ix;
   gs_status rc;
   const uint32_t n_set = b.big_batch ? b.n32 : b.n_o;
-  const uint32_t *ovf_list = (const uint32_t *)ix->w_ovf_list.p, *redo_pos = nullptr;
+  const uint32_t *ovf_list = (const uint32_t *)ix->w_batch.ovf_list.p, *redo_pos = nullptr;
   if (b.n_o) {
     if (b.ovf_arena_ok && gs_bigorder_fits(b.L, b.P, b.m, n_set)) {
       b.arena_direct = true; /* no copy at all: the ordering's first kernel reads slots and chunks */
     } else if (b.ovf_arena_ok) {
       /* the exact-size array the second pass would have filled, filled by copies */
       if ((rc = upload_exact_offsets(b, b.ovf_c2)) != GS_OK) return rc;
-      arena_gather(b, (const uint64_t *)ix->w_h_off.p, 0u);
+      arena_gather(b, (const uint64_t *)ix->w_batch.h_off.p, 0u);
     } else if ((rc = redo_exact(b)) != GS_OK) {
       return rc;
     }
     b.redo_big = true;
     if (b.big_batch) {
-      if ((rc = mark_list(b, ix->w_b_redo_pos, ovf_list, b.n_o)) != GS_OK) return rc;
-      redo_pos = (const uint32_t *)ix->w_b_redo_pos.p;
+      if ((rc = mark_list(b, ix->w_big.redo_pos, ovf_list, b.n_o)) != GS_OK) return rc;
+      redo_pos = (const uint32_t *)ix->w_big.redo_pos.p;
     }
   }
   gs_bigorder_in in = bigorder_in(b);
   in.n_set = n_set;
-  in.counts_main = b.big_batch ? (const uint32_t *)ix->w_counts.p : nullptr;
+  in.counts_main = b.big_batch ? (const uint32_t *)ix->w_batch.counts.p : nullptr;
   in.cap_main = b.big_batch ? b.cap : 0u;
   in.redo_pos = redo_pos;
-  in.slot_off2 = (const uint64_t *)ix->w_h_off.p;
-  in.counts2 = (const uint32_t *)ix->w_counts2.p;
-  in.nmatch = (uint32_t *)(b.big_batch ? ix->w_nmatch.p : ix->w_nmatch2.p);
-  in.nhits = (uint32_t *)(b.big_batch ? ix->w_nhits.p : ix->w_nhits2.p);
+  in.slot_off2 = (const uint64_t *)ix->w_batch.h_off.p;
+  in.counts2 = (const uint32_t *)ix->w_batch.counts2.p;
+  in.nmatch = (uint32_t *)(b.big_batch ? ix->w_batch.nmatch.p : ix->w_batch.nmatch2.p);
+  in.nhits = (uint32_t *)(b.big_batch ? ix->w_batch.nhits.p : ix->w_batch.nhits2.p);
   in.from_arena = b.arena_direct;
   in.arena_list = b.big_batch ? nullptr : ovf_list;
   if ((rc = gs_bigorder_run(ix, in, b.st, b.big)) != GS_OK) return rc;
   if (!b.big_batch) /* the redo list alone went through the device-wide sort */
     hipLaunchKernelGGL(k_patch_overflow, dim3((b.n_o + 255) / 256), dim3(256), 0, b.st, ovf_list, b.n_o,
-                       (const uint32_t *)ix->w_nhits2.p, (uint32_t *)ix->w_nhits.p);
+                       (const uint32_t *)ix->w_batch.nhits2.p, (uint32_t *)ix->w_batch.nhits.p);
   return GS_OK;
 }
 /* hit offsets (scan of nhits), the hit array, and the hits of the guides ordered in LDS */
 static gs_status scan_and_locate(batch &b) {
   gs_index *ix = b.ix;
   hipStream_t st = b.st;
-  gs_status rc;
-  hipLaunchKernelGGL(k_scan_partial, dim3(b.nb), dim3(SCAN_BLOCK), 0, st, (const uint32_t *)ix->w_nhits.p,
-                     (uint64_t *)ix->w_blocksums.p, b.n32);
-  hipLaunchKernelGGL(k_scan_blocksums, dim3(1), dim3(SCAN_BLOCK), 0, st, (uint64_t *)ix->w_blocksums.p, b.nb);
-  hipLaunchKernelGGL(k_scan_final, dim3(b.nb), dim3(SCAN_BLOCK), 0, st, (const uint32_t *)ix->w_nhits.p,
-                     (const uint64_t *)ix->w_blocksums.p, (uint64_t *)ix->w_offsets.p, b.n32, b.nb);
+  hipLaunchKernelGGL(k_scan_partial, dim3(b.nb), dim3(SCAN_BLOCK), 0, st, (const uint32_t *)ix->w_batch.nhits.p,
+                     (uint64_t *)ix->w_batch.blocksums.p, b.n32);
+  hipLaunchKernelGGL(k_scan_blocksums, dim3(1), dim3(SCAN_BLOCK), 0, st, (uint64_t *)ix->w_batch.blocksums.p, b.nb);
+  hipLaunchKernelGGL(k_scan_final, dim3(b.nb), dim3(SCAN_BLOCK), 0, st, (const uint32_t *)ix->w_batch.nhits.p,
+                     (const uint64_t *)ix->w_batch.blocksums.p, (uint64_t *)ix->w_batch.offsets.p, b.n32, b.nb);
   b.total = 0;
-  GS_HIP(hipMemcpyAsync(&b.total, (uint64_t *)ix->w_offsets.p + b.n, 8, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipMemcpyAsync(&b.total, (uint64_t *)ix->w_batch.offsets.p + b.n, 8, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
-  if ((rc = gs_reserve(ix->w_hits, sizeof(gs_hit) * (b.total + 1))) != GS_OK) return rc;
+  GS_TRY(gs_reserve(ix->w_batch.hits, sizeof(gs_hit) * (b.total + 1)));
   if (!b.big_batch) {
-    run_locate(b, (const uint4 *)ix->w_slots.p, (const uint32_t *)ix->w_nmatch.p, nullptr, b.n32, b.cap);
+    run_locate(b, (const uint4 *)ix->w_batch.slots.p, (const uint32_t *)ix->w_batch.nmatch.p, nullptr, b.n32, b.cap);
     if (b.n_o && b.lds_redo)
-      run_locate(b, (const uint4 *)ix->w_slots2.p, (const uint32_t *)ix->w_nmatch2.p, (const uint32_t *)ix->w_ovf_list.p, b.n_o,
+      run_locate(b, (const uint4 *)ix->w_batch.slots2.p, (const uint32_t *)ix->w_batch.nmatch2.p, (const uint32_t *)ix->w_batch.ovf_list.p, b.n_o,
                  b.cap2);
   }
   return GS_OK;
@@ -1544,10 +1538,10 @@ static gs_status order_left_out(batch &b, const gs_tileorder_state &ts, uint32_t
     return GS_ERR_UNSUPPORTED;
   }
   const uint32_t n_x = ts.n_excl;
-  const uint32_t *xlist = (const uint32_t *)ix->w_t_excl.p;
-  if ((rc = mark_list(b, ix->w_b_redo_pos2, xlist, n_x)) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_nmatch2, sizeof(uint32_t) * (size_t)std::max(n_x, b.n_o))) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_nhits2, sizeof(uint32_t) * (size_t)std::max(n_x, b.n_o))) != GS_OK) return rc;
+  const uint32_t *xlist = (const uint32_t *)ix->w_tile.excl.p;
+  if ((rc = mark_list(b, ix->w_big.redo_pos2, xlist, n_x)) != GS_OK) return rc;
+  GS_TRY(gs_reserve(ix->w_batch.nmatch2, sizeof(uint32_t) * (size_t)std::max(n_x, b.n_o)));
+  GS_TRY(gs_reserve(ix->w_batch.nhits2, sizeof(uint32_t) * (size_t)std::max(n_x, b.n_o)));
   if (b.n_used == 0) { /* (the chunks in use, when no earlier step asked for them) */
     GS_HIP(hipMemcpyAsync(&b.n_used, b.d_work + WK_ARENA_NEXT, 4, hipMemcpyDeviceToHost, b.st));
     GS_HIP(hipStreamSynchronize(b.st));
@@ -1555,18 +1549,18 @@ static gs_status order_left_out(batch &b, const gs_tileorder_state &ts, uint32_t
   }
   gs_bigorder_in in = bigorder_in(b);
   in.n_set = n_x;
-  in.nmatch = (uint32_t *)ix->w_nmatch2.p;
-  in.nhits = (uint32_t *)ix->w_nhits2.p;
+  in.nmatch = (uint32_t *)ix->w_batch.nmatch2.p;
+  in.nhits = (uint32_t *)ix->w_batch.nhits2.p;
   in.from_arena = true;
   in.arena_list = xlist;
-  in.arena_redo_pos = (const uint32_t *)ix->w_b_redo_pos2.p;
+  in.arena_redo_pos = (const uint32_t *)ix->w_big.redo_pos2.p;
   if ((rc = gs_bigorder_run(ix, in, b.st, b.big)) != GS_OK) return rc;
   std::vector<uint32_t> hx(n_x), lx(n_x), cx(2 * (size_t)n_x);
-  GS_HIP(hipMemcpy(hx.data(), ix->w_nhits2.p, 4 * (size_t)n_x, hipMemcpyDeviceToHost));
+  GS_HIP(hipMemcpy(hx.data(), ix->w_batch.nhits2.p, 4 * (size_t)n_x, hipMemcpyDeviceToHost));
   GS_HIP(hipMemcpy(lx.data(), xlist, 4 * (size_t)n_x, hipMemcpyDeviceToHost));
   bool same = true;
   for (uint32_t j = 0; j < n_x && same; j++) {
-    GS_HIP(hipMemcpy(&cx[2 * j], (const uint32_t *)ix->w_counts.p + 2 * (size_t)lx[j], 8, hipMemcpyDeviceToHost));
+    GS_HIP(hipMemcpy(&cx[2 * j], (const uint32_t *)ix->w_batch.counts.p + 2 * (size_t)lx[j], 8, hipMemcpyDeviceToHost));
     same = (uint64_t)hx[j] == (uint64_t)cx[2 * j] + cx[2 * j + 1];
   }
   if (!same) {
@@ -1603,11 +1597,11 @@ static gs_status order_set(batch &b) {
     if ((rc = scan_and_locate(b)) != GS_OK) return rc;
     if (!set_exists) break;
     if (!tile) {
-      gs_bigorder_locate(ix, b.big, b.big_batch ? nullptr : (const uint32_t *)ix->w_ovf_list.p, b.v_rem, b.st);
+      gs_bigorder_locate(ix, b.big, b.big_batch ? nullptr : (const uint32_t *)ix->w_batch.ovf_list.p, b.v_rem, b.st);
       break;
     }
-    ti.offsets = (const uint64_t *)ix->w_offsets.p;
-    ti.hits = (gs_hit *)ix->w_hits.p;
+    ti.offsets = (const uint64_t *)ix->w_batch.offsets.p;
+    ti.hits = (gs_hit *)ix->w_batch.hits.p;
     uint32_t viol = 0;
     if ((rc = gs_tileorder_run(ix, ti, ts, b.st, &viol)) != GS_OK) return rc;
     if (!viol && ts.n_excl != 0 && (rc = order_left_out(b, ts, &viol)) != GS_OK) return rc;
@@ -1659,8 +1653,8 @@ static gs_status finish(batch &b, const void **d_offsets, const void **d_hits, g
     ix->seen[b.m].key = shape_key(b.L, b.P, b.n_alt, b.flags);
   }
   GS_HIP(hipGetLastError());
-  if (d_offsets) *d_offsets = ix->w_offsets.p;
-  if (d_hits) *d_hits = ix->w_hits.p;
+  if (d_offsets) *d_offsets = ix->w_batch.offsets.p;
+  if (d_hits) *d_hits = ix->w_batch.hits.p;
   if (stats) {
     stats->n_guides = b.n;
     stats->n_ext = b.h_stats[0];
@@ -1708,10 +1702,10 @@ static gs_status enumerate_device_impl(gs_index *ix, const void *d_guides, uint6
   gs_status rc;
   if ((rc = prepare_workspace(b, alt_pams, n_alt)) != GS_OK) return rc;
   if (n == 0) {
-    GS_HIP(hipMemsetAsync(ix->w_offsets.p, 0, sizeof(uint64_t), b.st));
+    GS_HIP(hipMemsetAsync(ix->w_batch.offsets.p, 0, sizeof(uint64_t), b.st));
     GS_HIP(hipStreamSynchronize(b.st));
-    if (d_offsets) *d_offsets = ix->w_offsets.p;
-    if (d_hits) *d_hits = ix->w_hits.p;
+    if (d_offsets) *d_offsets = ix->w_batch.offsets.p;
+    if (d_hits) *d_hits = ix->w_batch.hits.p;
     if (stats) memset(stats, 0, sizeof(*stats));
     return GS_OK;
   }
@@ -1752,16 +1746,12 @@ static const size_t RELEASE_REDO_MIN = (size_t)1 << 30; /* released bytes from w
 static bool recover_release_workspace(gs_index *ix, gs_status rc) {
   if (rc != GS_ERR_NOMEM) return false;
   (void)hipGetLastError();
-  size_t freed = 0;
-  for (gs_buffer *b : {&ix->w_b_src, &ix->w_b_cnt, &ix->w_b_prefix, &ix->w_b_recs, &ix->w_b_w0, &ix->w_b_w0b, &ix->w_b_idx,
-                       &ix->w_b_idxb, &ix->w_b_keep, &ix->w_b_keeps, &ix->w_b_rows, &ix->w_b_rowss, &ix->w_b_s, &ix->w_slots2, &ix->w_h_tmp,
-                       &ix->w_t_buckets, &ix->w_t_tiles, &ix->w_t_chunkof, &ix->w_t_big, &ix->w_hits, &ix->w_score_tmp, &ix->w_score_io,
-                       &ix->w_arena, &ix->w_shq, &ix->w_slots, &ix->w_text_tmp, &ix->w_text_hex, &ix->w_text})
-    freed += gs_buffer_free(*b);
+  const size_t freed = ix->w_batch.release() + ix->w_big.release() + ix->w_tile.release() + ix->w_score.release() +
+                       ix->w_text.release() + ix->w_bgzf.release();
   size_t redo_min = RELEASE_REDO_MIN;
   if (const char *e = gs_opt(ix, "GS_DBG_RELEASE_MIN")) redo_min = (size_t)strtoull(e, nullptr, 10); /* (tests: bytes) */
   if (freed <= redo_min) return false;
-  if (gs_opt(ix, "GS_DEBUG")) fprintf(stderr, "[gs] out of device memory: %.1f GB of workspace released, batch redone\n", 1e-9 * (double)freed);
+  if (gs_opt(ix, "GS_DEBUG")) fprintf(stderr, "[gs] out of device memory: %.1f GB (%zu bytes) of workspace released, batch redone\n", 1e-9 * (double)freed, freed);
   return true;
 }
 /* the spaced tables go first: without them a batch of the headline's shape takes 17.0 instead of 15.7 ms, without any other table far more */

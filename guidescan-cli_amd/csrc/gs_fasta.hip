@@ -182,7 +182,8 @@ gs_status fa_run(gs_fasta *fa, const uint8_t *d_raw, uint64_t len, hipStream_t s
     GS_TRY(mem.get(sb, &bwd));
     GS_TRY(mem.get(cb, &counts));
     GS_TRY(mem.get(cb, &koff));
-    GS_TRY(mem.get(std::max(tb_f, std::max(tb_r, tb_c)), &tmp));
+    const size_t tb = std::max(tb_f, std::max(tb_r, tb_c));
+    GS_TRY(mem.get(tb, &tmp));
     fa_args a;
     memset(&a, 0, sizeof a);
     a.raw = d_raw;
@@ -206,13 +207,19 @@ gs_status fa_run(gs_fasta *fa, const uint8_t *d_raw, uint64_t len, hipStream_t s
     GS_HIP(hipEventRecord(ev.e[0], st));
     hipLaunchKernelGGL(k_fa_tile<FA_SUM>, dim3(grid), dim3(FA_THREADS), 0, st, a);
     GS_HIP(hipEventRecord(ev.e[1], st));
-    GS_HIP(rocprim::inclusive_scan(tmp, tb_f, a.sums, (gs_fa_sum *)fwd, (size_t)nt + 1, fa_fwd(), st));
-    GS_HIP(rocprim::inclusive_scan(tmp, tb_r, a.rsums, (gs_fa_sum *)bwd, (size_t)nt + 1, fa_rev(), st));
+    GS_TRY(gs_prim_carved("FASTA reader: forward scan of the tiles", tmp, tb, [&](void *t, size_t &b) {
+      return rocprim::inclusive_scan(t, b, a.sums, (gs_fa_sum *)fwd, (size_t)nt + 1, fa_fwd(), st);
+    }));
+    GS_TRY(gs_prim_carved("FASTA reader: backward scan of the tiles", tmp, tb, [&](void *t, size_t &b) {
+      return rocprim::inclusive_scan(t, b, a.rsums, (gs_fa_sum *)bwd, (size_t)nt + 1, fa_rev(), st);
+    }));
     GS_HIP(hipEventRecord(ev.e[2], st));
     GS_HIP(hipMemsetAsync((unsigned long long *)counts + nt, 0, 8, st));
     hipLaunchKernelGGL(k_fa_tile<FA_COUNT>, dim3(grid), dim3(FA_THREADS), 0, st, a);
     GS_HIP(hipEventRecord(ev.e[3], st));
-    GS_HIP(rocprim::exclusive_scan(tmp, tb_c, a.counts, (unsigned long long *)koff, 0ull, (size_t)nt + 1, fa_add(), st));
+    GS_TRY(gs_prim_carved("FASTA reader: scan of the kept bytes", tmp, tb, [&](void *t, size_t &b) {
+      return rocprim::exclusive_scan(t, b, a.counts, (unsigned long long *)koff, 0ull, (size_t)nt + 1, fa_add(), st);
+    }));
     GS_HIP(hipEventRecord(ev.e[4], st));
     gs_fa_sum whole;
     unsigned long long kept = 0;

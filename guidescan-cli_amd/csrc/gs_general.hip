@@ -381,7 +381,7 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
   gs_scratch mem;
   void *d_g = nullptr, *d_cnt = nullptr, *d_misc = nullptr, *d_a = nullptr, *d_b = nullptr, *d_flag = nullptr, *d_pos = nullptr, *d_uq = nullptr,
        *d_c64 = nullptr, *d_scan = nullptr, *d_nm = nullptr, *d_nh = nullptr, *d_first = nullptr, *d_frec = nullptr, *d_goff = nullptr,
-       *d_hits = nullptr, *d_tmp = nullptr, *d_gl = nullptr, *d_raw = nullptr;
+       *d_hits = nullptr, *d_gl = nullptr, *d_raw = nullptr;
   /* query = reverse_complement(sequence) consumed right to left == complement of the guide left to
    * right (process.hpp:63, index.hpp:218); with --start the guide itself right to left; PAMs likewise */
   std::vector<gs_gen_guide> hg(n);
@@ -557,26 +557,19 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
     mem.drop(d_raw);
   }
   /* canonical order: (guide, distance, index, sequence, row) */
-  size_t tb = 0, tb2 = 0, tb3 = 0;
+  gs_prim_tmp tmp; /* the sort's, which the two scans fit into */
   GS_TRY(mem.get(4 * T, &d_flag));
   GS_TRY(mem.get(4 * T, &d_pos));
   GS_TRY(mem.get(8 * (T + 1), &d_c64));
   GS_TRY(mem.get(8 * (T + 1), &d_scan));
-  GS_HIP(rocprim::merge_sort(nullptr, tb, (gs_grec *)d_a, (gs_grec *)d_b, (size_t)T, gs_grec_less(), st));
-  GS_HIP(rocprim::exclusive_scan(nullptr, tb2, (uint32_t *)d_flag, (uint32_t *)d_pos, 0u, (size_t)T,
-                                 rocprim::plus<uint32_t>(), st));
-  GS_HIP(rocprim::exclusive_scan(nullptr, tb3, (unsigned long long *)d_c64, (unsigned long long *)d_scan,
-                                 0ull, (size_t)T + 1, rocprim::plus<unsigned long long>(), st));
-  if (tb2 > tb) tb = tb2;
-  if (tb3 > tb) tb = tb3;
-  GS_TRY(mem.get(tb, &d_tmp));
-  size_t tbs = tb;
-  GS_HIP(rocprim::merge_sort(d_tmp, tbs, (gs_grec *)d_a, (gs_grec *)d_b, (size_t)T, gs_grec_less(), st));
+  GS_TRY(gs_prim("general path: sort of the records", mem, tmp, [&](void *t, size_t &tb) {
+    return rocprim::merge_sort(t, tb, (gs_grec *)d_a, (gs_grec *)d_b, (size_t)T, gs_grec_less(), st);
+  }));
   const unsigned gT = (unsigned)((T + 255) / 256);
   hipLaunchKernelGGL(k_gen_flags, dim3(gT), dim3(256), 0, st, (const gs_grec *)d_b, T, (uint32_t *)d_flag);
-  tbs = tb;
-  GS_HIP(rocprim::exclusive_scan(d_tmp, tbs, (uint32_t *)d_flag, (uint32_t *)d_pos, 0u, (size_t)T,
-                                 rocprim::plus<uint32_t>(), st));
+  GS_TRY(gs_prim("general path: scan of the flags", mem, tmp, [&](void *t, size_t &tb) {
+    return rocprim::exclusive_scan(t, tb, (uint32_t *)d_flag, (uint32_t *)d_pos, 0u, (size_t)T, rocprim::plus<uint32_t>(), st);
+  }));
   GS_TRY(mem.get(sizeof(gs_grec) * T, &d_uq));
   GS_TRY(mem.get(4 * n, &d_nm));
   GS_TRY(mem.get(8 * n, &d_nh));
@@ -599,9 +592,10 @@ static gs_status enumerate_general(gs_index *ix, const char *guides, uint64_t n,
   }
   first_rec[n] = nuq;
   const uint64_t H = res->offsets[n];
-  tbs = tb;
-  GS_HIP(rocprim::exclusive_scan(d_tmp, tbs, (unsigned long long *)d_c64, (unsigned long long *)d_scan,
-                                 0ull, (size_t)nuq + 1, rocprim::plus<unsigned long long>(), st));
+  GS_TRY(gs_prim("general path: scan of the counts", mem, tmp, [&](void *t, size_t &tb) {
+    return rocprim::exclusive_scan(t, tb, (unsigned long long *)d_c64, (unsigned long long *)d_scan, 0ull, (size_t)nuq + 1,
+                                   rocprim::plus<unsigned long long>(), st);
+  }));
   GS_TRY(mem.get(8 * (n + 1), &d_frec));
   GS_TRY(mem.get(8 * n, &d_first));
   GS_TRY(mem.get(8 * (n + 1), &d_goff));

@@ -155,9 +155,9 @@ static gs_status enumerate_host(gs_index *ix, const char *guides, uint64_t n, ui
                                 gs_result **out) {
   if (!ix || !out || (n && !guides) || (n && P && !guide_pams)) return GS_ERR_ARG;
   GS_HIP(hipSetDevice(ix->device));
-  gs_status rc = gs_reserve(ix->w_guides, n * (size_t)(L + P) + 16);
+  gs_status rc = gs_reserve(ix->w_batch.guides, n * (size_t)(L + P) + 16);
   if (rc != GS_OK) return rc;
-  char *d_g = (char *)ix->w_guides.p;
+  char *d_g = (char *)ix->w_batch.guides.p;
   char *d_p = d_g + n * (size_t)L;
   if (n) {
     GS_HIP(hipMemcpy(d_g, guides, n * (size_t)L, hipMemcpyHostToDevice));
@@ -186,14 +186,14 @@ static gs_status enumerate_host(gs_index *ix, const char *guides, uint64_t n, ui
   if (ix->last_unsupported) {
     r->flags = pin_acquire(n);
     if (!r->flags.p) return GS_ERR_NOMEM;
-    GS_HIP(hipMemcpy(r->flags.p, ix->w_flags.p, n, hipMemcpyDeviceToHost));
+    GS_HIP(hipMemcpy(r->flags.p, ix->w_batch.flags.p, n, hipMemcpyDeviceToHost));
     r->view.guide_flags = (const uint8_t *)r->flags.p;
   }
   r->view.raw_hits = nullptr;
   if ((flags & GS_FLAG_RAW_COUNTS) && ix->last_raw_valid && n) {
     r->raw = pin_acquire(4 * n);
     if (!r->raw.p) return GS_ERR_NOMEM;
-    GS_HIP(hipMemcpy(r->raw.p, ix->w_raw.p, 4 * n, hipMemcpyDeviceToHost));
+    GS_HIP(hipMemcpy(r->raw.p, ix->w_batch.raw.p, 4 * n, hipMemcpyDeviceToHost));
     r->view.raw_hits = (const uint32_t *)r->raw.p;
   }
   guard.p = nullptr;
@@ -388,11 +388,11 @@ static gs_status enumerate_text(gs_index *ix, bool on_device, const void *guides
                                 uint32_t *raw_hits) {
   GS_HIP(hipSetDevice(ix->device));
   gs_status rc;
-  if ((rc = gs_reserve(ix->w_text_spec, 4 * n + 16)) != GS_OK) return rc;
+  GS_TRY(gs_reserve(ix->w_text.spec, 4 * n + 16));
   const char *d_g = (const char *)guides, *d_p = (const char *)guide_pams;
   if (!on_device) {
-    if ((rc = gs_reserve(ix->w_guides, n * (size_t)(L + P) + 16)) != GS_OK) return rc;
-    char *up = (char *)ix->w_guides.p;
+    GS_TRY(gs_reserve(ix->w_batch.guides, n * (size_t)(L + P) + 16));
+    char *up = (char *)ix->w_batch.guides.p;
     if (n) {
       GS_HIP(hipMemcpy(up, guides, n * (size_t)L, hipMemcpyHostToDevice));
       if (P) GS_HIP(hipMemcpy(up + n * (size_t)L, guide_pams, n * (size_t)P, hipMemcpyHostToDevice));
@@ -421,21 +421,21 @@ static gs_status enumerate_text(gs_index *ix, bool on_device, const void *guides
       gs_set_error("the search kept no raw counts");
       return GS_ERR_UNSUPPORTED;
     }
-    if (n) GS_HIP(hipMemcpy(raw_hits, ix->w_raw.p, 4 * n, hipMemcpyDeviceToHost));
+    if (n) GS_HIP(hipMemcpy(raw_hits, ix->w_batch.raw.p, 4 * n, hipMemcpyDeviceToHost));
     return GS_OK;
   }
   uint64_t tl = 0;
   if (n) {
     rc = gs_score_device(ix, d_g, n, L, P, score_flags, max_off_targets, gs, d_off, d_hits, nullptr,
-                         nullptr, ix->w_text_spec.p);
+                         nullptr, ix->w_text.spec.p);
     if (rc != GS_OK) return rc;
     const uint32_t fflags = tflags | (sflags & GS_FLAG_PAM_AT_START);
     if (on_device)
-      rc = gs_format_device_ids(ix, gs, d_g, n, L, d_p, P, ids, id_offsets, senses, skip, d_off, d_hits, ix->w_text_spec.p,
+      rc = gs_format_device_ids(ix, gs, d_g, n, L, d_p, P, ids, id_offsets, senses, skip, d_off, d_hits, ix->w_text.spec.p,
                                 mismatches, fflags, max_off_targets, nullptr, &d_text, &tl);
     else
       rc = gs_format_device(ix, gs, d_g, n, L, d_p, P, (const char *)ids, (const uint64_t *)id_offsets, (const uint8_t *)senses,
-                            skip, d_off, d_hits, ix->w_text_spec.p, mismatches, fflags, max_off_targets, nullptr, &d_text, &tl);
+                            skip, d_off, d_hits, ix->w_text.spec.p, mismatches, fflags, max_off_targets, nullptr, &d_text, &tl);
     if (rc != GS_OK) return rc;
   }
   if ((rc = gs_text_to_host(d_text, tl, text)) != GS_OK) return rc;

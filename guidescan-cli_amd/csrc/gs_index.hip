@@ -155,16 +155,13 @@ gs_status gs_strand_from_device(const uint8_t *d_text, gs_scratch &sa_mem, uint3
   hipLaunchKernelGGL(k_build_words, dim3(nblk(nwords, 256)), dim3(256), 0, st, d_text, d_sa_owned, n,
                      nwords, blocks, wcount);
   {
-    size_t tmp_bytes = 0;
-    GS_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, wcount, wscan, 0u, nwords,
-                                   rocprim::plus<uint32_t>(), st));
-    void *tmp = nullptr;
-    GS_TRY(mem.get(tmp_bytes, &tmp));
+    gs_prim_tmp tmp;
     for (int c = 0; c < 4; c++)
-      GS_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, wcount + c * nwords, wscan + c * nwords, 0u,
-                                     nwords, rocprim::plus<uint32_t>(), st));
+      GS_TRY(gs_prim("strand: scan of the word counts", mem, tmp, [&](void *t, size_t &tb) {
+        return rocprim::exclusive_scan(t, tb, wcount + c * nwords, wscan + c * nwords, 0u, nwords, rocprim::plus<uint32_t>(), st);
+      }));
     GS_HIP(hipStreamSynchronize(st));
-    mem.drop(tmp);
+    mem.drop(tmp.p);
   }
   hipLaunchKernelGGL(k_write_headers, dim3(nblk(nblocks, 256)), dim3(256), 0, st, blocks, wscan,
                      nwords, nblocks);
@@ -345,6 +342,7 @@ __global__ void k_sa_count_heads(const uint32_t *head, uint64_t n, unsigned long
 }
 
 gs_status gs_device_suffix_array(const uint8_t *d_text, uint64_t n, uint32_t *d_sa, hipStream_t st) {
+  if (n == 0) return GS_ERR_ARG;
   /* dense alphabet */
   unsigned long long *d_hist = nullptr;
   gs_scratch mem;
@@ -377,14 +375,13 @@ gs_status gs_device_suffix_array(const uint8_t *d_text, uint64_t n, uint32_t *d_
   const unsigned g = nblk(n, 256);
   hipLaunchKernelGGL(k_sa_init_keys, dim3(g), dim3(256), 0, st, d_text, n, d_dense, bits, k0, keys_a,
                      idx_a);
-  size_t sort_bytes = 0, scan_bytes = 0;
-  GS_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys_a, keys_b, idx_a, d_sa, n, 0, 64, st));
-  GS_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, head, head, n, sa_flag_op(), st));
-  void *tmp = nullptr;
-  const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
-  GS_TRY(mem.get(tmp_bytes, &tmp));
-  size_t sb = tmp_bytes;
-  GS_HIP(rocprim::radix_sort_pairs(tmp, sb, keys_a, keys_b, idx_a, d_sa, n, 0, bits * k0, st));
+  gs_prim_tmp tmp; /* of the sorts and the scans: every round asks for its own shape */
+  auto sort = [&](unsigned key_bits) {
+    return gs_prim("suffix array: sort", mem, tmp, [&](void *t, size_t &tb) {
+      return rocprim::radix_sort_pairs(t, tb, keys_a, keys_b, idx_a, d_sa, n, 0, key_bits, st);
+    });
+  };
+  GS_TRY(sort(bits * k0));
   gs_status rc = GS_OK;
   for (uint64_t h = k0;; h *= 2) {
     /* keys_b sorted, d_sa = suffixes in that order */
@@ -400,13 +397,13 @@ gs_status gs_device_suffix_array(const uint8_t *d_text, uint64_t n, uint32_t *d_
       rc = GS_ERR_DEVICE;
       break;
     }
-    sb = tmp_bytes;
-    GS_HIP(rocprim::inclusive_scan(tmp, sb, head, head, n, sa_flag_op(), st));
+    GS_TRY(gs_prim("suffix array: scan of the group heads", mem, tmp, [&](void *t, size_t &tb) {
+      return rocprim::inclusive_scan(t, tb, head, head, n, sa_flag_op(), st);
+    }));
     hipLaunchKernelGGL(k_sa_scatter_rank, dim3(g), dim3(256), 0, st, d_sa, head, n, rank);
     hipLaunchKernelGGL(k_sa_pair_keys, dim3(g), dim3(256), 0, st, d_sa, rank, n, h, nbits, keys_a);
     GS_HIP(hipMemcpyAsync(idx_a, d_sa, 4 * n, hipMemcpyDeviceToDevice, st));
-    sb = tmp_bytes;
-    GS_HIP(rocprim::radix_sort_pairs(tmp, sb, keys_a, keys_b, idx_a, d_sa, n, 0, 2 * nbits, st));
+    GS_TRY(sort(2 * nbits));
   }
   GS_HIP(hipStreamSynchronize(st));
   return rc;
@@ -923,18 +920,6 @@ extern "C" void gs_index_close(gs_index *ix) {
   hipSetDevice(ix->device);
   gs_strand_free(&ix->strand[0]);
   gs_strand_free(&ix->strand[1]);
-  gs_buffer *bufs[] = {&ix->w_guides, &ix->w_slots, &ix->w_counts, &ix->w_nmatch, &ix->w_nhits,
-                       &ix->w_offsets, &ix->w_hits, &ix->w_misc, &ix->w_blocksums, &ix->w_grec, &ix->w_flags, &ix->w_raw,
-                       &ix->w_ovf_list, &ix->w_grec2, &ix->w_slots2, &ix->w_counts2, &ix->w_nmatch2,
-                       &ix->w_nhits2, &ix->w_h_off, &ix->w_h_tmp, &ix->w_b_src, &ix->w_b_cnt, &ix->w_b_prefix,
-                       &ix->w_b_recs, &ix->w_b_w0, &ix->w_b_w0b, &ix->w_b_idx, &ix->w_b_idxb,
-                       &ix->w_b_keep, &ix->w_b_keeps, &ix->w_b_rows, &ix->w_b_rowss, &ix->w_b_redo_pos, &ix->w_b_s, &ix->w_b_tab,
-                       &ix->w_cand, &ix->rec[0].buf, &ix->rec[1].buf, &ix->rec[0].prb_b, &ix->rec[1].prb_b, &ix->rec[0].prb_a[0].buf, &ix->rec[0].prb_a[1].buf,
-                       &ix->rec[1].prb_a[0].buf, &ix->rec[1].prb_a[1].buf, &ix->w_score, &ix->w_score_io, &ix->w_score_tmp, &ix->w_arena, &ix->w_arena_meta, &ix->w_nchunk, &ix->w_shq, &ix->w_sh_meta,
-                       &ix->w_cls, &ix->w_desc, &ix->w_sched, &ix->w_t_plan, &ix->w_t_tiles, &ix->w_t_buckets, &ix->w_t_chunkof, &ix->w_t_big, &ix->w_t_rel, &ix->w_t_tab, &ix->w_t_excl, &ix->w_t_spill, &ix->w_b_redo_pos2,
-                       &ix->w_text_in, &ix->w_text_tmp, &ix->w_text_hex, &ix->w_text, &ix->w_text_spec, &ix->w_text_goff,
-                       &ix->w_bgzf_in, &ix->w_bgzf_tmp, &ix->w_bgzf_out};
-  for (gs_buffer *b : bufs) gs_buffer_free(*b);
   for (int i = 0; i < 4; i++)
     if (ix->ev[i]) hipEventDestroy(ix->ev[i]);
   if (ix->ev_tile) hipEventDestroy(ix->ev_tile);
@@ -968,7 +953,7 @@ extern "C" gs_status gs_index_unlock(gs_index *ix) {
 extern "C" gs_status gs_index_last_guide_flags(const gs_index *ix, const void **d_flags, uint64_t *n_unsupported) {
   GS_HANDLE_LOCK(ix);
   if (!ix) return GS_ERR_ARG;
-  if (d_flags) *d_flags = ix->w_flags.p;
+  if (d_flags) *d_flags = ix->w_batch.flags.p;
   if (n_unsupported) *n_unsupported = ix->last_unsupported;
   return GS_OK;
 }
@@ -1021,14 +1006,14 @@ extern "C" gs_status gs_index_copy_sa(gs_index *ix, int strand, uint32_t *out) {
   return GS_OK;
 }
 
+/* the process's live gs_buffer allocations and their bytes (gs_debug_buffers_live) */
+static std::atomic<uint64_t> g_buffers_live{0}, g_buffer_bytes_live{0};
 gs_status gs_reserve(gs_buffer &b, size_t bytes) {
   if (b.cap >= bytes && b.p) return GS_OK;
   if (bytes > ((size_t)1 << 30) && gs_debug_any.load(std::memory_order_relaxed))
     fprintf(stderr, "[gs] workspace buffer grows from %.2f to %.2f GiB\n", (double)b.cap / (1 << 30), (double)bytes / (1 << 30));
   const bool again = b.p != nullptr && b.cap > ((size_t)1 << 30);
-  if (b.p) hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
+  gs_buffer_free(b);
   /* room to grow without another allocation: a quarter on top, a sixteenth for buffers beyond 1 GiB
    * (the workspace of a repeat-rich batch is tens of GB next to a 220 GB index) - and an eighth when such a buffer grows
    * a second time: batches of one kind differ by several per cent, and freeing and allocating 30 GB takes a second */
@@ -1044,12 +1029,44 @@ gs_status gs_reserve(gs_buffer &b, size_t bytes) {
     want = bytes;
   }
   b.cap = want;
+  g_buffers_live.fetch_add(1, std::memory_order_relaxed);
+  g_buffer_bytes_live.fetch_add(want, std::memory_order_relaxed);
   return GS_OK;
 }
 size_t gs_buffer_free(gs_buffer &b) {
-  const size_t freed = b.p ? b.cap : 0;
-  if (b.p) (void)hipFree(b.p);
+  if (!b.p) return b.cap = 0;
+  const size_t freed = b.cap;
+  (void)hipFree(b.p);
+  g_buffers_live.fetch_sub(1, std::memory_order_relaxed);
+  g_buffer_bytes_live.fetch_sub(freed, std::memory_order_relaxed);
   b.p = nullptr;
   b.cap = 0;
   return freed;
+}
+gs_buffer::~gs_buffer() { gs_buffer_free(*this); }
+gs_buffer &gs_buffer::operator=(gs_buffer &&o) noexcept {
+  if (this != &o) {
+    gs_buffer_free(*this);
+    p = o.p, cap = o.cap;
+    o.p = nullptr, o.cap = 0;
+  }
+  return *this;
+}
+extern "C" gs_status gs_debug_buffers_live(uint64_t out[2]) {
+  if (!out) return GS_ERR_ARG;
+  out[0] = g_buffers_live.load();
+  out[1] = g_buffer_bytes_live.load();
+  return GS_OK;
+}
+extern "C" gs_status gs_debug_workspace(gs_index *ix, uint64_t *out, uint32_t n_groups) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !out || n_groups != GS_WS_GROUPS) return GS_ERR_ARG;
+  memset(out, 0, 3 * sizeof(uint64_t) * GS_WS_GROUPS);
+  gs_ws_report(ix->w_batch, out);
+  gs_ws_report(ix->w_big, out + 3);
+  gs_ws_report(ix->w_tile, out + 6);
+  gs_ws_report(ix->w_score, out + 9);
+  gs_ws_report(ix->w_text, out + 12);
+  gs_ws_report(ix->w_bgzf, out + 15);
+  return GS_OK;
 }

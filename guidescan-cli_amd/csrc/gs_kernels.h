@@ -30,7 +30,7 @@
 #define META_PAM(m) ((uint32_t)(((m) >> 52) & 3))
 #define PATH_MASK ((1ull << 52) - 1)
 
-/* The handle's 512 bytes of counters (gs_index::w_misc), zeroed at the start of every batch: sixteen 64-bit stats words
+/* The handle's 512 bytes of counters (gs_index::w_batch.misc), zeroed at the start of every batch: sixteen 64-bit stats words
  * (k_search's counters, gs_index_last_counters), then 32-bit work words from byte 128, then k_prepare's PAM-pair
  * histogram from byte 256.  Indices into the stats words (ST_*) and into the work words (WK_*). */
 enum : uint32_t {
@@ -495,7 +495,7 @@ struct gs_bigorder_in {
   uint32_t cap_main;
   const uint64_t *slot_off2;
   bool from_arena;
-  const uint32_t *arena_list, *arena_redo_pos; /* arena_redo_pos nullptr: ix->w_b_redo_pos */
+  const uint32_t *arena_list, *arena_redo_pos; /* arena_redo_pos nullptr: ix->w_big.redo_pos */
   uint32_t n_used, arena_chunks, cap;         /* chunks in use, the arena's size, the batch's slots per item */
   uint32_t *nmatch, *nhits;                   /* per set guide */
   uint32_t L, P, m;

@@ -217,7 +217,8 @@ extern "C" gs_status gs_kmers_generate(int device, const uint8_t *chr, uint64_t 
   const uint32_t nb = (uint32_t)((chr_len + KM_BLOCK - 1) / KM_BLOCK);
   gs_scratch mem;
   void *d_chr_own = nullptr, *d_lut = nullptr, *d_cnt = nullptr, *d_off = nullptr, *d_keys = nullptr,
-       *d_keys2 = nullptr, *d_tmp = nullptr;
+       *d_keys2 = nullptr;
+  gs_prim_tmp tmp;
   const uint8_t *d_chr = chr;
   if (!chr_on_device) {
     GS_TRY(mem.get(chr_len, &d_chr_own));
@@ -238,12 +239,9 @@ extern "C" gs_status gs_kmers_generate(int device, const uint8_t *chr, uint64_t 
   a.n_exp = n_exp;
   a.start = (flags & GS_FLAG_PAM_AT_START) ? 1u : 0u;
   hipLaunchKernelGGL(k_km_count, dim3(nb), dim3(KM_BLOCK), 0, st, a, (uint32_t *)d_cnt);
-  size_t tb = 0;
-  GS_HIP(rocprim::exclusive_scan(nullptr, tb, (uint32_t *)d_cnt, (uint32_t *)d_off, 0u, (size_t)nb + 1,
-                                 rocprim::plus<uint32_t>(), st));
-  GS_TRY(mem.get(tb, &d_tmp));
-  GS_HIP(rocprim::exclusive_scan(d_tmp, tb, (uint32_t *)d_cnt, (uint32_t *)d_off, 0u, (size_t)nb + 1,
-                                 rocprim::plus<uint32_t>(), st));
+  GS_TRY(gs_prim("kmers: scan of the counts", mem, tmp, [&](void *t, size_t &tb) {
+    return rocprim::exclusive_scan(t, tb, (uint32_t *)d_cnt, (uint32_t *)d_off, 0u, (size_t)nb + 1, rocprim::plus<uint32_t>(), st);
+  }));
   uint32_t total = 0;
   GS_HIP(hipMemcpyAsync(&total, (uint32_t *)d_off + nb, 4, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
@@ -255,15 +253,9 @@ extern "C" gs_status gs_kmers_generate(int device, const uint8_t *chr, uint64_t 
     /* bucket (1 + 2*nn bits above bit 32), then position: the whole key, so the order does not
      * lean on the sort being stable */
     const unsigned end_bit = 32u + 1u + 2u * nn;
-    size_t sb = 0;
-    GS_HIP(rocprim::radix_sort_keys(nullptr, sb, (uint64_t *)d_keys, (uint64_t *)d_keys2, (size_t)total, 0u,
-                                    end_bit, st));
-    if (sb > tb) {
-      mem.drop(d_tmp);
-      GS_TRY(mem.get(sb, &d_tmp));
-    }
-    GS_HIP(rocprim::radix_sort_keys(d_tmp, sb, (uint64_t *)d_keys, (uint64_t *)d_keys2, (size_t)total, 0u,
-                                    end_bit, st));
+    GS_TRY(gs_prim("kmers: sort", mem, tmp, [&](void *t, size_t &tb) {
+      return rocprim::radix_sort_keys(t, tb, (uint64_t *)d_keys, (uint64_t *)d_keys2, (size_t)total, 0u, end_bit, st);
+    }));
     GS_TRY(km_alloc((size_t)total * k, &km->d_seqs));
     GS_TRY(km_alloc((size_t)total * P, &km->d_pams));
     GS_TRY(km_alloc(4 * (size_t)total, &km->d_pos));
@@ -407,7 +399,7 @@ static gs_status km_encode(gs_kmers *km, const char *prefix, const char *chr_nam
   GS_HIP(hipSetDevice(km->device));
   const uint64_t n = km->n;
   gs_scratch mem;
-  void *d_names = nullptr, *d_lens = nullptr, *d_tmp = nullptr, *off = nullptr, *text = nullptr, *s01 = nullptr;
+  void *d_names = nullptr, *d_lens = nullptr, *off = nullptr, *text = nullptr, *s01 = nullptr;
   std::string names = std::string(prefix) + chr_name;
   GS_TRY(mem.get(names.size(), &d_names));
   GS_HIP(hipMemcpyAsync(d_names, names.data(), names.size(), hipMemcpyHostToDevice, st));
@@ -430,10 +422,10 @@ static gs_status km_encode(gs_kmers *km, const char *prefix, const char *chr_nam
   a.rows = rows ? 1u : 0u;
   const unsigned grid = (unsigned)((n + 1 + KM_BLOCK - 1) / KM_BLOCK);
   hipLaunchKernelGGL(k_km_text_len, dim3(grid), dim3(KM_BLOCK), 0, st, a);
-  size_t tb = 0;
-  GS_HIP(rocprim::exclusive_scan(nullptr, tb, (uint64_t *)d_lens, (uint64_t *)off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
-  GS_TRY(mem.get(tb, &d_tmp));
-  GS_HIP(rocprim::exclusive_scan(d_tmp, tb, (uint64_t *)d_lens, (uint64_t *)off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+  gs_prim_tmp tmp;
+  GS_TRY(gs_prim("kmers text: scan of the lengths", mem, tmp, [&](void *t, size_t &tb) {
+    return rocprim::exclusive_scan(t, tb, (uint64_t *)d_lens, (uint64_t *)off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st);
+  }));
   uint64_t total = 0;
   GS_HIP(hipMemcpyAsync(&total, (uint64_t *)off + n, 8, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));

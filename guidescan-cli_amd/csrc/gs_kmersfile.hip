@@ -216,12 +216,10 @@ gs_status kf_run(int device, const uint8_t *d_raw, uint64_t len, hipStream_t st,
   a.phase = (uint32_t)((uintptr_t)d_raw & 15u);
   const uint64_t nt = (len + a.phase + KF_TILE - 1) / KF_TILE;
   a.n_tiles = nt;
-  size_t tb_s = 0, tb_p = 0;
-  GS_HIP(rocprim::inclusive_scan(nullptr, tb_s, (gs_km_sum *)nullptr, (gs_km_sum *)nullptr, (size_t)nt + 1, kf_compose(), st));
-  void *sums, *fwd, *tmp, *red;
+  void *sums, *fwd, *red;
+  gs_prim_tmp tmp, tmp_p;
   GS_TRY(mem.get(sizeof(gs_km_sum) * (nt + 1), &sums));
   GS_TRY(mem.get(sizeof(gs_km_sum) * (nt + 1), &fwd));
-  GS_TRY(mem.get(tb_s, &tmp));
   GS_TRY(mem.get(sizeof(kf_red), &red));
   a.sums = (gs_km_sum *)sums;
   a.fwd = (const gs_km_sum *)fwd;
@@ -234,7 +232,9 @@ gs_status kf_run(int device, const uint8_t *d_raw, uint64_t len, hipStream_t st,
   GS_HIP(hipMemsetAsync(sums, 0, sizeof(gs_km_sum), st)); /* gs_km_identity() */
   GS_HIP(hipEventRecord(ev.e[0], st));
   hipLaunchKernelGGL(k_kf_tile<KF_SUM>, dim3(tile_grid), dim3(KF_THREADS), 0, st, a);
-  GS_HIP(rocprim::inclusive_scan(tmp, tb_s, a.sums, (gs_km_sum *)fwd, (size_t)nt + 1, kf_compose(), st));
+  GS_TRY(gs_prim("kmers file: scan of the tiles", mem, tmp, [&](void *t, size_t &tb) {
+    return rocprim::inclusive_scan(t, tb, a.sums, (gs_km_sum *)fwd, (size_t)nt + 1, kf_compose(), st);
+  }));
   gs_km_sum whole;
   GS_HIP(hipMemcpyAsync(&whole, (const gs_km_sum *)fwd + nt, sizeof whole, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
@@ -261,12 +261,9 @@ gs_status kf_run(int device, const uint8_t *d_raw, uint64_t len, hipStream_t st,
   const int missing = gs_km_parse_header((const uint8_t *)header.data(), header.size(), a.hdr);
   if (missing >= 0) return kf_report_bad(rep, GS_KM_LACKS, 0, 0, 0, gs_km_column_name(missing));
   /* b. and c. */
-  GS_HIP(rocprim::exclusive_scan(nullptr, tb_p, rocprim::make_transform_iterator((const kf_rec *)nullptr, kf_to_pair()), (kf_pair *)nullptr,
-                                 kf_pair{0, 0}, (size_t)n_lines + 1, kf_pair_add(), st));
-  void *recs, *before, *tmp_p;
+  void *recs, *before;
   GS_TRY(mem.get(sizeof(kf_rec) * (n_lines + 1), &recs));
   GS_TRY(mem.get(sizeof(kf_pair) * (n_lines + 1), &before));
-  GS_TRY(mem.get(tb_p, &tmp_p));
   a.recs = (kf_rec *)recs;
   a.before = (const kf_pair *)before;
   const kf_red none{~0ull, ~0u, 0u, ~0u, 0u, 0u, 0u};
@@ -276,8 +273,10 @@ gs_status kf_run(int device, const uint8_t *d_raw, uint64_t len, hipStream_t st,
   GS_HIP(hipEventRecord(ev.e[3], st));
   hipLaunchKernelGGL(k_kf_lines, dim3(line_grid), dim3(KF_THREADS), 0, st, a);
   GS_HIP(hipEventRecord(ev.e[4], st));
-  GS_HIP(rocprim::exclusive_scan(tmp_p, tb_p, rocprim::make_transform_iterator((const kf_rec *)recs, kf_to_pair()), (kf_pair *)before,
-                                 kf_pair{0, 0}, (size_t)n_lines + 1, kf_pair_add(), st));
+  GS_TRY(gs_prim("kmers file: scan of the lines", mem, tmp_p, [&](void *t, size_t &tb) {
+    return rocprim::exclusive_scan(t, tb, rocprim::make_transform_iterator((const kf_rec *)recs, kf_to_pair()), (kf_pair *)before,
+                                   kf_pair{0, 0}, (size_t)n_lines + 1, kf_pair_add(), st);
+  }));
   GS_HIP(hipEventRecord(ev.e[5], st));
   kf_red got;
   kf_pair all;

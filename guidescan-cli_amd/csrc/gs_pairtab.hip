@@ -182,16 +182,15 @@ void gs_pairtab_free(gs_index *ix, uint32_t slot) {
 /* start[] = the exclusive sums of count[] over `entries` entries (the scan's temporary comes from mem and goes back);
  * *total = their sum */
 static gs_status scan_counts(gs_scratch &mem, uint32_t *count, uint32_t *start, uint64_t entries, hipStream_t st, uint64_t *total) {
-  size_t tmp_bytes = 0;
-  void *tmp = nullptr;
-  GS_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, count, start, 0u, entries, rocprim::plus<uint32_t>(), st));
-  GS_TRY(mem.get(tmp_bytes, &tmp));
-  GS_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, count, start, 0u, entries, rocprim::plus<uint32_t>(), st));
+  gs_prim_tmp tmp;
+  GS_TRY(gs_prim("scan_counts", mem, tmp, [&](void *t, size_t &tb) {
+    return rocprim::exclusive_scan(t, tb, count, start, 0u, entries, rocprim::plus<uint32_t>(), st);
+  }));
   uint32_t last_start = 0, last_count = 0;
   GS_HIP(hipMemcpyAsync(&last_start, start + entries - 1, 4, hipMemcpyDeviceToHost, st));
   GS_HIP(hipMemcpyAsync(&last_count, count + entries - 1, 4, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
-  mem.drop(tmp);
+  mem.drop(tmp.p);
   *total = (uint64_t)last_start + last_count;
   return GS_OK;
 }
@@ -491,11 +490,10 @@ static gs_status build_spaced(gs_index *ix, gs_pairtab_host &p, int s, uint32_t 
   a.vals = d_vals;
   hipLaunchKernelGGL(k_sp_fill, dim3(nb), dim3(256), 0, st, a);
   if (rows) {
-    size_t tmp_bytes = 0;
-    void *d_tmp = nullptr;
-    GS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys, d_keys2, d_vals, sp_rows, rows, 0, key_bits, st));
-    GS_TRY(mem.get(tmp_bytes, &d_tmp));
-    GS_HIP(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_vals, sp_rows, rows, 0, key_bits, st));
+    gs_prim_tmp tmp;
+    GS_TRY(gs_prim("spaced table: sort", mem, tmp, [&](void *t, size_t &tb) {
+      return rocprim::radix_sort_pairs(t, tb, d_keys, d_keys2, d_vals, sp_rows, rows, 0, key_bits, st);
+    }));
   }
   hipLaunchKernelGGL(k_sp_offsets, dim3((uint32_t)((rows + 1 + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_keys2, (uint32_t)rows, rem, d,
                      sp_off);

@@ -269,7 +269,7 @@ gs_status gs_recipes_for(gs_index *ix, uint32_t L, uint32_t P, uint32_t m, uint3
   if (n_b) {
     std::vector<uint2> pb(n_b);
     for (size_t i = 0; i < n_b; i++) pb[i] = gs_probe_b(R.host_ba[i], L - v_rem);
-    if ((rc = gs_reserve(R.prb_b, 8 * n_b + 64)) != GS_OK) return rc;
+    GS_TRY(gs_reserve(R.prb_b, 8 * n_b + 64));
     GS_HIP(hipMemcpyAsync(R.prb_b.p, pb.data(), 8 * n_b, hipMemcpyHostToDevice, st));
     GS_HIP(hipStreamSynchronize(st)); /* `pb` is a local */
   }

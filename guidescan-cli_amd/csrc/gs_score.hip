@@ -466,10 +466,9 @@ extern "C" gs_status gs_score_device(gs_index *ix, const void *d_guides, uint64_
   if (n == 0) return GS_OK;
   hipStream_t st = (hipStream_t)stream;
   GS_HIP(hipSetDevice(ix->device));
-  gs_status rc;
   const size_t cum_bytes = 8 * ((size_t)gs->n_chr + 1);
   const size_t bins_at = 336 * sizeof(double) + cum_bytes; /* behind the prefix sums: the bin table (uint16 x SC_BINS, as 1,024 uint64), 40 + 40 class words, the guide counter, the order */
-  if ((rc = gs_reserve(ix->w_score, bins_at + 2 * SC_BINS + 4 * 96 + 4 * ((size_t)n + 1))) != GS_OK) return rc;
+  GS_TRY(gs_reserve(ix->w_score.tab, bins_at + 2 * SC_BINS + 4 * 96 + 4 * ((size_t)n + 1)));
   std::vector<uint64_t> host(336 + (size_t)gs->n_chr + 1 + SC_BINS / 4);
   memcpy(host.data(), gs_cfd_mm, 320 * sizeof(double));
   memcpy(host.data() + 320, gs_cfd_pam, 16 * sizeof(double));
@@ -493,14 +492,14 @@ extern "C" gs_status gs_score_device(gs_index *ix, const void *d_guides, uint64_
       bins[b] = e;
     }
   }
-  GS_HIP(hipMemcpyAsync(ix->w_score.p, host.data(), 8 * host.size(), hipMemcpyHostToDevice, st));
+  GS_HIP(hipMemcpyAsync(ix->w_score.tab.p, host.data(), 8 * host.size(), hipMemcpyHostToDevice, st));
   GS_HIP(hipStreamSynchronize(st)); /* `host` is a local */
   gs_score_args a;
   a.guides = (const uint8_t *)d_guides;
   a.offsets = (const uint64_t *)d_offsets;
   a.hits = (const gs_hit *)d_hits;
-  a.tab = (const double *)ix->w_score.p;
-  a.chr_cum = (const uint64_t *)ix->w_score.p + 336;
+  a.tab = (const double *)ix->w_score.tab.p;
+  a.chr_cum = (const uint64_t *)ix->w_score.tab.p + 336;
   a.cfd = (float *)d_cfd;
   a.spec = (float *)d_specificity;
   a.max_off = (long long)max_off_targets;
@@ -518,16 +517,16 @@ extern "C" gs_status gs_score_device(gs_index *ix, const void *d_guides, uint64_
   /* --max-off-targets: every CFD (the caller's array or one of the handle's) and the fact bytes; else the scores as they
    * enter the sums (+ 8 KB: the last guide's unguarded loads reach up to three rounds beyond them) and a word per guide */
   const bool with_max = max_off_targets != -1;
-  if ((rc = gs_reserve(ix->w_score_tmp, with_max ? (d_cfd ? 0 : 4 * n_hits) + n_hits + 64 : 4 * n_hits + 8192 + 128 + 4 * (n + 1))) != GS_OK) return rc;
-  float *cf = d_cfd ? (float *)d_cfd : with_max ? (float *)ix->w_score_tmp.p : nullptr;
-  uint8_t *info = with_max ? (uint8_t *)ix->w_score_tmp.p + (d_cfd ? 0 : 4 * n_hits) : nullptr;
-  float *cfm = with_max ? nullptr : (float *)ix->w_score_tmp.p;
-  uint32_t *d_perfect = with_max ? nullptr : (uint32_t *)((char *)ix->w_score_tmp.p + ((4 * n_hits + 8192 + 63) & ~(size_t)63));
+  GS_TRY(gs_reserve(ix->w_score.tmp, with_max ? (d_cfd ? 0 : 4 * n_hits) + n_hits + 64 : 4 * n_hits + 8192 + 128 + 4 * (n + 1)));
+  float *cf = d_cfd ? (float *)d_cfd : with_max ? (float *)ix->w_score.tmp.p : nullptr;
+  uint8_t *info = with_max ? (uint8_t *)ix->w_score.tmp.p + (d_cfd ? 0 : 4 * n_hits) : nullptr;
+  float *cfm = with_max ? nullptr : (float *)ix->w_score.tmp.p;
+  uint32_t *d_perfect = with_max ? nullptr : (uint32_t *)((char *)ix->w_score.tmp.p + ((4 * n_hits + 8192 + 63) & ~(size_t)63));
   if (!with_max) GS_HIP(hipMemsetAsync(d_perfect, 0, 4 * n, st));
   gs_score_geo geo;
-  geo.bin_chr = (const uint16_t *)((const char *)ix->w_score.p + bins_at);
+  geo.bin_chr = (const uint16_t *)((const char *)ix->w_score.tab.p + bins_at);
   geo.bin_shift = bin_shift;
-  uint32_t *d_cls = (uint32_t *)((char *)ix->w_score.p + bins_at + 2 * SC_BINS), *d_cursor = d_cls + 40, *d_next = d_cls + 80, *d_order = d_cls + 96;
+  uint32_t *d_cls = (uint32_t *)((char *)ix->w_score.tab.p + bins_at + 2 * SC_BINS), *d_cursor = d_cls + 40, *d_next = d_cls + 80, *d_order = d_cls + 96;
   GS_HIP(hipMemsetAsync(d_cls, 0, 4 * 96, st));
   if (n_hits) {
     uint64_t gh = ((n_hits + SC_CHUNK - 1) / SC_CHUNK + 3) / 4; /* four waves per workgroup, a chunk per wave and visit */
@@ -571,9 +570,9 @@ extern "C" gs_status gs_score(gs_index *ix, const char *guides, uint64_t n, uint
   GS_HIP(hipSetDevice(ix->device));
   const size_t b_g = ((size_t)n * L + 15) & ~(size_t)15, b_o = (8 * ((size_t)n + 1) + 15) & ~(size_t)15,
                b_h = sizeof(gs_hit) * (size_t)nh, b_c = (4 * (size_t)nh + 15) & ~(size_t)15, b_s = 4 * (size_t)n;
-  gs_status rc = gs_reserve(ix->w_score_io, b_g + b_o + b_h + b_c + b_s + 64);
+  gs_status rc = gs_reserve(ix->w_score.io, b_g + b_o + b_h + b_c + b_s + 64);
   if (rc != GS_OK) return rc;
-  char *p = (char *)ix->w_score_io.p;
+  char *p = (char *)ix->w_score.io.p;
   char *d_g = p, *d_o = d_g + b_g, *d_h = d_o + b_o, *d_c = d_h + b_h, *d_s = d_c + b_c;
   GS_HIP(hipMemcpy(d_g, guides, (size_t)n * L, hipMemcpyHostToDevice));
   GS_HIP(hipMemcpy(d_o, offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice));

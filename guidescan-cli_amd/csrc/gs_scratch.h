@@ -7,12 +7,6 @@
 
 #include <chrono>
 
-#define GS_TRY(expr)                 \
-  do {                               \
-    gs_status rc__ = (expr);         \
-    if (rc__ != GS_OK) return rc__;  \
-  } while (0)
-
 double gs_ms_since(std::chrono::steady_clock::time_point t0);
 
 /* Device allocations of one call, all freed by the destructor unless handed on.  get(bytes) allocates bytes + 16: never an
@@ -40,6 +34,61 @@ struct gs_scratch {
     q = nullptr;
   }
 };
+
+/* rocPRIM's protocol - ask with a null temporary how much the call needs, make room, run - around ONE argument list:
+ * `call` is [&](void *tmp, size_t &bytes) { return rocprim::...(tmp, bytes, ...); }, `what` names the site in messages.
+ * The run with a temporary does not look at the size it is given, so no form runs before the need is known to fit. */
+inline gs_status gs_prim_fail(const char *what, hipError_t e, size_t need, size_t room) {
+  if (e != hipSuccess)
+    gs_set_error(std::string(what) + ": " + hipGetErrorString(e));
+  else
+    gs_set_error(std::string(what) + ": the temporary holds " + std::to_string(room) + " bytes, the call needs " + std::to_string(need));
+  return GS_ERR_DEVICE;
+}
+template <class F>
+gs_status gs_prim_need(const char *what, F &call, size_t &need) {
+  need = 0;
+  const hipError_t e = call(nullptr, need);
+  return e == hipSuccess ? GS_OK : gs_prim_fail(what, e, 0, 0);
+}
+template <class F>
+gs_status gs_prim_run(const char *what, void *tmp, size_t room, size_t need, F &call) {
+  if (!tmp || need > room) return gs_prim_fail(what, hipSuccess, need, room);
+  const hipError_t e = call(tmp, need);
+  return e == hipSuccess ? GS_OK : gs_prim_fail(what, e, 0, 0);
+}
+/* the temporary is carved out of a larger allocation sized up front: `room` bytes at tmp.  A need beyond it is an error */
+template <class F>
+gs_status gs_prim_carved(const char *what, void *tmp, size_t room, F &&call) {
+  size_t need;
+  GS_TRY(gs_prim_need(what, call, need));
+  return gs_prim_run(what, tmp, room, need, call);
+}
+/* the temporary grows: a buffer of a handle or a decoder ... */
+template <class F>
+gs_status gs_prim(const char *what, gs_buffer &tmp, F &&call) {
+  size_t need;
+  GS_TRY(gs_prim_need(what, call, need));
+  GS_TRY(gs_reserve(tmp, need + 16));
+  return gs_prim_run(what, tmp.p, tmp.cap, need, call);
+}
+/* ... or an allocation in a scratch, dropped and got again when the call needs more than it holds */
+struct gs_prim_tmp {
+  void *p = nullptr;
+  size_t bytes = 0;
+};
+template <class F>
+gs_status gs_prim(const char *what, gs_scratch &mem, gs_prim_tmp &tmp, F &&call) {
+  size_t need;
+  GS_TRY(gs_prim_need(what, call, need));
+  if (!tmp.p || need > tmp.bytes) {
+    tmp.bytes = 0;
+    if (tmp.p) mem.drop(tmp.p);
+    GS_TRY(mem.get(need, &tmp.p));
+    tmp.bytes = need;
+  }
+  return gs_prim_run(what, tmp.p, tmp.bytes, need, call);
+}
 
 /* N events; elapsed(): the milliseconds from event from[i] to event from[i] + 1, for n pairs */
 gs_status gs_events_elapsed(const hipEvent_t *e, const int *from, int n, double *out);

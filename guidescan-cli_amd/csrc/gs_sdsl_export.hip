@@ -14,6 +14,7 @@
  * The format is restated here from the reference's headers (file:line at each part); no SDSL code is part of the product.
  */
 #include "gs_common.h"
+#include "gs_scratch.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -529,8 +530,11 @@ static gs_status export_strand_device(gs_index *ix, int strand, const uint8_t *t
     EXP_HIP(d_bits.get(nbits));
     EXP_HIP(d_cnt.get(4 * nb));
     EXP_HIP(d_excl.get(4 * nb));
+    auto scan = [&](void *t, size_t &b) {
+      return rocprim::exclusive_scan(t, b, (uint32_t *)d_cnt.p, (uint32_t *)d_excl.p, 0u, (size_t)nb, rocprim::plus<uint32_t>(), st);
+    };
     size_t tb = 0;
-    EXP_HIP(rocprim::exclusive_scan(nullptr, tb, (uint32_t *)d_cnt.p, (uint32_t *)d_excl.p, 0u, (size_t)nb, rocprim::plus<uint32_t>(), st));
+    GS_TRY(gs_prim_need("export: scan of the chunk counts", scan, tb));
     EXP_HIP(d_tmp.get(tb + 16));
     for (size_t v = 0; v < T.nodes.size(); v++) {
       const exp_node &nd = T.nodes[v];
@@ -554,8 +558,7 @@ static gs_status export_strand_device(gs_index *ix, int strand, const uint8_t *t
       if (nd.bv_pos + nd.size > nbits) return GS_ERR_ARG; /* (never: bv_pos are sums of node sizes) */
       hipLaunchKernelGGL(k_exp_count, dim3(grid_for(nb, 4)), dim3(256), 0, st, (const uint8_t *)d_bwt.p, n, K, nb, (uint32_t *)d_cnt.p);
       EXP_HIP(hipGetLastError());
-      size_t t2 = tb;
-      EXP_HIP(rocprim::exclusive_scan(d_tmp.p, t2, (uint32_t *)d_cnt.p, (uint32_t *)d_excl.p, 0u, (size_t)nb, rocprim::plus<uint32_t>(), st));
+      GS_TRY(gs_prim_run("export: scan of the chunk counts", d_tmp.p, d_tmp.bytes, tb, scan));
       hipLaunchKernelGGL(k_exp_scatter, dim3(grid_for(nb, 4)), dim3(256), 0, st, (const uint8_t *)d_bwt.p, n, K, nb, (const uint32_t *)d_excl.p,
                          (uint8_t *)d_bits.p + nd.bv_pos, nd.size);
       EXP_HIP(hipGetLastError());
@@ -571,10 +574,13 @@ static gs_status export_strand_device(gs_index *ix, int strand, const uint8_t *t
   EXP_HIP(d_ob.get(8 * (W + 1)));
   {
     dbuf d_tmp;
+    auto scan = [&](void *t, size_t &b) {
+      return rocprim::exclusive_scan(t, b, (uint64_t *)d_pc.p, (uint64_t *)d_ob.p, (uint64_t)0, (size_t)(W + 1), rocprim::plus<uint64_t>(), st);
+    };
     size_t tb = 0;
-    EXP_HIP(rocprim::exclusive_scan(nullptr, tb, (uint64_t *)d_pc.p, (uint64_t *)d_ob.p, (uint64_t)0, (size_t)(W + 1), rocprim::plus<uint64_t>(), st));
+    GS_TRY(gs_prim_need("export: scan of the words' ones", scan, tb));
     EXP_HIP(d_tmp.get(tb + 16));
-    EXP_HIP(rocprim::exclusive_scan(d_tmp.p, tb, (uint64_t *)d_pc.p, (uint64_t *)d_ob.p, (uint64_t)0, (size_t)(W + 1), rocprim::plus<uint64_t>(), st));
+    GS_TRY(gs_prim_run("export: scan of the words' ones", d_tmp.p, d_tmp.bytes, tb, scan));
     EXP_HIP(hipMemcpy(&X.ones, (uint64_t *)d_ob.p + W, 8, hipMemcpyDeviceToHost));
   }
   d_pc.drop();

@@ -523,21 +523,19 @@ static gs_status sdsl_strand_on_device(const char *path, gs_scratch &keep, uint8
     return GS_ERR_FORMAT;
   }
   /* rows of each symbol before every chunk of 64 */
-  void *d_cnt = nullptr, *d_ck = nullptr, *d_tmp = nullptr;
+  void *d_cnt = nullptr, *d_ck = nullptr;
+  gs_prim_tmp tmp, sort_tmp;
   GS_TRY(mem.get(4 * (size_t)sigma * nb, &d_cnt));
   GS_TRY(mem.get(4 * (size_t)sigma * nb, &d_ck));
   hipLaunchKernelGGL(k_imp_chunks, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, 0, (const uint8_t *)d_bwt, n, L.D, sigma, nb, (uint32_t *)d_cnt);
-  size_t tb = 0;
-  GS_HIP(rocprim::exclusive_scan(nullptr, tb, (uint32_t *)d_cnt, (uint32_t *)d_ck, 0u, (size_t)nb, rocprim::plus<uint32_t>(), 0));
-  GS_TRY(mem.get(tb, &d_tmp));
-  for (uint32_t d = 0; d < sigma; d++) {
-    size_t t2 = tb;
-    GS_HIP(rocprim::exclusive_scan(d_tmp, t2, (uint32_t *)d_cnt + (size_t)d * nb, (uint32_t *)d_ck + (size_t)d * nb, 0u, (size_t)nb,
-                                    rocprim::plus<uint32_t>(), 0));
-  }
+  for (uint32_t d = 0; d < sigma; d++)
+    GS_TRY(gs_prim("import: scan of a symbol's chunk counts", mem, tmp, [&](void *t, size_t &tb) {
+      return rocprim::exclusive_scan(t, tb, (uint32_t *)d_cnt + (size_t)d * nb, (uint32_t *)d_ck + (size_t)d * nb, 0u, (size_t)nb,
+                                     rocprim::plus<uint32_t>(), 0);
+    }));
   mem.drop(d_cnt);
   /* the samples by text position */
-  void *d_packed = nullptr, *d_pos = nullptr, *d_idx = nullptr, *d_pos2 = nullptr, *d_idx2 = nullptr, *d_sorttmp = nullptr;
+  void *d_packed = nullptr, *d_pos = nullptr, *d_idx = nullptr, *d_pos2 = nullptr, *d_idx2 = nullptr;
   const uint64_t pw = (P.sa_samples.bits + 63) >> 6;
   GS_TRY(mem.get(8 * (pw + 2), &d_packed));
   GS_HIP(hipMemset(d_packed, 0, 8 * (pw + 2)));
@@ -548,10 +546,9 @@ static gs_status sdsl_strand_on_device(const char *path, gs_scratch &keep, uint8
   GS_TRY(mem.get(4 * ns, &d_idx2));
   hipLaunchKernelGGL(k_imp_samples, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, 0, (const uint64_t *)d_packed, width, ns, (uint32_t *)d_pos,
                      (uint32_t *)d_idx);
-  size_t sb = 0;
-  GS_HIP(rocprim::radix_sort_pairs(nullptr, sb, (uint32_t *)d_pos, (uint32_t *)d_pos2, (uint32_t *)d_idx, (uint32_t *)d_idx2, (size_t)ns, 0, 32, 0));
-  GS_TRY(mem.get(sb, &d_sorttmp));
-  GS_HIP(rocprim::radix_sort_pairs(d_sorttmp, sb, (uint32_t *)d_pos, (uint32_t *)d_pos2, (uint32_t *)d_idx, (uint32_t *)d_idx2, (size_t)ns, 0, 32, 0));
+  GS_TRY(gs_prim("import: sort of the samples", mem, sort_tmp, [&](void *t, size_t &tb) {
+    return rocprim::radix_sort_pairs(t, tb, (uint32_t *)d_pos, (uint32_t *)d_pos2, (uint32_t *)d_idx, (uint32_t *)d_idx2, (size_t)ns, 0, 32, 0);
+  }));
   uint32_t last = 0;
   GS_HIP(hipMemcpy(&last, (uint32_t *)d_pos2 + (ns - 1), 4, hipMemcpyDeviceToHost));
   if ((uint64_t)last != n - 1) { /* row 0 (the sentinel suffix) is always sampled */

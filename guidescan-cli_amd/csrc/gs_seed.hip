@@ -935,12 +935,11 @@ GS_DEF_SEED(k_seed_count_a, true, 1)
 
 /* ---- host: the descriptor pre-pass + the schedules, then the two launches (run_search's SPEC form) ---- */
 gs_status gs_seed_describe(gs_index *ix, const gs_search_args &sa, uint32_t ng, bool sorted, hipStream_t st, gs_search_args *out) {
-  gs_status rc;
-  if ((rc = gs_reserve(ix->w_desc, sizeof(gs_guide_desc) * ((size_t)ng + 1) * (sorted ? 3u : 1u))) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_sched, 4 * (2 * 65536 + 512 + 16))) != GS_OK) return rc;
-  uint32_t *base = (uint32_t *)ix->w_sched.p;
+  GS_TRY(gs_reserve(ix->w_batch.desc, sizeof(gs_guide_desc) * ((size_t)ng + 1) * (sorted ? 3u : 1u)));
+  GS_TRY(gs_reserve(ix->w_batch.sched, 4 * (2 * 65536 + 512 + 16)));
+  uint32_t *base = (uint32_t *)ix->w_batch.sched.p;
   uint32_t *xwork = base, *hist = base + 512;
-  gs_guide_desc *desc = (gs_guide_desc *)ix->w_desc.p, *desc_a = desc + ng, *desc_b = desc_a + ng;
+  gs_guide_desc *desc = (gs_guide_desc *)ix->w_batch.desc.p, *desc_a = desc + ng, *desc_b = desc_a + ng;
   gs_describe_args da;
   memset(&da, 0, sizeof(da));
   da.guides = sa.guides;

@@ -100,6 +100,7 @@ __global__ void k_sx_apply(const uint32_t *vals, const uint32_t *ngrp, const uin
 }
 
 gs_status gs_device_suffix_array_discarding(const uint8_t *d_text, uint64_t n, uint32_t *d_sa, hipStream_t st, bool debug) {
+  if (n == 0) return GS_ERR_ARG;
   gs_scratch B; /* everything the builder allocates: released on every way out */
   /* dense alphabet: as many symbols per first key as 64 bits hold */
   unsigned long long *d_hist = nullptr;
@@ -130,32 +131,42 @@ gs_status gs_device_suffix_array_discarding(const uint8_t *d_text, uint64_t n, u
   GS_TRY(B.get(4 * n, &head));
   const unsigned g = sx_blk(n, 256);
   hipLaunchKernelGGL(k_sx_init_keys, dim3(g), dim3(256), 0, st, d_text, n, d_dense, bits, k0, keys_a, idx_a);
-  size_t sort_bytes = 0, scan_bytes = 0, xscan_bytes = 0;
-  GS_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys_a, keys_b, idx_a, d_sa, n, 0, 64, st));
-  GS_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, head, head, n, sx_max_op(), st));
-  GS_HIP(rocprim::exclusive_scan(nullptr, xscan_bytes, head, head, 0u, n, rocprim::plus<uint32_t>(), st));
-  void *tmp = nullptr;
-  const size_t tmp_bytes = std::max(sort_bytes, std::max(scan_bytes, xscan_bytes));
-  GS_TRY(B.get(tmp_bytes, &tmp));
-  size_t sb = tmp_bytes;
+  /* the temporary of the sorts and the scans, and the three of them over `rows` rows: every round asks for its own shape */
+  gs_prim_tmp tmp;
+  auto sort = [&](uint64_t *k_in, uint64_t *k_out, uint32_t *v_in, uint32_t *v_out, uint64_t rows, unsigned key_bits) {
+    return gs_prim("suffix array: sort", B, tmp, [&](void *t, size_t &tb) {
+      return rocprim::radix_sort_pairs(t, tb, k_in, k_out, v_in, v_out, rows, 0, key_bits, st);
+    });
+  };
+  auto scan_heads = [&](uint32_t *heads, uint64_t rows) {
+    return gs_prim("suffix array: scan of the group heads", B, tmp, [&](void *t, size_t &tb) {
+      return rocprim::inclusive_scan(t, tb, heads, heads, rows, sx_max_op(), st);
+    });
+  };
+  auto scan_places = [&](uint32_t *flags, uint32_t *places, uint64_t rows) {
+    return gs_prim("suffix array: scan of the rows in play", B, tmp, [&](void *t, size_t &tb) {
+      return rocprim::exclusive_scan(t, tb, flags, places, 0u, rows, rocprim::plus<uint32_t>(), st);
+    });
+  };
   /* round 0, all rows: sort by the first k0 symbols; groups, ranks */
-  GS_HIP(rocprim::radix_sort_pairs(tmp, sb, keys_a, keys_b, idx_a, d_sa, n, 0, bits * k0, st));
+  GS_TRY(sort(keys_a, keys_b, idx_a, d_sa, n, bits * k0));
   hipLaunchKernelGGL(k_sx_heads, dim3(g), dim3(256), 0, st, keys_b, (const uint32_t *)nullptr, n, head);
-  sb = tmp_bytes;
-  GS_HIP(rocprim::inclusive_scan(tmp, sb, head, head, n, sx_max_op(), st));
+  GS_TRY(scan_heads(head, n));
   hipLaunchKernelGGL(k_sx_scatter_rank, dim3(g), dim3(256), 0, st, d_sa, head, n, rank);
   /* the rows in play: flag -> idx_a, places -> keys_a (as 32-bit words) */
   uint32_t *flag = idx_a, *place = (uint32_t *)keys_a;
   hipLaunchKernelGGL(k_sx_company, dim3(g), dim3(256), 0, st, head, n, flag);
-  sb = tmp_bytes;
-  GS_HIP(rocprim::exclusive_scan(tmp, sb, flag, place, 0u, n, rocprim::plus<uint32_t>(), st));
+  GS_TRY(scan_places(flag, place, n));
   uint32_t h_last[2] = {0, 0};
   GS_HIP(hipMemcpyAsync(&h_last[0], place + (n - 1), 4, hipMemcpyDeviceToHost, st));
   GS_HIP(hipMemcpyAsync(&h_last[1], flag + (n - 1), 4, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   uint64_t n_act = (uint64_t)h_last[0] + h_last[1];
   if (debug) fprintf(stderr, "[gs] suffix array: %llu rows, %u symbols per first key, %llu rows in groups with company\n", (unsigned long long)n, k0, (unsigned long long)n_act);
-  if (n_act == 0) return GS_OK;
+  if (n_act == 0) {
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+  }
   uint32_t *pos = nullptr, *pos2 = nullptr;
   GS_TRY(B.get(4 * n_act, &pos));
   hipLaunchKernelGGL(k_sx_compact, dim3(g), dim3(256), 0, st, flag, place, (const uint32_t *)nullptr, n, pos);
@@ -183,15 +194,12 @@ gs_status gs_device_suffix_array_discarding(const uint8_t *d_text, uint64_t n, u
     }
     const unsigned ga = sx_blk(n_act, 256);
     hipLaunchKernelGGL(k_sx_pair_keys, dim3(ga), dim3(256), 0, st, pos, d_sa, rank, n, h, nbits, n_act, keys, vals);
-    sb = tmp_bytes;
-    GS_HIP(rocprim::radix_sort_pairs(tmp, sb, keys, keys2, vals, vals2, n_act, 0, 2 * nbits, st));
+    GS_TRY(sort(keys, keys2, vals, vals2, n_act, 2 * nbits));
     hipLaunchKernelGGL(k_sx_heads, dim3(ga), dim3(256), 0, st, keys2, pos, n_act, ngrp);
-    sb = tmp_bytes;
-    GS_HIP(rocprim::inclusive_scan(tmp, sb, ngrp, ngrp, n_act, sx_max_op(), st));
+    GS_TRY(scan_heads(ngrp, n_act));
     hipLaunchKernelGGL(k_sx_apply, dim3(ga), dim3(256), 0, st, vals2, ngrp, pos, n_act, d_sa, rank);
     hipLaunchKernelGGL(k_sx_company, dim3(ga), dim3(256), 0, st, ngrp, n_act, cflag);
-    sb = tmp_bytes;
-    GS_HIP(rocprim::exclusive_scan(tmp, sb, cflag, cplace, 0u, n_act, rocprim::plus<uint32_t>(), st));
+    GS_TRY(scan_places(cflag, cplace, n_act));
     GS_HIP(hipMemcpyAsync(&h_last[0], cplace + (n_act - 1), 4, hipMemcpyDeviceToHost, st));
     GS_HIP(hipMemcpyAsync(&h_last[1], cflag + (n_act - 1), 4, hipMemcpyDeviceToHost, st));
     hipLaunchKernelGGL(k_sx_compact, dim3(ga), dim3(256), 0, st, cflag, cplace, pos, n_act, pos2);

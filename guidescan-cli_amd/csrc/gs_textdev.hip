@@ -23,6 +23,7 @@
  */
 #include "gs_device.h"
 #include "gs_bgzf_huff.h"
+#include "gs_scratch.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -689,7 +690,6 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
   try {
     hipStream_t st = (hipStream_t)stream;
     GS_HIP(hipSetDevice(ix->device));
-    gs_status rc;
     /* what the call uploads: id offsets and bytes, chromosome prefix sums and names, senses, skip */
     const uint64_t id0 = up ? id_offsets[0] : 0, id_bytes = up ? id_offsets[n] - id0 : 0;
     std::vector<uint32_t> name_off(gs->n_chr + 1, 0);
@@ -713,9 +713,9 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
     }
     uint64_t genome = 0;
     for (uint32_t c = 0; c < gs->n_chr; c++) genome += gs->chr_lengths[c];
-    if ((rc = gs_reserve(ix->w_text_in, in.at + 16)) != GS_OK) return rc;
-    const uint8_t *din = (const uint8_t *)ix->w_text_in.p;
-    GS_HIP(hipMemcpyAsync(ix->w_text_in.p, host.data(), in.at, hipMemcpyHostToDevice, st));
+    GS_TRY(gs_reserve(ix->w_text.in, in.at + 16));
+    const uint8_t *din = (const uint8_t *)ix->w_text.in.p;
+    GS_HIP(hipMemcpyAsync(ix->w_text.in.p, host.data(), in.at, hipMemcpyHostToDevice, st));
     uint64_t ends[2] = {0, 0};
     GS_HIP(hipMemcpyAsync(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost, st));
     GS_HIP(hipMemcpyAsync(&ends[1], (const uint64_t *)d_offsets + n, 8, hipMemcpyDeviceToHost, st));
@@ -745,12 +745,12 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
     }
     bump tm;
     const size_t t_err = tm.take(16), t_lens = tm.take(4 * slots), t_tsum = tm.take(8 * ((size_t)n_tiles + 1)),
-                 t_toff = tm.take(8 * ((size_t)n_tiles + 1)), t_scan = tm.take(std::max(tb_tiles, std::max(tb_hits, tb_guides))),
+                 t_toff = tm.take(8 * ((size_t)n_tiles + 1)), tb_scan = std::max(tb_tiles, std::max(tb_hits, tb_guides)), t_scan = tm.take(tb_scan),
                  t_okf = tm.take(sam ? 4 * (nh + 1) : 0), t_S = tm.take(sam ? 4 * (nh + 1) : 0), t_cnt = tm.take(sam ? 32 * n : 0),
                  t_sbase = tm.take(sam ? 32 * n : 0), t_kbase = tm.take(sam ? 32 * n : 0), t_hu = tm.take(sam ? 8 * (n + 1) : 0),
                  t_ho = tm.take(sam ? 8 * (n + 1) : 0);
-    if ((rc = gs_reserve(ix->w_text_tmp, tm.at + 16)) != GS_OK) return rc;
-    char *tmp = (char *)ix->w_text_tmp.p;
+    GS_TRY(gs_reserve(ix->w_text.tmp, tm.at + 16));
+    char *tmp = (char *)ix->w_text.tmp.p;
 
     tx_args a;
     memset(&a, 0, sizeof a);
@@ -799,20 +799,26 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
     if (sam) {
       const uint32_t gh = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nh + 256) / 256, (uint64_t)cus * 32u));
       hipLaunchKernelGGL(k_tx_sam_ok, dim3(gh), dim3(256), 0, st, a);
-      GS_HIP(rocprim::exclusive_scan(tmp + t_scan, tb_hits, a.okf, a.S, 0u, (size_t)nh + 1, rocprim::plus<uint32_t>(), st));
+      GS_TRY(gs_prim_carved("gs_format_device: scan of the hits", tmp + t_scan, tb_scan, [&](void *t, size_t &b) {
+        return rocprim::exclusive_scan(t, b, a.okf, a.S, 0u, (size_t)nh + 1, rocprim::plus<uint32_t>(), st);
+      }));
       hipLaunchKernelGGL(k_tx_sam_guide, dim3((uint32_t)((n + 256) / 256)), dim3(256), 0, st, a);
-      GS_HIP(rocprim::exclusive_scan(tmp + t_scan, tb_guides, a.hex_units, a.hex_off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+      GS_TRY(gs_prim_carved("gs_format_device: scan of the guides' fields", tmp + t_scan, tb_scan, [&](void *t, size_t &b) {
+        return rocprim::exclusive_scan(t, b, a.hex_units, a.hex_off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st);
+      }));
       uint64_t units = 0;
       GS_HIP(hipMemcpyAsync(&units, a.hex_off + n, 8, hipMemcpyDeviceToHost, st));
       GS_HIP(hipStreamSynchronize(st));
       if (units) {
-        if ((rc = gs_reserve(ix->w_text_hex, 16 * units + 16)) != GS_OK) return rc;
-        a.hex = (char *)ix->w_text_hex.p;
+        GS_TRY(gs_reserve(ix->w_text.hex, 16 * units + 16));
+        a.hex = (char *)ix->w_text.hex.p;
         hipLaunchKernelGGL(k_tx_sam_hex, dim3(grid), dim3(WAVE * TX_WAVES), 0, st, a, n_tiles);
       }
     }
     hipLaunchKernelGGL(k_tx_len, dim3(grid), dim3(WAVE * TX_WAVES), 0, st, a, n_tiles);
-    GS_HIP(rocprim::exclusive_scan(tmp + t_scan, tb_tiles, a.tile_sum, a.tile_off, 0ull, (size_t)n_tiles + 1, rocprim::plus<uint64_t>(), st));
+    GS_TRY(gs_prim_carved("gs_format_device: scan of the tiles", tmp + t_scan, tb_scan, [&](void *t, size_t &b) {
+      return rocprim::exclusive_scan(t, b, a.tile_sum, a.tile_off, 0ull, (size_t)n_tiles + 1, rocprim::plus<uint64_t>(), st);
+    }));
     /* the length and the device's verdict come back together */
     uint64_t total = 0;
     uint32_t err = 0;
@@ -832,20 +838,20 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
       gs_set_error("gs_format_device: a line of 32 MB or more");
       return GS_ERR_UNSUPPORTED;
     }
-    if ((rc = gs_reserve(ix->w_text, total + 16)) != GS_OK) return rc;
-    a.text = (char *)ix->w_text.p;
-    if ((rc = gs_reserve(ix->w_text_goff, 8 * (n + 1) + 16)) != GS_OK) return rc;
+    GS_TRY(gs_reserve(ix->w_text.text, total + 16));
+    a.text = (char *)ix->w_text.text.p;
+    GS_TRY(gs_reserve(ix->w_text.goff, 8 * (n + 1) + 16));
     if (total) hipLaunchKernelGGL(k_tx_write, dim3(grid), dim3(WAVE * TX_WAVES), 0, st, a, n_tiles);
     /* where each guide's lines begin (gs_index_last_text_offsets): 8 bytes per guide, kept beside the text */
     hipLaunchKernelGGL(k_tx_guide_off, dim3((uint32_t)((n + 256) / 256)), dim3(256), 0, st, a.offsets, a.off0, a.n, (const uint32_t *)a.lens,
-                       (const uint64_t *)a.tile_off, (uint64_t *)ix->w_text_goff.p);
+                       (const uint64_t *)a.tile_off, (uint64_t *)ix->w_text.goff.p);
     GS_HIP(hipStreamSynchronize(st));
     GS_HIP(hipGetLastError());
-    *d_text = ix->w_text.p;
+    *d_text = ix->w_text.text.p;
     *text_len = total;
     ix->tx_n = n;
     /* the records as BGZF members (gs_bgzf.hip): its output is a buffer of its own */
-    if (flags & GS_TEXT_BGZF) return gs_bgzf_compress_device(ix, ix->w_text.p, total, stream, d_text, text_len);
+    if (flags & GS_TEXT_BGZF) return gs_bgzf_compress_device(ix, ix->w_text.text.p, total, stream, d_text, text_len);
     return GS_OK;
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;
@@ -892,6 +898,6 @@ extern "C" gs_status gs_index_last_text_offsets(gs_index *ix, uint64_t *out, uin
   GS_HANDLE_LOCK(ix);
   if (!ix || !out || ix->tx_n == 0 || n != ix->tx_n) return GS_ERR_ARG;
   GS_HIP(hipSetDevice(ix->device));
-  GS_HIP(hipMemcpy(out, ix->w_text_goff.p, 8 * (n + 1), hipMemcpyDeviceToHost));
+  GS_HIP(hipMemcpy(out, ix->w_text.goff.p, 8 * (n + 1), hipMemcpyDeviceToHost));
   return GS_OK;
 }

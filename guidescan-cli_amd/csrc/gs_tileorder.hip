@@ -1152,17 +1152,16 @@ gs_status gs_tileorder_plan(gs_index *ix, const gs_tileorder_in &in, hipStream_t
   *usable = false;
   gs_to_tab tab;
   if (!to_make_tab(in.L, in.P, in.m, tab)) return GS_OK;
-  gs_status rc;
   const uint32_t n_it = 2u * in.n_set;
   S = gs_tileorder_state();
   S.n_it = n_it;
-  if ((rc = gs_reserve(ix->w_t_plan, 5 * 4 * ((size_t)n_it + 1) + 64)) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_t_tab, sizeof(gs_to_tab) + 192)) != GS_OK) return rc; /* the table, flags (128 bytes), list lengths */
-  if ((rc = gs_reserve(ix->w_t_rel, 64 * ((size_t)in.n_set + 1))) != GS_OK) return rc;
-  uint32_t *tbase = (uint32_t *)ix->w_t_plan.p, *bbase = tbase + (n_it + 1), *cbase = bbase + (n_it + 1), *gbase = cbase + (n_it + 1);
+  GS_TRY(gs_reserve(ix->w_tile.plan, 5 * 4 * ((size_t)n_it + 1) + 64));
+  GS_TRY(gs_reserve(ix->w_tile.tab, sizeof(gs_to_tab) + 192)); /* the table, flags (128 bytes), list lengths */
+  GS_TRY(gs_reserve(ix->w_tile.rel, 64 * ((size_t)in.n_set + 1)));
+  uint32_t *tbase = (uint32_t *)ix->w_tile.plan.p, *bbase = tbase + (n_it + 1), *cbase = bbase + (n_it + 1), *gbase = cbase + (n_it + 1);
   uint32_t *dbase = gbase + (n_it + 1);
-  uint32_t *d_flags = (uint32_t *)((char *)ix->w_t_tab.p + sizeof(gs_to_tab));
-  GS_HIP(hipMemcpyAsync(ix->w_t_tab.p, &tab, sizeof(tab), hipMemcpyHostToDevice, st));
+  uint32_t *d_flags = (uint32_t *)((char *)ix->w_tile.tab.p + sizeof(gs_to_tab));
+  GS_HIP(hipMemcpyAsync(ix->w_tile.tab.p, &tab, sizeof(tab), hipMemcpyHostToDevice, st));
   GS_HIP(hipMemsetAsync(d_flags, 0, 192, st));
   gs_to_plan_args pa;
   pa.counts = in.counts;
@@ -1190,17 +1189,17 @@ gs_status gs_tileorder_plan(gs_index *ix, const gs_tileorder_in &in, hipStream_t
   S.n_chunks = tot[2];
   S.n_big = tot[3];
   S.n_deal = tot[4];
-  if ((rc = gs_reserve(ix->w_t_tiles, (16 + 8) * ((size_t)S.n_tiles + 1))) != GS_OK) return rc; /* descriptors, then the splitters */
+  GS_TRY(gs_reserve(ix->w_tile.tiles, (16 + 8) * ((size_t)S.n_tiles + 1))); /* descriptors, then the splitters */
   /* bucket space: the planned slots, an eighth more for the buckets that outgrow theirs (k_to_respill), the spill list
    * (an eighth of the dealt records: 20 bytes each), a word per tile and a job per moved bucket */
   S.spill_units = S.n_btiles / 8u + 2048u;
   S.spill_cap = S.n_deal * (TO_DEAL / 8u) + 65536u;
   if (gs_opt(ix, "GS_TILE_NO_SPILL")) S.spill_units = S.spill_cap = 0u; /* (tests: a bucket beyond its slot then sends the batch to the device-wide ordering) */
-  if ((rc = gs_reserve(ix->w_t_buckets, 16 * (size_t)TO_BU * ((size_t)S.n_btiles + S.spill_units) + 16)) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_t_spill, 20 * (size_t)S.spill_cap + (4 + 16) * ((size_t)S.n_tiles + 1) + 64)) != GS_OK) return rc;
-  if ((rc = gs_reserve(ix->w_t_chunkof, 4 * ((size_t)S.n_chunks + 1) + 12 * ((size_t)S.n_tiles + 1))) != GS_OK) return rc; /* the chunk index, then the three lists */
+  GS_TRY(gs_reserve(ix->w_tile.buckets, 16 * (size_t)TO_BU * ((size_t)S.n_btiles + S.spill_units) + 16));
+  GS_TRY(gs_reserve(ix->w_tile.spill, 20 * (size_t)S.spill_cap + (4 + 16) * ((size_t)S.n_tiles + 1) + 64));
+  GS_TRY(gs_reserve(ix->w_tile.chunkof, 4 * ((size_t)S.n_chunks + 1) + 12 * ((size_t)S.n_tiles + 1))); /* the chunk index, then the three lists */
   const size_t deal_at = (4 * ((size_t)S.n_big + 1) + 31) & ~(size_t)31; /* the list, then the deal map */
-  if ((rc = gs_reserve(ix->w_t_big, deal_at + 32 * ((size_t)S.n_deal + 1))) != GS_OK) return rc;
+  GS_TRY(gs_reserve(ix->w_tile.big, deal_at + 32 * ((size_t)S.n_deal + 1)));
   gs_to_fill_args fa;
   fa.counts = in.counts;
   fa.cls = in.cls;
@@ -1211,19 +1210,19 @@ gs_status gs_tileorder_plan(gs_index *ix, const gs_tileorder_in &in, hipStream_t
   fa.bbase = bbase;
   fa.gbase = gbase;
   fa.dbase = dbase;
-  fa.dealmap = (uint4 *)((char *)ix->w_t_big.p + deal_at);
-  fa.slow[0] = (uint32_t *)ix->w_t_chunkof.p + (S.n_chunks + 1);
+  fa.dealmap = (uint4 *)((char *)ix->w_tile.big.p + deal_at);
+  fa.slow[0] = (uint32_t *)ix->w_tile.chunkof.p + (S.n_chunks + 1);
   fa.slow[1] = fa.slow[0] + (S.n_tiles + 1);
   fa.slow[2] = fa.slow[1] + (S.n_tiles + 1);
   fa.slow_n = d_flags + 32;
   fa.cbase = cbase;
-  fa.tiles = (uint4 *)ix->w_t_tiles.p;
-  fa.biglist = (uint32_t *)ix->w_t_big.p;
-  fa.rel = (uint32_t *)ix->w_t_rel.p;
+  fa.tiles = (uint4 *)ix->w_tile.tiles.p;
+  fa.biglist = (uint32_t *)ix->w_tile.big.p;
+  fa.rel = (uint32_t *)ix->w_tile.rel.p;
   fa.nhits = in.nhits;
   fa.flags = d_flags;
-  if ((rc = gs_reserve(ix->w_t_excl, 4 * ((size_t)in.n_set + 1))) != GS_OK) return rc;
-  fa.excl = (uint32_t *)ix->w_t_excl.p;
+  GS_TRY(gs_reserve(ix->w_tile.excl, 4 * ((size_t)in.n_set + 1)));
+  fa.excl = (uint32_t *)ix->w_tile.excl.p;
   hipLaunchKernelGGL(k_to_fill, dim3((n_it + 255) / 256), dim3(256), 0, st, fa);
   hipLaunchKernelGGL(k_to_total, dim3(std::min<uint32_t>((n_it + 255) / 256, 512u)), dim3(256), 0, st, in.counts, in.list, n_it,
                      (unsigned long long *)(d_flags + 2));
@@ -1234,7 +1233,7 @@ gs_status gs_tileorder_plan(gs_index *ix, const gs_tileorder_in &in, hipStream_t
     ca.chunk_seq = in.chunk_seq;
     ca.redo_pos = in.redo_pos;
     ca.cbase = cbase;
-    ca.chunk_of = (uint32_t *)ix->w_t_chunkof.p;
+    ca.chunk_of = (uint32_t *)ix->w_tile.chunkof.p;
     ca.n_used = in.n_used;
     ca.cap = in.cap;
     ca.by_list = in.list ? 1u : 0u;
@@ -1247,36 +1246,36 @@ gs_status gs_tileorder_plan(gs_index *ix, const gs_tileorder_in &in, hipStream_t
 gs_status gs_tileorder_run(gs_index *ix, const gs_tileorder_in &in, gs_tileorder_state &S, hipStream_t st, uint32_t *violations) {
   *violations = 0;
   const uint32_t n_it = S.n_it;
-  uint32_t *tbase = (uint32_t *)ix->w_t_plan.p, *bbase = tbase + (n_it + 1), *cbase = bbase + (n_it + 1);
-  uint32_t *d_flags = (uint32_t *)((char *)ix->w_t_tab.p + sizeof(gs_to_tab));
+  uint32_t *tbase = (uint32_t *)ix->w_tile.plan.p, *bbase = tbase + (n_it + 1), *cbase = bbase + (n_it + 1);
+  uint32_t *d_flags = (uint32_t *)((char *)ix->w_tile.tab.p + sizeof(gs_to_tab));
   gs_to_run_args ra;
   ra.src.slots = in.slots;
   ra.src.arena = in.arena;
-  ra.src.chunk_of = (const uint32_t *)ix->w_t_chunkof.p;
+  ra.src.chunk_of = (const uint32_t *)ix->w_tile.chunkof.p;
   ra.src.cap = in.cap;
   ra.counts = in.counts;
   ra.list = in.list;
   ra.tbase = tbase;
   ra.bbase = bbase;
   ra.cbase = cbase;
-  ra.biglist = (const uint32_t *)ix->w_t_big.p;
-  ra.dealmap = (const uint4 *)((const char *)ix->w_t_big.p + ((4 * ((size_t)S.n_big + 1) + 31) & ~(size_t)31));
-  ra.spl = (unsigned long long *)((char *)ix->w_t_tiles.p + 16 * ((size_t)S.n_tiles + 1));
-  ra.slow[0] = (uint32_t *)ix->w_t_chunkof.p + (S.n_chunks + 1);
+  ra.biglist = (const uint32_t *)ix->w_tile.big.p;
+  ra.dealmap = (const uint4 *)((const char *)ix->w_tile.big.p + ((4 * ((size_t)S.n_big + 1) + 31) & ~(size_t)31));
+  ra.spl = (unsigned long long *)((char *)ix->w_tile.tiles.p + 16 * ((size_t)S.n_tiles + 1));
+  ra.slow[0] = (uint32_t *)ix->w_tile.chunkof.p + (S.n_chunks + 1);
   ra.slow[1] = ra.slow[0] + (S.n_tiles + 1);
   ra.slow[2] = ra.slow[1] + (S.n_tiles + 1);
   ra.slow_n = d_flags + 32;
-  ra.tiles = (uint4 *)ix->w_t_tiles.p;
-  ra.buckets = (uint4 *)ix->w_t_buckets.p;
-  ra.spill_rec = (uint4 *)ix->w_t_spill.p;
+  ra.tiles = (uint4 *)ix->w_tile.tiles.p;
+  ra.buckets = (uint4 *)ix->w_tile.buckets.p;
+  ra.spill_rec = (uint4 *)ix->w_tile.spill.p;
   ra.jobs = ra.spill_rec + S.spill_cap;
   ra.spill_tile = (uint32_t *)(ra.jobs + (S.n_tiles + 1));
   ra.fill2 = ra.spill_tile + S.spill_cap;
   ra.spill_cap = S.spill_cap;
   ra.spill_unit0 = S.n_btiles;
   ra.spill_units = S.spill_units;
-  ra.tab = (const gs_to_tab *)ix->w_t_tab.p;
-  ra.rel = (const uint32_t *)ix->w_t_rel.p;
+  ra.tab = (const gs_to_tab *)ix->w_tile.tab.p;
+  ra.rel = (const uint32_t *)ix->w_tile.rel.p;
   ra.offsets = in.offsets;
   ra.hits = in.hits;
   ra.sa[0] = ix->strand[0].d.sa;
@@ -1340,7 +1339,7 @@ gs_status gs_tileorder_run(gs_index *ix, const gs_tileorder_in &in, gs_tileorder
             "%u buckets moved to %u units of the %u kept for that\n", S.n_it, S.n_big, S.n_btiles, S.n_tiles, h[41], h[43], h[42], S.spill_units);
   *violations = h[0];
   S.n_records = ((uint64_t)h[3] << 32) | h[2];
-  S.n_excl = h[40]; /* guides left to the device-wide ordering (ix->w_t_excl) */
+  S.n_excl = h[40]; /* guides left to the device-wide ordering (ix->w_tile.excl) */
   GS_HIP(hipGetLastError());
   return GS_OK;
 }

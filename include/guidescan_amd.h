@@ -322,6 +322,13 @@ gs_status gs_debug_rot_index(uint32_t pidx, uint32_t k, uint32_t rs, uint32_t *o
  * [1] bytes of the two strands (Occ blocks, suffix array, tables, context and inverse arrays, rotated copies), [2] arrays and
  * [3] bytes of the PAM-pair table slots (pair, deep and spaced tables).  [1] + [3] = gs_index_device_bytes.  Tests only. */
 gs_status gs_debug_resident(gs_index *ix, uint64_t out[4]);
+/* The workspace buffers (what handles and decoders grow on demand and keep from call to call, and what gs_bgzf_inflate
+ * holds for one call) alive in the process: [0] allocations, [1] their bytes.  Tests only. */
+gs_status gs_debug_buffers_live(uint64_t out[2]);
+/* The handle's per-batch workspace, three words per group, n_groups = 6 groups in the order batch pipeline, device-wide
+ * ordering, tile ordering, score, text, BGZF: buffers held, bytes held, and the bytes of those that an out-of-memory
+ * recovery releases.  Tests only. */
+gs_status gs_debug_workspace(gs_index *ix, uint64_t *out, uint32_t n_groups);
 /* The rows under `key` (X symbols << 2 |R| | R symbols, both in consumption order) in the spaced table of a PAM-pair table
  * slot and strand, four words per row: {row in the table's row arrays, its O symbols, its row in the strand's suffix array,
  * its context word}; *n = rows under the key (out holds the first cap); info = {1 = the slot has spaced tables, pair code,

@@ -219,6 +219,7 @@ def test_options_are_validated_without_a_device():
     assert L.gs_index_last_sharing(None, out) == 1
     assert L.gs_debug_general_last(None, out) == 1
     assert L.gs_debug_resident(None, out) == 1
+    assert L.gs_debug_workspace(None, out, 6) == 1
     assert L.gs_index_prepare(None, 10, 20, b"NGG", 3, None, 0, 3, 0) == 1      # no handle: GS_ERR_ARG, nothing touched
 
 
