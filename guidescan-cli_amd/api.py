@@ -85,6 +85,12 @@ class GsKmersReport(C.Structure):
                 ("bad_off", C.c_uint64), ("bad_len", C.c_uint64), ("bad_text", C.c_void_p), ("ms", C.c_double * 8)]
 
 
+class GsRegionsReport(C.Structure):
+    _fields_ = [("n_lines", C.c_uint64), ("n_intervals", C.c_uint64), ("n_groups", C.c_uint64),
+                ("bad_kind", C.c_uint32), ("pad", C.c_uint32), ("bad_line", C.c_uint64), ("bad_len", C.c_uint64),
+                ("bad_text", C.c_void_p)]
+
+
 def build_library():
     subprocess.run(["make", "-s", "-C", str(PKG / "csrc")], check=True, timeout=3600)
 
@@ -312,6 +318,36 @@ def lib():
     L.gs_debug_kmers_chunk_bytes.argtypes = [u64]
     L.gs_debug_kmers_host.restype = i32
     L.gs_debug_kmers_host.argtypes = [vp, u64, u64, C.POINTER(vp), C.POINTER(GsKmersReport)]
+    pgs, f32 = C.POINTER(GsGenomeStructure), C.c_float
+    L.gs_regions_parse.restype = i32
+    L.gs_regions_parse.argtypes = [vp, u64, pgs, C.c_char_p, C.POINTER(vp), C.POINTER(GsRegionsReport)]
+    L.gs_regions_parse_file.restype = i32
+    L.gs_regions_parse_file.argtypes = [C.c_char_p, pgs, C.c_char_p, C.POINTER(vp), C.POINTER(GsRegionsReport)]
+    L.gs_regions_info.restype = i32
+    L.gs_regions_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.gs_regions_free.restype = None
+    L.gs_regions_free.argtypes = [vp]
+    L.gs_design_restrict.restype = i32
+    L.gs_design_restrict.argtypes = [vp, u32, vp, vp, C.POINTER(vp)]
+    L.gs_design_concat.restype = i32
+    L.gs_design_concat.argtypes = [vp, u32, C.POINTER(vp)]
+    L.gs_design_score.restype = i32
+    L.gs_design_score.argtypes = [vp, vp, C.c_char_p, u32, u32, u32, C.c_int64, u64, vp]
+    L.gs_design_select.restype = i32
+    L.gs_design_select.argtypes = [vp, C.c_char_p, u32, f32, vp, C.POINTER(vp)]
+    L.gs_design_rows.restype = i32
+    L.gs_design_rows.argtypes = [vp, C.c_char_p, u32, f32, vp, C.POINTER(vp), C.POINTER(u64)]
+    L.gs_design_get.restype = i32
+    L.gs_design_get.argtypes = [vp, C.POINTER(u64)] + [C.POINTER(vp)] * 6
+    L.gs_design_info.restype = i32
+    L.gs_design_info.argtypes = [vp, C.POINTER(u64), C.POINTER(C.c_int)]
+    L.gs_design_last_select.restype = i32
+    L.gs_design_last_select.argtypes = [vp, vp]
+    L.gs_design_free.restype = None
+    L.gs_design_free.argtypes = [vp]
+    L.gs_debug_design_host.restype = i32
+    L.gs_debug_design_host.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, C.c_char_p, u32, C.c_char_p, u32, f32,
+                                       C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.gs_status_string.restype = C.c_char_p
     L.gs_status_string.argtypes = [i32]
     L.gs_version.restype = C.c_char_p
@@ -346,7 +382,10 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_fasta_free", "gs_decoder_open_fasta", "gs_debug_fasta_tile_bytes", "gs_debug_fasta_host",
            "gs_debug_fasta_chunk_bytes", "gs_debug_fasta_ms",
            "gs_kmers_parse", "gs_kmers_parse_file", "gs_kmers_parse_device", "gs_debug_kmers_tile_bytes",
-           "gs_debug_kmers_chunk_bytes", "gs_debug_kmers_host"]
+           "gs_debug_kmers_chunk_bytes", "gs_debug_kmers_host",
+           "gs_regions_parse", "gs_regions_parse_file", "gs_regions_info", "gs_regions_free", "gs_design_restrict",
+           "gs_design_concat", "gs_design_score", "gs_design_select", "gs_design_rows", "gs_design_get", "gs_design_info",
+           "gs_design_last_select", "gs_design_free", "gs_debug_design_host"]
 
 
 def _check(rc):
@@ -710,6 +749,13 @@ class DeviceKmers:
         lib().gs_free(out)
         return s
 
+    def restrict(self, regions, chr_index):
+        """the records of this scan - of chromosome chr_index of the regions' structure - that lie in a group of
+        `regions` (gs_design_restrict) -> Design"""
+        h = C.c_void_p()
+        _check(lib().gs_design_restrict(regions._h, chr_index, self._h, None, C.byref(h)))
+        return Design(h, regions, self.k, self.P)
+
     def close(self):
         if self._h:
             lib().gs_kmers_free(self._h)
@@ -720,6 +766,224 @@ class DeviceKmers:
             self.close()
         except Exception:
             pass
+
+
+def _selected_kmers(h, k, P):
+    """a DeviceKmers over the object gs_design_select / gs_debug_design_host made: ids from the start"""
+    km = DeviceKmers.__new__(DeviceKmers)
+    km._h, km.k, km.P = h, k, P
+    n = C.c_uint64()
+    _check(lib().gs_kmers_get(h, 0, C.byref(n), None, None, None, None))
+    km.n = int(n.value)
+    return km
+
+
+class RegionsFileError(GsError):
+    """a regions file that the parser refuses: .message is "regions line N: REASON"; kind and line as in
+    gs_regions_report"""
+
+    def __init__(self, status, msg, kind, line):
+        super().__init__(status, msg)
+        self.message, self.kind, self.line = msg, kind, line
+
+
+class Regions:
+    """The intervals of a BED file, grouped and merged against a genome structure (gs_regions_parse; host side)."""
+
+    def __init__(self, handle, structure, report):
+        self._h, self.structure, self.report = handle, structure, report
+        self.n_groups, self.n_intervals = report["n_groups"], report["n_intervals"]
+
+    @classmethod
+    def parse(cls, src, structure, prefix=""):
+        """src: a path, or the file's bytes.  structure: a GsGenomeStructure (make_genome_structure), or (names,
+        lengths).  prefix: the id prefix the cap on group names is checked with.  Raises RegionsFileError (status 6)
+        with the 1-based line and the reason."""
+        gs = structure if isinstance(structure, GsGenomeStructure) else make_genome_structure(*structure)
+        h, rep = C.c_void_p(), GsRegionsReport()
+        if isinstance(src, (str, os.PathLike)):
+            rc = lib().gs_regions_parse_file(os.fsencode(src), C.byref(gs), prefix.encode(), C.byref(h), C.byref(rep))
+        else:
+            raw = bytes(src)
+            rc = lib().gs_regions_parse(raw if raw else None, len(raw), C.byref(gs), prefix.encode(), C.byref(h), C.byref(rep))
+        text = C.string_at(rep.bad_text, rep.bad_len).decode("latin-1") if rep.bad_text else ""
+        if rep.bad_text:
+            lib().gs_free(rep.bad_text)
+        if rc != 0 and rep.bad_kind:
+            raise RegionsFileError(rc, text, int(rep.bad_kind), int(rep.bad_line))
+        _check(rc)
+        return cls(h, gs, {k: int(getattr(rep, k)) for k in ("n_lines", "n_intervals", "n_groups")})
+
+    def close(self):
+        if self._h:
+            lib().gs_regions_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _select_args(per_region, min_specificity):
+    n = 0 if per_region is None else int(per_region)
+    if per_region is not None and n < 1:
+        raise ValueError("per_region >= 1")
+    s = -1.0 if min_specificity is None else float(min_specificity)
+    if min_specificity is not None and not 0.0 <= s <= 1.0:
+        raise ValueError("0 <= min_specificity <= 1")
+    return n, s
+
+
+class Design:
+    """The (candidate, group) records of a set of regions in HBM (gs_design_restrict / gs_design_concat); keeps its
+    Regions alive."""
+
+    def __init__(self, handle, regions, k, P):
+        self._h, self.regions, self.k, self.P = handle, regions, k, P
+
+    @classmethod
+    def concat(cls, parts):
+        arr = (C.c_void_p * len(parts))(*[p._h for p in parts])
+        h = C.c_void_p()
+        _check(lib().gs_design_concat(arr, len(parts), C.byref(h)))
+        return cls(h, parts[0].regions, parts[0].k, parts[0].P)
+
+    def score(self, index, mismatches=3, alt_pams=(), start=False, threshold=-1, batch=0, no_new_tables=False):
+        """the specificity of every record through the index's search and scoring (gs_design_score); threshold >= 0
+        also runs the counting pass of --threshold and marks what it would drop as not eligible"""
+        alt = b"".join(p.encode() for p in alt_pams)
+        flags = (GS_FLAG_PAM_AT_START if start else 0) | (GS_FLAG_NO_NEW_TABLES if no_new_tables else 0)
+        _check(lib().gs_design_score(index._h, self._h, alt if alt_pams else None, len(alt_pams), mismatches, flags,
+                                     threshold, batch, None))
+        return self
+
+    def select(self, prefix="", per_region=None, min_specificity=None):
+        """the records in order, cut to the first per_region eligible ones of each group with specificity >=
+        min_specificity (gs_design_select) -> DeviceKmers with ids"""
+        n, s = _select_args(per_region, min_specificity)
+        h = C.c_void_p()
+        _check(lib().gs_design_select(self._h, prefix.encode(), n, s, None, C.byref(h)))
+        km = _selected_kmers(h, self.k, self.P)
+        a, b, c, d = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().gs_kmers_get(h, 1, None, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        km.seqs_ptr, km.pams_ptr, km.pos_ptr, km.sense_ptr = a.value, b.value, c.value, d.value
+        _check(lib().gs_kmers_get_ids(h, 1, C.byref(a), C.byref(b), C.byref(c)))
+        km.ids_ptr, km.id_offsets_ptr, km.sense_positive_ptr = a.value, b.value, c.value
+        return km
+
+    def rows(self, prefix="", per_region=None, min_specificity=None) -> bytes:
+        """the same selection as rows of the kmers file, no header (gs_design_rows)"""
+        n, s = _select_args(per_region, min_specificity)
+        out, ln = C.c_void_p(), C.c_uint64()
+        _check(lib().gs_design_rows(self._h, prefix.encode(), n, s, None, C.byref(out), C.byref(ln)))
+        t = C.string_at(out, ln.value)
+        lib().gs_free(out)
+        return t
+
+    def to_host(self):
+        """-> dict(n, group uint32[n], chr uint32[n], pos uint32[n], sense uint8[n], spec float32[n], eligible uint8[n])"""
+        n = C.c_uint64()
+        p = [C.c_void_p() for _ in range(6)]
+        _check(lib().gs_design_get(self._h, C.byref(n), *[C.byref(x) for x in p]))
+        m = int(n.value)
+        out = {"n": m}
+        for name, x, dt in zip(("group", "chr", "pos", "sense", "spec", "eligible"), p,
+                               (np.uint32, np.uint32, np.uint32, np.uint8, np.float32, np.uint8)):
+            out[name] = np.frombuffer(C.string_at(x, m * np.dtype(dt).itemsize), dtype=dt).copy() if m else np.empty(0, dt)
+        return out
+
+    def info(self):
+        """-> (records, scored) without copying anything (gs_design_info)"""
+        n, sc = C.c_uint64(), C.c_int()
+        _check(lib().gs_design_info(self._h, C.byref(n), C.byref(sc)))
+        return int(n.value), bool(sc.value)
+
+    def last_select(self):
+        out = (C.c_uint64 * 4)()
+        _check(lib().gs_design_last_select(self._h, out))
+        return dict(zip(("records", "kept", "groups_empty", "groups_short"), (int(x) for x in out)))
+
+    def close(self):
+        if self._h:
+            lib().gs_design_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def design(index, regions, pam, k, per_region=None, min_specificity=None, *, chromosomes, mismatches=3, alt_pams=(),
+           start=False, threshold=-1, prefix="", device=0):
+    """Guides for regions in one call: scan, restrict, (score,) select -> DeviceKmers with ids.  chromosomes: iterable of
+    (index in the regions' structure, the chromosome's bytes).  `index` (a GenomeIndex) may be None when neither
+    per_region, min_specificity nor threshold asks for scores."""
+    parts = []
+    try:
+        for ci, chrm in chromosomes:
+            km = generate_kmers(chrm, pam, k, start, device)
+            try:
+                parts.append(km.restrict(regions, ci))
+            finally:
+                km.close()
+        whole = Design.concat(parts)
+    finally:
+        for p in parts:
+            p.close()
+    try:
+        if per_region is not None or min_specificity is not None or threshold >= 0:
+            whole.score(index, mismatches, alt_pams, start, threshold)
+        return whole.select(prefix, per_region, min_specificity)
+    finally:
+        whole.close()
+
+
+def design_host_model(regions, parts, pam, k, prefix="", per_region=None, min_specificity=None, rows=False):
+    """the stages of Design on the host through the kernels' shared header, no GPU (gs_debug_design_host).  parts: list of
+    (chr_index, seqs uint8[n,k], positions uint32[n], senses uint8[n], specificity float32[n] or None, eligible
+    uint8[n] or None) -> dict as kmers_arrays plus pos, and rows bytes when asked for"""
+    npart = len(parts)
+    keep = []
+
+    def col(i, dt):
+        ptrs = (C.c_void_p * max(1, npart))()
+        given = False
+        for j, p in enumerate(parts):
+            if p[i] is not None:
+                a = np.ascontiguousarray(p[i], dtype=dt)
+                keep.append(a)
+                ptrs[j] = a.ctypes.data if a.size else None
+                given = True
+        return ptrs, given
+
+    chr_index = np.array([p[0] for p in parts], dtype=np.uint32)
+    counts = np.array([len(p[2]) for p in parts], dtype=np.uint64)
+    seqs, _ = col(1, np.uint8)
+    pos, _ = col(2, np.uint32)
+    sense, _ = col(3, np.uint8)
+    spec, have_spec = col(4, np.float32)
+    elig, have_elig = col(5, np.uint8)
+    n, s = _select_args(per_region, min_specificity)
+    h, text, ln = C.c_void_p(), C.c_void_p(), C.c_uint64()
+    _check(lib().gs_debug_design_host(regions._h, npart, chr_index.ctypes.data, counts.ctypes.data, seqs, pos, sense,
+                                      spec if have_spec else None, elig if have_elig else None, pam.encode(), k,
+                                      prefix.encode(), n, s, C.byref(h), C.byref(text) if rows else None, C.byref(ln)))
+    km = _selected_kmers(h, k, len(pam))
+    try:
+        sq, pm, ps, sn = km.to_host()
+        ids, off, sp = km.ids_to_host()
+        out = {"n": km.n, "seqs": sq.tobytes(), "pams": pm.tobytes(), "pos": ps, "sense_chars": sn, "ids": ids,
+               "id_off": off, "sense": sp}
+        if rows:
+            out["rows"] = C.string_at(text, ln.value)
+            lib().gs_free(text)
+        return out
+    finally:
+        km.close()
 
 
 class KmersFileError(GsError):

@@ -462,6 +462,10 @@ extern "C" gs_status gs_kmers_encode_ids(gs_kmers *km, const char *prefix, const
     gs_set_error("gs_kmers_encode_ids on the rows of a kmers file: the ids are the file's");
     return GS_ERR_ARG;
   }
+  if (km->ids_fixed) {
+    gs_set_error("gs_kmers_encode_ids on the records of gs_design_select: their ids name group and chromosome");
+    return GS_ERR_ARG;
+  }
   uint64_t bytes = 0;
   try {
     return km_encode(km, prefix, chr_name, false, (hipStream_t)stream, nullptr, nullptr, &bytes);
@@ -552,6 +556,7 @@ extern "C" gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, g
   for (uint32_t i = 0; i < n_parts; i++) {
     km->n += parts[i]->n;
     km->id_bytes += parts[i]->id_bytes;
+    km->ids_fixed = km->ids_fixed || parts[i]->ids_fixed;
   }
   const uint32_t k = km->k, P = km->P;
   GS_HIP(hipSetDevice(km->device));

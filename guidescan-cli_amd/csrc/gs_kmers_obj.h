@@ -12,6 +12,9 @@ struct gs_kmers {
   /* parsed from a kmers file: no positions, the ids are the file's (have_ids from the start), and gs_kmers_encode_ids /
    * gs_kmers_csv are GS_ERR_ARG */
   bool parsed = false;
+  /* selected for regions (gs_design.hip): positions as a scan's, but the ids name each record's group and chromosome
+   * (have_ids from the start) and gs_kmers_encode_ids is GS_ERR_ARG */
+  bool ids_fixed = false;
   uint64_t n = 0;
   uint32_t k = 0, P = 0;
   void *d_seqs = nullptr, *d_pams = nullptr, *d_pos = nullptr, *d_sense = nullptr;

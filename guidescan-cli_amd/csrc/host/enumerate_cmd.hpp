@@ -59,6 +59,12 @@ struct options {
   bool all_candidates = false, verbose = false;
   std::string kmers; /* --kmers host|gpu: who reads the kmers file; empty: not given (host) */
   cli::candidate_opts co; /* co.start is --start, with or without --all-candidates */
+  /* --regions BED [--per-region N] [--min-specificity S] (with --all-candidates): the candidates inside the file's
+   * intervals, one record per group of intervals, the best N of each group (gs_design_*) */
+  std::string regions;
+  long long per_region = 0; /* 0: not given */
+  float min_spec = -1.0f;   /* < 0: not given */
+  bool selects() const { return per_region > 0 || min_spec >= 0.0f; }
 };
 
 /* the command line into `o`, validated.  0: go on; otherwise the exit status */
@@ -100,6 +106,24 @@ inline int parse_options(int argc, char **argv, int (*usage)(), options &o) {
     else if (a == "--bgzf") o.bgzf = need("--bgzf");
     else if (a == "--kmers") o.kmers = need("--kmers");
     else if (a == "--verbose") o.verbose = true;
+    else if (a == "--regions") o.regions = need("--regions");
+    else if (a == "--per-region") {
+      const char *v = need("--per-region");
+      char *end = nullptr;
+      o.per_region = strtoll(v, &end, 10);
+      if (end == v || *end || o.per_region < 1) {
+        std::cerr << "error: --per-region " << v << ": a number of guides per group, at least 1\n";
+        return 2;
+      }
+    } else if (a == "--min-specificity") {
+      const char *v = need("--min-specificity");
+      char *end = nullptr;
+      o.min_spec = strtof(v, &end);
+      if (end == v || *end || !(o.min_spec >= 0.0f && o.min_spec <= 1.0f)) {
+        std::cerr << "error: --min-specificity " << v << ": a specificity, 0 to 1\n";
+        return 2;
+      }
+    }
     else if (!a.empty() && a[0] != '-' && o.prefix.empty()) o.prefix = a;
     else return usage();
   }
@@ -117,6 +141,14 @@ inline int parse_options(int argc, char **argv, int (*usage)(), options &o) {
   if (o.all_candidates && o.co.k < 1) return usage();
   if (!o.all_candidates && candidate_opts_given) {
     std::cerr << "error: --pam, --kmer-length, --min-chr-length, --prefix and --chromosomes describe the scan of --all-candidates; with -f the kmers file says what the guides are\n";
+    return usage();
+  }
+  if (!o.regions.empty() && !o.all_candidates) {
+    std::cerr << "error: --regions restricts the scan of --all-candidates; with -f the kmers file says what the guides are\n";
+    return usage();
+  }
+  if (o.selects() && o.regions.empty()) {
+    std::cerr << "error: --per-region and --min-specificity select within the groups of --regions\n";
     return usage();
   }
   if ((o.format != "csv" && o.format != "sam" && o.format != "bam") || (o.mode != "succinct" && o.mode != "complete")) return usage();
@@ -207,8 +239,14 @@ struct candidate_set {
   std::mutex mtx;
   bool on_host = false;
   std::string host_error;
+  /* --regions: the file's tables and, while a selection waits for the index, the records of (candidate, group) */
+  gs_regions *regions = nullptr;
+  gs_design *design = nullptr;
+  uint64_t n_scanned = 0;
   ~candidate_set() {
     if (all) gs_kmers_free(all);
+    if (design) gs_design_free(design);
+    if (regions) gs_regions_free(regions);
   }
 };
 
@@ -702,6 +740,75 @@ inline bool read_guides_device(const options &o, enumerate_job &job, candidate_s
   return true;
 }
 
+/* --regions: the BED file against PREFIX.gs; the parser's message with its line number */
+inline bool read_regions(const std::string &path, const genome_structure &gs, const std::string &prefix, candidate_set &cand) {
+  std::vector<const char *> names;
+  for (auto &n : gs.names) names.push_back(n.c_str());
+  const gs_genome_structure cgs{names.data(), gs.lengths.data(), (uint32_t)names.size()};
+  gs_regions_report rep;
+  const gs_status rc = gs_regions_parse_file(path.c_str(), &cgs, prefix.c_str(), &cand.regions, &rep);
+  if (rc == GS_OK) return true;
+  if (rc == GS_ERR_FORMAT && rep.bad_text)
+    std::cerr << "error: " << rep.bad_text << " (" << path << ")\n";
+  else if (rc == GS_ERR_IO)
+    std::cerr << "error: cannot read the regions file " << path << "\n";
+  else
+    std::cerr << "error: regions file " << path << ": " << gs_status_string(rc) << "\n";
+  gs_free(rep.bad_text);
+  return false;
+}
+
+/* --regions: the records scored on the first device where an option asks for it (ix; the search options are the
+ * command's own -m, -a, --start, and -t marks what the counting pass would drop as not eligible), ordered, cut to the
+ * best of each group, and handed to the candidate set as the guides of the command */
+inline bool select_design(const options &o, enumerate_job &job, candidate_set &cand, gs_index *ix) {
+  const auto ts = std::chrono::steady_clock::now();
+  gs_status rc = GS_OK;
+  if (ix) {
+    std::string alts;
+    for (auto &a : o.alt_pams) {
+      if (a.size() != cand.P) {
+        std::cerr << "error: --regions with --per-region or --min-specificity scores on the fast path: alt PAM " << a
+                  << " is not of the PAM's length\n";
+        return false;
+      }
+      alts += a;
+    }
+    if (o.rna > 0 || o.dna > 0 || o.mismatches > 7 || o.threshold > 7) {
+      std::cerr << "error: --regions with --per-region or --min-specificity scores on the fast path: no bulges, at most 7 mismatches\n";
+      return false;
+    }
+    uint64_t n_rec = 0, glen = 0;
+    gs_design_info(cand.design, &n_rec, nullptr);
+    for (uint64_t l : job.gs.lengths) glen += l;
+    const uint32_t flags = (o.co.start ? GS_FLAG_PAM_AT_START : 0u) | ((double)n_rec < 6e-4 * (double)glen ? GS_FLAG_NO_NEW_TABLES : 0u);
+    rc = gs_design_score(ix, cand.design, alts.data(), (uint32_t)o.alt_pams.size(), (uint32_t)o.mismatches, flags,
+                         o.threshold > 0 ? o.threshold : -1, o.batch_size, nullptr);
+    if (rc == GS_ERR_UNSUPPORTED) {
+      std::cerr << "error: --regions with --per-region or --min-specificity scores on the fast path, which does not take this job: "
+                << gs_status_string(rc) << "\n";
+      return false;
+    }
+  }
+  if (rc == GS_OK) rc = gs_design_select(cand.design, o.co.prefix.c_str(), (uint32_t)o.per_region, o.min_spec, nullptr, &cand.all);
+  uint64_t last[4] = {0, 0, 0, 0};
+  if (rc == GS_OK) gs_design_last_select(cand.design, last);
+  if (rc == GS_OK) rc = view_kmers(cand.all, 1, &cand.n, cand.d);
+  if (rc != GS_OK) {
+    std::cerr << "error: selection for --regions: " << gs_status_string(rc) << "\n";
+    return false;
+  }
+  gs_design_free(cand.design);
+  cand.design = nullptr;
+  job.cand = &cand;
+  job.cand_device = (o.encoder == "gpu" || o.bgzf == "gpu") && o.gpus == 1 && cand.L <= 31 && 2 * cand.L + 3 * cand.P <= 59;
+  std::cout << "Selected " << cand.n << " guide(s) of " << last[0] << " record(s) in "
+            << std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count() << " s\n";
+  if (o.verbose)
+    std::cout << "Regions: " << last[2] << " group(s) left without a guide, " << last[3] << " group(s) short of --per-region\n";
+  return true;
+}
+
 /* --all-candidates: scan first, search afterwards - the table rule of derive_job needs the true candidate count.  Every
  * selected chromosome is scanned and its ids are encoded on the first device; one concatenation makes the stream the
  * batches are cut from */
@@ -716,15 +823,51 @@ inline bool scan_candidates(const options &o, const std::string &text, enumerate
     return false;
   }
   std::vector<gs_kmers *> parts;
+  std::vector<gs_design *> dparts;
   gs_status rc = GS_OK;
+  if (!o.regions.empty() && !read_regions(o.regions, job.gs, co.prefix, cand)) return false;
   for (size_t c : sel) {
     gs_kmers *km = nullptr;
     rc = gs_kmers_generate(o.device, (const uint8_t *)text.data() + begin[c], job.gs.lengths[c], 0, co.pam.c_str(), (uint32_t)co.k,
                            co.start ? GS_FLAG_PAM_AT_START : 0u, nullptr, &km);
     if (rc != GS_OK) break;
+    if (cand.regions) { /* the chromosome's candidates inside the intervals; the scan itself is dropped */
+      gs_design *dp = nullptr;
+      uint64_t n = 0;
+      gs_kmers_get(km, 1, &n, nullptr, nullptr, nullptr, nullptr);
+      cand.n_scanned += n;
+      rc = gs_design_restrict(cand.regions, (uint32_t)c, km, nullptr, &dp);
+      gs_kmers_free(km);
+      if (rc != GS_OK) break;
+      dparts.push_back(dp);
+      continue;
+    }
     parts.push_back(km);
     rc = gs_kmers_encode_ids(km, co.prefix.c_str(), job.gs.names[c].c_str(), nullptr);
     if (rc != GS_OK) break;
+  }
+  if (cand.regions) {
+    if (rc == GS_OK && dparts.empty()) {
+      std::cerr << "error: --regions: no chromosome selected\n";
+      rc = GS_ERR_ARG;
+    } else if (rc == GS_OK) {
+      rc = gs_design_concat(dparts.data(), (uint32_t)dparts.size(), &cand.design);
+    }
+    for (gs_design *dp : dparts) gs_design_free(dp);
+    if (rc != GS_OK) {
+      std::cerr << "error: candidate scan for --regions (--pam " << co.pam << ", --kmer-length " << co.k << "): " << gs_status_string(rc) << "\n";
+      return false;
+    }
+    cand.n_chr = sel.size();
+    cand.L = (uint32_t)co.k;
+    cand.P = (uint32_t)co.pam.size();
+    uint64_t n_rec = 0;
+    gs_design_info(cand.design, &n_rec, nullptr);
+    std::cout << "Scanned " << cand.n_scanned << " candidate(s) of " << sel.size() << " chromosome(s), " << n_rec
+              << " record(s) inside the regions, in " << std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count() << " s\n";
+    /* a selection by specificity waits for the index (select_design); otherwise the records are ordered now, and -t is the
+     * pipeline's own threshold pass over them, on whatever route a batch takes */
+    return o.selects() ? true : select_design(o, job, cand, nullptr);
   }
   if (rc == GS_OK && parts.empty()) { /* no chromosome selected: an empty set with ids */
     gs_kmers *km = nullptr;
@@ -922,10 +1065,11 @@ inline int run(int argc, char **argv, int (*usage)()) {
   candidate_set cand;
   if (!(o.all_candidates ? scan_candidates(o, text, job, cand) : o.kmers == "gpu" ? read_guides_device(o, job, cand) : read_guides(o, job)))
     return 1;
-  const size_t n_guides = job.cand ? (size_t)cand.n : job.kmers.size();
   cli::index_set idx((size_t)o.gpus);
   if (!build_indexes(o, text, from_sdsl, idx)) return 1;
   text = std::string();
+  if (cand.design && !select_design(o, job, cand, idx.ix[0])) return 1; /* the score phase: on the first device */
+  const size_t n_guides = job.cand ? (size_t)cand.n : job.kmers.size();
   derive_job(o, n_guides, job);
   output_file out;
   if (!out.open(o.output)) return 1;

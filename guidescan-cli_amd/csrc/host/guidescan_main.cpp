@@ -23,6 +23,11 @@
  *       the kmers file of every candidate guide of the indexed genome, byte for byte what the reference's
  *       scripts/generate_kmers.py prints for the FASTA: PREFIX.gs cuts PREFIX.dna into chromosomes, each is scanned
  *       and its rows are encoded on the device (gs_kmers_generate, gs_kmers_csv).  --chromosomes: these only.
+ *       --regions BED: only the candidates whose protospacer and PAM lie inside an interval of the file (columns:
+ *       chromosome, start, end, 0-based half-open, and optionally the name of the line's group), one row per group a
+ *       candidate lies in, the id "{prefix}{group}:{chr}:{position}:{sense}", ordered by group (first appearance in the
+ *       file), chromosome, position, sense (gs_design_restrict, gs_design_rows).  --per-region and --min-specificity
+ *       are refused here: this command has no index to search.
  *   guidescan enumerate PREFIX (-f KMERS.csv | --all-candidates) -o OUT [-m 3] [-a PAM ...] [--format csv|sam|bam]
  *       [--mode succinct|complete] [--max-off-targets N] [--start] [--device D] [--gpus N] [--batch-size B]
  *       --all-candidates [--pam ...] [--kmer-length ...] [--min-chr-length ...] [--prefix ...] [--chromosomes ...]:
@@ -30,6 +35,13 @@
  *       `enumerate -f` writes for that kmers file.  With --encoder gpu on one device the candidates, their ids and
  *       senses stay in HBM from the scan to the text (gs_enumerate_text_device); any other batch is copied to the
  *       host and takes the route of a kmers file's batch.
+ *       --all-candidates --regions BED [--per-region N] [--min-specificity S]: the guides are the candidates inside the
+ *       file's intervals, as `kmers --regions` writes them.  --per-region N keeps the N most specific guides of each
+ *       group, --min-specificity S those of specificity >= S; the specificity is the CSV column's with no cap on the
+ *       off-targets, from a search with the command's own -m, -a and --start, and with -t a guide the threshold would
+ *       drop is not eligible.  That score phase runs on the first device only, on the fast path (2L + 3P <= 59, alt
+ *       PAMs of the PAM's length, no bulges).  A group left without a guide writes nothing; --verbose counts them.
+ *       With -t and neither selection option there is no score phase: the pipeline's own threshold pass drops the guides.
  *       -f KMERS.csv --kmers gpu: the kmers file is parsed on the first device (gs_kmers_parse_file, the rules of
  *       cli::read_kmers) and the command goes on as --all-candidates does from its scan: sequences, PAMs, ids and
  *       senses stay in HBM where the batch allows it.  Same output, messages and exit status as --kmers host (the
@@ -138,7 +150,9 @@ int usage() {
                "                 --fasta gpu: GENOME.fa is parsed on the device; the files are those of --fasta host.  GENOME.fa\n"
                "                 must then be a regular file (no pipe).\n"
                "       guidescan kmers PREFIX -o KMERS [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S]\n"
-               "                 [--start] [--chromosomes a,b,...] [--device D]\n"
+               "                 [--start] [--chromosomes a,b,...] [--device D] [--regions BED]\n"
+               "                 --regions BED: only candidates inside the file's intervals (chromosome, start, end, [group]),\n"
+               "                 one row per group, ids {prefix}{group}:{chr}:{position}:{sense}, ordered by group\n"
                "       guidescan enumerate PREFIX (-f KMERS | --all-candidates) -o OUT [-m N] [-a PAM]... [--format csv|sam|bam]\n"
                "                 [--mode succinct|complete] [--max-off-targets N] [--start]\n"
                "                 [--rna-bulges N] [--dna-bulges N] [--bulge-form walk|seeded] [-t THRESHOLD] [-n FORMAT_THREADS]\n"
@@ -146,7 +160,10 @@ int usage() {
                "                 [--kmers host|gpu] [--verbose]\n"
                "                 --kmers gpu (with -f): the kmers file is parsed on the first device; same output and messages\n"
                "                 with --all-candidates: [--pam NGG] [--kmer-length 20] [--min-chr-length 0] [--prefix S]\n"
-               "                 [--chromosomes a,b,...]\n"
+               "                 [--chromosomes a,b,...] [--regions BED [--per-region N] [--min-specificity S]]\n"
+               "                 --regions: the guides are the candidates inside the BED file's intervals, one per group of\n"
+               "                 intervals they lie in; --per-region N: the N most specific of each group; --min-specificity S:\n"
+               "                 those of specificity >= S.  That score phase uses the first device only.\n"
                "       guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--verbose]\n"
                "                 [--bgzf host|gpu] [--fasta host|gpu] DATABASE GENOME.fa\n"
                "                 --bgzf gpu (a BAM database only): the file is inflated and split into records on the device.\n"
@@ -255,7 +272,7 @@ int do_index(int argc, char **argv) {
 }
 
 int do_kmers(int argc, char **argv) {
-  std::string prefix, output;
+  std::string prefix, output, regions;
   candidate_opts co;
   int device = 0;
   for (int i = 0; i < argc; i++) {
@@ -265,6 +282,12 @@ int do_kmers(int argc, char **argv) {
       if (bad) return 2;
     } else if ((a == "-o" || a == "--output") && i + 1 < argc)
       output = argv[++i];
+    else if (a == "--regions" && i + 1 < argc)
+      regions = argv[++i];
+    else if (a == "--per-region" || a == "--min-specificity") {
+      std::cerr << "error: " << a << " ranks guides by specificity, which takes the index: use guidescan enumerate --all-candidates --regions\n";
+      return 2;
+    }
     else if (a == "--start")
       co.start = true;
     else if (a == "--device" && i + 1 < argc)
@@ -303,6 +326,13 @@ int do_kmers(int argc, char **argv) {
   uint64_t total = 0;
   double s_scan = 0, s_rows = 0, s_write = 0;
   gs_status rc = GS_OK;
+  enumerate_cmd::candidate_set rset; /* --regions: owns the file's tables */
+  std::vector<gs_design *> dparts;
+  if (!regions.empty() && !enumerate_cmd::read_regions(regions, gs, co.prefix, rset)) {
+    fclose(out);
+    unlink(tmp.c_str());
+    return 1;
+  }
   for (size_t c : sel) {
     auto t1 = std::chrono::steady_clock::now();
     gs_kmers *km = nullptr;
@@ -311,6 +341,14 @@ int do_kmers(int argc, char **argv) {
     if (rc != GS_OK) break;
     auto t2 = std::chrono::steady_clock::now();
     s_scan += std::chrono::duration<double>(t2 - t1).count();
+    if (rset.regions) { /* the rows come once every chromosome is restricted: they are ordered by group */
+      gs_design *dp = nullptr;
+      rc = gs_design_restrict(rset.regions, (uint32_t)c, km, nullptr, &dp);
+      gs_kmers_free(km);
+      if (rc != GS_OK) break;
+      dparts.push_back(dp);
+      continue;
+    }
     uint64_t n = 0, len = 0;
     char *rows = nullptr;
     gs_kmers_get(km, 1, &n, nullptr, nullptr, nullptr, nullptr);
@@ -324,6 +362,28 @@ int do_kmers(int argc, char **argv) {
     s_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - t3).count();
     total += n;
   }
+  if (rset.regions && rc == GS_OK) {
+    auto t2 = std::chrono::steady_clock::now();
+    uint64_t len = 0, last[4] = {0, 0, 0, 0};
+    char *rows = nullptr;
+    if (dparts.empty()) {
+      std::cerr << "error: --regions: no chromosome selected\n";
+      rc = GS_ERR_ARG;
+    } else {
+      rc = gs_design_concat(dparts.data(), (uint32_t)dparts.size(), &rset.design);
+    }
+    if (rc == GS_OK) rc = gs_design_rows(rset.design, co.prefix.c_str(), 0, -1.0f, nullptr, &rows, &len);
+    if (rc == GS_OK) {
+      gs_design_last_select(rset.design, last);
+      total = last[1];
+      auto t3 = std::chrono::steady_clock::now();
+      s_rows += std::chrono::duration<double>(t3 - t2).count();
+      ok = ok && fwrite(rows, 1, len, out) == len;
+      gs_free(rows);
+      s_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - t3).count();
+    }
+  }
+  for (gs_design *dp : dparts) gs_design_free(dp);
   ok = (fclose(out) == 0) && ok;
   if (rc != GS_OK || !ok) {
     if (rc != GS_OK)

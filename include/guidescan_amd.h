@@ -742,6 +742,96 @@ uint64_t gs_debug_kmers_chunk_bytes(uint64_t set);
  * device side: gs_kmers_get / gs_kmers_get_ids with on_device != 0 are GS_ERR_ARG. */
 gs_status gs_debug_kmers_host(const uint8_t *raw, uint64_t len, uint64_t tile_bytes, gs_kmers **out, gs_kmers_report *rep);
 
+/* ---- guides for regions: candidates restricted to the intervals of a BED file, ranked within groups of them ---- */
+/* The reference has no counterpart for anything in this section: the pipelines of its manual (manual/manual.tex:321-656)
+ * filter the genome-wide table by coordinate and specificity in scripts.  The rules, stated once (gs_regions_scan.h):
+ * a candidate printed at 1-based `position` occupies the forward-strand bases [position - 1, position - 1 + k + P) for both
+ * senses, with and without --start (scripts/generate_kmers.py:70-100), and belongs to a group iff that footprint lies inside
+ * one of the group's intervals on its chromosome, the group's intervals merged first where they overlap or abut.  A
+ * candidate inside intervals of several groups gives one record per group.  A record's id is
+ * "{prefix}{group}:{chr}:{position}:{sense}".  Records are ordered by group number, then (with per_region: specificity
+ * descending first) by chromosome in structure order, position, sense with '+' first. */
+
+typedef struct gs_regions gs_regions;
+typedef struct gs_design gs_design;
+
+#define GS_REGIONS_BAD_FEW 1u        /* fewer than three fields */
+#define GS_REGIONS_BAD_INTEGER 2u    /* a start or end that is not a non-negative integer (digits only, at most 18) */
+#define GS_REGIONS_BAD_ORDER 3u      /* start >= end */
+#define GS_REGIONS_BAD_CHROMOSOME 4u /* a chromosome the structure does not have */
+#define GS_REGIONS_BAD_BEYOND 5u     /* end beyond the chromosome's length */
+#define GS_REGIONS_BAD_COMMA 6u      /* a group name with ',': it would break the CSV id column */
+#define GS_REGIONS_BAD_LONG 7u       /* a group name with which an id could pass 254 bytes, the BAM encoder's cap */
+#define GS_REGIONS_BAD_EMPTY 8u      /* no interval in the file (bad_line 0) */
+typedef struct gs_regions_report { /* in the shape of gs_kmers_report */
+  uint64_t n_lines;     /* lines of the file, the skipped ones included */
+  uint64_t n_intervals; /* after merging */
+  uint64_t n_groups;
+  uint32_t bad_kind, pad;
+  uint64_t bad_line; /* 1-based, of the first failing line */
+  uint64_t bad_len;
+  char *bad_text; /* the message, "regions line N: REASON"; malloc'ed, NUL terminated: release with gs_free.  NULL when bad_kind is 0 */
+} gs_regions_report;
+
+/* A BED file (no counterpart in the reference) against a genome structure, on the host: a file of every human exon is a
+ * few megabytes.  Fields are separated by tabs or blanks; lines that are empty or start with '#', "track" or "browser" are
+ * skipped; a trailing '\r' is dropped.  Columns 1-3: chromosome, start, end, 0-based and half-open.  Column 4, if present,
+ * names the line's group, otherwise the group is "{chr}:{start}-{end}"; groups are numbered by first appearance and may lie
+ * on several chromosomes.  `prefix` (or NULL) is the id prefix the length cap is checked with, against the longest
+ * chromosome name and ten position digits.  GS_ERR_FORMAT: rep->bad_* say which line and why, and
+ * gs_status_string(GS_ERR_FORMAT) reads as that message.  The object keeps, per chromosome, the merged intervals of all
+ * groups sorted by start with the running maximum of their ends, ready to upload. */
+gs_status gs_regions_parse(const uint8_t *raw, uint64_t len, const gs_genome_structure *gs, const char *prefix, gs_regions **out,
+                           gs_regions_report *rep);
+/* the same (no counterpart in the reference) from a file; GS_ERR_IO when it cannot be read */
+gs_status gs_regions_parse_file(const char *path, const gs_genome_structure *gs, const char *prefix, gs_regions **out,
+                                gs_regions_report *rep);
+gs_status gs_regions_info(const gs_regions *regions, uint64_t *n_groups, uint64_t *n_intervals);
+void gs_regions_free(gs_regions *regions);
+
+/* The records of one chromosome's scan (gs_kmers_generate on chromosome chr_index of the structure) that lie in a group,
+ * made in HBM (no counterpart in the reference): a count per candidate, a scan, and one record per (candidate, group)
+ * holding sequence, PAM, position, sense, group and chromosome.  `regions` must outlive every design made from it. */
+gs_status gs_design_restrict(const gs_regions *regions, uint32_t chr_index, gs_kmers *scan, void *stream, gs_design **part);
+/* one design holding the records of parts[0], parts[1], ... (same device, regions, k and P); the parts stay the caller's */
+gs_status gs_design_concat(gs_design *const *parts, uint32_t n_parts, gs_design **out);
+/* The specificity of every record, in the design's float[n] in HBM (no counterpart in the reference): the records go in
+ * batches of `batch` (0: 2^17) through gs_enumerate_device and gs_score_device under the CSV rule with max_off_targets
+ * = -1, whatever the database is written as.  flags: GS_FLAG_PAM_AT_START, GS_FLAG_NO_NEW_TABLES.  threshold >= 0: the
+ * counting pass of --threshold (GS_FLAG_RAW_COUNTS, process.hpp:66-76) runs too, its raw counts read in HBM where the
+ * search leaves them, and a record it would drop is not eligible for selection.  GS_ERR_UNSUPPORTED where the fast path's key does not fit (2L + 3P > 59) or a record needs
+ * the general path. */
+gs_status gs_design_score(gs_index *ix, gs_design *design, const char *alt_pams, uint32_t n_alt, uint32_t mismatches,
+                          uint32_t flags, int64_t threshold, uint64_t batch, void *stream);
+/* The records in order, as a gs_kmers object in HBM with their ids (no counterpart in the reference).  per_region N > 0
+ * keeps the first N eligible records of each group with specificity >= min_specificity; min_specificity < 0: no bound;
+ * both need gs_design_score first (GS_ERR_ARG).  With neither, every eligible record is ordered and emitted.  The object
+ * has ids from the start: gs_kmers_encode_ids on it is GS_ERR_ARG; gs_kmers_get, gs_kmers_get_ids and gs_kmers_concat
+ * work as on a scan's. */
+gs_status gs_design_select(gs_design *design, const char *prefix, uint32_t per_region, float min_specificity, void *stream,
+                           gs_kmers **out);
+/* the same selection as rows of the kmers file, `id,sequence,pam,chromosome,position,sense\n` (scripts/generate_kmers.py:120-125
+ * with the group in the id), no header; *text is malloc'ed (NUL terminated): release with gs_free */
+gs_status gs_design_rows(gs_design *design, const char *prefix, uint32_t per_region, float min_specificity, void *stream,
+                         char **text, uint64_t *len);
+/* host copies of the records' arrays, owned by the design: groups, chromosomes, positions uint32; senses '+' / '-';
+ * specificity float; eligible bytes.  Any pointer may be NULL. */
+gs_status gs_design_get(gs_design *design, uint64_t *n, const void **groups, const void **chromosomes, const void **positions,
+                        const void **senses, const void **specificity, const void **eligible);
+/* the number of records and whether gs_design_score has run; nothing is copied */
+gs_status gs_design_info(const gs_design *design, uint64_t *n, int *scored);
+/* of the last gs_design_select / gs_design_rows: records, kept records, groups left without a record, groups short of N */
+gs_status gs_design_last_select(const gs_design *design, uint64_t out[4]);
+void gs_design_free(gs_design *design);
+/* Host only: restrict, order, select and ids through gs_regions_scan.h, with no device (no counterpart in the reference).
+ * Part i: n[i] candidates of chromosome chr_index[i] as a scan gives them; specificity / eligible (or NULL) are per
+ * candidate.  *out has no device side; rows (or NULL): the kmers-file rows, malloc'ed. */
+gs_status gs_debug_design_host(const gs_regions *regions, uint32_t n_parts, const uint32_t *chr_index, const uint64_t *n,
+                               const uint8_t *const *seqs, const uint32_t *const *positions, const uint8_t *const *senses,
+                               const float *const *specificity, const uint8_t *const *eligible, const char *pam, uint32_t k,
+                               const char *prefix, uint32_t per_region, float min_specificity, gs_kmers **out, char **rows,
+                               uint64_t *rows_len);
+
 /* ---- SAM/BAM databases back to CSV on the device (scripts/decode_database.py) --------------------------------- */
 
 typedef struct gs_decoder gs_decoder;
