@@ -69,6 +69,7 @@ GS_TEXT_SAM = 0x100
 GS_TEXT_COMPLETE = 0x200
 GS_TEXT_BAM = 0x800    # gs_format_device / gs_enumerate_text: BAM alignment blocks in place of SAM lines
 GS_TEXT_BGZF = 0x1000  # with GS_TEXT_BAM: the blocks as BGZF members
+GS_TEXT_FEATURES = 0x4000
 GS_DECODE_NO_HEADER = 0x400
 GS_DECODE_BAM_END = 0x2000  # gs_decode_bam: the data ends with these members (a cut record is an error)
 
@@ -348,6 +349,34 @@ def lib():
     L.gs_debug_design_host.restype = i32
     L.gs_debug_design_host.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, C.c_char_p, u32, C.c_char_p, u32, f32,
                                        C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+    L.gs_regions_group_name.restype = i32
+    L.gs_regions_group_name.argtypes = [vp, u64, C.POINTER(C.c_char_p)]
+    L.gs_annot_build.restype = i32
+    L.gs_annot_build.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.gs_annot_info.restype = i32
+    L.gs_annot_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.gs_annot_free.restype = None
+    L.gs_annot_free.argtypes = [vp]
+    L.gs_debug_annot_entry_cap.restype = u64
+    L.gs_debug_annot_entry_cap.argtypes = [u64]
+    L.gs_annotate_device.restype = i32
+    L.gs_annotate_device.argtypes = [vp, vp, pgs, u64, u32, u32, u32, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.gs_annotate.restype = i32
+    L.gs_annotate.argtypes = [vp, vp, pgs, u64, u32, u32, u32, vp, vp, vp, C.POINTER(vp), C.POINTER(u64), vp]
+    L.gs_debug_annotate_host.restype = i32
+    L.gs_debug_annotate_host.argtypes = [vp, pgs, u64, u32, u32, u32, vp, vp, vp, C.POINTER(vp), C.POINTER(u64), vp]
+    L.gs_index_set_annotation.restype = i32
+    L.gs_index_set_annotation.argtypes = [vp, vp]
+    L.gs_format_guides_features.restype = i32
+    L.gs_format_guides_features.argtypes = [pgs, vp, u64, vp, vp, vp, vp, u32, u32, C.c_int64, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.gs_format_guide_features.restype = i32
+    L.gs_format_guide_features.argtypes = [pgs, vp, vp, u64, u32, u32, C.c_int64, f32, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.gs_format_guide_ex_features.restype = i32
+    L.gs_format_guide_ex_features.argtypes = [pgs, vp, vp, u64, u32, u32, C.c_int64, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.gs_design_set_feature_rule.restype = i32
+    L.gs_design_set_feature_rule.argtypes = [vp, vp, u32, u32]
+    L.gs_design_get_feature_hits.restype = i32
+    L.gs_design_get_feature_hits.argtypes = [vp, C.POINTER(vp)]
     L.gs_status_string.restype = C.c_char_p
     L.gs_status_string.argtypes = [i32]
     L.gs_version.restype = C.c_char_p
@@ -385,7 +414,11 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_debug_kmers_chunk_bytes", "gs_debug_kmers_host",
            "gs_regions_parse", "gs_regions_parse_file", "gs_regions_info", "gs_regions_free", "gs_design_restrict",
            "gs_design_concat", "gs_design_score", "gs_design_select", "gs_design_rows", "gs_design_get", "gs_design_info",
-           "gs_design_last_select", "gs_design_free", "gs_debug_design_host"]
+           "gs_design_last_select", "gs_design_free", "gs_debug_design_host",
+           "gs_regions_group_name", "gs_annot_build", "gs_annot_info", "gs_annot_free", "gs_debug_annot_entry_cap",
+           "gs_annotate_device", "gs_annotate", "gs_debug_annotate_host", "gs_index_set_annotation",
+           "gs_format_guides_features", "gs_format_guide_features", "gs_format_guide_ex_features",
+           "gs_design_set_feature_rule", "gs_design_get_feature_hits"]
 
 
 def _check(rc):
@@ -403,7 +436,7 @@ def buffers_live():
     return int(out[0]), int(out[1])
 
 
-WORKSPACE_GROUPS = ("batch", "big", "tile", "score", "text", "bgzf")
+WORKSPACE_GROUPS = ("batch", "big", "tile", "score", "text", "bgzf", "annot")
 
 
 BULGE_SEED_DTYPE = np.dtype([("index", "<u4"), ("state", "<u4"), ("seq", "S32")])
@@ -592,9 +625,9 @@ def make_genome_structure(names, lengths):
     return g
 
 
-def format_header(gs, sam=False, complete=True) -> str:
+def format_header(gs, sam=False, complete=True, features=False) -> str:
     out, n = C.c_void_p(), C.c_size_t()
-    flags = (GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0)
+    flags = (GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) | (GS_TEXT_FEATURES if features else 0)
     _check(lib().gs_format_header(C.byref(gs), flags, C.byref(out), C.byref(n)))
     s = C.string_at(out, n.value).decode()
     lib().gs_free(out)
@@ -602,15 +635,20 @@ def format_header(gs, sam=False, complete=True) -> str:
 
 
 def format_guide(gs, gid, sequence, pam, sense_positive, hits, mismatches, sam=False, complete=True,
-                 start=False, max_off_targets=-1, specificity=None) -> str:
+                 start=False, max_off_targets=-1, specificity=None, features=None) -> str:
     """hits: numpy HIT_DTYPE array of this guide (canonical order, as gs_enumerate returns);
-    specificity: the guide's float from GenomeIndex.score (then the host does no CFD arithmetic)"""
+    specificity: the guide's float from GenomeIndex.score (then the host does no CFD arithmetic);
+    features: an Annotation - the match_features column (gs_format_guide_features; needs the specificity)"""
     hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
     k = GsKmer(gid.encode(), sequence.encode(), pam.encode(), int(sense_positive))
     out, n = C.c_void_p(), C.c_size_t()
     flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
              (GS_FLAG_PAM_AT_START if start else 0))
-    if specificity is None:
+    if features is not None:
+        _check(lib().gs_format_guide_features(C.byref(gs), C.byref(k), hits.ctypes.data, hits.shape[0], mismatches,
+                                              flags | GS_TEXT_FEATURES, max_off_targets, float(specificity), features._h,
+                                              C.byref(out), C.byref(n)))
+    elif specificity is None:
         _check(lib().gs_format_guide(C.byref(gs), C.byref(k), hits.ctypes.data, hits.shape[0], mismatches,
                                      flags, max_off_targets, C.byref(out), C.byref(n)))
     else:
@@ -623,8 +661,9 @@ def format_guide(gs, gid, sequence, pam, sense_positive, hits, mismatches, sam=F
 
 
 def format_guides(gs, ids, seqs, pams, senses_positive, offsets, hits, specificity, mismatches, sam=False,
-                  complete=True, start=False, max_off_targets=-1, skip=None) -> bytes:
-    """the lines of a whole batch in one call (gs_format_guides_scored)"""
+                  complete=True, start=False, max_off_targets=-1, skip=None, features=None) -> bytes:
+    """the lines of a whole batch in one call (gs_format_guides_scored); features: an Annotation - with the
+    match_features column (gs_format_guides_features)"""
     n = len(ids)
     arr = (GsKmer * n)(*[GsKmer(ids[i].encode(), seqs[i].encode(), pams[i].encode(), int(senses_positive[i]))
                          for i in range(n)])
@@ -635,10 +674,16 @@ def format_guides(gs, ids, seqs, pams, senses_positive, offsets, hits, specifici
     out, ln = C.c_void_p(), C.c_size_t()
     flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
              (GS_FLAG_PAM_AT_START if start else 0))
-    _check(lib().gs_format_guides_scored(C.byref(gs), arr, n, offsets.ctypes.data,
-                                         hits.ctypes.data if hits.shape[0] else None, spec.ctypes.data,
-                                         sk.ctypes.data if sk is not None else None, mismatches, flags,
-                                         max_off_targets, C.byref(out), C.byref(ln)))
+    if features is not None:
+        _check(lib().gs_format_guides_features(C.byref(gs), arr, n, offsets.ctypes.data,
+                                               hits.ctypes.data if hits.shape[0] else None, spec.ctypes.data,
+                                               sk.ctypes.data if sk is not None else None, mismatches,
+                                               flags | GS_TEXT_FEATURES, max_off_targets, features._h, C.byref(out), C.byref(ln)))
+    else:
+        _check(lib().gs_format_guides_scored(C.byref(gs), arr, n, offsets.ctypes.data,
+                                             hits.ctypes.data if hits.shape[0] else None, spec.ctypes.data,
+                                             sk.ctypes.data if sk is not None else None, mismatches, flags,
+                                             max_off_targets, C.byref(out), C.byref(ln)))
     s = C.string_at(out, ln.value)
     lib().gs_free(out)
     return s
@@ -826,6 +871,70 @@ class Regions:
             pass
 
 
+class Annotation:
+    """The lookup table of a BED file's features (gs_annot_build): which groups a printed off-target row touches.
+    device None: host only (the host encoders and annotate_host_model)."""
+
+    def __init__(self, handle, regions, device):
+        self._h, self.structure, self.device = handle, regions.structure, device
+        name = C.c_char_p()
+        self.names = []
+        for g in range(regions.n_groups):
+            _check(lib().gs_regions_group_name(regions._h, g, C.byref(name)))
+            self.names.append(name.value.decode("latin-1"))
+
+    @classmethod
+    def build(cls, regions, device=0):
+        h = C.c_void_p()
+        _check(lib().gs_annot_build(regions._h, -1 if device is None else device, C.byref(h)))
+        return cls(h, regions, device)
+
+    def info(self):
+        """-> dict(groups, segments, entries) (gs_annot_info)"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().gs_annot_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"groups": int(a.value), "segments": int(b.value), "entries": int(c.value)}
+
+    def close(self):
+        if self._h:
+            lib().gs_annot_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def annot_entry_cap(set_to=0) -> int:
+    """the entry cap of Annotation.build; set_to != 0 sets it (gs_debug_annot_entry_cap)"""
+    return int(lib().gs_debug_annot_entry_cap(set_to))
+
+
+def _annotate_call(fn, head, annotation, gs, offsets, hits, L, P, mismatches):
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n = offsets.shape[0] - 1
+    nh = int(offsets[n] - offsets[0]) if n > 0 else 0
+    foff = np.zeros(nh + 1, dtype=np.uint64)
+    gcnt = np.zeros((max(n, 0), mismatches + 1), dtype=np.uint32)
+    feats, nf = C.c_void_p(), C.c_uint64()
+    _check(fn(*head, annotation._h, C.byref(gs), max(n, 0), L, P, mismatches, offsets.ctypes.data,
+              hits.ctypes.data if hits.shape[0] else None, foff.ctypes.data, C.byref(feats), C.byref(nf),
+              gcnt.ctypes.data if gcnt.size else None))
+    try:
+        f = np.frombuffer(C.string_at(feats, 4 * nf.value), dtype=np.uint32).copy() if nf.value else np.empty(0, np.uint32)
+    finally:
+        lib().gs_free(feats)
+    return foff, f, gcnt
+
+
+def annotate_host_model(annotation, gs, offsets, hits, L, P, mismatches):
+    """GenomeIndex.annotate on the host through the kernels' shared header, no GPU (gs_debug_annotate_host)"""
+    return _annotate_call(lib().gs_debug_annotate_host, (), annotation, gs, offsets, hits, L, P, mismatches)
+
+
 def _select_args(per_region, min_specificity):
     n = 0 if per_region is None else int(per_region)
     if per_region is not None and n < 1:
@@ -859,6 +968,14 @@ class Design:
                                      threshold, batch, None))
         return self
 
+    def set_feature_rule(self, annotation, distance, max_hits):
+        """before score(): count, per record, the off-target hits within `distance` that touch a feature of `annotation`
+        (the record's own site left out); more than max_hits and the record is not eligible
+        (gs_design_set_feature_rule).  annotation None takes the rule off."""
+        _check(lib().gs_design_set_feature_rule(self._h, annotation._h if annotation is not None else None, distance, max_hits))
+        self._rule = annotation   # keeps it alive through score()
+        return self
+
     def select(self, prefix="", per_region=None, min_specificity=None):
         """the records in order, cut to the first per_region eligible ones of each group with specificity >=
         min_specificity (gs_design_select) -> DeviceKmers with ids"""
@@ -883,7 +1000,8 @@ class Design:
         return t
 
     def to_host(self):
-        """-> dict(n, group uint32[n], chr uint32[n], pos uint32[n], sense uint8[n], spec float32[n], eligible uint8[n])"""
+        """-> dict(n, group uint32[n], chr uint32[n], pos uint32[n], sense uint8[n], spec float32[n], eligible uint8[n]);
+        after a score() under set_feature_rule also feature_hits uint32[n]"""
         n = C.c_uint64()
         p = [C.c_void_p() for _ in range(6)]
         _check(lib().gs_design_get(self._h, C.byref(n), *[C.byref(x) for x in p]))
@@ -892,6 +1010,9 @@ class Design:
         for name, x, dt in zip(("group", "chr", "pos", "sense", "spec", "eligible"), p,
                                (np.uint32, np.uint32, np.uint32, np.uint8, np.float32, np.uint8)):
             out[name] = np.frombuffer(C.string_at(x, m * np.dtype(dt).itemsize), dtype=dt).copy() if m else np.empty(0, dt)
+        fh = C.c_void_p()
+        if getattr(self, "_rule", None) is not None and lib().gs_design_get_feature_hits(self._h, C.byref(fh)) == 0:
+            out["feature_hits"] = np.frombuffer(C.string_at(fh, 4 * m), dtype=np.uint32).copy() if m else np.empty(0, np.uint32)
         return out
 
     def info(self):
@@ -1449,15 +1570,20 @@ def decode_sequence_ex(hit) -> str:
 
 
 def format_guide_ex(gs, gid, sequence, pam, sense_positive, hits, mismatches, sam=False, complete=True,
-                    start=False, max_off_targets=-1) -> str:
-    """hits: numpy HIT_EX_DTYPE array of this guide (bulge path)"""
+                    start=False, max_off_targets=-1, features=None) -> str:
+    """hits: numpy HIT_EX_DTYPE array of this guide (bulge path); features: an Annotation - with the match_features
+    column (gs_format_guide_ex_features)"""
     hits = np.ascontiguousarray(hits, dtype=HIT_EX_DTYPE)
     k = GsKmer(gid.encode(), sequence.encode(), pam.encode(), int(sense_positive))
     out, n = C.c_void_p(), C.c_size_t()
     flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
              (GS_FLAG_PAM_AT_START if start else 0))
-    _check(lib().gs_format_guide_ex(C.byref(gs), C.byref(k), hits.ctypes.data, hits.shape[0], mismatches,
-                                    flags, max_off_targets, C.byref(out), C.byref(n)))
+    if features is not None:
+        _check(lib().gs_format_guide_ex_features(C.byref(gs), C.byref(k), hits.ctypes.data, hits.shape[0], mismatches,
+                                                 flags | GS_TEXT_FEATURES, max_off_targets, features._h, C.byref(out), C.byref(n)))
+    else:
+        _check(lib().gs_format_guide_ex(C.byref(gs), C.byref(k), hits.ctypes.data, hits.shape[0], mismatches,
+                                        flags, max_off_targets, C.byref(out), C.byref(n)))
     s = C.string_at(out, n.value).decode()
     lib().gs_free(out)
     return s
@@ -1608,6 +1734,26 @@ class GenomeIndex:
             lib().gs_result_free(r)
         return offsets, hits, stats
 
+    def annotate(self, annotation, gs, offsets, hits, L, P, mismatches):
+        """the features of every hit of a CSR hit list (gs_annotate; offsets[0] need not be 0) -> (feat_offsets
+        uint64[n_hits + 1], feats uint32 group numbers, guide_counts uint32[n, mismatches + 1]: per guide and distance the
+        hits that have a row and a feature)"""
+        return _annotate_call(lib().gs_annotate, (self._h,), annotation, gs, offsets, hits, L, P, mismatches)
+
+    def annotate_device(self, annotation, gs, n, L, P, mismatches, d_offsets_ptr, d_hits_ptr, stream=None):
+        """device-resident variant (gs_annotate_device): raw device addresses in, (feat_offsets, feats, guide_counts)
+        device addresses out, owned by the handle until the next call on it"""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().gs_annotate_device(self._h, annotation._h, C.byref(gs), n, L, P, mismatches, d_offsets_ptr, d_hits_ptr,
+                                        stream, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def set_annotation(self, annotation):
+        """attach the Annotation the text calls' features=True looks rows up in; None detaches
+        (gs_index_set_annotation)"""
+        _check(lib().gs_index_set_annotation(self._h, annotation._h if annotation is not None else None))
+        self._annotation = annotation
+
     def score(self, gs, seqs, P, offsets, hits, sam=False, start=False, max_off_targets=-1, want_cfd=True):
         """CFD per hit and specificity per guide on the device (printer.hpp:98-113, 115-170, 251-297)
         -> (cfd float32[n_hits] or None, specificity float32[n])"""
@@ -1631,7 +1777,8 @@ class GenomeIndex:
                                      d_offsets_ptr, d_hits_ptr, stream, d_cfd_ptr, d_spec_ptr))
 
     def format_device(self, gs, d_guides_ptr, n, L, d_pams_ptr, P, ids, senses, skip, d_offsets_ptr, d_hits_ptr,
-                      d_spec_ptr, mismatches, sam=False, complete=True, start=False, max_off_targets=-1, stream=None, bam=False, bgzf=False):
+                      d_spec_ptr, mismatches, sam=False, complete=True, start=False, max_off_targets=-1, stream=None, bam=False, bgzf=False,
+                      features=False):
         """the database text of a fast-path batch encoded in HBM (gs_format_device): raw device addresses in (ids,
         senses and skip are host sequences, the last two may be None), (d_text_ptr, length) out - device memory of
         the handle, valid until the next call on it; the bytes are those of format_guides.  bam=True (in place of sam):
@@ -1641,7 +1788,8 @@ class GenomeIndex:
             raise ValueError("one id per guide")
         se, sk = _bytes_or_none(senses, n), _bytes_or_none(skip, n)
         flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
-                 (GS_FLAG_PAM_AT_START if start else 0) | (GS_TEXT_BAM if bam else 0) | (GS_TEXT_BGZF if bgzf else 0))
+                 (GS_FLAG_PAM_AT_START if start else 0) | (GS_TEXT_BAM if bam else 0) | (GS_TEXT_BGZF if bgzf else 0) |
+                 (GS_TEXT_FEATURES if features else 0))
         d_text, ln = C.c_void_p(), C.c_uint64()
         keep = C.create_string_buffer(blob, len(blob) + 1)
         _check(lib().gs_format_device(self._h, C.byref(gs), d_guides_ptr, n, L, d_pams_ptr, P, C.addressof(keep),
@@ -1651,7 +1799,7 @@ class GenomeIndex:
         return d_text.value, int(ln.value)
 
     def enumerate_text(self, seqs, pams, ids, senses, gs, mismatches=3, alt_pams=(), start=False, sam=False,
-                       complete=True, max_off_targets=-1, skip=None, bam=False, bgzf=False) -> bytes:
+                       complete=True, max_off_targets=-1, skip=None, bam=False, bgzf=False, features=False) -> bytes:
         """guides in, database text out (gs_enumerate_text): search, scoring and encoding on the device.  Raises
         GsError with status 3 (GS_ERR_UNSUPPORTED) when a guide of the batch needs the general path."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
@@ -1668,7 +1816,8 @@ class GenomeIndex:
         blob, off = _id_blob(ids)
         se, sk = _bytes_or_none(senses, n), _bytes_or_none(skip, n)
         flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
-                 (GS_FLAG_PAM_AT_START if start else 0) | (GS_TEXT_BAM if bam else 0) | (GS_TEXT_BGZF if bgzf else 0))
+                 (GS_FLAG_PAM_AT_START if start else 0) | (GS_TEXT_BAM if bam else 0) | (GS_TEXT_BGZF if bgzf else 0) |
+                 (GS_TEXT_FEATURES if features else 0))
         keep = C.create_string_buffer(blob, len(blob) + 1)
         out, ln = C.c_void_p(), C.c_uint64()
         _check(lib().gs_enumerate_text(self._h, seqs.ctypes.data, n, L, pams.ctypes.data if P else None, P,
@@ -1682,12 +1831,13 @@ class GenomeIndex:
 
     def format_device_ids(self, gs, d_guides_ptr, n, L, d_pams_ptr, P, d_ids_ptr, d_id_offsets_ptr, d_senses_ptr, skip,
                           d_offsets_ptr, d_hits_ptr, d_spec_ptr, mismatches, sam=False, complete=True, start=False,
-                          max_off_targets=-1, stream=None, bam=False, bgzf=False):
+                          max_off_targets=-1, stream=None, bam=False, bgzf=False, features=False):
         """format_device with ids, id offsets and senses that are in HBM already (gs_format_device_ids): raw device
         addresses; `skip` stays a host sequence or None"""
         sk = _bytes_or_none(skip, n)
         flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
-                 (GS_FLAG_PAM_AT_START if start else 0) | (GS_TEXT_BAM if bam else 0) | (GS_TEXT_BGZF if bgzf else 0))
+                 (GS_FLAG_PAM_AT_START if start else 0) | (GS_TEXT_BAM if bam else 0) | (GS_TEXT_BGZF if bgzf else 0) |
+                 (GS_TEXT_FEATURES if features else 0))
         d_text, ln = C.c_void_p(), C.c_uint64()
         _check(lib().gs_format_device_ids(self._h, C.byref(gs), d_guides_ptr, n, L, d_pams_ptr, P, d_ids_ptr,
                                           d_id_offsets_ptr, d_senses_ptr, sk.ctypes.data if sk is not None else None,
@@ -1697,13 +1847,14 @@ class GenomeIndex:
 
     def enumerate_text_device(self, d_guides_ptr, n, L, d_pams_ptr, P, d_ids_ptr, d_id_offsets_ptr, d_senses_ptr, gs,
                               mismatches=3, alt_pams=(), start=False, sam=False, complete=True, max_off_targets=-1,
-                              skip=None, bam=False, bgzf=False) -> bytes:
+                              skip=None, bam=False, bgzf=False, features=False) -> bytes:
         """enumerate_text over guides, ids and senses in HBM (gs_enumerate_text_device): only the text comes back.
         Raises GsError with status 3 when a guide needs the general path or 2L + 3P > 59."""
         alt = b"".join(p.encode() for p in alt_pams)
         sk = _bytes_or_none(skip, n)
         flags = ((GS_TEXT_SAM if sam else 0) | (GS_TEXT_COMPLETE if complete else 0) |
-                 (GS_FLAG_PAM_AT_START if start else 0) | (GS_TEXT_BAM if bam else 0) | (GS_TEXT_BGZF if bgzf else 0))
+                 (GS_FLAG_PAM_AT_START if start else 0) | (GS_TEXT_BAM if bam else 0) | (GS_TEXT_BGZF if bgzf else 0) |
+                 (GS_TEXT_FEATURES if features else 0))
         out, ln = C.c_void_p(), C.c_uint64()
         _check(lib().gs_enumerate_text_device(self._h, d_guides_ptr, n, L, d_pams_ptr, P, alt if alt_pams else None,
                                               len(alt_pams), mismatches, flags, max_off_targets, C.byref(gs), d_ids_ptr,

@@ -220,7 +220,18 @@ struct gs_ws_bgzf {
   }
   size_t release() { return gs_ws_release(*this); }
 };
-#define GS_WS_GROUPS 6
+/* gs_annot.hip: the chromosome prefix sums a call uploads; the counts and the scan's temporary; what gs_annotate_device
+ * returns - feature offsets and features per hit, counts per guide and distance; gs_annotate's staging */
+struct gs_ws_annot {
+  gs_buffer in, cnt, tmp, foff, feats, gcnt, io;
+  template <class F>
+  void each(F f) {
+    for (gs_buffer *b : {&cnt, &foff, &feats, &io}) f(*b, true);
+    for (gs_buffer *b : {&in, &tmp, &gcnt}) f(*b, false);
+  }
+  size_t release() { return gs_ws_release(*this); }
+};
+#define GS_WS_GROUPS 7
 
 /* The device arrays a handle keeps between calls (a strand's, a PAM-pair slot's): each with the bytes it counts for in
  * gs_index_device_bytes - what the fit estimates reckon with, not the allocation's size.  Frees them when it goes.
@@ -337,6 +348,8 @@ struct gs_index {
   gs_ws_score w_score;
   gs_ws_text w_text;
   gs_ws_bgzf w_bgzf;
+  gs_ws_annot w_annot;
+  const struct gs_annot *annot = nullptr; /* gs_index_set_annotation: what GS_TEXT_FEATURES looks rows up in; the caller's */
   uint32_t share_backoff = 0; /* batches this handle still runs without sharing after a sharing launch was not resident as a whole */
   bool share_timed_out = false; /* a helping wave gave up waiting for a package (k_search_body): the call fails, gs_enumerate_device redoes the batch without sharing */
   uint32_t opt_share_min = 512, opt_share_max = 2048; /* groups of eight rows: a verification pass of share_min or more is handed out, in packages of at most share_max (0: items are never shared) */

@@ -30,6 +30,8 @@
 #include "gs_scratch.h"
 #include "gs_kmers_obj.h"
 #include "gs_regions_scan.h"
+#include "gs_regions_obj.h"
+#include "gs_annot_obj.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -39,20 +41,6 @@
 #define DS_BLOCK 256
 
 /* ---- the regions file ------------------------------------------------------------------------------------------ */
-
-struct gs_rg_chr { /* one chromosome's table, as uploaded */
-  std::vector<uint32_t> start, end, maxend, group;
-};
-struct gs_regions {
-  std::vector<std::string> chr_names, group_names;
-  std::vector<uint64_t> chr_lengths;
-  std::vector<const char *> chr_name_ptrs;
-  std::vector<gs_rg_chr> chr;
-  uint64_t n_intervals = 0;
-  gs_genome_structure structure() const {
-    return gs_genome_structure{chr_name_ptrs.data(), chr_lengths.data(), (uint32_t)chr_names.size()};
-  }
-};
 
 static const char *const RG_REASON[9] = {"",
                                          "fewer than three fields",
@@ -251,14 +239,21 @@ struct gs_design {
   std::vector<float> h_spec;
   bool have_host = false;
   uint64_t last[4] = {0, 0, 0, 0}; /* of the last select: records, kept, groups left empty, groups short of N */
+  /* gs_design_set_feature_rule: the score phase counts, per record, the off-target hits within rule_distance that have a
+   * feature of rule_annot (d_fhits, uint32[n]); more than rule_max of them and the record is not eligible */
+  const gs_annot *rule_annot = nullptr;
+  uint32_t rule_distance = 0, rule_max = 0;
+  void *d_fhits = nullptr;
+  bool have_fhits = false;
+  std::vector<uint32_t> h_fhits;
 };
 
 static void ds_release(gs_design *d) {
   if (!d) return;
   bool any = false;
-  for (void *p : {d->d_seqs, d->d_pams, d->d_pos, d->d_sense, d->d_group, d->d_chr, d->d_spec, d->d_elig}) any = any || p;
+  for (void *p : {d->d_seqs, d->d_pams, d->d_pos, d->d_sense, d->d_group, d->d_chr, d->d_spec, d->d_elig, d->d_fhits}) any = any || p;
   if (any) hipSetDevice(d->device);
-  for (void *p : {d->d_seqs, d->d_pams, d->d_pos, d->d_sense, d->d_group, d->d_chr, d->d_spec, d->d_elig})
+  for (void *p : {d->d_seqs, d->d_pams, d->d_pos, d->d_sense, d->d_group, d->d_chr, d->d_spec, d->d_elig, d->d_fhits})
     if (p) hipFree(p);
   delete d;
 }
@@ -510,6 +505,39 @@ __global__ __launch_bounds__(DS_BLOCK) void k_ds_eligible(const uint32_t *raw, u
   if (j < n) elig[j] = raw[j] > 1u ? 0 : 1; /* process.hpp:66-76: more than one hit within the threshold drops the guide */
 }
 
+__global__ __launch_bounds__(DS_BLOCK) void k_ds_feature_rule(const uint32_t *fhits, uint64_t n, uint32_t max_hits, uint8_t *elig) {
+  const uint64_t j = (uint64_t)blockIdx.x * DS_BLOCK + threadIdx.x;
+  if (j < n && fhits[j] > max_hits) elig[j] = 0; /* as a --threshold drop */
+}
+
+extern "C" gs_status gs_design_set_feature_rule(gs_design *d, const gs_annot *annot, uint32_t distance, uint32_t max_hits) {
+  if (!d || d->device < 0) return GS_ERR_ARG;
+  if (annot && annot->device != d->device) {
+    gs_set_error("gs_design_set_feature_rule: the annotation was built for another device, or for the host only");
+    return GS_ERR_ARG;
+  }
+  d->rule_annot = annot;
+  d->rule_distance = distance;
+  d->rule_max = max_hits;
+  d->have_fhits = false;
+  return GS_OK;
+}
+
+extern "C" gs_status gs_design_get_feature_hits(gs_design *d, const void **counts) {
+  if (!d || !counts || !d->have_fhits) return GS_ERR_ARG;
+  try {
+    d->h_fhits.resize((size_t)d->n);
+    if (d->n) {
+      GS_HIP(hipSetDevice(d->device));
+      GS_HIP(hipMemcpy(d->h_fhits.data(), d->d_fhits, 4 * (size_t)d->n, hipMemcpyDeviceToHost));
+    }
+  } catch (const std::bad_alloc &) {
+    return GS_ERR_NOMEM;
+  }
+  *counts = d->h_fhits.data();
+  return GS_OK;
+}
+
 extern "C" gs_status gs_design_score(gs_index *ix, gs_design *d, const char *alt_pams, uint32_t n_alt, uint32_t mismatches,
                                      uint32_t flags, int64_t threshold, uint64_t batch, void *stream) {
   if (!ix || !d || (n_alt && !alt_pams) || d->device < 0 || mismatches > 7 || threshold > 7 || n_alt > 31) return GS_ERR_ARG;
@@ -532,6 +560,11 @@ extern "C" gs_status gs_design_score(gs_index *ix, gs_design *d, const char *alt
     GS_HIP(hipSetDevice(d->device));
     GS_TRY(gs_index_lock(ix));
     lock.held = true;
+    if (d->rule_annot) {
+      if (!d->d_fhits) GS_TRY(ds_array(4 * (size_t)d->n, &d->d_fhits));
+      GS_HIP(hipMemsetAsync(d->d_fhits, 0, 4 * (size_t)d->n + 16, st));
+      if (threshold < 0) GS_HIP(hipMemsetAsync(d->d_elig, 1, (size_t)d->n + 16, st)); /* the rule alone decides */
+    }
     for (uint64_t lo = 0; lo < d->n; lo += batch) {
       const uint64_t nb = std::min<uint64_t>(batch, d->n - lo);
       const char *g = (const char *)d->d_seqs + lo * d->k, *p = (const char *)d->d_pams + lo * d->P;
@@ -559,11 +592,20 @@ extern "C" gs_status gs_design_score(gs_index *ix, gs_design *d, const char *alt
       /* the CSV rule with no cap on the off-targets, whatever the database is written as */
       GS_TRY(gs_score_device(ix, g, nb, d->k, d->P, sflags & GS_FLAG_PAM_AT_START, -1, &gs, d_off, d_hits, st, nullptr,
                              (float *)d->d_spec + lo));
+      if (d->rule_annot) { /* the hit lists are still the handle's: which of them touch a feature */
+        const gs_annot_own own{(const uint32_t *)d->d_chr + lo, (const uint32_t *)d->d_pos + lo, (const uint8_t *)d->d_sense + lo,
+                               (uint32_t *)d->d_fhits + lo, d->rule_distance};
+        const void *fo = nullptr, *ft = nullptr, *gc = nullptr;
+        GS_TRY(gs_annotate_device_own(ix, d->rule_annot, &gs, nb, d->k, d->P, mismatches, d_off, d_hits, st, &own, &fo, &ft, &gc));
+        hipLaunchKernelGGL(k_ds_feature_rule, dim3((unsigned)((nb + DS_BLOCK - 1) / DS_BLOCK)), dim3(DS_BLOCK), 0, st,
+                           (const uint32_t *)d->d_fhits + lo, nb, d->rule_max, (uint8_t *)d->d_elig + lo);
+      }
     }
     GS_HIP(hipStreamSynchronize(st));
     GS_HIP(hipGetLastError());
     d->scored = true;
     d->have_host = false;
+    d->have_fhits = d->rule_annot != nullptr;
     return GS_OK;
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;

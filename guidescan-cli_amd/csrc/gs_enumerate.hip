@@ -1747,7 +1747,7 @@ static bool recover_release_workspace(gs_index *ix, gs_status rc) {
   if (rc != GS_ERR_NOMEM) return false;
   (void)hipGetLastError();
   const size_t freed = ix->w_batch.release() + ix->w_big.release() + ix->w_tile.release() + ix->w_score.release() +
-                       ix->w_text.release() + ix->w_bgzf.release();
+                       ix->w_text.release() + ix->w_bgzf.release() + ix->w_annot.release();
   size_t redo_min = RELEASE_REDO_MIN;
   if (const char *e = gs_opt(ix, "GS_DBG_RELEASE_MIN")) redo_min = (size_t)strtoull(e, nullptr, 10); /* (tests: bytes) */
   if (freed <= redo_min) return false;

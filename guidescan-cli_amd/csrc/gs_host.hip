@@ -403,9 +403,13 @@ static gs_status enumerate_text(gs_index *ix, bool on_device, const void *guides
   const void *d_off = nullptr, *d_hits = nullptr, *d_text = nullptr;
   gs_result_view v;
   memset(&v, 0, sizeof v);
-  const uint32_t text_bits = GS_TEXT_SAM | GS_TEXT_COMPLETE | GS_TEXT_BAM | GS_TEXT_BGZF;
+  const uint32_t text_bits = GS_TEXT_SAM | GS_TEXT_COMPLETE | GS_TEXT_BAM | GS_TEXT_BGZF | GS_TEXT_FEATURES;
   const uint32_t tflags = flags & text_bits, sflags = flags & ~text_bits;
   if ((tflags & GS_TEXT_BAM) && (tflags & GS_TEXT_SAM)) return GS_ERR_ARG;
+  if ((tflags & GS_TEXT_FEATURES) && ((tflags & (GS_TEXT_SAM | GS_TEXT_BAM)) || !ix->annot)) { /* before the search */
+    gs_set_error("GS_TEXT_FEATURES goes with CSV text and an annotation attached to the handle (gs_index_set_annotation)");
+    return GS_ERR_ARG;
+  }
   if ((tflags & GS_TEXT_BGZF) && !(tflags & GS_TEXT_BAM)) return GS_ERR_ARG;
   /* BAM records carry the SAM line's specificity */
   const uint32_t score_flags = ((tflags & (GS_TEXT_SAM | GS_TEXT_BAM)) ? GS_TEXT_SAM : 0u) | (sflags & GS_FLAG_PAM_AT_START);

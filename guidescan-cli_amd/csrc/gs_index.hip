@@ -1068,5 +1068,6 @@ extern "C" gs_status gs_debug_workspace(gs_index *ix, uint64_t *out, uint32_t n_
   gs_ws_report(ix->w_score, out + 9);
   gs_ws_report(ix->w_text, out + 12);
   gs_ws_report(ix->w_bgzf, out + 15);
+  gs_ws_report(ix->w_annot, out + 18);
   return GS_OK;
 }

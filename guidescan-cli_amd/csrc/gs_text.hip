@@ -5,6 +5,7 @@
  * resolve_absolute (src/genomics/structures.cxx:7-52).  Host code only; no kernels.
  */
 #include "gs_common.h"
+#include "gs_annot_obj.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -97,6 +98,26 @@ struct decoded_hit {
   uint32_t rna_bulges = 0, dna_bulges = 0;
 };
 
+/* GS_TEXT_FEATURES: ",name;name" of the row printed at s on chromosome c, or ",NA" (gs_annot_scan.h) */
+void feature_tail(const gs_annot *an, const gs_genome_structure *gs, int c, int64_t s, size_t w, std::string &out) {
+  out += ',';
+  const size_t before = out.size();
+  gs_an_visit(an->h.table(), (uint32_t)c, (long long)s, (uint32_t)w, gs->chr_lengths[c], [&](uint32_t g) {
+    if (out.size() > before) out += ';';
+    out += an->group_names[g];
+  });
+  if (out.size() == before) out += "NA";
+}
+/* the flag's argument checks, shared by the entry points */
+gs_status features_args(const gs_genome_structure *gs, uint32_t flags, const gs_annot *an) {
+  if (!(flags & GS_TEXT_FEATURES)) return GS_OK;
+  if (!an || (flags & (GS_TEXT_SAM | GS_TEXT_BAM))) return GS_ERR_ARG;
+  if (gs->n_chr != an->chr_lengths.size()) return GS_ERR_ARG;
+  for (uint32_t c = 0; c < gs->n_chr; c++)
+    if (gs->chr_lengths[c] != an->chr_lengths[c]) return GS_ERR_ARG;
+  return GS_OK;
+}
+
 }  // namespace
 
 /* spec: the guide's specificity when the caller already has it (gs_score / gs_score_device:
@@ -104,7 +125,8 @@ struct decoded_hit {
 static gs_status format_decoded(const gs_genome_structure *gs, const gs_kmer *k,
                                 const std::vector<std::vector<decoded_hit>> &off, uint32_t mismatches,
                                 uint32_t flags, int64_t max_off_targets, char **out_text, size_t *out_len,
-                                const float *spec = nullptr) {
+                                const float *spec = nullptr, const gs_annot *an = nullptr) {
+  if (!(flags & GS_TEXT_FEATURES)) an = nullptr;
   const bool start = flags & GS_FLAG_PAM_AT_START;
   const bool sam = flags & GS_TEXT_SAM;
   const bool complete = flags & GS_TEXT_COMPLETE;
@@ -116,7 +138,7 @@ static gs_status format_decoded(const gs_genome_structure *gs, const gs_kmer *k,
     /* printer.hpp:245-300 */
     float cfd_sum = 0.0f;
     bool perfect = false, none = true;
-    std::vector<std::string> lines;
+    std::vector<std::string> lines, tails; /* tails: what follows the specificity (GS_TEXT_FEATURES) */
     for (uint32_t d = 0; d <= mismatches; d++) {
       for (int64_t i = 0; i < (int64_t)off[d].size(); i++) {
         none = false;
@@ -147,6 +169,10 @@ static gs_status format_decoded(const gs_genome_structure *gs, const gs_kmer *k,
           line += std::to_string(h.dna_bulges);
         }
         lines.push_back(std::move(line));
+        if (an) {
+          tails.emplace_back();
+          feature_tail(an, gs, c, s, (size_t)L + P, tails.back());
+        }
         if (!spec) cfd_sum += gs_calculate_cfd(k->sequence, h.match_sequence.c_str(), h.pam.c_str());
       }
     }
@@ -156,17 +182,18 @@ static gs_status format_decoded(const gs_genome_structure *gs, const gs_kmer *k,
       out += sequence;
       out += ",NA,NA,NA,0";
       if (complete) out += ",NA,NA,NA";
-      out += ",1.0\n";
+      out += an ? ",1.0,NA\n" : ",1.0\n";
     } else {
       float specificity = 0.0f;
       if (!perfect) cfd_sum += 1;
       if (cfd_sum > 0) specificity = 1 / cfd_sum;
       if (spec) specificity = *spec;
       const std::string sp = f2s(specificity);
-      for (const auto &l : lines) {
-        out += l;
+      for (size_t i = 0; i < lines.size(); i++) {
+        out += lines[i];
         out += ',';
         out += sp;
+        if (an) out += tails[i];
         out += '\n';
       }
     }
@@ -241,9 +268,10 @@ static gs_status format_decoded(const gs_genome_structure *gs, const gs_kmer *k,
 static gs_status format_guide_impl(const gs_genome_structure *gs, const gs_kmer *k,
                                    const gs_hit *hits, uint64_t n_hits, uint32_t mismatches,
                                    uint32_t flags, int64_t max_off_targets, char **out_text,
-                                   size_t *out_len, const float *spec) {
+                                   size_t *out_len, const float *spec, const gs_annot *an = nullptr) {
   if (!gs || !k || !k->id || !k->sequence || !k->pam || (n_hits && !hits) || !out_text)
     return GS_ERR_ARG;
+  GS_TRY(features_args(gs, flags, an));
   const uint32_t L = (uint32_t)strlen(k->sequence), P = (uint32_t)strlen(k->pam);
   /* split by distance; hits arrive in canonical order (distance ascending) */
   std::vector<std::vector<decoded_hit>> off(mismatches + 1);
@@ -262,22 +290,27 @@ static gs_status format_guide_impl(const gs_genome_structure *gs, const gs_kmer 
     dh.pam = dh.match_sequence.size() < 20 ? std::string() : dh.match_sequence.substr(20, 3);
     off[d].push_back(std::move(dh));
   }
-  return format_decoded(gs, k, off, mismatches, flags, max_off_targets, out_text, out_len, spec);
+  return format_decoded(gs, k, off, mismatches, flags, max_off_targets, out_text, out_len, spec, an);
 }
 
 extern "C" gs_status gs_format_guide(const gs_genome_structure *gs, const gs_kmer *k,
                                      const gs_hit *hits, uint64_t n_hits, uint32_t mismatches,
                                      uint32_t flags, int64_t max_off_targets, char **out_text,
                                      size_t *out_len) {
-  return format_guide_impl(gs, k, hits, n_hits, mismatches, flags, max_off_targets, out_text, out_len, nullptr);
+  return format_guide_impl(gs, k, hits, n_hits, mismatches, flags & ~GS_TEXT_FEATURES, max_off_targets, out_text, out_len, nullptr);
 }
 
 extern "C" gs_status gs_format_guide_scored(const gs_genome_structure *gs, const gs_kmer *k,
                                             const gs_hit *hits, uint64_t n_hits, uint32_t mismatches,
                                             uint32_t flags, int64_t max_off_targets, float specificity,
                                             char **out_text, size_t *out_len) {
-  return format_guide_impl(gs, k, hits, n_hits, mismatches, flags, max_off_targets, out_text, out_len,
+  return format_guide_impl(gs, k, hits, n_hits, mismatches, flags & ~GS_TEXT_FEATURES, max_off_targets, out_text, out_len,
                            &specificity);
+}
+extern "C" gs_status gs_format_guide_features(const gs_genome_structure *gs, const gs_kmer *k, const gs_hit *hits, uint64_t n_hits,
+                                              uint32_t mismatches, uint32_t flags, int64_t max_off_targets, float specificity,
+                                              const gs_annot *annot, char **out_text, size_t *out_len) {
+  return format_guide_impl(gs, k, hits, n_hits, mismatches, flags, max_off_targets, out_text, out_len, &specificity, annot);
 }
 
 /* ---- the CSV rows of many guides in one buffer: what the writer of `guidescan enumerate` calls.
@@ -321,7 +354,8 @@ struct outbuf {
 
 static gs_status format_csv_fast(const gs_genome_structure *gs, const uint64_t *chr_end /* prefix sums */,
                                  const gs_kmer *k, const gs_hit *hits, uint64_t n_hits, uint32_t mismatches,
-                                 uint32_t flags, int64_t max_off_targets, float spec, outbuf &o) {
+                                 uint32_t flags, int64_t max_off_targets, float spec, outbuf &o, const gs_annot *an,
+                                 std::string &tail) {
   const bool start = flags & GS_FLAG_PAM_AT_START, complete = flags & GS_TEXT_COMPLETE;
   const size_t L = strlen(k->sequence), P = strlen(k->pam), idl = strlen(k->id);
   if (L < 1 || 2 * L + 3 * P > 59) return GS_ERR_ARG;
@@ -334,7 +368,10 @@ static gs_status format_csv_fast(const gs_genome_structure *gs, const uint64_t *
     if (!start) o.put(k->pam, P);
     o.put(",NA,NA,NA,0", 11);
     if (complete) o.put(",NA,NA,NA", 9);
-    o.put(",1.0\n", 5);
+    if (an)
+      o.put(",1.0,NA\n", 8);
+    else
+      o.put(",1.0\n", 5);
     return GS_OK;
   }
   char sp[64];
@@ -421,17 +458,25 @@ static gs_status format_csv_fast(const gs_genome_structure *gs, const uint64_t *
     }
     o.ch(',');
     o.put(sp, (size_t)spl);
+    if (an) {
+      tail.clear();
+      feature_tail(an, gs, (int)lo, s, L + P, tail);
+      if (!o.need(tail.size() + 1)) return GS_ERR_NOMEM;
+      o.put(tail.data(), tail.size());
+    }
     o.ch('\n');
   }
   return GS_OK;
 }
 
-extern "C" gs_status gs_format_guides_scored(const gs_genome_structure *gs, const gs_kmer *kmers, uint64_t n,
-                                             const uint64_t *offsets, const gs_hit *hits, const float *specificity,
-                                             const uint8_t *skip, uint32_t mismatches, uint32_t flags,
-                                             int64_t max_off_targets, char **out_text, size_t *out_len) {
+static gs_status format_guides_impl(const gs_genome_structure *gs, const gs_kmer *kmers, uint64_t n, const uint64_t *offsets,
+                                    const gs_hit *hits, const float *specificity, const uint8_t *skip, uint32_t mismatches,
+                                    uint32_t flags, int64_t max_off_targets, const gs_annot *an, char **out_text, size_t *out_len) {
   if (!gs || (n && (!kmers || !offsets || !specificity)) || !out_text) return GS_ERR_ARG;
+  GS_TRY(features_args(gs, flags, an));
+  if (!(flags & GS_TEXT_FEATURES)) an = nullptr;
   try {
+    std::string tail;
     std::vector<uint64_t> chr_end(gs->n_chr + 1, 0);
     for (uint32_t i = 0; i < gs->n_chr; i++) chr_end[i + 1] = chr_end[i] + gs->chr_lengths[i];
     outbuf o;
@@ -456,7 +501,7 @@ extern "C" gs_status gs_format_guides_scored(const gs_genome_structure *gs, cons
         }
       } else {
         rc = format_csv_fast(gs, chr_end.data(), k, hits + b, e - b, mismatches, flags, max_off_targets,
-                             specificity[g], o);
+                             specificity[g], o, an, tail);
       }
       if (rc != GS_OK) {
         free(o.p);
@@ -476,6 +521,21 @@ extern "C" gs_status gs_format_guides_scored(const gs_genome_structure *gs, cons
   }
 }
 
+extern "C" gs_status gs_format_guides_scored(const gs_genome_structure *gs, const gs_kmer *kmers, uint64_t n,
+                                             const uint64_t *offsets, const gs_hit *hits, const float *specificity,
+                                             const uint8_t *skip, uint32_t mismatches, uint32_t flags,
+                                             int64_t max_off_targets, char **out_text, size_t *out_len) {
+  return format_guides_impl(gs, kmers, n, offsets, hits, specificity, skip, mismatches, flags & ~GS_TEXT_FEATURES, max_off_targets,
+                            nullptr, out_text, out_len);
+}
+extern "C" gs_status gs_format_guides_features(const gs_genome_structure *gs, const gs_kmer *kmers, uint64_t n,
+                                               const uint64_t *offsets, const gs_hit *hits, const float *specificity,
+                                               const uint8_t *skip, uint32_t mismatches, uint32_t flags,
+                                               int64_t max_off_targets, const gs_annot *annot, char **out_text, size_t *out_len) {
+  return format_guides_impl(gs, kmers, n, offsets, hits, specificity, skip, mismatches, flags, max_off_targets, annot, out_text,
+                            out_len);
+}
+
 extern "C" gs_status gs_decode_sequence_ex(const gs_hit_ex *hit, char *out) {
   if (!hit || !out || hit->seq_len > 32) return GS_ERR_ARG;
   memcpy(out, hit->seq, hit->seq_len);
@@ -483,12 +543,12 @@ extern "C" gs_status gs_decode_sequence_ex(const gs_hit_ex *hit, char *out) {
   return GS_OK;
 }
 
-extern "C" gs_status gs_format_guide_ex(const gs_genome_structure *gs, const gs_kmer *k,
-                                        const gs_hit_ex *hits, uint64_t n_hits, uint32_t mismatches,
-                                        uint32_t flags, int64_t max_off_targets, char **out_text,
-                                        size_t *out_len) {
+static gs_status format_guide_ex_impl(const gs_genome_structure *gs, const gs_kmer *k, const gs_hit_ex *hits, uint64_t n_hits,
+                                      uint32_t mismatches, uint32_t flags, int64_t max_off_targets, const gs_annot *an,
+                                      char **out_text, size_t *out_len) {
   if (!gs || !k || !k->id || !k->sequence || !k->pam || (n_hits && !hits) || !out_text)
     return GS_ERR_ARG;
+  GS_TRY(features_args(gs, flags, an));
   std::vector<std::vector<decoded_hit>> off(mismatches + 1);
   char buf[40];
   for (uint64_t h = 0; h < n_hits; h++) {
@@ -506,12 +566,24 @@ extern "C" gs_status gs_format_guide_ex(const gs_genome_structure *gs, const gs_
     dh.dna_bulges = hits[h].dna_bulges;
     off[dh.mismatches].push_back(std::move(dh));
   }
-  return format_decoded(gs, k, off, mismatches, flags, max_off_targets, out_text, out_len);
+  return format_decoded(gs, k, off, mismatches, flags, max_off_targets, out_text, out_len, nullptr, an);
+}
+extern "C" gs_status gs_format_guide_ex(const gs_genome_structure *gs, const gs_kmer *k,
+                                        const gs_hit_ex *hits, uint64_t n_hits, uint32_t mismatches,
+                                        uint32_t flags, int64_t max_off_targets, char **out_text,
+                                        size_t *out_len) {
+  return format_guide_ex_impl(gs, k, hits, n_hits, mismatches, flags & ~GS_TEXT_FEATURES, max_off_targets, nullptr, out_text, out_len);
+}
+extern "C" gs_status gs_format_guide_ex_features(const gs_genome_structure *gs, const gs_kmer *k, const gs_hit_ex *hits,
+                                                 uint64_t n_hits, uint32_t mismatches, uint32_t flags, int64_t max_off_targets,
+                                                 const gs_annot *annot, char **out_text, size_t *out_len) {
+  return format_guide_ex_impl(gs, k, hits, n_hits, mismatches, flags, max_off_targets, annot, out_text, out_len);
 }
 
 extern "C" gs_status gs_format_header(const gs_genome_structure *gs, uint32_t flags, char **out_text,
                                       size_t *out_len) {
   if (!gs || !out_text) return GS_ERR_ARG;
+  if ((flags & GS_TEXT_FEATURES) && (flags & (GS_TEXT_SAM | GS_TEXT_BAM))) return GS_ERR_ARG;
   std::string out;
   if (flags & GS_TEXT_SAM) { /* printer.hpp:173-179 */
     out += "@HD\tVN:1.0\tSO:unknown\n";
@@ -526,7 +598,7 @@ extern "C" gs_status gs_format_header(const gs_genome_structure *gs, uint32_t fl
   } else { /* printer.hpp:181-187 */
     out += "id,sequence,match_chrm,match_position,match_strand,match_distance";
     if (flags & GS_TEXT_COMPLETE) out += ",match_sequence,rna_bulges,dna_bulges";
-    out += ",specificity\n";
+    out += (flags & GS_TEXT_FEATURES) ? ",specificity,match_features\n" : ",specificity\n";
   }
   char *p = (char *)malloc(out.size() + 1);
   if (!p) return GS_ERR_NOMEM;

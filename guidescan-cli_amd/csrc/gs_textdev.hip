@@ -24,6 +24,8 @@
 #include "gs_device.h"
 #include "gs_bgzf_huff.h"
 #include "gs_scratch.h"
+#include "gs_resolve.h"
+#include "gs_annot_obj.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -60,6 +62,11 @@ struct tx_args {
   long long max_off, delim;
   uint32_t n, L, P, n_chr, m, start, sam, complete;
   uint32_t bam; /* with sam: the lines as BAM alignment blocks (tx_bam_row) */
+  /* GS_TEXT_FEATURES: what gs_annotate_device left for the same hit list (offsets from 0, by hit - off0), the group names */
+  const uint64_t *feat_off;
+  const uint32_t *feats, *gname_off;
+  const uint8_t *gnames;
+  uint32_t features;
 };
 
 /* ---- small pieces -------------------------------------------------------------------------------------------- */
@@ -108,46 +115,9 @@ __device__ __forceinline__ uint32_t tx_spec_q(uint32_t bits) {
   return (uint32_t)q;
 }
 
-struct tx_loc {
-  int c; /* chromosome, -1: dropped at a boundary */
-  long long s;
-  char st;
-};
-/* src/genomics/structures.cxx:7-52 by binary search over the prefix sums (as format_csv_fast restates it) */
-__device__ __forceinline__ tx_loc tx_resolve(const tx_args &a, long long pos) {
-  tx_loc r;
-  r.c = -1;
-  r.s = 0;
-  r.st = '+';
-  unsigned long long ab = (unsigned long long)pos;
-  if (pos < 0) {
-    ab = 0ull - ab;
-    r.st = '-';
-  }
-  if (a.n_chr == 0u || ab >= a.chr_cum[a.n_chr]) return r;
-  uint32_t lo = 0, hi = a.n_chr; /* first chromosome whose end exceeds ab */
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (ab < a.chr_cum[mid + 1u])
-      hi = mid;
-    else
-      lo = mid + 1u;
-  }
-  if (lo >= a.n_chr) return r;
-  const long long in_chr = (long long)(ab - a.chr_cum[lo]), len = (long long)(a.chr_cum[lo + 1u] - a.chr_cum[lo]);
-  long long s, e;
-  if (r.st == '+') {
-    e = in_chr + 1;
-    s = e - (long long)a.L - (long long)a.P + 1;
-  } else {
-    s = in_chr + 1;
-    e = s + (long long)a.L + (long long)a.P - 1;
-  }
-  if (s < 0 || e > len) return r; /* :46-48, s < 0 not s < 1 */
-  r.c = (int)lo;
-  r.s = s;
-  return r;
-}
+/* src/genomics/structures.cxx:7-52 by binary search over the prefix sums (gs_resolve.h: the annotation kernels share it) */
+typedef gs_loc tx_loc;
+__device__ __forceinline__ tx_loc tx_resolve(const tx_args &a, long long pos) { return gs_resolve_abs(a.chr_cum, a.n_chr, a.L, a.P, pos); }
 
 /* slots: guide g's own slot, then its hits */
 __device__ __forceinline__ uint64_t tx_slot_of(const tx_args &a, uint32_t g) { return a.offsets[g] - a.off0 + g; }
@@ -257,6 +227,22 @@ __device__ __forceinline__ void tx_chr_name(S &o, const tx_args &a, int c) {
   o.put(a.chr_names + b, a.chr_name_off[c + 1] - b);
 }
 
+/* GS_TEXT_FEATURES: the row's tail, ",name;name" or ",NA" (i: the hit's index from off0) */
+template <class S>
+__device__ __forceinline__ void tx_features(S &o, const tx_args &a, uint64_t i) {
+  o.ch(',');
+  const uint64_t b = a.feat_off[i], e = a.feat_off[i + 1u];
+  if (b == e) {
+    TX_LIT(o, "NA");
+    return;
+  }
+  for (uint64_t x = b; x < e; x++) {
+    if (x > b) o.ch(';');
+    const uint32_t g = a.feats[x], nb = a.gname_off[g];
+    o.put(a.gnames + nb, a.gname_off[g + 1u] - nb);
+  }
+}
+
 /* the guide's own slot: its NA row (printer.hpp:189-199), and the checks made once per guide */
 template <class S>
 __device__ __forceinline__ void tx_guide_row(S &o, const tx_args &a, uint32_t g, uint32_t &err) {
@@ -276,7 +262,10 @@ __device__ __forceinline__ void tx_guide_row(S &o, const tx_args &a, uint32_t g,
   tx_sequence(o, a, g);
   TX_LIT(o, ",NA,NA,NA,0");
   if (a.complete) TX_LIT(o, ",NA,NA,NA");
-  TX_LIT(o, ",1.0\n");
+  if (a.features)
+    TX_LIT(o, ",1.0,NA\n");
+  else
+    TX_LIT(o, ",1.0\n");
 }
 
 /* one CSV row (printer.hpp:245-300 as format_csv_fast restates it) */
@@ -340,6 +329,7 @@ __device__ __forceinline__ void tx_csv_row(S &o, const tx_args &a, uint32_t g, u
   }
   o.ch(',');
   tx_specificity(o, tx_spec_q(__float_as_uint(a.spec[g])));
+  if (a.features) tx_features(o, a, h - a.off0);
   o.ch('\n');
 }
 
@@ -686,10 +676,20 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
   ix->tx_n = 0;
   if ((flags & GS_TEXT_BAM) && (flags & GS_TEXT_SAM)) return GS_ERR_ARG;
   if ((flags & GS_TEXT_BGZF) && !(flags & GS_TEXT_BAM)) return GS_ERR_ARG;
+  const bool features = (flags & GS_TEXT_FEATURES) != 0;
+  if (features && (flags & (GS_TEXT_SAM | GS_TEXT_BAM))) return GS_ERR_ARG;
+  if (features && !ix->annot) {
+    gs_set_error("GS_TEXT_FEATURES without an annotation attached to the handle (gs_index_set_annotation)");
+    return GS_ERR_ARG;
+  }
   if (n == 0) return GS_OK;
   try {
     hipStream_t st = (hipStream_t)stream;
     GS_HIP(hipSetDevice(ix->device));
+    /* the features of every hit, left in the handle's annotation workspace: nothing below touches it */
+    const void *d_foff = nullptr, *d_feats = nullptr, *d_gcnt = nullptr;
+    if (features)
+      GS_TRY(gs_annotate_device_own(ix, ix->annot, gs, n, L, P, mismatches, d_offsets, d_hits, stream, nullptr, &d_foff, &d_feats, &d_gcnt));
     /* what the call uploads: id offsets and bytes, chromosome prefix sums and names, senses, skip */
     const uint64_t id0 = up ? id_offsets[0] : 0, id_bytes = up ? id_offsets[n] - id0 : 0;
     std::vector<uint32_t> name_off(gs->n_chr + 1, 0);
@@ -791,6 +791,13 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
     a.sam = sam ? 1u : 0u;
     a.bam = bam ? 1u : 0u;
     a.complete = complete ? 1u : 0u;
+    if (features) {
+      a.features = 1u;
+      a.feat_off = (const uint64_t *)d_foff;
+      a.feats = (const uint32_t *)d_feats;
+      a.gname_off = ix->annot->d_name_off;
+      a.gnames = ix->annot->d_names;
+    }
 
     const uint32_t cus = (uint32_t)gs_num_cus(ix->device);
     const uint32_t grid = std::max(1u, std::min((n_tiles + TX_WAVES - 1) / TX_WAVES, cus * 32u));

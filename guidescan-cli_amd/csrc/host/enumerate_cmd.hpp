@@ -64,7 +64,12 @@ struct options {
   std::string regions;
   long long per_region = 0; /* 0: not given */
   float min_spec = -1.0f;   /* < 0: not given */
-  bool selects() const { return per_region > 0 || min_spec >= 0.0f; }
+  /* --annotate BED: the CSV's match_features column, the groups of the file that each printed off-target touches
+   * (gs_annot_*); --max-feature-hits K [--feature-distance D] (with --regions): a candidate with more than K off-targets
+   * within D mismatches (default: -m) inside a feature is not eligible */
+  std::string annotate;
+  long long max_feature_hits = -1, feature_distance = -1; /* -1: not given */
+  bool selects() const { return per_region > 0 || min_spec >= 0.0f || max_feature_hits >= 0; }
 };
 
 /* the command line into `o`, validated.  0: go on; otherwise the exit status */
@@ -124,6 +129,17 @@ inline int parse_options(int argc, char **argv, int (*usage)(), options &o) {
         return 2;
       }
     }
+    else if (a == "--annotate") o.annotate = need("--annotate");
+    else if (a == "--max-feature-hits" || a == "--feature-distance") {
+      const char *v = need(a.c_str());
+      char *end = nullptr;
+      const long long k = strtoll(v, &end, 10);
+      if (end == v || *end || k < 0 || k > 0xFFFFFFFFll) {
+        std::cerr << "error: " << a << " " << v << ": a number, 0 or more\n";
+        return 2;
+      }
+      (a == "--max-feature-hits" ? o.max_feature_hits : o.feature_distance) = k;
+    }
     else if (!a.empty() && a[0] != '-' && o.prefix.empty()) o.prefix = a;
     else return usage();
   }
@@ -147,9 +163,21 @@ inline int parse_options(int argc, char **argv, int (*usage)(), options &o) {
     std::cerr << "error: --regions restricts the scan of --all-candidates; with -f the kmers file says what the guides are\n";
     return usage();
   }
-  if (o.selects() && o.regions.empty()) {
+  if ((o.per_region > 0 || o.min_spec >= 0.0f) && o.regions.empty()) {
     std::cerr << "error: --per-region and --min-specificity select within the groups of --regions\n";
     return usage();
+  }
+  if (o.max_feature_hits >= 0 && (o.regions.empty() || o.annotate.empty())) {
+    std::cerr << "error: --max-feature-hits selects among the candidates of --regions by the features of --annotate: give both\n";
+    return usage();
+  }
+  if (o.feature_distance >= 0 && o.max_feature_hits < 0) {
+    std::cerr << "error: --feature-distance is the distance --max-feature-hits counts within\n";
+    return usage();
+  }
+  if (!o.annotate.empty() && o.format != "csv") {
+    std::cerr << "error: --annotate adds a column to the CSV database; --format " << o.format << " has none\n";
+    return 2;
   }
   if ((o.format != "csv" && o.format != "sam" && o.format != "bam") || (o.mode != "succinct" && o.mode != "complete")) return usage();
   if (o.gpus < 1 || o.mismatches < 0 || o.rna < 0 || o.dna < 0) return usage();
@@ -279,6 +307,7 @@ struct enumerate_job {
   std::mutex tally_mtx;   /* the device threads count under it: */
   size_t enc_device = 0;  /* batches the device encoded; every other batch went to the host encoders */
   size_t bgzf_device = 0; /* batches the device compressed */
+  const gs_annot *annot = nullptr; /* --annotate: what the host encoders look rows up in (tflags has GS_TEXT_FEATURES) */
   uint32_t text_flags() const { return bgzf_gpu ? (tflags & ~GS_TEXT_SAM) | GS_TEXT_BAM | GS_TEXT_BGZF : tflags; }
 };
 
@@ -367,9 +396,9 @@ inline gs_status format_range(const enumerate_job &job, const batch &b, const gs
       const kmer_row &k = b.rows[g];
       ck[g - lo] = gs_kmer{k.id.c_str(), k.sequence.c_str(), k.pam.c_str(), k.sense == "+" ? 1 : 0};
     }
-    const gs_status rc = gs_format_guides_scored(&job.cgs, ck.data(), hi - lo, v.guide_offsets + lo, v.hits, b.spec.data() + lo,
-                                                 b.skip.empty() ? nullptr : (const uint8_t *)b.skip.data() + lo, job.mismatches,
-                                                 job.tflags | job.sflags, job.max_off, &part.p, &part.n);
+    const gs_status rc = gs_format_guides_features(&job.cgs, ck.data(), hi - lo, v.guide_offsets + lo, v.hits, b.spec.data() + lo,
+                                                   b.skip.empty() ? nullptr : (const uint8_t *)b.skip.data() + lo, job.mismatches,
+                                                   job.tflags | job.sflags, job.max_off, job.annot, &part.p, &part.n);
     if (rc != GS_OK) return rc;
     return job.bam && !part_to_bam(job, part) ? GS_ERR_FORMAT : GS_OK;
   }
@@ -383,12 +412,12 @@ inline gs_status format_range(const enumerate_job &job, const batch &b, const gs
     const uint32_t gx = b.gen_of.empty() ? ~0u : b.gen_of[g];
     if (gx == ~0u) {
       const uint64_t s0 = v.guide_offsets[g], s1 = v.guide_offsets[g + 1];
-      r = gs_format_guide_scored(&job.cgs, &ck, v.hits + s0, s1 - s0, job.mismatches, job.tflags | job.sflags,
-                                 job.max_off, b.spec[g], &tx, &tl);
+      r = gs_format_guide_features(&job.cgs, &ck, v.hits + s0, s1 - s0, job.mismatches, job.tflags | job.sflags,
+                                   job.max_off, b.spec[g], job.annot, &tx, &tl);
     } else {
       const uint64_t s0 = xoff[gx], s1 = xoff[gx + 1];
-      r = gs_format_guide_ex(&job.cgs, &ck, xhits + s0, s1 - s0, job.mismatches, job.tflags | job.sflags,
-                             job.max_off, &tx, &tl);
+      r = gs_format_guide_ex_features(&job.cgs, &ck, xhits + s0, s1 - s0, job.mismatches, job.tflags | job.sflags,
+                                      job.max_off, job.annot, &tx, &tl);
     }
     if (r != GS_OK) return r;
     part.s.append(tx, tl);
@@ -741,41 +770,87 @@ inline bool read_guides_device(const options &o, enumerate_job &job, candidate_s
 }
 
 /* --regions: the BED file against PREFIX.gs; the parser's message with its line number */
-inline bool read_regions(const std::string &path, const genome_structure &gs, const std::string &prefix, candidate_set &cand) {
+inline bool read_bed(const std::string &path, const genome_structure &gs, const std::string &prefix, const std::string &what,
+                     gs_regions **out) {
   std::vector<const char *> names;
   for (auto &n : gs.names) names.push_back(n.c_str());
   const gs_genome_structure cgs{names.data(), gs.lengths.data(), (uint32_t)names.size()};
   gs_regions_report rep;
-  const gs_status rc = gs_regions_parse_file(path.c_str(), &cgs, prefix.c_str(), &cand.regions, &rep);
+  const gs_status rc = gs_regions_parse_file(path.c_str(), &cgs, prefix.c_str(), out, &rep);
   if (rc == GS_OK) return true;
-  if (rc == GS_ERR_FORMAT && rep.bad_text)
-    std::cerr << "error: " << rep.bad_text << " (" << path << ")\n";
-  else if (rc == GS_ERR_IO)
-    std::cerr << "error: cannot read the regions file " << path << "\n";
+  if (rc == GS_ERR_FORMAT && rep.bad_text) { /* the parser says "regions line N: ..." / "regions file: ..." */
+    const std::string msg = rep.bad_text;
+    std::cerr << "error: " << (msg.compare(0, 7, "regions") == 0 ? what + msg.substr(7) : msg) << " (" << path << ")\n";
+  } else if (rc == GS_ERR_IO)
+    std::cerr << "error: cannot read the " << what << " file " << path << "\n";
   else
-    std::cerr << "error: regions file " << path << ": " << gs_status_string(rc) << "\n";
+    std::cerr << "error: " << what << " file " << path << ": " << gs_status_string(rc) << "\n";
   gs_free(rep.bad_text);
   return false;
+}
+inline bool read_regions(const std::string &path, const genome_structure &gs, const std::string &prefix, candidate_set &cand) {
+  return read_bed(path, gs, prefix, "regions", &cand.regions);
+}
+
+/* --annotate: the BED file under the rules and messages of --regions, then one lookup table per device, attached to its
+ * index; the host encoders read the first one's host copy.  Declared before the indexes: freed after they are closed */
+struct annotation_set {
+  gs_regions *bed = nullptr;
+  std::vector<gs_annot *> an;
+  ~annotation_set() {
+    for (gs_annot *a : an) gs_annot_free(a);
+    if (bed) gs_regions_free(bed);
+  }
+};
+inline bool read_annotation(const options &o, const genome_structure &gs, annotation_set &as) {
+  return read_bed(o.annotate, gs, "", "annotation", &as.bed);
+}
+inline bool attach_annotation(const options &o, const std::vector<gs_index *> &ix, annotation_set &as, enumerate_job &job) {
+  const int dev_step = getenv("GS_CLI_SAME_DEVICE") ? 0 : 1; /* as build_indexes places the indexes */
+  for (size_t d = 0; d < ix.size(); d++) {
+    gs_annot *a = nullptr;
+    gs_status rc = gs_annot_build(as.bed, o.device + (int)d * dev_step, &a);
+    if (rc == GS_OK) {
+      as.an.push_back(a);
+      rc = gs_index_set_annotation(ix[d], a);
+    }
+    if (rc != GS_OK) {
+      std::cerr << "error: annotation file " << o.annotate << ": " << gs_status_string(rc) << "\n";
+      return false;
+    }
+  }
+  uint64_t groups = 0, segments = 0, entries = 0;
+  gs_annot_info(as.an[0], &groups, &segments, &entries);
+  std::cout << "Annotation: " << groups << " group(s), " << segments << " segment(s), " << entries << " table entries on "
+            << ix.size() << " device(s)\n";
+  job.annot = as.an[0];
+  return true;
 }
 
 /* --regions: the records scored on the first device where an option asks for it (ix; the search options are the
  * command's own -m, -a, --start, and -t marks what the counting pass would drop as not eligible), ordered, cut to the
  * best of each group, and handed to the candidate set as the guides of the command */
 inline bool select_design(const options &o, enumerate_job &job, candidate_set &cand, gs_index *ix) {
+  if (ix && o.max_feature_hits >= 0 &&
+      gs_design_set_feature_rule(cand.design, job.annot, (uint32_t)(o.feature_distance >= 0 ? o.feature_distance : o.mismatches),
+                                 (uint32_t)o.max_feature_hits) != GS_OK) {
+    std::cerr << "error: --max-feature-hits: " << gs_status_string(GS_ERR_ARG) << "\n";
+    return false;
+  }
   const auto ts = std::chrono::steady_clock::now();
   gs_status rc = GS_OK;
   if (ix) {
     std::string alts;
     for (auto &a : o.alt_pams) {
       if (a.size() != cand.P) {
-        std::cerr << "error: --regions with --per-region or --min-specificity scores on the fast path: alt PAM " << a
+        std::cerr << "error: --regions with --per-region, --min-specificity or --max-feature-hits scores on the fast path: alt PAM " << a
                   << " is not of the PAM's length\n";
         return false;
       }
       alts += a;
     }
     if (o.rna > 0 || o.dna > 0 || o.mismatches > 7 || o.threshold > 7) {
-      std::cerr << "error: --regions with --per-region or --min-specificity scores on the fast path: no bulges, at most 7 mismatches\n";
+      std::cerr << "error: --regions with --per-region, --min-specificity or --max-feature-hits scores on the fast path: no bulges, at most 7 mismatches\n";
       return false;
     }
     uint64_t n_rec = 0, glen = 0;
@@ -785,7 +860,7 @@ inline bool select_design(const options &o, enumerate_job &job, candidate_set &c
     rc = gs_design_score(ix, cand.design, alts.data(), (uint32_t)o.alt_pams.size(), (uint32_t)o.mismatches, flags,
                          o.threshold > 0 ? o.threshold : -1, o.batch_size, nullptr);
     if (rc == GS_ERR_UNSUPPORTED) {
-      std::cerr << "error: --regions with --per-region or --min-specificity scores on the fast path, which does not take this job: "
+      std::cerr << "error: --regions with --per-region, --min-specificity or --max-feature-hits scores on the fast path, which does not take this job: "
                 << gs_status_string(rc) << "\n";
       return false;
     }
@@ -936,7 +1011,8 @@ inline bool build_indexes(const options &o, const std::string &text, bool from_s
 inline void derive_job(const options &o, size_t n_guides, enumerate_job &job) {
   for (auto &n : job.gs.names) job.names.push_back(n.c_str());
   job.cgs = gs_genome_structure{job.names.data(), job.gs.lengths.data(), (uint32_t)job.names.size()};
-  job.tflags = (o.format != "csv" ? GS_TEXT_SAM : 0u) | (o.mode == "complete" ? GS_TEXT_COMPLETE : 0u);
+  job.tflags = (o.format != "csv" ? GS_TEXT_SAM : 0u) | (o.mode == "complete" ? GS_TEXT_COMPLETE : 0u) |
+               (job.annot ? GS_TEXT_FEATURES : 0u);
   job.bam = o.format == "bam";
   job.encoder_gpu = o.encoder == "gpu";
   job.bgzf_gpu = o.bgzf == "gpu";
@@ -1062,12 +1138,15 @@ inline int run(int argc, char **argv, int (*usage)()) {
   std::string text;
   bool from_sdsl = false;
   if (!load_genome(o, job.gs, text, from_sdsl)) return 1;
+  annotation_set annot;
+  if (!o.annotate.empty() && !read_annotation(o, job.gs, annot)) return 1;
   candidate_set cand;
   if (!(o.all_candidates ? scan_candidates(o, text, job, cand) : o.kmers == "gpu" ? read_guides_device(o, job, cand) : read_guides(o, job)))
     return 1;
   cli::index_set idx((size_t)o.gpus);
   if (!build_indexes(o, text, from_sdsl, idx)) return 1;
   text = std::string();
+  if (annot.bed && !attach_annotation(o, idx.ix, annot, job)) return 1;
   if (cand.design && !select_design(o, job, cand, idx.ix[0])) return 1; /* the score phase: on the first device */
   const size_t n_guides = job.cand ? (size_t)cand.n : job.kmers.size();
   derive_job(o, n_guides, job);

@@ -41,6 +41,12 @@
  *       off-targets, from a search with the command's own -m, -a and --start, and with -t a guide the threshold would
  *       drop is not eligible.  That score phase runs on the first device only, on the fast path (2L + 3P <= 59, alt
  *       PAMs of the PAM's length, no bulges).  A group left without a guide writes nothing; --verbose counts them.
+ *       --annotate BED (CSV only, any guide source, both encoders, any number of devices): every row gets a last column,
+ *       match_features, with the names of the BED file's groups that the printed off-target overlaps (its footprint
+ *       [match_position - 1, match_position - 1 + L + P) clipped to the chromosome; gs_annot_scan.h), joined by ';', or NA.
+ *       The file follows the rules of --regions.  --max-feature-hits K [--feature-distance D] (with --regions): the score
+ *       phase also counts, per candidate, the off-targets within D mismatches (default: -m) that have a feature, the
+ *       candidate's own site left out; more than K and the candidate is not eligible.
  *       With -t and neither selection option there is no score phase: the pipeline's own threshold pass drops the guides.
  *       -f KMERS.csv --kmers gpu: the kmers file is parsed on the first device (gs_kmers_parse_file, the rules of
  *       cli::read_kmers) and the command goes on as --all-candidates does from its scan: sequences, PAMs, ids and
@@ -164,6 +170,10 @@ int usage() {
                "                 --regions: the guides are the candidates inside the BED file's intervals, one per group of\n"
                "                 intervals they lie in; --per-region N: the N most specific of each group; --min-specificity S:\n"
                "                 those of specificity >= S.  That score phase uses the first device only.\n"
+               "                 [--annotate BED [--max-feature-hits K [--feature-distance D]]]\n"
+               "                 --annotate (CSV only): a match_features column, the groups of the BED file that each printed\n"
+               "                 off-target overlaps, joined by ';', or NA.  --max-feature-hits K (with --regions): a candidate\n"
+               "                 with more than K off-targets within D mismatches (default: -m) inside a feature is not eligible\n"
                "       guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--verbose]\n"
                "                 [--bgzf host|gpu] [--fasta host|gpu] DATABASE GENOME.fa\n"
                "                 --bgzf gpu (a BAM database only): the file is inflated and split into records on the device.\n"

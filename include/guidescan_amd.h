@@ -325,8 +325,8 @@ gs_status gs_debug_resident(gs_index *ix, uint64_t out[4]);
 /* The workspace buffers (what handles and decoders grow on demand and keep from call to call, and what gs_bgzf_inflate
  * holds for one call) alive in the process: [0] allocations, [1] their bytes.  Tests only. */
 gs_status gs_debug_buffers_live(uint64_t out[2]);
-/* The handle's per-batch workspace, three words per group, n_groups = 6 groups in the order batch pipeline, device-wide
- * ordering, tile ordering, score, text, BGZF: buffers held, bytes held, and the bytes of those that an out-of-memory
+/* The handle's per-batch workspace, three words per group, n_groups = 7 groups in the order batch pipeline, device-wide
+ * ordering, tile ordering, score, text, BGZF, annotation: buffers held, bytes held, and the bytes of those that an out-of-memory
  * recovery releases.  Tests only. */
 gs_status gs_debug_workspace(gs_index *ix, uint64_t *out, uint32_t n_groups);
 /* The rows under `key` (X symbols << 2 |R| | R symbols, both in consumption order) in the spaced table of a PAM-pair table
@@ -831,6 +831,92 @@ gs_status gs_debug_design_host(const gs_regions *regions, uint32_t n_parts, cons
                                const float *const *specificity, const uint8_t *const *eligible, const char *pam, uint32_t k,
                                const char *prefix, uint32_t per_region, float min_specificity, gs_kmers **out, char **rows,
                                uint64_t *rows_len);
+
+/* ---- off-targets annotated with the features of a BED file ------------------------------------------------------------- */
+/* The reference has no counterpart for anything in this section: its users join the CSV against a BED file in a script.  The
+ * rule, stated once (gs_annot_scan.h): a printed row whose match_position is s (as resolve_absolute returns it) occupies
+ * the forward-strand bases [s - 1, s - 1 + L + P) of match_chrm, clipped to [0, chromosome length) - the reference prints
+ * rows with s == 0 - with the guide's own L and P for every row.  The row has feature g iff that footprint shares a base
+ * with an interval of group g on the chromosome (overlap, not the containment of the regions section).  A row's features
+ * are distinct and ascend by group number, the order of first appearance in the file.  A hit that resolve_absolute drops has
+ * no row, no features and is counted nowhere. */
+
+typedef struct gs_annot gs_annot;
+
+/* the name of group g of a parsed BED file (no counterpart in the reference); the string is the object's */
+gs_status gs_regions_group_name(const gs_regions *regions, uint64_t g, const char **name);
+/* The lookup table of a parsed BED file (no counterpart in the reference): per chromosome the sorted distinct interval ends
+ * cut it into elementary segments, each with the ascending list of the groups over it (CSR), and the group names as one
+ * blob; both are uploaded to `device` (-1: host only, for the host encoders and gs_debug_annotate_host) and kept on the host.
+ * The object is independent of `regions` afterwards.  GS_ERR_FORMAT, the message naming the group: a group name with ';',
+ * which would break the joined column.  GS_ERR_ARG: a table of more than 2^31 entries (the sum of the segments' depths),
+ * refused before it is allocated. */
+gs_status gs_annot_build(const gs_regions *regions, int device, gs_annot **out);
+/* groups, elementary segments and table entries (no counterpart in the reference); any pointer may be NULL */
+gs_status gs_annot_info(const gs_annot *annot, uint64_t *n_groups, uint64_t *n_segments, uint64_t *n_entries);
+/* (no counterpart in the reference) a handle the annotation is attached to must be detached first */
+void gs_annot_free(gs_annot *annot);
+/* the entry cap of gs_annot_build (no counterpart in the reference): set != 0 sets it (at most 2^31); -> the cap.  For tests */
+uint64_t gs_debug_annot_entry_cap(uint64_t set);
+
+/* The features of every hit of a CSR hit list, in HBM (no counterpart in the reference): one lane per hit, a count pass, a
+ * scan, an emit pass.  d_offsets, d_hits: the layout gs_score_device takes; d_offsets[0] need not be 0.  `gs` must have the
+ * chromosome lengths the BED file was parsed against.  With n_hits = d_offsets[n] - d_offsets[0], hit i being
+ * d_hits[d_offsets[0] + i]:
+ *   *d_feat_offsets : uint64[n_hits + 1], from 0
+ *   *d_feats        : uint32 group numbers, hit i's at [feat_offsets[i], feat_offsets[i + 1])
+ *   *d_guide_counts : uint32[n * (mismatches + 1)]: the hits of guide g at distance d that have a row and at least one
+ *                     feature, at [g * (mismatches + 1) + d]; whatever --max-off-targets is
+ * all owned by the handle and valid until the next call on it.  GS_ERR_ARG: a hit at a distance beyond `mismatches`, an
+ * annotation of another device. */
+gs_status gs_annotate_device(gs_index *ix, const gs_annot *annot, const gs_genome_structure *gs, uint64_t n, uint32_t L,
+                             uint32_t P, uint32_t mismatches, const void *d_offsets, const void *d_hits, void *stream,
+                             const void **d_feat_offsets, const void **d_feats, const void **d_guide_counts);
+/* The same with host arrays in and out, the copies made inside (no counterpart in the reference): feat_offsets
+ * (n_hits + 1) and guide_counts (n * (mismatches + 1)) are the caller's, *feats is malloc'ed (*n_feats entries): release
+ * with gs_free. */
+gs_status gs_annotate(gs_index *ix, const gs_annot *annot, const gs_genome_structure *gs, uint64_t n, uint32_t L, uint32_t P,
+                      uint32_t mismatches, const uint64_t *offsets, const gs_hit *hits, uint64_t *feat_offsets, uint32_t **feats,
+                      uint64_t *n_feats, uint32_t *guide_counts);
+/* Host only: the same results through gs_annot_scan.h with no device (no counterpart in the reference) */
+gs_status gs_debug_annotate_host(const gs_annot *annot, const gs_genome_structure *gs, uint64_t n, uint32_t L, uint32_t P,
+                                 uint32_t mismatches, const uint64_t *offsets, const gs_hit *hits, uint64_t *feat_offsets,
+                                 uint32_t **feats, uint64_t *n_feats, uint32_t *guide_counts);
+
+/* The selection rule for guides for regions (no counterpart in the reference), set before gs_design_score: the score phase
+ * then also runs gs_annotate_device on each batch and stores, per record, the number of off-target hits at distance <=
+ * `distance` that have a feature of `annot`.  The record's own site - the distance-0 hit whose resolved chromosome, position
+ * and strand equal the record's chromosome, position and sense - does not count.  A record with more than max_hits is
+ * not eligible, exactly as one a --threshold drops.  annot NULL takes the rule off; without a rule gs_design_score is
+ * unchanged.  The annotation must outlive the score phase. */
+gs_status gs_design_set_feature_rule(gs_design *design, const gs_annot *annot, uint32_t distance, uint32_t max_hits);
+/* those counts of the last gs_design_score as uint32[n] on the host, owned by the design (no counterpart in the
+ * reference); GS_ERR_ARG when that score phase ran without a rule */
+gs_status gs_design_get_feature_hits(gs_design *design, const void **counts);
+
+/* The column (no counterpart in the reference).  GS_TEXT_FEATURES: the CSV header ends in ",match_features" and every CSV
+ * row ends in ',' and the names of the row's features joined by ';', or "NA" if it has none; the `NA` row of a guide without
+ * hits ends in ",NA" too.  Both modes.  Together with GS_TEXT_SAM or GS_TEXT_BAM: GS_ERR_ARG, in every entry point below
+ * and in gs_format_header.  The entry points that existed before the flag ignore it: their bytes do not change. */
+#define GS_TEXT_FEATURES 0x4000u
+/* Attaches an annotation (built for the handle's device) to the handle, NULL detaches it (no counterpart in the reference);
+ * the annotation stays the caller's and must outlive its attachment.  With GS_TEXT_FEATURES in their flags, gs_format_device,
+ * gs_format_device_ids, gs_enumerate_text and gs_enumerate_text_device run gs_annotate_device between scoring and formatting
+ * and append the column on the device; the flag without an attached annotation is GS_ERR_ARG. */
+gs_status gs_index_set_annotation(gs_index *ix, const gs_annot *annot);
+/* The host encoders' twins (no counterpart in the reference): gs_format_guides_scored, gs_format_guide_scored and
+ * gs_format_guide_ex with the rows looked up on the CPU through gs_annot_scan.h when GS_TEXT_FEATURES is set (then `annot`
+ * is required); without the flag, the bytes of the entry point each is the twin of. */
+gs_status gs_format_guides_features(const gs_genome_structure *gs, const gs_kmer *kmers, uint64_t n, const uint64_t *offsets,
+                                    const gs_hit *hits, const float *specificity, const uint8_t *skip, uint32_t mismatches,
+                                    uint32_t flags, int64_t max_off_targets, const gs_annot *annot, char **out_text,
+                                    size_t *out_len);
+gs_status gs_format_guide_features(const gs_genome_structure *gs, const gs_kmer *k, const gs_hit *hits, uint64_t n_hits,
+                                   uint32_t mismatches, uint32_t flags, int64_t max_off_targets, float specificity,
+                                   const gs_annot *annot, char **out_text, size_t *out_len);
+gs_status gs_format_guide_ex_features(const gs_genome_structure *gs, const gs_kmer *k, const gs_hit_ex *hits, uint64_t n_hits,
+                                      uint32_t mismatches, uint32_t flags, int64_t max_off_targets, const gs_annot *annot,
+                                      char **out_text, size_t *out_len);
 
 /* ---- SAM/BAM databases back to CSV on the device (scripts/decode_database.py) --------------------------------- */
 
