@@ -401,7 +401,7 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_kmers_concat", "gs_decoder_open", "gs_decoder_close", "gs_decode_records", "gs_decode_records_device",
            "gs_decode_sam", "gs_debug_repr_doubles", "gs_debug_decode_tables",
            "gs_index_last_spaced", "gs_debug_seed_recipes_a8", "gs_debug_spaced_rows", "gs_debug_resident",
-           "gs_debug_buffers_live", "gs_debug_workspace",
+           "gs_debug_buffers_live", "gs_debug_workspace", "gs_debug_index_layout", "gs_debug_index_array",
            "gs_debug_seed_probes", "gs_debug_seed_path", "gs_debug_rot_index",
            "gs_debug_bulge_last", "gs_debug_bulge_seeds", "gs_debug_bulge_verify",
            "gs_bgzf_compress_device", "gs_bgzf_compress", "gs_debug_huffman_lengths", "gs_debug_sp_float",
@@ -2033,6 +2033,43 @@ class GenomeIndex:
         out = (C.c_uint64 * 4)()
         _check(L_.gs_debug_resident(self._h, out))
         return dict(zip(("strand_arrays", "strand_bytes", "pairtab_arrays", "pairtab_bytes"), (int(x) for x in out)))
+
+    STRAND_LAYOUT = ("n", "blocks", "k", "mask_off", "n_exc", "nruns", "C0", "C1", "C2", "C3", "CN", "has_n", "rot_first",
+                     "rot_copies", "xr_entries")
+    SLOT_LAYOUT = ("valid", "v_rem", "code", "rot_first", "rot_copies", "n_slots", "deep", "deep_P", "deep_kb", "spaced", "sp_x",
+                   "sp_g", "sp_rem", "sp_rows", "d", "k")
+    # element types of the arrays gs_debug_index_array names (uint4 / uint2 entries come back as rows of words)
+    STRAND_ARRAYS = dict(blocks=("<u4", 16), sa=("<u4", 1), ptab=("<u4", 4), ptab_rot=("<u4", 4), ctx=("<u4", 1), ctx16=("<u2", 1),
+                         isa=("<u4", 1), exc_row=("<u4", 1), exc_sym=("<u8", 1), run_start=("<u4", 1), run_cum=("<u4", 1),
+                         xr_seg=("<u4", 2), xr_start=("<u4", 1), xr_cum=("<u4", 1), C256=("<u4", 1))
+    SLOT_ARRAYS = dict(tab=("<u4", 2), rot=("<u4", 2), c16=("<u2", 1), ctx=("<u4", 1), rowid=("<u4", 1), deep=("<u4", 4),
+                       sp_off=("<u4", 1), sp_rows=("<u4", 2))
+
+    def debug_layout(self, strand, slot=-1):
+        """the scalars that size and explain the index's device arrays (gs_debug_index_layout): a strand's, or a PAM-pair
+        table slot's as `strand` holds it.  Tests only."""
+        L_ = lib()
+        L_.gs_debug_index_layout.restype = C.c_int
+        L_.gs_debug_index_layout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        out = (C.c_uint64 * 32)()
+        _check(L_.gs_debug_index_layout(self._h, slot, strand, out))
+        return dict(zip(self.STRAND_LAYOUT if slot < 0 else self.SLOT_LAYOUT, (int(x) for x in out)))
+
+    def debug_array(self, strand, which, slot=-1):
+        """one named device array of a strand or a slot as a numpy array, or None when the handle does not hold it
+        (gs_debug_index_array).  Tests only."""
+        L_ = lib()
+        L_.gs_debug_index_array.restype = C.c_int
+        L_.gs_debug_index_array.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        dtype, width = (self.STRAND_ARRAYS if slot < 0 else self.SLOT_ARRAYS)[which]
+        total = C.c_uint64()
+        _check(L_.gs_debug_index_array(self._h, slot, strand, which.encode(), 0, None, 0, C.byref(total)))
+        if not total.value:
+            return None
+        out = np.empty(int(total.value), dtype=np.uint8)
+        _check(L_.gs_debug_index_array(self._h, slot, strand, which.encode(), 0, out.ctypes.data, out.nbytes, C.byref(total)))
+        a = out.view(dtype)
+        return a.reshape(-1, width) if width > 1 else a
 
     def workspace(self):
         """per group of the handle's workspace (WORKSPACE_GROUPS): buffers held, bytes held, bytes an out-of-memory

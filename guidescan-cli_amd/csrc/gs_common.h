@@ -73,7 +73,8 @@ struct gs_strand_dev {
    * start) within the 16 symbols preceding its suffix, so it must take the Occ walk;
    * mask (64 bits in z, w): four 16-bit sets; bit 16j + v: some row of the interval is preceded by
    * the symbol pair v (two symbols, 2 bits each, nearest first) at distances mask_off[j],
-   * mask_off[j]+1 (0 = the symbol right before the suffix).  The offsets are 0, 2, 4 and - so that
+   * mask_off[j]+1 (0 = the symbol right before the suffix); a symbol outside A,C,G,T and a position before the text start
+   * read as A there, as in ctx[] (surplus bits cost time, never a hit).  The offsets are 0, 2, 4 and - so that
    * for 20-mers with a 3-symbol PAM whose first symbol is a wildcard the fourth pair is the PAM's two
    * fixed symbols - 21-k (7 at k = 14); any offsets are correct, they only set the filter's power.  A site with at
    * most b substitutions among the symbols a seed still has to match leaves at least (pairs - b)
@@ -281,6 +282,7 @@ struct gs_strand {
   uint32_t rot_plan_first = 31, rot_plan_n = 0, rot_k = 0;
   uint64_t n = 0;
   uint64_t C_acgtn[5] = {0, 0, 0, 0, 0};
+  uint64_t xr_entries = 0; /* entries of xr_start / xr_cum: the runs and one closing entry per symbol that has any */
 };
 
 /* a maximal run of 'N' bytes in the forward text with the bytes around it (host side; used per
@@ -420,6 +422,12 @@ void gs_pairtab_free(gs_index *ix, uint32_t slot);
 gs_status gs_pairtab_ensure_spaced(gs_index *ix, uint32_t slot, uint32_t x_len, uint32_t g, hipStream_t st);
 /* false: the slot had none */
 bool gs_pairtab_free_spaced(gs_index *ix, uint32_t slot);
+/* tests (gs_debug_index_layout, gs_debug_index_array): a slot's scalars and arrays (gs_pairtab.hip); bytes of a device array to the host (gs_index.hip) */
+gs_status gs_debug_pairtab_layout(const gs_index *ix, uint32_t slot, int strand, uint64_t out[32]);
+gs_status gs_debug_pairtab_array(const gs_index *ix, uint32_t slot, int strand, const char *which, uint64_t offset_bytes, void *out,
+                                 uint64_t cap_bytes, uint64_t *total_bytes);
+gs_status gs_debug_copy_array(const gs_index *ix, const void *p, uint64_t bytes, uint64_t offset_bytes, void *out, uint64_t cap_bytes,
+                              uint64_t *total_bytes);
 /* gs_index.hip: the strand tables' rotated copies, built by the first batch that reads them */
 gs_status gs_strand_rot_ensure(gs_index *ix, hipStream_t st);
 bool gs_strand_rot_release(gs_index *ix);

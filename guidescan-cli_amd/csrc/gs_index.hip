@@ -242,6 +242,7 @@ gs_status gs_strand_from_device(const uint8_t *d_text, gs_scratch &sa_mem, uint3
     return GS_OK;
   };
   void *xr_seg = nullptr, *C256 = nullptr, *xr_start = nullptr, *xr_cum = nullptr, *run_start = nullptr, *run_cum = nullptr;
+  uint64_t xr_entries = 0;
   {
     std::vector<uint32_t> xs, xc, c256(256, 0);
     std::vector<uint2> seg(256, make_uint2(0u, 0u));
@@ -263,6 +264,7 @@ gs_status gs_strand_from_device(const uint8_t *d_text, gs_scratch &sa_mem, uint3
     GS_TRY(upload(c256.data(), 4 * 256, &C256));
     GS_TRY(upload(xs.data(), 4 * xs.size(), &xr_start));
     GS_TRY(upload(xc.data(), 4 * xc.size(), &xr_cum));
+    xr_entries = xs.size();
   }
   if (!starts.empty()) {
     GS_TRY(upload(starts.data(), 4 * starts.size(), &run_start));
@@ -270,6 +272,7 @@ gs_status gs_strand_from_device(const uint8_t *d_text, gs_scratch &sa_mem, uint3
   }
   /* nothing fails from here on: the strand takes the arrays, the suffix array among them */
   out->n = n;
+  out->xr_entries = xr_entries;
   gs_strand_dev &d = out->d;
   out->own.take(mem, d.blocks, blocks, nblocks * 64);
   out->own.take(sa_mem, d.sa, d_sa_owned, n * 4);
@@ -989,6 +992,70 @@ extern "C" gs_status gs_debug_resident(gs_index *ix, uint64_t out[4]) {
   out[2] = ix->pairtab[0].own.count() + ix->pairtab[1].own.count();
   out[3] = ix->pairtab[0].own.bytes() + ix->pairtab[1].own.bytes();
   return GS_OK;
+}
+/* tests: the scalars and the arrays of one strand as they lie in HBM (guidescan_amd.h; a PAM-pair slot's: gs_pairtab.hip) */
+struct dbg_array {
+  const char *name;
+  const void *p;
+  uint64_t bytes;
+};
+gs_status gs_debug_copy_array(const gs_index *ix, const void *p, uint64_t bytes, uint64_t offset_bytes, void *out, uint64_t cap_bytes,
+                              uint64_t *total_bytes) {
+  *total_bytes = p ? bytes : 0;
+  if (!p || offset_bytes >= bytes || !cap_bytes) return GS_OK;
+  GS_HIP(hipSetDevice(ix->device));
+  GS_HIP(hipMemcpy(out, (const char *)p + offset_bytes, (size_t)std::min<uint64_t>(cap_bytes, bytes - offset_bytes), hipMemcpyDeviceToHost));
+  return GS_OK;
+}
+extern "C" gs_status gs_debug_index_layout(gs_index *ix, int slot, int strand, uint64_t out[32]) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !out || strand < 0 || strand > 1 || slot < -1 || slot > 1) return GS_ERR_ARG;
+  memset(out, 0, 32 * sizeof(uint64_t));
+  if (slot >= 0) return gs_debug_pairtab_layout(ix, (uint32_t)slot, strand, out);
+  const gs_strand &S = ix->strand[strand];
+  const gs_strand_dev &d = S.d;
+  out[0] = d.n;
+  out[1] = d.blocks ? ((uint64_t)d.n >> GS_BLOCK_SHIFT) + 1 : 0;
+  out[2] = d.ptab ? ix->pt_k : 0;
+  out[3] = d.mask_off;
+  out[4] = d.n_exc;
+  out[5] = d.nruns;
+  for (int c = 0; c < 4; c++) out[6 + c] = d.C[c];
+  out[10] = d.CN;
+  out[11] = d.has_n;
+  out[12] = d.rot_first;
+  out[13] = d.ptab_rot ? S.rot_plan_n : 0;
+  out[14] = S.xr_entries;
+  return GS_OK;
+}
+extern "C" gs_status gs_debug_index_array(gs_index *ix, int slot, int strand, const char *which, uint64_t offset_bytes, void *out,
+                                          uint64_t cap_bytes, uint64_t *total_bytes) {
+  GS_HANDLE_LOCK(ix);
+  if (!ix || !which || !total_bytes || strand < 0 || strand > 1 || slot < -1 || slot > 1 || (cap_bytes && !out)) return GS_ERR_ARG;
+  if (slot >= 0) return gs_debug_pairtab_array(ix, (uint32_t)slot, strand, which, offset_bytes, out, cap_bytes, total_bytes);
+  const gs_strand &S = ix->strand[strand];
+  const gs_strand_dev &d = S.d;
+  const uint64_t n = d.n, entries = 1ull << (2 * ix->pt_k);
+  const dbg_array arrays[] = {
+      {"blocks", d.blocks, 64 * ((n >> GS_BLOCK_SHIFT) + 1)},
+      {"sa", d.sa, 4 * n},
+      {"ptab", d.ptab, 16 * entries},
+      {"ptab_rot", d.ptab_rot, 16 * entries * S.rot_plan_n},
+      {"ctx", d.ctx, 4 * n},
+      {"ctx16", d.ctx16, 2 * n}, /* (without the padding behind it, which nothing initialises) */
+      {"isa", d.isa, 4 * n},
+      {"exc_row", d.exc_row, 4 * (uint64_t)d.n_exc},
+      {"exc_sym", d.exc_sym, 8 * (uint64_t)d.n_exc},
+      {"run_start", d.run_start, 4 * (uint64_t)d.nruns},
+      {"run_cum", d.run_cum, 4 * ((uint64_t)d.nruns + 1)},
+      {"xr_seg", d.xr_seg, sizeof(uint2) * 256},
+      {"xr_start", d.xr_start, 4 * S.xr_entries},
+      {"xr_cum", d.xr_cum, 4 * S.xr_entries},
+      {"C256", d.C256, 4 * 256},
+  };
+  for (const dbg_array &a : arrays)
+    if (!strcmp(a.name, which)) return gs_debug_copy_array(ix, a.p, a.bytes, offset_bytes, out, cap_bytes, total_bytes);
+  return GS_ERR_ARG;
 }
 extern "C" gs_status gs_index_meta(const gs_index *ix, int strand, uint64_t C_acgtn[5],
                                    uint64_t *size) {

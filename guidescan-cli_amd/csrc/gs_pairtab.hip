@@ -600,3 +600,54 @@ extern "C" gs_status gs_debug_spaced_rows(gs_index *ix, uint32_t slot, int stran
   }
   return GS_OK;
 }
+
+/* tests (gs_debug_index_layout, gs_debug_index_array): the scalars and the arrays of one slot and strand as they lie in HBM */
+gs_status gs_debug_pairtab_layout(const gs_index *ix, uint32_t slot, int strand, uint64_t out[32]) {
+  const gs_pairtab_host &p = ix->pairtab[slot];
+  const gs_pairtab_dev &d = p.d[strand];
+  const uint32_t k = ix->pt_k;
+  out[0] = p.valid ? 1 : 0;
+  if (!p.valid) return GS_OK;
+  out[1] = p.v_rem;
+  out[2] = p.code;
+  out[3] = d.rot_first;
+  out[4] = d.rot && d.rot_first + 2 < k ? k - 2 - d.rot_first : 0;
+  out[5] = p.n_slots[strand];
+  out[6] = p.deep ? 1 : 0;
+  out[7] = p.deep ? p.deep_P : 0;
+  out[8] = p.deep ? p.deep_kb : 0;
+  out[9] = p.spaced ? 1 : 0;
+  if (p.spaced) {
+    out[10] = p.sp_x;
+    out[11] = p.sp_g;
+    out[12] = d.sp_rem;
+    out[13] = p.sp_rows[strand];
+    out[14] = 2u * (p.sp_x + p.sp_g) - d.sp_rem; /* the offsets array is addressed by the key's top d bits */
+  }
+  out[15] = k;
+  return GS_OK;
+}
+gs_status gs_debug_pairtab_array(const gs_index *ix, uint32_t slot, int strand, const char *which, uint64_t offset_bytes, void *out,
+                                 uint64_t cap_bytes, uint64_t *total_bytes) {
+  uint64_t lay[32] = {0};
+  GS_TRY(gs_debug_pairtab_layout(ix, slot, strand, lay));
+  const gs_pairtab_dev &d = ix->pairtab[slot].d[strand];
+  const uint64_t entries = 1ull << (2 * ix->pt_k), slots = lay[5];
+  const struct {
+    const char *name;
+    const void *p;
+    uint64_t bytes;
+  } arrays[] = {
+      {"tab", d.tab, sizeof(uint2) * entries},
+      {"rot", d.rot, sizeof(uint2) * entries * lay[4]},
+      {"c16", d.c16, 2 * slots + 64}, /* with the zeroed row groups' padding */
+      {"ctx", d.ctx, 4 * slots},
+      {"rowid", d.rowid, 4 * slots},
+      {"deep", lay[6] ? d.deep : nullptr, 64ull << (2 * lay[8])},
+      {"sp_off", lay[9] ? d.sp_off : nullptr, 4 * ((1ull << lay[14]) + 1)},
+      {"sp_rows", lay[9] ? d.sp_rows : nullptr, 8 * lay[13]},
+  };
+  for (const auto &a : arrays)
+    if (!strcmp(a.name, which)) return gs_debug_copy_array(ix, lay[0] ? a.p : nullptr, a.bytes, offset_bytes, out, cap_bytes, total_bytes);
+  return GS_ERR_ARG;
+}

@@ -23,7 +23,17 @@ __global__ void k_v_revcomp(const uint8_t *in, uint8_t *out, uint64_t len) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= len) return;
   uint8_t c = in[len - 1 - i];
-  c = c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c; /* sequences.cxx:14-26 (text is upper case) */
+  switch (c) { /* sequences.cxx:14-26, lower case included: the text the index was built from (gs_index.hip k_revcomp) */
+    case 'A': c = 'T'; break;
+    case 'T': c = 'A'; break;
+    case 'C': c = 'G'; break;
+    case 'G': c = 'C'; break;
+    case 'a': c = 't'; break;
+    case 't': c = 'a'; break;
+    case 'c': c = 'g'; break;
+    case 'g': c = 'c'; break;
+    default: break;
+  }
   out[i] = c;
 }
 

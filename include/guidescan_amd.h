@@ -322,6 +322,22 @@ gs_status gs_debug_rot_index(uint32_t pidx, uint32_t k, uint32_t rs, uint32_t *o
  * [1] bytes of the two strands (Occ blocks, suffix array, tables, context and inverse arrays, rotated copies), [2] arrays and
  * [3] bytes of the PAM-pair table slots (pair, deep and spaced tables).  [1] + [3] = gs_index_device_bytes.  Tests only. */
 gs_status gs_debug_resident(gs_index *ix, uint64_t out[4]);
+/* The scalars a reader needs to interpret and size the index's device arrays.  Tests only; takes the handle's lock, changes
+ * nothing, launches no kernel.
+ * slot = -1, a strand: [0] rows n, [1] Occ blocks, [2] table depth k (0: no table), [3] mask_off, [4] n_exc, [5] nruns,
+ *   [6..9] C of A,C,G,T, [10] CN, [11] has_n, [12] rot_first (31: none), [13] rotated copies present, [14] entries of
+ *   xr_start / xr_cum.
+ * slot = 0, 1, a PAM-pair table slot as `strand` holds it: [0] valid (the rest is 0 if not), [1] v_rem, [2] code, [3] rot_first
+ *   (31: none), [4] rotated copies present, [5] slots of the row arrays, [6] deep, [7] deep_P, [8] deep_kb, [9] spaced, [10] sp_x,
+ *   [11] sp_g, [12] sp_rem, [13] rows of the spaced table, [14] d = the key bits that address sp_off directly, [15] table depth k. */
+gs_status gs_debug_index_layout(gs_index *ix, int slot, int strand, uint64_t out[32]);
+/* One of these arrays, device to host: *total_bytes = its size by the layout above (0: the handle does not hold it), and its
+ * bytes from offset_bytes on, cap_bytes at most, go to out.  A strand's (slot = -1): blocks, sa, ptab, ptab_rot, ctx, ctx16
+ * (without the padding behind it), isa, exc_row, exc_sym, run_start, run_cum, xr_seg, xr_start, xr_cum, C256; a slot's: tab, rot,
+ * c16 (with the 64 zero bytes behind it), ctx, rowid, deep, sp_off, sp_rows.  Any other name: GS_ERR_ARG.  Tests only; takes the
+ * handle's lock, changes nothing, launches no kernel. */
+gs_status gs_debug_index_array(gs_index *ix, int slot, int strand, const char *which, uint64_t offset_bytes, void *out,
+                               uint64_t cap_bytes, uint64_t *total_bytes);
 /* The workspace buffers (what handles and decoders grow on demand and keep from call to call, and what gs_bgzf_inflate
  * holds for one call) alive in the process: [0] allocations, [1] their bytes.  Tests only. */
 gs_status gs_debug_buffers_live(uint64_t out[2]);

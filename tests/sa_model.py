@@ -6,7 +6,7 @@ small texts (tests/test_sa_model.py).
 A report is the dict GenomeIndex.verify_sa returns: rows, not_permutation, sampled, out_of_order, undecided, bwt_mismatch.
 
  * text: the FORWARD genome text (uint8, no sentinel) the array is checked against; strand 1 means its reverse complement
-   (A<->T, C<->G, every other byte as it is: k_v_revcomp), and `sa` is then that strand's array.
+   (A<->T, C<->G, a<->t, c<->g, every other byte as it is: k_v_revcomp, as the index's k_revcomp), and `sa` is then that strand's array.
  * built_text: the forward text the index was BUILT from, where that is another one (same length).  The index keeps two
    things of it that the verifier reads: the BWT symbol class of every row (built_text[sa[r] - 1]: A, C, G, T, or "extra"
    for every other byte and for the sentinel), and the list of its runs of 'N', by which sampled mode skips.
@@ -23,7 +23,7 @@ def as_text(s):
 
 
 _COMPLEMENT = np.arange(256, dtype=np.uint8)
-for _a, _b in ("AT", "TA", "CG", "GC"):
+for _a, _b in ("AT", "TA", "CG", "GC", "at", "ta", "cg", "gc"):
     _COMPLEMENT[ord(_a)] = ord(_b)
 _CLASS = np.full(256, 4, dtype=np.int64)      # A, C, G, T -> 0..3; every other byte, the sentinel included -> 4 ("extra")
 for _i, _b in enumerate(b"ACGT"):
@@ -44,7 +44,7 @@ def base_text(seed=7, n=40_000):
 
 
 def reverse_complement(text):
-    """k_v_revcomp: the text backwards, A<->T and C<->G, the rest unchanged"""
+    """k_v_revcomp: the text backwards, A<->T and C<->G in either case, the rest unchanged"""
     return _COMPLEMENT[np.asarray(text, dtype=np.uint8)[::-1]]
 
 
