@@ -72,6 +72,7 @@ GS_TEXT_BGZF = 0x1000  # with GS_TEXT_BAM: the blocks as BGZF members
 GS_TEXT_FEATURES = 0x4000
 GS_DECODE_NO_HEADER = 0x400
 GS_DECODE_BAM_END = 0x2000  # gs_decode_bam: the data ends with these members (a cut record is an error)
+GS_DECODE_FEATURES_ONLY = 0x8000  # with GS_TEXT_FEATURES | GS_TEXT_COMPLETE: only the rows that have a feature
 
 
 class GsDecodeBatch(C.Structure):
@@ -377,6 +378,10 @@ def lib():
     L.gs_design_set_feature_rule.argtypes = [vp, vp, u32, u32]
     L.gs_design_get_feature_hits.restype = i32
     L.gs_design_get_feature_hits.argtypes = [vp, C.POINTER(vp)]
+    L.gs_decoder_set_annotation.restype = i32
+    L.gs_decoder_set_annotation.argtypes = [vp, vp]
+    L.gs_debug_decode_annot_ms.restype = i32
+    L.gs_debug_decode_annot_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.gs_status_string.restype = C.c_char_p
     L.gs_status_string.argtypes = [i32]
     L.gs_version.restype = C.c_char_p
@@ -418,7 +423,8 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_regions_group_name", "gs_annot_build", "gs_annot_info", "gs_annot_free", "gs_debug_annot_entry_cap",
            "gs_annotate_device", "gs_annotate", "gs_debug_annotate_host", "gs_index_set_annotation",
            "gs_format_guides_features", "gs_format_guide_features", "gs_format_guide_ex_features",
-           "gs_design_set_feature_rule", "gs_design_get_feature_hits"]
+           "gs_design_set_feature_rule", "gs_design_get_feature_hits",
+           "gs_decoder_set_annotation", "gs_debug_decode_annot_ms"]
 
 
 def _check(rc):
@@ -1443,12 +1449,29 @@ class Decoder:
                           rev.ctypes.data, chrm.ctypes.data, pos0.ctypes.data, hexs.ctypes.data, hex_off.ctypes.data)
         return b, keep
 
-    def decode_records(self, records, complete=False, first_record=0, on_device=False) -> str:
+    def set_annotation(self, annotation):
+        """attaches an Annotation built for the decoder's device against its @SQ lines, None detaches
+        (gs_decoder_set_annotation); the decoder keeps it alive.  features=True in the decode_* calls then adds the
+        columns, features_only=True (complete mode) leaves out the rows without a feature"""
+        _check(lib().gs_decoder_set_annotation(self._h, annotation._h if annotation is not None else None))
+        self._annotation = annotation
+
+    def annot_ms(self) -> float:
+        """the annotation pass of the last batch that ran one, in milliseconds (gs_debug_decode_annot_ms)"""
+        ms = C.c_double()
+        _check(lib().gs_debug_decode_annot_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    @staticmethod
+    def _feature_flags(features, features_only):
+        return (GS_TEXT_FEATURES if features else 0) | (GS_DECODE_FEATURES_ONLY if features_only else 0)
+
+    def decode_records(self, records, complete=False, first_record=0, on_device=False, features=False, features_only=False) -> str:
         """on_device: through gs_decode_records_device, the text copied back from HBM here"""
         if not records:
             return ""
         b, keep = self._batch(records)
-        flags = GS_TEXT_COMPLETE if complete else 0
+        flags = (GS_TEXT_COMPLETE if complete else 0) | self._feature_flags(features, features_only)
         out, ln, rows = C.c_void_p(), C.c_uint64(), C.c_uint64()
         fn = lib().gs_decode_records_device if on_device else lib().gs_decode_records
         _check(fn(self._h, C.byref(b), flags, first_record, C.byref(out), C.byref(ln), C.byref(rows)))
@@ -1466,8 +1489,9 @@ class Decoder:
         lib().gs_free(out)
         return s
 
-    def decode_sam(self, sam: bytes, complete=False, header=True, first_record=0) -> str:
-        flags = (GS_TEXT_COMPLETE if complete else 0) | (0 if header else GS_DECODE_NO_HEADER)
+    def decode_sam(self, sam: bytes, complete=False, header=True, first_record=0, features=False, features_only=False) -> str:
+        flags = ((GS_TEXT_COMPLETE if complete else 0) | (0 if header else GS_DECODE_NO_HEADER) |
+                 self._feature_flags(features, features_only))
         out, ln, n = C.c_void_p(), C.c_uint64(), C.c_uint64()
         _check(lib().gs_decode_sam(self._h, sam, len(sam), flags, first_record, C.byref(out), C.byref(ln), C.byref(n)))
         s = C.string_at(out, ln.value).decode("latin-1")
@@ -1493,12 +1517,14 @@ class Decoder:
             raise GsError(2, "copy of the inflated bytes")
         return host.tobytes()
 
-    def decode_bam(self, bgzf: bytes, skip=0, ref_to_sq=(), complete=False, first_record=0, end=False, on_device=False):
+    def decode_bam(self, bgzf: bytes, skip=0, ref_to_sq=(), complete=False, first_record=0, end=False, on_device=False,
+                   features=False, features_only=False):
         """whole BGZF members of a BAM database -> (rows without the header line, complete records, bytes of a cut record
         that the decoder keeps for the next call) (gs_decode_bam; on_device: gs_decode_bam_device, the text copied back
         here).  skip: inflated bytes of the BAM header, in the first call of a file; ref_to_sq: the binary reference
         list's entries as indices into sq (negative: none); end: the data ends here"""
-        flags = (GS_TEXT_COMPLETE if complete else 0) | (GS_DECODE_BAM_END if end else 0)
+        flags = ((GS_TEXT_COMPLETE if complete else 0) | (GS_DECODE_BAM_END if end else 0) |
+                 self._feature_flags(features, features_only))
         m = np.ascontiguousarray(ref_to_sq, dtype=np.int32)
         out, ln, n, tail = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64()
         fn = lib().gs_decode_bam_device if on_device else lib().gs_decode_bam

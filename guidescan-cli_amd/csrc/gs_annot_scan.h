@@ -51,6 +51,16 @@ GS_AN_HD bool gs_an_footprint(long long s, uint32_t w, uint64_t len, uint64_t &a
   b = (uint64_t)(hi > 0 ? hi : 0);
   return lo < hi;
 }
+/* Footprint of a decoded off-target (gs_decode.hip, `decode --annotate`).  A database word gives a chromosome, the
+ * coordinate x that the script's map_int_to_coord returns and a strand; the record's stored SEQ has n symbols and the
+ * chromosome has ln bases by its @SQ line.  The row occupies the forward-strand bases whose symbols the script slices,
+ * [x + 1 - n, x + 1) on '+' and [x, x + n) on '-', clipped to [0, ln): by LN, not by the FASTA record's length, and
+ * without Python's wrap of a negative slice start, so a row whose printed sequence is short or wrapped is annotated by
+ * where it lies.  These are the L + P bases of the row `enumerate` prints at s = x + 2 - n ('+') or s = x + 1 ('-'), so
+ * the two commands give a site the same features.  false: no base left */
+GS_AN_HD bool gs_an_decoded_footprint(uint64_t x, bool plus, uint32_t n, uint64_t ln, uint64_t &a, uint64_t &b) {
+  return gs_an_footprint(plus ? (long long)x + 2 - (long long)n : (long long)x + 1, n, ln, a, b);
+}
 /* how many of the n ascending breakpoints are <= q */
 GS_AN_HD uint32_t gs_an_count_le(const uint32_t *bp, uint32_t n, uint64_t q) {
   uint32_t lo = 0, hi = n;
@@ -117,6 +127,17 @@ GS_AN_HD uint32_t gs_an_visit(const gs_an_table &t, uint32_t c, long long s, uin
 }
 GS_AN_HD uint32_t gs_an_count(const gs_an_table &t, uint32_t c, long long s, uint32_t w, uint64_t len) {
   return gs_an_visit(t, c, s, w, len, [](uint32_t) {});
+}
+/* the same for a decoded off-target at x on chromosome c (ln bases), the record's SEQ of n symbols */
+template <class F>
+GS_AN_HD uint32_t gs_an_decoded_visit(const gs_an_table &t, uint32_t c, uint64_t x, bool plus, uint32_t n, uint64_t ln, F f) {
+  uint64_t a, b;
+  uint32_t i0, i1;
+  if (c >= t.n_chr || !gs_an_decoded_footprint(x, plus, n, ln, a, b) || !gs_an_range(t, c, a, b, i0, i1)) return 0;
+  return gs_an_merge(t, i0, i1, f);
+}
+GS_AN_HD uint32_t gs_an_decoded_count(const gs_an_table &t, uint32_t c, uint64_t x, bool plus, uint32_t n, uint64_t ln) {
+  return gs_an_decoded_visit(t, c, x, plus, n, ln, [](uint32_t) {});
 }
 
 /* ---- construction, on the host ------------------------------------------------------------------------------------ */

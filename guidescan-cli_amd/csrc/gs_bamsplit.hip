@@ -404,7 +404,7 @@ gs_status decode_bam_device(gs_decoder *d, const void *bgzf, uint64_t len, uint6
     db.word_off = (const uint64_t *)(rec + t_ow);
     db.chr = a.chr;
     db.pos0 = a.pos0;
-    if ((rc = gs_decode_run_device(d, db, n, totals[3], flags & GS_TEXT_COMPLETE, first_record, nullptr, d_text, text_len, nullptr)) != GS_OK)
+    if ((rc = gs_decode_run_device(d, db, n, totals[3], flags & (GS_TEXT_COMPLETE | GS_TEXT_FEATURES | GS_DECODE_FEATURES_ONLY), first_record, nullptr, d_text, text_len, nullptr)) != GS_OK)
       return rc;
   }
   d->last_bam_ms[3] = ms_since(t0);
@@ -424,6 +424,7 @@ extern "C" gs_status gs_decode_bam_device(gs_decoder *d, const void *bgzf, uint6
   *text_len = 0;
   if (n_records) *n_records = 0;
   if (tail) *tail = 0;
+  GS_TRY(gs_decode_check_flags(d, flags)); /* before anything is inflated or kept */
   try {
     return decode_bam_device(d, bgzf, len, skip, ref_to_sq, n_ref, flags, first_record, d_text, text_len, n_records, tail);
   } catch (const std::bad_alloc &) {

@@ -26,6 +26,19 @@
  *               tile composed in the wave's LDS slice and streamed out in 16-byte stores.  Doubles are printed as
  *               Python's repr by gs_repr.h (integer arithmetic).
  * The error word travels back with the total length: (record << 8 | reason), the smallest over the batch.
+ *
+ * With an annotation attached (gs_decoder_set_annotation) and GS_TEXT_FEATURES, the rows carry the features of a BED file:
+ * the rule is gs_an_decoded_footprint (gs_annot_scan.h), the table the one `enumerate --annotate` looks up.
+ *   k_dc_feat   behind k_dc_eval, one lane per word: a position is placed again (chromosome and x only, no gather), its
+ *               footprint looked up by two binary searches, the number of distinct groups kept per word
+ *   k_dc_fold   counts, next to the counters per distance, the off-targets at that distance that have a feature
+ *   k_dc_len / k_dc_write   complete mode: the row routine appends ',' and the names joined by ';', or NA, through the
+ *               same two sinks; under GS_DECODE_FEATURES_ONLY a word without a feature has a row of length 0.  A lane with
+ *               features walks its segments' lists while the lanes without wait: nearly every row has none or one or two
+ *               groups (a footprint is about 23 bases), so the wave pays for its longest list, as it pays for its longest
+ *               id or number already.  A row longer than the LDS slice takes k_dc_write's straight-to-HBM branch.
+ * The script's failures are found by k_dc_hex, k_dc_rec and k_dc_eval before any row is measured, and k_dc_len gives up
+ * when one is recorded: they win over a row that the annotation makes too long.
  */
 #include "gs_device.h"
 
@@ -38,6 +51,8 @@
 #include "gs_repr.h"
 #include "gs_decoder.h"
 #include "gs_scratch.h"
+#include "gs_annot_scan.h"
+#include "gs_annot_obj.h"
 
 #define DC_WAVES 4
 #define DC_LDS 12288u         /* bytes of a wave's slice */
@@ -78,6 +93,13 @@ struct dc_args {
   uint64_t slots, total;
   int64_t delim;
   uint32_t n, n_words, n_chr, complete;
+  /* the annotation (features != 0): its table and names; per word the number of its features, per record and distance the
+   * off-targets that have one; only != 0: rows without a feature are left out */
+  gs_an_table an;
+  const uint32_t *an_name_off;
+  const uint8_t *an_names;
+  uint32_t *nfeat, *fcnt;
+  uint32_t features, only;
 };
 
 /* ---- small pieces -------------------------------------------------------------------------------------------- */
@@ -116,13 +138,11 @@ struct dc_site {
   char strand;
   uint8_t seq[DC_MAX_SEQ];
 };
-/* map_int_to_coord (:38-50) and map_coord_to_sequence (:52-59) with revcom for '-' (:135) -> 0 or the reason it fails */
-__device__ __forceinline__ uint32_t dc_resolve(const dc_args &a, int64_t word, uint32_t n, dc_site &s) {
-  s.strand = word > 0 ? '+' : '-';
+/* map_int_to_coord (:38-50): the chromosome that holds |word| and the coordinate on it -> 0 or the reason it fails */
+__device__ __forceinline__ uint32_t dc_place(const dc_args &a, int64_t word, uint32_t &c, uint64_t &x) {
   const uint64_t ab = word < 0 ? 0ull - (uint64_t)word : (uint64_t)word;
-  s.len = 0;
-  s.c = 0;
-  s.x = 0;
+  c = 0;
+  x = 0;
   if (ab >= a.total) return DC_ERR_WORD;
   uint32_t lo = 0, hi = a.n_chr; /* first chromosome whose end exceeds ab: the walk `while LN <= x` */
   while (lo < hi) {
@@ -133,8 +153,16 @@ __device__ __forceinline__ uint32_t dc_resolve(const dc_args &a, int64_t word, u
       lo = mid + 1u;
   }
   if (lo >= a.n_chr) return DC_ERR_WORD;
-  s.c = lo;
-  s.x = ab - a.cum[lo];
+  c = lo;
+  x = ab - a.cum[lo];
+  return 0u;
+}
+/* dc_place and map_coord_to_sequence (:52-59) with revcom for '-' (:135) -> 0 or the reason it fails */
+__device__ __forceinline__ uint32_t dc_resolve(const dc_args &a, int64_t word, uint32_t n, dc_site &s) {
+  s.strand = word > 0 ? '+' : '-';
+  s.len = 0;
+  if (const uint32_t bad = dc_place(a, word, s.c, s.x)) return bad;
+  const uint32_t lo = s.c;
   const uint64_t fl = a.flen[lo];
   if (fl == ~0ull) return DC_ERR_CHROMOSOME;
   /* a Python slice of a sequence of fl symbols */
@@ -277,13 +305,32 @@ __global__ __launch_bounds__(256) void k_dc_eval(dc_args a) {
   }
 }
 
+/* GS_TEXT_FEATURES: how many groups of the annotation every off-target touches (gs_an_decoded_footprint); the site is placed
+ * again, without the gather of its symbols.  A word that is no position, or one that k_dc_eval has refused the batch for,
+ * has none */
+__global__ __launch_bounds__(256) void k_dc_feat(dc_args a) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_words; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t w = (uint32_t)i;
+    uint32_t k = 0;
+    if (a.ispos[w]) {
+      const uint32_t r = a.rec[w];
+      const uint64_t stored = a.seq_off[r + 1u] - a.seq_off[r];
+      uint32_t c;
+      uint64_t x;
+      if (stored <= DC_MAX_SEQ && !dc_place(a, a.words[w], c, x))
+        k = gs_an_decoded_count(a.an, c, x, a.words[w] > 0, (uint32_t)stored, a.cum[c + 1u] - a.cum[c]);
+    }
+    a.nfeat[w] = k;
+  }
+}
+
 /* output_succinct (:156-187): a wave per record */
 __global__ __launch_bounds__(WAVE *DC_WAVES) void k_dc_fold(dc_args a) {
   const uint32_t lane = threadIdx.x & (WAVE - 1u);
   const uint32_t wave0 = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE, n_waves = gridDim.x * blockDim.x / WAVE;
   for (uint32_t r = wave0; r < a.n; r += n_waves) {
     const uint64_t w0 = a.word_off[r], w1 = a.word_off[r + 1u];
-    uint32_t cnt[4] = {0, 0, 0, 0};
+    uint32_t cnt[4] = {0, 0, 0, 0}, fcnt[4] = {0, 0, 0, 0};
     bool any = false, all_have = true, seen0 = false;
     double sum = 0.0, first0 = 0.0;
     for (uint64_t base = w0; base < w1; base += WAVE) {
@@ -302,6 +349,10 @@ __global__ __launch_bounds__(WAVE *DC_WAVES) void k_dc_fold(dc_args a) {
       if (m == 0ull) continue;
       any = true;
       for (uint32_t k = 0; k < 4u; k++) cnt[k] += (uint32_t)__popcll(__ballot(pos && d == k));
+      if (a.features) { /* counted as cnt is: every off-target of the list, the record's own site among them */
+        const bool has = pos && a.nfeat[w] != 0u;
+        for (uint32_t k = 0; k < 4u; k++) fcnt[k] += (uint32_t)__popcll(__ballot(has && d == k));
+      }
       if (__ballot(pos && c == DC_ABSENT)) all_have = false;
       /* the ordered part: every lane folds the same 64 values one after the other */
       uint64_t todo = m;
@@ -319,6 +370,8 @@ __global__ __launch_bounds__(WAVE *DC_WAVES) void k_dc_fold(dc_args a) {
     }
     if (lane == 0u) {
       for (uint32_t k = 0; k < 4u; k++) a.cnt[(size_t)r * 4u + k] = cnt[k];
+      if (a.features)
+        for (uint32_t k = 0; k < 4u; k++) a.fcnt[(size_t)r * 4u + k] = fcnt[k];
       double spec = 0.0; /* 0.0: the column is empty (a specificity is never 0) */
       if (any && all_have) {
         if (seen0) sum = sum - first0;
@@ -375,9 +428,26 @@ __device__ __forceinline__ void dc_chr_name(S &o, const dc_args &a, uint32_t c) 
 }
 
 /* complete mode (:148-154): the row of word w, if it is a position */
+/* the match_features column of the off-target of word w: ',' and the names of its groups joined by ';', or NA */
+template <class S>
+__device__ __forceinline__ void dc_features(S &o, const dc_args &a, uint32_t w, const dc_site &s, uint32_t n) {
+  o.ch(',');
+  if (!a.nfeat[w]) {
+    o.ch('N'), o.ch('A');
+    return;
+  }
+  bool first = true;
+  gs_an_decoded_visit(a.an, s.c, s.x, s.strand == '+', n, a.cum[s.c + 1u] - a.cum[s.c], [&](uint32_t g) {
+    if (!first) o.ch(';');
+    first = false;
+    const uint32_t b = a.an_name_off[g];
+    o.put(a.an_names + b, a.an_name_off[g + 1u] - b);
+  });
+}
 template <class S>
 __device__ __forceinline__ void dc_complete_row(S &o, const dc_args &a, uint32_t w) {
   if (!a.ispos[w]) return;
+  if (a.only && !a.nfeat[w]) return; /* GS_DECODE_FEATURES_ONLY: no row; match_number below is the rank among all rows */
   const uint32_t r = a.rec[w];
   uint32_t dist_at = 0;
   dc_is_position(a, w, r, dist_at);
@@ -401,6 +471,7 @@ __device__ __forceinline__ void dc_complete_row(S &o, const dc_args &a, uint32_t
   o.ch(',');
   const double cfd = a.cfd[w];
   if (cfd != DC_ABSENT && cfd != 0.0) dc_double(o, a, cfd); /* `cfd or ''` */
+  if (a.features) dc_features(o, a, w, s, n);
   o.ch('\n');
 }
 /* succinct mode (:185-187): the row of record r */
@@ -425,6 +496,11 @@ __device__ __forceinline__ void dc_succinct_row(S &o, const dc_args &a, uint32_t
   }
   o.ch(',');
   if (a.spec[r] != 0.0) dc_double(o, a, a.spec[r]);
+  if (a.features)
+    for (uint32_t k = 0; k < 4u; k++) {
+      o.ch(',');
+      o.u64(a.fcnt[(size_t)r * 4u + k]);
+    }
   o.ch('\n');
 }
 template <class S>
@@ -515,6 +591,14 @@ const char *const dc_reasons[] = {"",
 const char dc_header_succinct[] =
     "id,sequence,chromosome,position,sense,distance_0_matches,distance_1_matches,distance_2_matches,distance_3_matches,specificity\n";
 const char dc_header_complete[] = "id,match_number,sequence,chromosome,position,sense,distance,cfd\n";
+/* GS_TEXT_FEATURES, in front of the newline.  distance_k_feature_matches: the off-targets that distance_k_matches counts and
+ * that have at least one feature - counted exactly as that column counts, the record's own site included */
+const char dc_header_succinct_features[] =
+    ",distance_0_feature_matches,distance_1_feature_matches,distance_2_feature_matches,distance_3_feature_matches";
+const char dc_header_complete_features[] = ",match_features";
+struct dc_widen_nonzero {
+  __host__ __device__ uint64_t operator()(uint32_t v) const { return v ? 1ull : 0ull; }
+};
 
 gs_status dc_record_error(const gs_decode_batch *b, uint64_t first_record, uint64_t r, uint32_t reason) {
   std::string id;
@@ -549,6 +633,7 @@ gs_status gs_decoder_open_text(int device, const uint8_t *text, uint64_t len, in
     for (uint32_t c = 0; c < nc; c++) {
       d->names.emplace_back(sq->chr_names[c]);
       name_off[c + 1] = name_off[c] + (uint32_t)d->names[c].size();
+      d->lengths.push_back(sq->chr_lengths[c]);
     }
     bump in;
     const size_t i_cum = in.take(8 * ((size_t)nc + 1)), i_toff = in.take(8 * (size_t)nc), i_flen = in.take(8 * (size_t)nc),
@@ -606,6 +691,40 @@ extern "C" void gs_decoder_close(gs_decoder *d) {
   if (!d) return;
   (void)hipSetDevice(d->device);
   delete d;
+}
+
+extern "C" gs_status gs_decoder_set_annotation(gs_decoder *d, const gs_annot *an) {
+  GS_HANDLE_LOCK(d);
+  if (!d) return GS_ERR_ARG;
+  if (an && an->device != d->device) {
+    gs_set_error("gs_decoder_set_annotation: the annotation was built for another device, or for the host only");
+    return GS_ERR_ARG;
+  }
+  if (an && an->chr_lengths != d->lengths) { /* as an_same_structure (gs_annot.hip): the count and every length */
+    gs_set_error("gs_decoder_set_annotation: the @SQ lines are not the genome structure the annotation was made against");
+    return GS_ERR_ARG;
+  }
+  d->annot = an;
+  return GS_OK;
+}
+
+extern "C" gs_status gs_debug_decode_annot_ms(gs_decoder *d, double *ms) {
+  GS_HANDLE_LOCK(d);
+  if (!d || !ms) return GS_ERR_ARG;
+  *ms = d->last_annot_ms;
+  return GS_OK;
+}
+
+gs_status gs_decode_check_flags(const gs_decoder *d, uint32_t flags) {
+  if ((flags & GS_TEXT_FEATURES) && !d->annot) {
+    gs_set_error("gs_decode: GS_TEXT_FEATURES without an annotation (gs_decoder_set_annotation)");
+    return GS_ERR_ARG;
+  }
+  if ((flags & GS_DECODE_FEATURES_ONLY) && (flags & (GS_TEXT_FEATURES | GS_TEXT_COMPLETE)) != (GS_TEXT_FEATURES | GS_TEXT_COMPLETE)) {
+    gs_set_error("gs_decode: GS_DECODE_FEATURES_ONLY selects rows of the complete table by their features: it needs GS_TEXT_FEATURES | GS_TEXT_COMPLETE");
+    return GS_ERR_ARG;
+  }
+  return GS_OK;
 }
 
 static gs_status decode_device(gs_decoder *d, const gs_decode_batch *b, uint32_t flags, uint64_t first_record, const void **d_text,
@@ -684,9 +803,14 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
   hipStream_t st = nullptr;
   GS_HIP(hipSetDevice(d->device));
   const bool complete = (flags & GS_TEXT_COMPLETE) != 0;
+  const gs_annot *an = (flags & GS_TEXT_FEATURES) ? d->annot : nullptr; /* the entry points have checked the flags */
+  const bool only = an && complete && (flags & GS_DECODE_FEATURES_ONLY);
   const uint64_t slots = complete ? nw : n;
   const uint32_t n_tiles = (uint32_t)((slots + WAVE - 1) / WAVE);
-  size_t tb_next = 0, tb_rank = 0, tb_tiles = 0;
+  size_t tb_next = 0, tb_rank = 0, tb_tiles = 0, tb_rows = 0;
+  if (only) /* the rows written: the words with a feature */
+    GS_HIP(rocprim::reduce(nullptr, tb_rows, rocprim::make_transform_iterator((const uint32_t *)nullptr, dc_widen_nonzero()), (uint64_t *)nullptr,
+                           0ull, (size_t)nw, rocprim::plus<uint64_t>(), st));
   GS_HIP(rocprim::inclusive_scan(nullptr, tb_next, (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)nw, dc_min(), st));
   GS_HIP(rocprim::exclusive_scan(nullptr, tb_rank, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)nw + 1, rocprim::plus<uint32_t>(), st));
   GS_HIP(rocprim::exclusive_scan(nullptr, tb_tiles, (uint64_t *)nullptr, (uint64_t *)nullptr, 0ull, (size_t)n_tiles + 1,
@@ -695,7 +819,9 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
   const size_t t_err = tm.take(16), t_words = tm.take(8 * nw), t_cfd = tm.take(8 * nw), t_rec = tm.take(4 * nw), t_mark = tm.take(4 * nw),
                t_next = tm.take(4 * nw), t_ispos = tm.take(4 * (nw + 1)), t_rank = tm.take(4 * (nw + 1)), t_lens = tm.take(4 * slots),
                t_cnt = tm.take(complete ? 0 : 16 * n), t_spec = tm.take(complete ? 0 : 8 * n), t_tsum = tm.take(8 * ((size_t)n_tiles + 1)),
-               t_toff = tm.take(8 * ((size_t)n_tiles + 1)), tb_scan = std::max(tb_next, std::max(tb_rank, tb_tiles)), t_scan = tm.take(tb_scan);
+               t_toff = tm.take(8 * ((size_t)n_tiles + 1)), tb_scan = std::max(std::max(tb_next, tb_rows), std::max(tb_rank, tb_tiles)),
+               t_scan = tm.take(tb_scan), t_nfeat = tm.take(an ? 4 * nw : 0), t_fcnt = tm.take(an && !complete ? 16 * n : 0),
+               t_nrows = tm.take(only ? 8 : 0);
   GS_TRY(gs_reserve(d->w_tmp, tm.at + 16));
   char *tmp = (char *)d->w_tmp.p;
 
@@ -738,6 +864,19 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
   a.n_words = (uint32_t)nw;
   a.n_chr = d->n_chr;
   a.complete = complete ? 1u : 0u;
+  if (an) {
+    a.an = an->d_table;
+    a.an_name_off = an->d_name_off;
+    a.an_names = an->d_names;
+    a.nfeat = (uint32_t *)(tmp + t_nfeat);
+    a.fcnt = (uint32_t *)(tmp + t_fcnt);
+    a.features = 1u;
+    a.only = only ? 1u : 0u;
+  }
+  uint64_t *d_nrows = (uint64_t *)(tmp + t_nrows);
+  gs_events<2> ev;
+  if (an)
+    for (hipEvent_t &e : ev.e) GS_HIP(hipEventCreate(&e));
 
   const uint32_t cus = (uint32_t)gs_num_cus(d->device);
   const uint32_t gw = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nw + 256) / 256, (uint64_t)cus * 32u));
@@ -752,6 +891,19 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
   }
   hipLaunchKernelGGL(k_dc_rec, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_dc_eval, dim3(gw), dim3(256), 0, st, a);
+  if (an) {
+    GS_HIP(hipEventRecord(ev.e[0], st));
+    if (nw) hipLaunchKernelGGL(k_dc_feat, dim3(gw), dim3(256), 0, st, a);
+    GS_HIP(hipEventRecord(ev.e[1], st));
+    if (only) {
+      GS_HIP(hipMemsetAsync(d_nrows, 0, 8, st));
+      if (nw)
+        GS_TRY(gs_prim_carved("gs_decode: count of the rows with a feature", tmp + t_scan, tb_scan, [&](void *t, size_t &tb) {
+          return rocprim::reduce(t, tb, rocprim::make_transform_iterator((const uint32_t *)a.nfeat, dc_widen_nonzero()), d_nrows, 0ull,
+                                 (size_t)nw, rocprim::plus<uint64_t>(), st);
+        }));
+    }
+  }
   GS_TRY(gs_prim_carved("gs_decode: scan of the positions", tmp + t_scan, tb_scan, [&](void *t, size_t &tb) {
     return rocprim::exclusive_scan(t, tb, a.ispos, a.rank, 0u, (size_t)nw + 1, rocprim::plus<uint32_t>(), st);
   }));
@@ -770,8 +922,14 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
   GS_HIP(hipMemcpyAsync(&total, a.tile_off + n_tiles, 8, hipMemcpyDeviceToHost, st));
   GS_HIP(hipMemcpyAsync(&err, a.err, 8, hipMemcpyDeviceToHost, st));
   GS_HIP(hipMemcpyAsync(&n_pos, a.rank + nw, 4, hipMemcpyDeviceToHost, st));
+  uint64_t n_featured = 0;
+  if (only) GS_HIP(hipMemcpyAsync(&n_featured, d_nrows, 8, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   GS_HIP(hipGetLastError());
+  if (an) {
+    const int from = 0;
+    GS_TRY(ev.elapsed(&from, 1, &d->last_annot_ms));
+  }
   if (err != ~0ull) {
     const uint32_t reason = (uint32_t)(err & 255u);
     if (reason == DC_ERR_BIG) {
@@ -795,7 +953,7 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
   GS_HIP(hipGetLastError());
   *d_text = d->w_text.p;
   *text_len = total;
-  if (n_rows) *n_rows = complete ? (uint64_t)n_pos : n;
+  if (n_rows) *n_rows = only ? n_featured : complete ? (uint64_t)n_pos : n;
   return GS_OK;
 }
 
@@ -808,6 +966,7 @@ extern "C" gs_status gs_decode_records_device(gs_decoder *d, const gs_decode_bat
                                               const void **d_text, uint64_t *len, uint64_t *n_rows) {
   GS_HANDLE_LOCK(d);
   if (!d || !d_text || !len || !dc_batch_ok(b)) return GS_ERR_ARG;
+  GS_TRY(gs_decode_check_flags(d, flags));
   try {
     return decode_device(d, b, flags, first_record, d_text, len, n_rows);
   } catch (const std::bad_alloc &) {
@@ -838,6 +997,7 @@ extern "C" gs_status gs_decode_sam(gs_decoder *d, const char *sam, uint64_t sam_
   *text = nullptr;
   *len = 0;
   if (n_records) *n_records = 0;
+  GS_TRY(gs_decode_check_flags(d, flags));
   try {
     std::string ids, seqs;
     std::vector<uint64_t> id_off{0}, seq_off{0}, hex_off;
@@ -913,14 +1073,19 @@ extern "C" gs_status gs_decode_sam(gs_decoder *d, const char *sam, uint64_t sam_
     gs_status rc = n ? gs_decode_records(d, &b, flags, first_record, &rows, &rl, nullptr) : GS_OK;
     if (rc != GS_OK) return rc;
     const bool header = !(flags & GS_DECODE_NO_HEADER);
-    const char *h = (flags & GS_TEXT_COMPLETE) ? dc_header_complete : dc_header_succinct;
-    const size_t hl = header ? strlen(h) : 0;
+    std::string h;
+    if (header) {
+      const bool complete = (flags & GS_TEXT_COMPLETE) != 0;
+      h = complete ? dc_header_complete : dc_header_succinct;
+      if (flags & GS_TEXT_FEATURES) h.insert(h.size() - 1, complete ? dc_header_complete_features : dc_header_succinct_features);
+    }
+    const size_t hl = h.size();
     char *outp = (char *)malloc(hl + rl + 1);
     if (!outp) {
       free(rows);
       return GS_ERR_NOMEM;
     }
-    memcpy(outp, h, hl);
+    memcpy(outp, h.data(), hl);
     if (rl) memcpy(outp + hl, rows, rl);
     outp[hl + rl] = 0;
     free(rows);

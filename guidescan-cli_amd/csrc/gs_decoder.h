@@ -6,12 +6,17 @@
 #include "gs_common.h"
 #include "gs_repr.h"
 
+struct gs_annot;
+
 struct gs_decoder {
   std::recursive_mutex mtx;
   int device = 0;
   uint32_t n_chr = 0;
   uint64_t total = 0;
   std::vector<std::string> names;
+  std::vector<uint64_t> lengths;   /* the @SQ LN values: what an attached annotation must have been parsed against */
+  const gs_annot *annot = nullptr; /* gs_decoder_set_annotation: the caller's, for GS_TEXT_FEATURES */
+  double last_annot_ms = 0;        /* the annotation pass of the last batch, by stream events (gs_debug_decode_annot_ms) */
   gs_buffer text, tabs; /* the FASTA bytes; prefix sums, text offsets, record lengths, name offsets, names, powers of five */
   const uint64_t *d_cum = nullptr, *d_toff = nullptr, *d_flen = nullptr;
   const uint32_t *d_name_off = nullptr;
@@ -44,6 +49,9 @@ struct gs_decode_batch_dev {
 /* gs_decoder_open with the text in host memory or, text_on_device != 0, in HBM already (gs_fasta.hip: copied device to device) */
 gs_status gs_decoder_open_text(int device, const uint8_t *text, uint64_t len, int text_on_device, const gs_genome_structure *sq,
                                const uint64_t *chr_text_off, const uint64_t *chr_text_len, gs_decoder **out);
+/* the flags of a decode entry point against the decoder's state: GS_TEXT_FEATURES needs an annotation, GS_DECODE_FEATURES_ONLY
+ * needs GS_TEXT_FEATURES | GS_TEXT_COMPLETE; GS_ERR_ARG with the message otherwise */
+gs_status gs_decode_check_flags(const gs_decoder *d, uint32_t flags);
 gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uint64_t n, uint64_t nw, uint32_t flags, uint64_t first_record,
                                const gs_decode_batch *host_batch, const void **d_text, uint64_t *text_len, uint64_t *n_rows);
 

@@ -42,6 +42,27 @@ inline bool read_gs(const std::string &path, genome_structure &gs, std::string &
   return true;
 }
 
+/* a BED file (`enumerate --regions`, `--annotate`; `decode --annotate`) against a genome structure; the parser's message
+ * with its line number, "regions" replaced by `what` */
+inline bool read_bed(const std::string &path, const genome_structure &gs, const std::string &prefix, const std::string &what,
+                     gs_regions **out) {
+  std::vector<const char *> names;
+  for (auto &n : gs.names) names.push_back(n.c_str());
+  const gs_genome_structure cgs{names.data(), gs.lengths.data(), (uint32_t)names.size()};
+  gs_regions_report rep;
+  const gs_status rc = gs_regions_parse_file(path.c_str(), &cgs, prefix.c_str(), out, &rep);
+  if (rc == GS_OK) return true;
+  if (rc == GS_ERR_FORMAT && rep.bad_text) { /* the parser says "regions line N: ..." / "regions file: ..." */
+    const std::string msg = rep.bad_text;
+    std::cerr << "error: " << (msg.compare(0, 7, "regions") == 0 ? what + msg.substr(7) : msg) << " (" << path << ")\n";
+  } else if (rc == GS_ERR_IO)
+    std::cerr << "error: cannot read the " << what << " file " << path << "\n";
+  else
+    std::cerr << "error: " << what << " file " << path << ": " << gs_status_string(rc) << "\n";
+  gs_free(rep.bad_text);
+  return false;
+}
+
 /* what the candidate scan takes (scripts/generate_kmers.py:14-47) */
 struct candidate_opts {
   std::string pam = "NGG", prefix;

@@ -24,6 +24,13 @@
  * run.  The table and the messages are those of --fasta host, with one difference: GENOME.fa must be a regular file (the
  * device buffer is sized from its length), so a pipe or a process substitution, which read_fasta takes, is "cannot read".
  * --verbose's "FASTA read" then covers file read, upload and the device stage, and a second line gives them apart.
+ * --annotate BED [--features-only]: the table gains the features of a BED file in the pass that decodes it (no counterpart
+ * in the reference; the rule is gs_an_decoded_footprint, gs_annot_scan.h).  The file is parsed against the database's @SQ
+ * names and lengths under the rules and with the messages of `enumerate --annotate` (cli::read_bed: 1-based line and reason;
+ * ';' in a group name), and its table is built and attached once, when the decoder is opened, before the first batch.
+ * Complete mode gains the column match_features, succinct mode the four columns distance_k_feature_matches.
+ * --features-only (complete mode, with --annotate; anything else is a usage error before any file is read): only the rows
+ * that have a feature, match_number as in the full table.  Every --bgzf, --fasta, input and output choice takes it.
  */
 #ifndef GS_DECODE_CMD_HPP
 #define GS_DECODE_CMD_HPP
@@ -42,6 +49,7 @@
 #include <vector>
 
 #include "guidescan_amd.h"
+#include "cli_common.hpp"
 #include "fasta_names.hpp"
 
 namespace decode_cmd {
@@ -216,6 +224,25 @@ struct job {
   uint64_t done = 0; /* records decoded so far */
   FILE *out = nullptr;
   std::string err;
+  std::string annotate;      /* --annotate BED: parsed against the database's @SQ lines when the decoder is opened */
+  gs_annot *annot = nullptr; /* its table on the decoder's device; freed after the decoder is closed */
+  bool reported = false;     /* the failure has been printed already (cli::read_bed prints its own) */
+  /* the annotation, once, before the first batch: the rules and messages of `enumerate --annotate` */
+  bool attach_annotation(int device, const cli::genome_structure &gs) {
+    gs_regions *bed = nullptr;
+    if (!cli::read_bed(annotate, gs, "", "annotation", &bed)) {
+      reported = true;
+      return false;
+    }
+    gs_status rc = gs_annot_build(bed, device, &annot);
+    gs_regions_free(bed);
+    if (rc == GS_OK) rc = gs_decoder_set_annotation(dec, annot);
+    if (rc != GS_OK) {
+      err = "annotation file " + annotate + ": " + gs_status_string(rc);
+      return false;
+    }
+    return true;
+  }
   bool write(const char *p, size_t n) {
     const double t0 = now_s();
     const bool ok = !n || fwrite(p, 1, n, out) == n;
@@ -309,6 +336,7 @@ inline bool open_decoder(job &j, int device, const sq_list &sq, const fasta_reco
     j.err = gs_status_string(rc);
     return false;
   }
+  if (!j.annotate.empty() && !j.attach_annotation(device, cli::genome_structure{sq.names, sq.lengths})) return false;
   return j.write_header();
 }
 
@@ -597,9 +625,9 @@ inline bool decode_bam_file_gpu(job &j, const std::string &path, int device, con
 
 /* -> exit status; 2 = usage */
 inline int run(int argc, char **argv) {
-  std::string mode = "succinct", output, database, fasta, bgzf = "host", fasta_on = "host";
+  std::string mode = "succinct", output, database, fasta, bgzf = "host", fasta_on = "host", annotate;
   int device = 0;
-  bool verbose = false;
+  bool verbose = false, features_only = false;
   long long batch_records = 1 << 20;
   std::vector<std::string> positional;
   for (int i = 0; i < argc; i++) {
@@ -617,6 +645,10 @@ inline int run(int argc, char **argv) {
       bgzf = argv[++i];
     } else if (a == "--fasta" && i + 1 < argc) {
       fasta_on = argv[++i];
+    } else if (a == "--annotate" && i + 1 < argc) {
+      annotate = argv[++i];
+    } else if (a == "--features-only") {
+      features_only = true;
     } else if (a == "--verbose") {
       verbose = true;
     } else if (a == "-o" && i + 1 < argc) {
@@ -630,10 +662,16 @@ inline int run(int argc, char **argv) {
   if (positional.size() != 2 || (mode != "succinct" && mode != "complete") || (bgzf != "host" && bgzf != "gpu") ||
       (fasta_on != "host" && fasta_on != "gpu"))
     return 2;
+  if (features_only && (annotate.empty() || mode != "complete")) { /* before any file is read */
+    std::cerr << "error: --features-only leaves out the rows of --mode complete that have no feature of --annotate: give both\n";
+    return 2;
+  }
   database = positional[0];
   fasta = positional[1];
   job j;
-  j.flags = mode == "complete" ? GS_TEXT_COMPLETE : 0u;
+  j.annotate = annotate;
+  j.flags = (mode == "complete" ? GS_TEXT_COMPLETE : 0u) | (annotate.empty() ? 0u : GS_TEXT_FEATURES) |
+            (features_only ? GS_DECODE_FEATURES_ONLY : 0u);
   unsigned char magic[2] = {0, 0};
   {
     std::ifstream in(database, std::ios::binary);
@@ -672,6 +710,7 @@ inline int run(int argc, char **argv) {
             : bgzf == "gpu" ? decode_bam_file_gpu(j, database, device, fa, (uint64_t)batch_records, batch_bytes, &dev_members, &dev_inflated)
                             : decode_bam_file(j, database, device, fa, (uint64_t)batch_records, batch_bytes);
   if (j.dec) gs_decoder_close(j.dec);
+  gs_annot_free(j.annot); /* after the decoder it was attached to */
   gs_fasta_free(j.gfa); /* still there when the database failed before the decoder was opened */
   if (ok && fflush(j.out) != 0) {
     ok = false;
@@ -679,7 +718,7 @@ inline int run(int argc, char **argv) {
   }
   if (!output.empty()) fclose(j.out);
   if (!ok) {
-    std::cerr << "error: " << j.err << "\n";
+    if (!j.reported) std::cerr << "error: " << j.err << "\n";
     if (!output.empty()) remove(output.c_str());
     return 1;
   }

@@ -39,6 +39,7 @@ namespace enumerate_cmd {
 
 using cli::genome_structure;
 using cli::kmer_row;
+using cli::read_bed;
 
 /* --bulge-form's default.  Measured at hg38 size (profiles/bulge_seeded.json): 4,096 guides at -m 1 with one
  * bulge of each kind take the walk 0.22 s and the seeded form 1.10 s at best, so the walk stays the default */
@@ -769,25 +770,7 @@ inline bool read_guides_device(const options &o, enumerate_job &job, candidate_s
   return true;
 }
 
-/* --regions: the BED file against PREFIX.gs; the parser's message with its line number */
-inline bool read_bed(const std::string &path, const genome_structure &gs, const std::string &prefix, const std::string &what,
-                     gs_regions **out) {
-  std::vector<const char *> names;
-  for (auto &n : gs.names) names.push_back(n.c_str());
-  const gs_genome_structure cgs{names.data(), gs.lengths.data(), (uint32_t)names.size()};
-  gs_regions_report rep;
-  const gs_status rc = gs_regions_parse_file(path.c_str(), &cgs, prefix.c_str(), out, &rep);
-  if (rc == GS_OK) return true;
-  if (rc == GS_ERR_FORMAT && rep.bad_text) { /* the parser says "regions line N: ..." / "regions file: ..." */
-    const std::string msg = rep.bad_text;
-    std::cerr << "error: " << (msg.compare(0, 7, "regions") == 0 ? what + msg.substr(7) : msg) << " (" << path << ")\n";
-  } else if (rc == GS_ERR_IO)
-    std::cerr << "error: cannot read the " << what << " file " << path << "\n";
-  else
-    std::cerr << "error: " << what << " file " << path << ": " << gs_status_string(rc) << "\n";
-  gs_free(rep.bad_text);
-  return false;
-}
+/* --regions: the BED file against PREFIX.gs (cli::read_bed) */
 inline bool read_regions(const std::string &path, const genome_structure &gs, const std::string &prefix, candidate_set &cand) {
   return read_bed(path, gs, prefix, "regions", &cand.regions);
 }

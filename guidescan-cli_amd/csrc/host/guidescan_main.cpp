@@ -60,7 +60,7 @@
  *       reference's fan-out over threads).  On every device the search of batch i+1 overlaps the text
  *       formatting of batch i.
  *   guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--bgzf host|gpu] [--fasta host|gpu]
- *       DATABASE GENOME.fa
+ *       [--annotate BED [--features-only]] DATABASE GENOME.fa
  *       the CSV scripts/decode_database.py prints for a SAM/BAM database, decoded on the device (decode_cmd.hpp);
  *       stdout unless -o.  SEQ of at most 32 symbols.  The table streams, so only -o is all or nothing: stdout has
  *       the header and the earlier batches' rows when a later record fails.
@@ -175,7 +175,11 @@ int usage() {
                "                 off-target overlaps, joined by ';', or NA.  --max-feature-hits K (with --regions): a candidate\n"
                "                 with more than K off-targets within D mismatches (default: -m) inside a feature is not eligible\n"
                "       guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--verbose]\n"
-               "                 [--bgzf host|gpu] [--fasta host|gpu] DATABASE GENOME.fa\n"
+               "                 [--bgzf host|gpu] [--fasta host|gpu] [--annotate BED [--features-only]] DATABASE GENOME.fa\n"
+               "                 --annotate: the features of a BED file, read against the database's @SQ lines, in the pass that\n"
+               "                 decodes: --mode complete gains the column match_features (the groups each off-target overlaps,\n"
+               "                 joined by ';', or NA), --mode succinct the columns distance_k_feature_matches.  --features-only\n"
+               "                 (--mode complete): only the rows with a feature; match_number as in the full table.\n"
                "                 --bgzf gpu (a BAM database only): the file is inflated and split into records on the device.\n"
                "                 --fasta gpu: GENOME.fa is parsed on the device and its text stays there; same table and messages,\n"
                "                 but GENOME.fa must be a regular file (a pipe, which --fasta host reads, is \"cannot read\").\n"

@@ -982,6 +982,36 @@ gs_status gs_decode_records_device(gs_decoder *dec, const gs_decode_batch *batch
  * fewer than eleven fields or a FLAG or POS that is no number: GS_ERR_FORMAT. */
 gs_status gs_decode_sam(gs_decoder *dec, const char *sam, uint64_t sam_len, uint32_t flags, uint64_t first_record, char **text,
                         uint64_t *len, uint64_t *n_records);
+
+/* A decoded database annotated with the features of a BED file, in the pass that decodes it (no counterpart in the
+ * reference: its users join the decoded CSV against the BED file in a script; the database keeps the reference's format, no
+ * tag is added, so any database is annotatable).  The rule, stated once (gs_annot_scan.h: gs_an_decoded_footprint): an
+ * off-target of a record whose stored SEQ has n symbols, decoded to chromosome c (LN bases by its @SQ line), coordinate x (as
+ * map_int_to_coord, :38-50, gives it) and a strand, occupies the forward-strand bases the script slices: [x + 1 - n, x + 1)
+ * on '+', [x, x + n) on '-', clipped to [0, LN) - by LN, not by the FASTA record's length, and without Python's wrap of a
+ * negative slice start: a row whose printed sequence is short or wrapped is annotated by where it lies.  The row has
+ * feature g iff that footprint shares a base with an interval of group g on c (overlap, as for GS_TEXT_FEATURES above);
+ * features are distinct and ascend by group number; an empty footprint has none.
+ * gs_decoder_set_annotation attaches an annotation, NULL detaches it; the annotation stays the caller's and must outlive
+ * its attachment.  GS_ERR_ARG: an annotation built for another device or for the host only, or one whose chromosome count
+ * or lengths differ from the decoder's @SQ table.
+ * GS_TEXT_FEATURES is then valid in the flags of gs_decode_records, gs_decode_records_device, gs_decode_sam, gs_decode_bam
+ * and gs_decode_bam_device; without an attached annotation it is GS_ERR_ARG; without the flag every byte is what it was.
+ *   complete mode: the header (gs_decode_sam) ends in ",match_features", every row in ',' and the group names joined by
+ *     ';', or NA.
+ *   succinct mode: the header ends in ",distance_0_feature_matches,...,distance_3_feature_matches", every row in those four
+ *     counts: the record's off-targets at that distance that have at least one feature, counted exactly as
+ *     distance_k_matches counts - every off-target of the list, the record's own site included.
+ * GS_DECODE_FEATURES_ONLY (only with GS_TEXT_FEATURES | GS_TEXT_COMPLETE, else GS_ERR_ARG): rows without a feature are left
+ * out; match_number stays the rank among all of the record's off-targets, so the table joins against the full one; *n_rows
+ * counts the rows written.
+ * The script's failures stay GS_ERR_FORMAT with the same record and reason as without the flag, and win over anything the
+ * annotation does (a row of 32 MB or more, GS_ERR_UNSUPPORTED, is looked for only in a batch that has none). */
+#define GS_DECODE_FEATURES_ONLY 0x8000u
+gs_status gs_decoder_set_annotation(gs_decoder *dec, const gs_annot *annot);
+/* the milliseconds of the annotation pass in the decoder's last batch that ran one, between two stream events (no
+ * counterpart in the reference) */
+gs_status gs_debug_decode_annot_ms(gs_decoder *dec, double *ms);
 /* Host only: Python's repr() of n doubles, 32 bytes each, NUL padded - the routine the decoder's kernels print with. */
 gs_status gs_debug_repr_doubles(const double *v, uint64_t n, char *out);
 /* Host only: the CFD tables the decoder uploads: mm[(r * 4 + d) * 20 + i] for the key r{ACGU}:d{ACGT},i+1 (320), pam[16] */
@@ -1032,7 +1062,8 @@ gs_status gs_debug_bgzf_members(const void *bgzf, uint64_t len, uint64_t *member
  * belong to the BAM header (magic, text, reference list); a call with skip != 0 begins a file, and a file's header lies
  * within its first call.  ref_to_sq[n_ref]: the binary reference list's entries as indices of the decoder's
  * chromosomes, negative: no @SQ line (such a record, like one with a negative refID, prints None).  Rows only, no header
- * line; flags: GS_TEXT_COMPLETE, GS_DECODE_BAM_END.  *n_records: the complete records of this call (the next call's
+ * line; flags: GS_TEXT_COMPLETE, GS_DECODE_BAM_END, GS_TEXT_FEATURES [| GS_DECODE_FEATURES_ONLY] as gs_decode_records takes
+ * them (checked before anything is inflated).  *n_records: the complete records of this call (the next call's
  * first_record grows by it); *tail: the bytes of a record cut by the end of these members.  The decoder keeps them
  * and the next call's records begin with them, so a file streams in groups of members and the output does not depend
  * on where the groups are cut.  With GS_DECODE_BAM_END a tail is an error.  GS_ERR_FORMAT names the first record in

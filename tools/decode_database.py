@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Turns the SAM or BAM database that `guidescan enumerate --format sam|bam` wrote back into a readable CSV table.  It
 takes the arguments of the reference's scripts/decode_database.py and prints the same bytes, without that script's
-pysam and Biopython dependencies."""
+pysam and Biopython dependencies.  --annotate BED (this project's own, as `guidescan decode --annotate`) adds the features
+of a BED file to the table."""
 import argparse
 import sys
 from importlib import import_module
@@ -19,8 +20,16 @@ if __name__ == "__main__":
                     help="one row per database record with counts and specificity, or one row per off-target")
     ap.add_argument("--device", type=int, default=None,
                     help="decode on this GPU (gs_decode_records) instead of the Python restatement")
+    ap.add_argument("--annotate", metavar="BED", default=None,
+                    help="a match_features column (complete) or four distance_k_feature_matches columns (succinct): the "
+                         "groups of the BED file that each off-target overlaps")
+    ap.add_argument("--features-only", action="store_true",
+                    help="with --annotate and --mode complete: only the rows that have a feature")
     a = ap.parse_args()
+    if a.features_only and (a.annotate is None or a.mode != "complete"):
+        ap.error("--features-only needs --annotate and --mode complete")
     try:
-        sys.stdout.write(decode.decode_database(a.grna_database, a.fasta_file, a.mode, a.device))
-    except (decode.DecodeError, RuntimeError) as e:
+        sys.stdout.write(decode.decode_database(a.grna_database, a.fasta_file, a.mode, a.device, annotate=a.annotate,
+                                                features_only=a.features_only))
+    except (decode.DecodeError, RuntimeError, ValueError) as e:
         sys.exit(f"error: {e}")
