@@ -93,6 +93,11 @@ class GsRegionsReport(C.Structure):
                 ("bad_text", C.c_void_p)]
 
 
+class GsPairRule(C.Structure):
+    _fields_ = [("min_span", C.c_uint64), ("max_span", C.c_uint64), ("cut_offset", C.c_uint32), ("orientation", C.c_uint32),
+                ("per_region", C.c_uint32), ("flags", C.c_uint32), ("min_specificity", C.c_float), ("pad", C.c_uint32)]
+
+
 def build_library():
     subprocess.run(["make", "-s", "-C", str(PKG / "csrc")], check=True, timeout=3600)
 
@@ -378,6 +383,22 @@ def lib():
     L.gs_design_set_feature_rule.argtypes = [vp, vp, u32, u32]
     L.gs_design_get_feature_hits.restype = i32
     L.gs_design_get_feature_hits.argtypes = [vp, C.POINTER(vp)]
+    L.gs_design_pairs.restype = i32
+    L.gs_design_pairs.argtypes = [vp, C.c_char_p, C.POINTER(GsPairRule), vp, C.POINTER(vp), C.POINTER(vp)]
+    L.gs_pairs_get.restype = i32
+    L.gs_pairs_get.argtypes = [vp, C.POINTER(u64)] + [C.POINTER(vp)] * 8
+    L.gs_pairs_rows.restype = i32
+    L.gs_pairs_rows.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(u64)]
+    L.gs_pairs_last.restype = i32
+    L.gs_pairs_last.argtypes = [vp, vp]
+    L.gs_pairs_ms.restype = i32
+    L.gs_pairs_ms.argtypes = [vp, vp]
+    L.gs_pairs_free.restype = None
+    L.gs_pairs_free.argtypes = [vp]
+    L.gs_debug_pairs_host.restype = i32
+    L.gs_debug_pairs_host.argtypes = [u64, vp, vp, vp, vp, vp, vp, u32, u32, u32, C.POINTER(GsPairRule), C.POINTER(vp)]
+    L.gs_debug_pairs_chunk.restype = u64
+    L.gs_debug_pairs_chunk.argtypes = [u64]
     L.gs_decoder_set_annotation.restype = i32
     L.gs_decoder_set_annotation.argtypes = [vp, vp]
     L.gs_debug_decode_annot_ms.restype = i32
@@ -424,7 +445,9 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_annotate_device", "gs_annotate", "gs_debug_annotate_host", "gs_index_set_annotation",
            "gs_format_guides_features", "gs_format_guide_features", "gs_format_guide_ex_features",
            "gs_design_set_feature_rule", "gs_design_get_feature_hits",
-           "gs_decoder_set_annotation", "gs_debug_decode_annot_ms"]
+           "gs_decoder_set_annotation", "gs_debug_decode_annot_ms",
+           "gs_design_pairs", "gs_pairs_get", "gs_pairs_rows", "gs_pairs_last", "gs_pairs_ms", "gs_pairs_free", "gs_debug_pairs_host",
+           "gs_debug_pairs_chunk"]
 
 
 def _check(rc):
@@ -1005,6 +1028,22 @@ class Design:
         lib().gs_free(out)
         return t
 
+    def pairs(self, prefix, max_span, min_span=1, cut_offset=3, orientation="any", per_region=None, min_specificity=None,
+              start=False):
+        """the guide pairs of every group under the rule of csrc/gs_pairs_scan.h (gs_design_pairs): cuts min_span to
+        max_span apart on one chromosome, orientation "any", "pam-out" or "pam-in", ranked by the smaller specificity, the
+        first per_region of each group -> (DeviceKmers with ids: the guides of the kept pairs, Pairs)"""
+        rule = _pair_rule(max_span, min_span, cut_offset, orientation, per_region, min_specificity, start)
+        h, ph = C.c_void_p(), C.c_void_p()
+        _check(lib().gs_design_pairs(self._h, prefix.encode(), C.byref(rule), None, C.byref(h), C.byref(ph)))
+        km = _selected_kmers(h, self.k, self.P)
+        a, b, c, d = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().gs_kmers_get(h, 1, None, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        km.seqs_ptr, km.pams_ptr, km.pos_ptr, km.sense_ptr = a.value, b.value, c.value, d.value
+        _check(lib().gs_kmers_get_ids(h, 1, C.byref(a), C.byref(b), C.byref(c)))
+        km.ids_ptr, km.id_offsets_ptr, km.sense_positive_ptr = a.value, b.value, c.value
+        return km, Pairs(ph)
+
     def to_host(self):
         """-> dict(n, group uint32[n], chr uint32[n], pos uint32[n], sense uint8[n], spec float32[n], eligible uint8[n]);
         after a score() under set_feature_rule also feature_hits uint32[n]"""
@@ -1042,6 +1081,90 @@ class Design:
             self.close()
         except Exception:
             pass
+
+
+ORIENTATIONS = {"any": 0, "pam-out": 1, "pam-in": 2}
+
+
+def _pair_rule(max_span, min_span, cut_offset, orientation, per_region, min_specificity, start):
+    if orientation not in ORIENTATIONS:
+        raise ValueError('orientation: "any", "pam-out" or "pam-in"')
+    n, s = _select_args(per_region, min_specificity)
+    return GsPairRule(int(min_span), int(max_span), int(cut_offset), ORIENTATIONS[orientation], n,
+                      GS_FLAG_PAM_AT_START if start else 0, s, 0)
+
+
+class Pairs:
+    """The kept pairs of Design.pairs / pairs_host (gs_pairs), on the host."""
+    COLUMNS = (("group", np.uint32), ("chr", np.uint32), ("a", np.uint32), ("b", np.uint32), ("cut_a", np.uint32),
+               ("cut_b", np.uint32), ("spec_a", np.float32), ("spec_b", np.float32))
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def to_host(self):
+        """-> dict(n, group, chr, a, b, cut_a, cut_b uint32[n], spec_a, spec_b float32[n]); a and b are places in the
+        guides object (record indices from pairs_host)"""
+        n = C.c_uint64()
+        p = [C.c_void_p() for _ in range(8)]
+        _check(lib().gs_pairs_get(self._h, C.byref(n), *[C.byref(x) for x in p]))
+        m = int(n.value)
+        out = {"n": m}
+        for (name, dt), x in zip(self.COLUMNS, p):
+            out[name] = np.frombuffer(C.string_at(x, 4 * m), dtype=dt).copy() if m else np.empty(0, dt)
+        return out
+
+    def rows(self, guides) -> bytes:
+        """the table, header included, with the ids of `guides`, the object that came with these pairs (gs_pairs_rows)"""
+        out, ln = C.c_void_p(), C.c_uint64()
+        _check(lib().gs_pairs_rows(self._h, guides._h, C.byref(out), C.byref(ln)))
+        t = C.string_at(out, ln.value)
+        lib().gs_free(out)
+        return t
+
+    def last(self):
+        out = (C.c_uint64 * 6)()
+        _check(lib().gs_pairs_last(self._h, out))
+        return dict(zip(("eligible", "counted", "kept", "chunks", "groups_without", "groups_short"), (int(x) for x in out)))
+
+    def ms(self):
+        """the milliseconds of Design.pairs' stages between stream events (gs_pairs_ms)"""
+        out = (C.c_double * 8)()
+        _check(lib().gs_pairs_ms(self._h, out))
+        return dict(zip(("compact", "order", "count", "offsets", "emit", "rank", "keep", "guides"), (float(x) for x in out)))
+
+    def close(self):
+        if self._h:
+            lib().gs_pairs_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pairs_chunk(set_to=0) -> int:
+    """the most pairs a chunk of Design.pairs holds; set_to != 0 sets it (gs_debug_pairs_chunk)"""
+    return int(lib().gs_debug_pairs_chunk(set_to))
+
+
+def pairs_host(group, chr, pos, sense, spec, eligible, k, P, n_groups, max_span, min_span=1, cut_offset=3, orientation="any",
+               per_region=None, min_specificity=None, start=False):
+    """the passes of Design.pairs on the host through the kernels' shared header, no GPU (gs_debug_pairs_host), over
+    plain arrays of records -> (Pairs.to_host() with a and b as record indices, Pairs.last())"""
+    rule = _pair_rule(max_span, min_span, cut_offset, orientation, per_region, min_specificity, start)
+    cols = [np.ascontiguousarray(x, dtype=dt) for x, dt in
+            ((group, np.uint32), (chr, np.uint32), (pos, np.uint32), (sense, np.uint8), (spec, np.float32), (eligible, np.uint8))]
+    n = cols[0].shape[0]
+    h = C.c_void_p()
+    _check(lib().gs_debug_pairs_host(n, *[c.ctypes.data if n else None for c in cols], k, P, n_groups, C.byref(rule), C.byref(h)))
+    pr = Pairs(h)
+    try:
+        return pr.to_host(), pr.last()
+    finally:
+        pr.close()
 
 
 def design(index, regions, pam, k, per_region=None, min_specificity=None, *, chromosomes, mismatches=3, alt_pams=(),

@@ -490,6 +490,8 @@ void gs_opts_from_env(gs_index *ix);
 extern std::atomic<int> gs_debug_any; /* some handle has GS_DEBUG set: the allocator reports large growth */
 /* gs_host.hip: tl bytes of text in HBM -> *text, malloc'ed and NUL terminated, through page-locked staging */
 gs_status gs_text_to_host(const void *d_text, uint64_t tl, char **text);
+/* gs_text.hip: a float as the CSV's specificity column prints it, std::to_string(float) */
+std::string gs_f2s(float f);
 
 /* GPU suffix array: d_text (n bytes incl. sentinel) -> d_sa (n uint32) */
 gs_status gs_device_suffix_array(const uint8_t *d_text, uint64_t n, uint32_t *d_sa, hipStream_t st);

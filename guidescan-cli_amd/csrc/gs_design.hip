@@ -32,6 +32,7 @@
 #include "gs_regions_scan.h"
 #include "gs_regions_obj.h"
 #include "gs_annot_obj.h"
+#include "gs_design_obj.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -225,29 +226,6 @@ extern "C" void gs_regions_free(gs_regions *rg) { delete rg; }
 
 /* ---- the design: the records of (candidate, group) ---------------------------------------------------------------- */
 
-struct gs_design {
-  int device = 0; /* -1: made on the host (gs_debug_design_host), nothing in HBM */
-  const gs_regions *rg = nullptr;
-  uint64_t n = 0;
-  uint32_t k = 0, P = 0;
-  bool scored = false;
-  /* per record, in HBM: the layout gs_enumerate_device takes, then where the record comes from and what it scored */
-  void *d_seqs = nullptr, *d_pams = nullptr, *d_pos = nullptr, *d_sense = nullptr, *d_group = nullptr, *d_chr = nullptr,
-       *d_spec = nullptr, *d_elig = nullptr;
-  std::vector<uint8_t> h_seqs, h_pams, h_sense, h_elig;
-  std::vector<uint32_t> h_pos, h_group, h_chr;
-  std::vector<float> h_spec;
-  bool have_host = false;
-  uint64_t last[4] = {0, 0, 0, 0}; /* of the last select: records, kept, groups left empty, groups short of N */
-  /* gs_design_set_feature_rule: the score phase counts, per record, the off-target hits within rule_distance that have a
-   * feature of rule_annot (d_fhits, uint32[n]); more than rule_max of them and the record is not eligible */
-  const gs_annot *rule_annot = nullptr;
-  uint32_t rule_distance = 0, rule_max = 0;
-  void *d_fhits = nullptr;
-  bool have_fhits = false;
-  std::vector<uint32_t> h_fhits;
-};
-
 static void ds_release(gs_design *d) {
   if (!d) return;
   bool any = false;
@@ -259,7 +237,7 @@ static void ds_release(gs_design *d) {
 }
 typedef std::unique_ptr<gs_design, void (*)(gs_design *)> ds_owner;
 
-static gs_status ds_array(size_t bytes, void **out) { /* an array of an object: its release frees it */
+gs_status gs_ds_array(size_t bytes, void **out) { /* an array of an object: its release frees it */
   gs_scratch one;
   GS_TRY(one.get(bytes, out));
   one.keep(*out);
@@ -268,14 +246,14 @@ static gs_status ds_array(size_t bytes, void **out) { /* an array of an object: 
 /* the arrays of n records; every record eligible and unscored */
 static gs_status ds_alloc(gs_design *d, hipStream_t st) {
   const size_t n = (size_t)d->n;
-  GS_TRY(ds_array(n * d->k, &d->d_seqs));
-  GS_TRY(ds_array(n * d->P, &d->d_pams));
-  GS_TRY(ds_array(4 * n, &d->d_pos));
-  GS_TRY(ds_array(n, &d->d_sense));
-  GS_TRY(ds_array(4 * n, &d->d_group));
-  GS_TRY(ds_array(4 * n, &d->d_chr));
-  GS_TRY(ds_array(4 * n, &d->d_spec));
-  GS_TRY(ds_array(n, &d->d_elig));
+  GS_TRY(gs_ds_array(n * d->k, &d->d_seqs));
+  GS_TRY(gs_ds_array(n * d->P, &d->d_pams));
+  GS_TRY(gs_ds_array(4 * n, &d->d_pos));
+  GS_TRY(gs_ds_array(n, &d->d_sense));
+  GS_TRY(gs_ds_array(4 * n, &d->d_group));
+  GS_TRY(gs_ds_array(4 * n, &d->d_chr));
+  GS_TRY(gs_ds_array(4 * n, &d->d_spec));
+  GS_TRY(gs_ds_array(n, &d->d_elig));
   GS_HIP(hipMemsetAsync(d->d_spec, 0, 4 * n + 16, st));
   GS_HIP(hipMemsetAsync(d->d_elig, 1, n + 16, st));
   return GS_OK;
@@ -561,7 +539,7 @@ extern "C" gs_status gs_design_score(gs_index *ix, gs_design *d, const char *alt
     GS_TRY(gs_index_lock(ix));
     lock.held = true;
     if (d->rule_annot) {
-      if (!d->d_fhits) GS_TRY(ds_array(4 * (size_t)d->n, &d->d_fhits));
+      if (!d->d_fhits) GS_TRY(gs_ds_array(4 * (size_t)d->n, &d->d_fhits));
       GS_HIP(hipMemsetAsync(d->d_fhits, 0, 4 * (size_t)d->n + 16, st));
       if (threshold < 0) GS_HIP(hipMemsetAsync(d->d_elig, 1, (size_t)d->n + 16, st)); /* the rule alone decides */
     }
@@ -670,6 +648,7 @@ struct gs_ds_gather_args {
   const uint32_t *pos, *group, *chr, *order, *keep, *place;
   uint8_t *o_seqs, *o_pams, *o_sense;
   uint32_t *o_pos, *o_group, *o_chr;
+  uint32_t *place_of; /* or null: per record, where it went */
   uint64_t n;
   uint32_t k, P;
 };
@@ -683,6 +662,7 @@ __global__ __launch_bounds__(DS_BLOCK) void k_ds_gather(gs_ds_gather_args a) {
   a.o_sense[o] = a.sense[r];
   a.o_group[o] = a.group[r];
   a.o_chr[o] = a.chr[r];
+  if (a.place_of) a.place_of[r] = (uint32_t)o;
 }
 
 struct gs_ds_text_args {
@@ -787,9 +767,12 @@ static void ds_group_tally(gs_design *d, uint64_t kept, const std::vector<uint32
 }
 
 /* the kept records in order as a gs_kmers with ids (rows == false), or their kmers-file rows in HBM (*d_text, the
- * caller's to free) */
-static gs_status ds_select(gs_design *d, const char *prefix, uint32_t per_region, bool filter, float min_spec, hipStream_t st,
-                           bool rows, gs_kmers **out, void **d_text, uint64_t *text_bytes) {
+ * caller's to free); gs_design_obj.h */
+gs_status gs_ds_select(gs_design *d, const char *prefix, const gs_ds_select_rule &rule, hipStream_t st, bool rows, gs_kmers **out,
+                       void **d_text, uint64_t *text_bytes) {
+  const uint32_t per_region = rule.per_region;
+  const bool filter = rule.filter;
+  const float min_spec = rule.min_spec;
   const uint64_t n = d->n;
   const uint32_t k = d->k, P = d->P;
   const size_t n_groups = d->rg->group_names.size();
@@ -822,7 +805,7 @@ static gs_status ds_select(gs_design *d, const char *prefix, uint32_t per_region
     a.chr = (const uint32_t *)d->d_chr;
     a.pos = (const uint32_t *)d->d_pos;
     a.sense = (const uint8_t *)d->d_sense;
-    a.elig = (const uint8_t *)d->d_elig;
+    a.elig = rule.d_elig;
     a.spec = (const float *)d->d_spec;
     a.hi = hi;
     a.lo = lo;
@@ -869,10 +852,10 @@ static gs_status ds_select(gs_design *d, const char *prefix, uint32_t per_region
     GS_HIP(hipStreamSynchronize(st));
     m = m32;
     if (m) {
-      GS_TRY(ds_array((size_t)m * k, &km->d_seqs));
-      GS_TRY(ds_array((size_t)m * P, &km->d_pams));
-      GS_TRY(ds_array(4 * (size_t)m, &km->d_pos));
-      GS_TRY(ds_array((size_t)m, &km->d_sense));
+      GS_TRY(gs_ds_array((size_t)m * k, &km->d_seqs));
+      GS_TRY(gs_ds_array((size_t)m * P, &km->d_pams));
+      GS_TRY(gs_ds_array(4 * (size_t)m, &km->d_pos));
+      GS_TRY(gs_ds_array((size_t)m, &km->d_sense));
       GS_TRY(mem.get(4 * m, &o_group));
       GS_TRY(mem.get(4 * m, &o_chr));
       gs_ds_gather_args ga;
@@ -892,13 +875,14 @@ static gs_status ds_select(gs_design *d, const char *prefix, uint32_t per_region
       ga.o_pos = (uint32_t *)km->d_pos;
       ga.o_group = o_group;
       ga.o_chr = o_chr;
+      ga.place_of = rule.d_place;
       ga.n = n;
       ga.k = k;
       ga.P = P;
       hipLaunchKernelGGL(k_ds_gather, grid, block, 0, st, ga);
     }
   }
-  ds_group_tally(d, m, kept_of_group, per_region);
+  if (rule.tally) ds_group_tally(d, m, kept_of_group, per_region);
   km->n = m;
   /* the text: ids or rows */
   std::string names;
@@ -982,7 +966,8 @@ extern "C" gs_status gs_design_select(gs_design *d, const char *prefix, uint32_t
   if (d->device < 0) return GS_ERR_ARG;
   *out = nullptr;
   try {
-    return ds_select(d, prefix, per_region, filter, min_specificity, (hipStream_t)stream, false, out, nullptr, nullptr);
+    const gs_ds_select_rule rule{(const uint8_t *)d->d_elig, per_region, filter, min_specificity, nullptr, true};
+    return gs_ds_select(d, prefix, rule, (hipStream_t)stream, false, out, nullptr, nullptr);
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;
   }
@@ -1000,7 +985,8 @@ extern "C" gs_status gs_design_rows(gs_design *d, const char *prefix, uint32_t p
   uint64_t bytes = 0;
   gs_status rc;
   try {
-    rc = ds_select(d, prefix, per_region, filter, min_specificity, (hipStream_t)stream, true, nullptr, &d_text, &bytes);
+    const gs_ds_select_rule rule{(const uint8_t *)d->d_elig, per_region, filter, min_specificity, nullptr, true};
+    rc = gs_ds_select(d, prefix, rule, (hipStream_t)stream, true, nullptr, &d_text, &bytes);
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;
   }

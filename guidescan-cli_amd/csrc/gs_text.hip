@@ -120,6 +120,8 @@ gs_status features_args(const gs_genome_structure *gs, uint32_t flags, const gs_
 
 }  // namespace
 
+std::string gs_f2s(float f) { return f2s(f); } /* for the other tables that print a specificity (gs_pairs.hip) */
+
 /* spec: the guide's specificity when the caller already has it (gs_score / gs_score_device:
  * the same float, computed on the device); nullptr = compute CFD and the sum here */
 static gs_status format_decoded(const gs_genome_structure *gs, const gs_kmer *k,

@@ -70,7 +70,11 @@ struct options {
    * within D mismatches (default: -m) inside a feature is not eligible */
   std::string annotate;
   long long max_feature_hits = -1, feature_distance = -1; /* -1: not given */
-  bool selects() const { return per_region > 0 || min_spec >= 0.0f || max_feature_hits >= 0; }
+  /* --pairs FILE --max-span X [--min-span Y] [--cut-offset C] [--pair-orientation any|pam-out|pam-in] (with --regions): the
+   * guides are those of the best --per-region pairs of each group (gs_design_pairs), and FILE is the table of the pairs */
+  std::string pairs, pair_orientation;
+  long long max_span = -1, min_span = -1, cut_offset = -1; /* -1: not given */
+  bool selects() const { return per_region > 0 || min_spec >= 0.0f || max_feature_hits >= 0 || !pairs.empty(); }
 };
 
 /* the command line into `o`, validated.  0: go on; otherwise the exit status */
@@ -141,8 +145,46 @@ inline int parse_options(int argc, char **argv, int (*usage)(), options &o) {
       }
       (a == "--max-feature-hits" ? o.max_feature_hits : o.feature_distance) = k;
     }
+    else if (a == "--pairs") o.pairs = need("--pairs");
+    else if (a == "--max-span" || a == "--min-span" || a == "--cut-offset") {
+      const char *v = need(a.c_str());
+      char *end = nullptr;
+      const long long k = v[0] >= '0' && v[0] <= '9' && strlen(v) <= 18 ? strtoll(v, &end, 10) : -1;
+      if (k < 0 || !end || *end) {
+        std::cerr << "error: " << a << " " << v << ": a number, 0 or more\n";
+        return 2;
+      }
+      (a == "--max-span" ? o.max_span : a == "--min-span" ? o.min_span : o.cut_offset) = k;
+    } else if (a == "--pair-orientation") {
+      o.pair_orientation = need("--pair-orientation");
+      if (o.pair_orientation != "any" && o.pair_orientation != "pam-out" && o.pair_orientation != "pam-in") {
+        std::cerr << "error: --pair-orientation " << o.pair_orientation << ": any, pam-out or pam-in\n";
+        return 2;
+      }
+    }
     else if (!a.empty() && a[0] != '-' && o.prefix.empty()) o.prefix = a;
     else return usage();
+  }
+  if (o.pairs.empty() && (o.max_span >= 0 || o.min_span >= 0 || o.cut_offset >= 0 || !o.pair_orientation.empty())) {
+    std::cerr << "error: --max-span, --min-span, --cut-offset and --pair-orientation describe the pairs of --pairs FILE\n";
+    return 2;
+  }
+  if (!o.pairs.empty()) { /* refused with one line each, before the genome is read */
+    const char *why = nullptr;
+    if (o.regions.empty() || !o.all_candidates) why = "--pairs pairs the guides within the groups of --all-candidates --regions BED";
+    else if (o.max_span < 0) why = "--pairs needs --max-span X, the largest distance between the two cuts";
+    else if (o.min_span > o.max_span) why = "--min-span is larger than --max-span";
+    else if (o.cut_offset > (long long)o.co.k) why = "--cut-offset lies beyond the k-mer length";
+    else if (o.rna > 0 || o.dna > 0 || o.mismatches > 7 || o.threshold > 7)
+      why = "--pairs scores on the fast path: no bulges, at most 7 mismatches";
+    else if (o.co.k > 31 || 2 * o.co.k + 3 * (long long)o.co.pam.size() > 59)
+      why = "--pairs scores on the fast path: 2L + 3P > 59, the shape is outside its key";
+    for (auto &a : o.alt_pams)
+      if (!why && a.size() != o.co.pam.size()) why = "--pairs scores on the fast path: an alt PAM is not of the PAM's length";
+    if (why) {
+      std::cerr << "error: " << why << "\n";
+      return 2;
+    }
   }
   if (!o.prefix.empty() && !o.output.empty() && o.kmers_file.empty() == !o.all_candidates) {
     std::cerr << (o.all_candidates ? "error: -f KMERS and --all-candidates exclude each other: the guides come from the file or from the scan\n"
@@ -848,18 +890,57 @@ inline bool select_design(const options &o, enumerate_job &job, candidate_set &c
       return false;
     }
   }
-  if (rc == GS_OK) rc = gs_design_select(cand.design, o.co.prefix.c_str(), (uint32_t)o.per_region, o.min_spec, nullptr, &cand.all);
-  uint64_t last[4] = {0, 0, 0, 0};
-  if (rc == GS_OK) gs_design_last_select(cand.design, last);
+  const bool paired = !o.pairs.empty();
+  uint64_t last[4] = {0, 0, 0, 0}, plast[6] = {0, 0, 0, 0, 0, 0};
+  if (rc == GS_OK && paired) { /* --per-region counts pairs: the guides are the members of the kept ones */
+    gs_pair_rule rule;
+    memset(&rule, 0, sizeof rule);
+    rule.min_span = o.min_span >= 0 ? (uint64_t)o.min_span : 1;
+    rule.max_span = (uint64_t)o.max_span;
+    rule.cut_offset = o.cut_offset >= 0 ? (uint32_t)o.cut_offset : 3;
+    rule.orientation = o.pair_orientation == "pam-out" ? GS_PAIRS_PAM_OUT : o.pair_orientation == "pam-in" ? GS_PAIRS_PAM_IN : GS_PAIRS_ANY;
+    rule.per_region = (uint32_t)o.per_region;
+    rule.flags = o.co.start ? GS_FLAG_PAM_AT_START : 0u;
+    rule.min_specificity = o.min_spec;
+    gs_pairs *pr = nullptr;
+    rc = gs_design_pairs(cand.design, o.co.prefix.c_str(), &rule, nullptr, &cand.all, &pr);
+    char *table = nullptr;
+    uint64_t len = 0;
+    if (rc == GS_OK) rc = gs_pairs_rows(pr, cand.all, &table, &len);
+    if (rc == GS_OK) gs_pairs_last(pr, plast);
+    gs_pairs_free(pr);
+    if (rc == GS_OK) { /* all or nothing, as -o is */
+      output_file pf;
+      bool ok = pf.open(o.pairs);
+      if (ok) {
+        pf.append(table, (size_t)len);
+        ok = pf.finish(false);
+      }
+      gs_free(table);
+      if (!ok) return false;
+    }
+  } else if (rc == GS_OK) {
+    rc = gs_design_select(cand.design, o.co.prefix.c_str(), (uint32_t)o.per_region, o.min_spec, nullptr, &cand.all);
+    if (rc == GS_OK) gs_design_last_select(cand.design, last);
+  }
   if (rc == GS_OK) rc = view_kmers(cand.all, 1, &cand.n, cand.d);
   if (rc != GS_OK) {
-    std::cerr << "error: selection for --regions: " << gs_status_string(rc) << "\n";
+    std::cerr << "error: " << (paired ? "pairs" : "selection") << " for --regions: " << gs_status_string(rc) << "\n";
     return false;
   }
   gs_design_free(cand.design);
   cand.design = nullptr;
   job.cand = &cand;
   job.cand_device = (o.encoder == "gpu" || o.bgzf == "gpu") && o.gpus == 1 && cand.L <= 31 && 2 * cand.L + 3 * cand.P <= 59;
+  if (paired) {
+    uint64_t n_groups = 0;
+    gs_regions_info(cand.regions, &n_groups, nullptr);
+    std::cout << "Paired " << plast[2] << " pair(s) of " << cand.n << " guide(s) in " << n_groups - plast[4] << " group(s)\n";
+    if (o.verbose)
+      std::cout << "Pairs: " << plast[1] << " counted among " << plast[0] << " eligible record(s) in " << plast[3] << " chunk(s); "
+                << plast[4] << " group(s) left without a pair, " << plast[5] << " group(s) short of --per-region\n";
+    return true;
+  }
   std::cout << "Selected " << cand.n << " guide(s) of " << last[0] << " record(s) in "
             << std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count() << " s\n";
   if (o.verbose)

@@ -47,6 +47,14 @@
  *       The file follows the rules of --regions.  --max-feature-hits K [--feature-distance D] (with --regions): the score
  *       phase also counts, per candidate, the off-targets within D mismatches (default: -m) that have a feature, the
  *       candidate's own site left out; more than K and the candidate is not eligible.
+ *       --pairs PAIRS.csv --max-span X [--min-span Y] [--cut-offset C] [--pair-orientation any|pam-out|pam-in] (with
+ *       --regions): pairs of guides inside each group whose cuts lie Y (default 1) to X bases apart on one chromosome
+ *       (gs_design_pairs; the rule is csrc/gs_pairs_scan.h's).  The cut leaves C (default 3) protospacer bases between it
+ *       and the PAM.  pam-out: the PAMs face away from each other; pam-in: towards each other.  Pairs are ranked by the
+ *       smaller of the two specificities, then the larger; --per-region N then keeps the best N pairs of each group, and
+ *       --min-specificity, -t and --max-feature-hits say which guides may pair.  PAIRS.csv is the table
+ *       group,id_a,id_b,chromosome,cut_a,cut_b,span,specificity_a,specificity_b,pair_specificity; the guides of the kept
+ *       pairs are the guides of the command, so OUT is their database in any format.  The score phase always runs.
  *       With -t and neither selection option there is no score phase: the pipeline's own threshold pass drops the guides.
  *       -f KMERS.csv --kmers gpu: the kmers file is parsed on the first device (gs_kmers_parse_file, the rules of
  *       cli::read_kmers) and the command goes on as --all-candidates does from its scan: sequences, PAMs, ids and
@@ -170,6 +178,11 @@ int usage() {
                "                 --regions: the guides are the candidates inside the BED file's intervals, one per group of\n"
                "                 intervals they lie in; --per-region N: the N most specific of each group; --min-specificity S:\n"
                "                 those of specificity >= S.  That score phase uses the first device only.\n"
+               "                 [--pairs PAIRS.csv --max-span X [--min-span Y] [--cut-offset C] [--pair-orientation any|pam-out|pam-in]]\n"
+               "                 --pairs (with --regions): pairs of guides of one group and chromosome whose cuts lie Y (default 1)\n"
+               "                 to X bases apart, the cut C (default 3) protospacer bases from the PAM; pam-out: the PAMs face\n"
+               "                 away from each other.  Ranked by the smaller specificity of the two; --per-region N keeps the best\n"
+               "                 N pairs of each group.  PAIRS.csv is their table, OUT the database of their guides.\n"
                "                 [--annotate BED [--max-feature-hits K [--feature-distance D]]]\n"
                "                 --annotate (CSV only): a match_features column, the groups of the BED file that each printed\n"
                "                 off-target overlaps, joined by ';', or NA.  --max-feature-hits K (with --regions): a candidate\n"
@@ -298,7 +311,7 @@ int do_kmers(int argc, char **argv) {
       output = argv[++i];
     else if (a == "--regions" && i + 1 < argc)
       regions = argv[++i];
-    else if (a == "--per-region" || a == "--min-specificity") {
+    else if (a == "--per-region" || a == "--min-specificity" || a == "--pairs") {
       std::cerr << "error: " << a << " ranks guides by specificity, which takes the index: use guidescan enumerate --all-candidates --regions\n";
       return 2;
     }

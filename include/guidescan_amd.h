@@ -910,6 +910,68 @@ gs_status gs_design_set_feature_rule(gs_design *design, const gs_annot *annot, u
  * reference); GS_ERR_ARG when that score phase ran without a rule */
 gs_status gs_design_get_feature_hits(gs_design *design, const void **counts);
 
+/* ---- guide pairs for regions ----------------------------------------------------------------------------------------- */
+/* The reference has no counterpart for anything in this section.  The rule, stated once (gs_pairs_scan.h): a record of a
+ * design with footprint [q, q + k + P), q = position - 1, has its PAM on the right of the protospacer on the forward
+ * strand iff (sense == '+') != GS_FLAG_PAM_AT_START.  Its cut is the boundary x - between bases x - 1 and x - that leaves
+ * cut_offset protospacer bases between cut and PAM: x = q + k - cut_offset with the PAM on the right, x = q + P + cut_offset
+ * otherwise.  A pair is two distinct eligible records a, b of one group and one chromosome, a before b in the order
+ * (chromosome, cut, sense with '+' first), with min_span <= x_b - x_a <= max_span; eligible: the design's eligibility byte,
+ * and specificity >= min_specificity where that is >= 0.  GS_PAIRS_PAM_OUT: a's PAM on the left and b's on the right (the
+ * PAMs face away from each other); GS_PAIRS_PAM_IN: the reverse.  Within a group the pairs are ranked by the smaller of the
+ * two specificities descending, then the larger descending, then by a and b in the order above; per_region N > 0 keeps the
+ * first N of each group, 0 keeps all.  Pairs never span groups or chromosomes; membership in a group is still by
+ * footprint, not by cut. */
+typedef struct gs_pairs gs_pairs;
+#define GS_PAIRS_ANY 0u
+#define GS_PAIRS_PAM_OUT 1u
+#define GS_PAIRS_PAM_IN 2u
+typedef struct gs_pair_rule {
+  uint64_t min_span, max_span;
+  uint32_t cut_offset, orientation /* GS_PAIRS_ANY | _PAM_OUT | _PAM_IN */, per_region /* 0: all */, flags /* GS_FLAG_PAM_AT_START */;
+  float min_specificity; /* < 0: none */
+  uint32_t pad;
+} gs_pair_rule;
+/* The kept pairs of a scored design and the guides they are made of, in HBM passes of one lane per element (no counterpart
+ * in the reference; gs_pairs.hip).  *guides: the records that are a member of at least one kept pair, once per group, in the
+ * order and with the ids of gs_design_select(per_region = 0); it behaves as that call's object.  *pairs: the kept pairs,
+ * group by group in ranked order.  A design with no pair gives two empty objects.  GS_ERR_ARG: a design gs_design_score has
+ * not scored, min_span > max_span, cut_offset > k, an unknown orientation, a bound that is NaN or above 1.
+ * GS_ERR_UNSUPPORTED, the message naming the group and its pair count: a group with more pairs than one chunk holds (2^26;
+ * gs_debug_pairs_chunk).  The design is unchanged. */
+gs_status gs_design_pairs(gs_design *design, const char *prefix, const gs_pair_rule *rule, void *stream, gs_kmers **guides,
+                          gs_pairs **pairs);
+/* host copies of the kept pairs, the object's (no counterpart in the reference): group, chr, a, b, cut_a, cut_b uint32[n],
+ * spec_a, spec_b float[n]; a and b are places in the guides object; cuts are 0-based as defined above.  Any pointer may be
+ * NULL. */
+gs_status gs_pairs_get(gs_pairs *pairs, uint64_t *n, const void **group, const void **chr, const void **a, const void **b,
+                       const void **cut_a, const void **cut_b, const void **spec_a, const void **spec_b);
+/* the table, header included (no counterpart in the reference), formatted on the host - it has per_region rows a group:
+ * `group,id_a,id_b,chromosome,cut_a,cut_b,span,specificity_a,specificity_b,pair_specificity`, ids exactly those of `guides`
+ * (the object gs_design_pairs made with these pairs), the floats as the CSV's specificity column (std::to_string(float)),
+ * pair_specificity the smaller one.  *text is malloc'ed (NUL terminated): release with gs_free */
+gs_status gs_pairs_rows(gs_pairs *pairs, const gs_kmers *guides, char **text, uint64_t *len);
+/* (no counterpart in the reference) eligible records, pairs counted, pairs kept, chunks, groups without a pair, groups
+ * short of per_region */
+gs_status gs_pairs_last(const gs_pairs *pairs, uint64_t out[6]);
+/* the milliseconds of gs_design_pairs' stages between events on its stream (no counterpart in the reference): marking and
+ * compacting the eligible records; ordering them (two sorts, the sorted arrays, the prefix counts); the count pass; the
+ * offsets and group heads; the emit pass; the ranking sorts; cut, gather and flags; the guides object and the result
+ * arrays - the chunked ones summed over the chunks.  Zeros from gs_debug_pairs_host. */
+#define GS_PAIRS_STAGES 8
+gs_status gs_pairs_ms(const gs_pairs *pairs, double out[GS_PAIRS_STAGES]);
+/* (no counterpart in the reference) */
+void gs_pairs_free(gs_pairs *pairs);
+/* Host only: the same passes through gs_pairs_scan.h on plain arrays of n records, with no device (no counterpart in the
+ * reference).  groups are < n_groups.  *out holds what gs_pairs_get gives, a and b as indices of the records given; it has
+ * no names, so gs_pairs_rows on it is GS_ERR_ARG. */
+gs_status gs_debug_pairs_host(uint64_t n, const uint32_t *group, const uint32_t *chr, const uint32_t *position, const uint8_t *sense,
+                              const float *specificity, const uint8_t *eligible, uint32_t k, uint32_t P, uint32_t n_groups,
+                              const gs_pair_rule *rule, gs_pairs **out);
+/* the most pairs a chunk of gs_design_pairs holds (no counterpart in the reference): set != 0 sets it (below 2^32); -> the
+ * value.  For tests */
+uint64_t gs_debug_pairs_chunk(uint64_t set);
+
 /* The column (no counterpart in the reference).  GS_TEXT_FEATURES: the CSV header ends in ",match_features" and every CSV
  * row ends in ',' and the names of the row's features joined by ';', or "NA" if it has none; the `NA` row of a guide without
  * hits ends in ",NA" too.  Both modes.  Together with GS_TEXT_SAM or GS_TEXT_BAM: GS_ERR_ARG, in every entry point below
