@@ -21,10 +21,11 @@
  *   (rocPRIM)   exclusive scan of the position marks: row slots, match_number = rank - rank at the record's first word
  *   k_dc_fold   succinct mode, a wave per record: counters per distance, and the CFDs folded strictly in list order
  *               ((0 + c0) + c1) + ... - the lanes load 64 at a time, every lane adds them one after the other (:156-187)
- *   k_dc_len / (rocPRIM scan of the tile sums) / k_dc_write   as k_tx_len / k_tx_write: a tile is 64 slots (words in
- *               complete mode, records in succinct mode), one row routine over a counting and a writing sink, the
- *               tile composed in the wave's LDS slice and streamed out in 16-byte stores.  Doubles are printed as
- *               Python's repr by gs_repr.h (integer arithmetic).
+ *   k_dc_len / (rocPRIM scan of the tile sums) / k_dc_write   the tile composer of gs_rowtext.h (gs_tile_len, gs_tile_write:
+ *               the one gs_textdev.hip uses) over dc_slot_row: a tile is 64 slots (words in complete mode, records in
+ *               succinct mode), one row routine over the counting and the writing sink, the tile composed in the wave's
+ *               LDS slice and streamed out in 16-byte stores.  Doubles are printed as Python's repr by gs_repr.h
+ *               (integer arithmetic).
  * The error word travels back with the total length: (record << 8 | reason), the smallest over the batch.
  *
  * With an annotation attached (gs_decoder_set_annotation) and GS_TEXT_FEATURES, the rows carry the features of a BED file:
@@ -41,6 +42,7 @@
  * when one is recorded: they win over a row that the annotation makes too long.
  */
 #include "gs_device.h"
+#include "gs_rowtext.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -54,9 +56,7 @@
 #include "gs_annot_scan.h"
 #include "gs_annot_obj.h"
 
-#define DC_WAVES 4
-#define DC_LDS 12288u         /* bytes of a wave's slice */
-#define DC_MAX_ROW (1u << 25) /* as TX_MAX_ROW */
+#define DC_FOLD_WAVES 4 /* waves of a k_dc_fold block, a record each */
 #define DC_MAX_SEQ 32u
 #define DC_NONE 0xFFFFFFFFu
 #define DC_ERR_HEX 1u
@@ -121,14 +121,6 @@ __device__ __forceinline__ int dc_hexval(uint32_t c) {
 }
 __device__ __forceinline__ void dc_fail(const dc_args &a, uint32_t r, uint32_t reason) {
   atomicMin(a.err, ((unsigned long long)r << 8) | reason);
-}
-__device__ __forceinline__ uint32_t dc_digits(uint64_t v) {
-  uint32_t k = 1;
-  while (v >= 10ull) {
-    v /= 10ull;
-    k++;
-  }
-  return k;
 }
 
 /* one off-target of record r: where it lies and the symbols the script prints for it */
@@ -325,7 +317,7 @@ __global__ __launch_bounds__(256) void k_dc_feat(dc_args a) {
 }
 
 /* output_succinct (:156-187): a wave per record */
-__global__ __launch_bounds__(WAVE *DC_WAVES) void k_dc_fold(dc_args a) {
+__global__ __launch_bounds__(WAVE *DC_FOLD_WAVES) void k_dc_fold(dc_args a) {
   const uint32_t lane = threadIdx.x & (WAVE - 1u);
   const uint32_t wave0 = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE, n_waves = gridDim.x * blockDim.x / WAVE;
   for (uint32_t r = wave0; r < a.n; r += n_waves) {
@@ -382,30 +374,7 @@ __global__ __launch_bounds__(WAVE *DC_WAVES) void k_dc_fold(dc_args a) {
   }
 }
 
-/* ---- the two sinks (as tx_count / tx_write) -------------------------------------------------------------------- */
-struct dc_count {
-  uint64_t n = 0;
-  __device__ __forceinline__ void ch(uint32_t) { n++; }
-  __device__ __forceinline__ void put(const uint8_t *, uint64_t k) { n += k; }
-  __device__ __forceinline__ void u64(uint64_t v) { n += dc_digits(v); }
-};
-struct dc_write {
-  char *p;
-  __device__ __forceinline__ void ch(uint32_t c) { *p++ = (char)c; }
-  __device__ __forceinline__ void put(const uint8_t *s, uint64_t k) {
-    for (uint64_t i = 0; i < k; i++) p[i] = (char)s[i];
-    p += k;
-  }
-  __device__ __forceinline__ void u64(uint64_t v) {
-    const uint32_t k = dc_digits(v);
-    char *q = p + k;
-    do {
-      *--q = (char)('0' + (uint32_t)(v % 10ull));
-      v /= 10ull;
-    } while (v);
-    p += k;
-  }
-};
+/* ---- the rows: templates over the sinks of gs_rowtext.h -------------------------------------------------------- */
 template <class S>
 __device__ __forceinline__ void dc_i64(S &o, int64_t v) {
   if (v < 0) {
@@ -511,59 +480,21 @@ __device__ __forceinline__ void dc_slot_row(S &o, const dc_args &a, uint64_t s) 
     dc_succinct_row(o, a, (uint32_t)s);
 }
 
-__global__ __launch_bounds__(WAVE *DC_WAVES) void k_dc_len(dc_args a, uint32_t n_tiles) {
-  const uint32_t lane = threadIdx.x & (WAVE - 1u);
-  const uint32_t wave0 = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE, n_waves = gridDim.x * blockDim.x / WAVE;
+/* the tile composer of gs_rowtext.h over dc_slot_row; a row that is too long fails its record */
+__global__ __launch_bounds__(WAVE *GS_ROW_WAVES) void k_dc_len(dc_args a, uint32_t n_tiles) {
   if (*(volatile unsigned long long *)a.err != ~0ull) return; /* the batch is refused already: no text */
-  for (uint32_t tile = wave0; tile < n_tiles; tile += n_waves) {
-    const uint64_t s = (uint64_t)tile * WAVE + lane;
-    uint32_t len = 0;
-    if (s < a.slots) {
-      dc_count o;
-      dc_slot_row(o, a, s);
-      if (o.n >= DC_MAX_ROW) {
-        dc_fail(a, a.complete ? a.rec[s] : (uint32_t)s, DC_ERR_BIG);
-        o.n = 0;
-      }
-      len = (uint32_t)o.n;
-      a.lens[s] = len;
-    }
-    const uint32_t incl = wave_incl_sum(len);
-    if (lane == WAVE - 1u) a.tile_sum[tile] = incl;
-  }
+  gs_tile_len(
+      a, a.slots, n_tiles, a.lens, a.tile_sum,
+      [](const dc_args &a, gs_row_count &o, uint64_t s, uint64_t, uint32_t &) { dc_slot_row(o, a, s); },
+      [](const dc_args &a, uint64_t s, uint32_t, bool too_long) {
+        if (too_long) dc_fail(a, a.complete ? a.rec[s] : (uint32_t)s, DC_ERR_BIG);
+        return !too_long;
+      });
 }
 
-__global__ __launch_bounds__(WAVE *DC_WAVES) void k_dc_write(dc_args a, uint32_t n_tiles) {
-  __shared__ __attribute__((aligned(16))) char s_buf[DC_WAVES][DC_LDS];
-  const uint32_t lane = threadIdx.x & (WAVE - 1u);
-  char *buf = s_buf[threadIdx.x / WAVE];
-  const uint32_t wave0 = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE, n_waves = gridDim.x * blockDim.x / WAVE;
-  for (uint32_t tile = wave0; tile < n_tiles; tile += n_waves) {
-    const uint64_t s = (uint64_t)tile * WAVE + lane;
-    const uint32_t len = s < a.slots ? a.lens[s] : 0u;
-    const uint32_t incl = wave_incl_sum(len);
-    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
-    if (total == 0u) continue;
-    const uint64_t base = a.tile_off[tile];
-    const uint32_t a0 = (uint32_t)(base & 15u); /* the slice holds the span at the same address mod 16 as HBM does */
-    const bool in_lds = a0 + total <= DC_LDS;
-    dc_write o;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); /* (the tile before has been read out of the slice) */
-    o.p = in_lds ? buf + a0 + (incl - len) : a.out + base + (incl - len);
-    if (len) dc_slot_row(o, a, s);
-    if (!in_lds) continue;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    char *out = a.out + (base - a0); /* 16-byte aligned */
-    const uint32_t end = a0 + total, c_first = (a0 + 15u) >> 4, c_last = end >> 4; /* whole 16-byte chunks [c_first, c_last) */
-    if (c_first >= c_last) {
-      for (uint32_t i = a0 + lane; i < end; i += WAVE) out[i] = buf[i];
-    } else {
-      for (uint32_t i = a0 + lane; i < c_first * 16u; i += WAVE) out[i] = buf[i];
-      for (uint32_t c = c_first + lane; c < c_last; c += WAVE) ((uint4 *)out)[c] = ((const uint4 *)buf)[c];
-      for (uint32_t i = c_last * 16u + lane; i < end; i += WAVE) out[i] = buf[i];
-    }
-  }
+__global__ __launch_bounds__(WAVE *GS_ROW_WAVES) void k_dc_write(dc_args a, uint32_t n_tiles) {
+  gs_tile_write<gs_row_write>(a, a.slots, n_tiles, a.lens, a.tile_off, a.out,
+                              [](const dc_args &a, gs_row_write &o, uint64_t s, uint64_t) { dc_slot_row(o, a, s); });
 }
 
 /* ---- host ---------------------------------------------------------------------------------------------------- */
@@ -880,7 +811,7 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
 
   const uint32_t cus = (uint32_t)gs_num_cus(d->device);
   const uint32_t gw = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nw + 256) / 256, (uint64_t)cus * 32u));
-  const uint32_t grid = std::max(1u, std::min((n_tiles + DC_WAVES - 1) / DC_WAVES, cus * 32u));
+  const uint32_t grid = gs_tile_grid(n_tiles, cus);
   GS_HIP(hipMemsetAsync(tmp + t_err, 0xFF, 16, st));
   GS_HIP(hipMemsetAsync(a.tile_sum + n_tiles, 0, 8, st));
   if (nw) {
@@ -908,10 +839,10 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
     return rocprim::exclusive_scan(t, tb, a.ispos, a.rank, 0u, (size_t)nw + 1, rocprim::plus<uint32_t>(), st);
   }));
   if (!complete) {
-    const uint32_t gf = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + DC_WAVES - 1) / DC_WAVES, (uint64_t)cus * 32u));
-    hipLaunchKernelGGL(k_dc_fold, dim3(gf), dim3(WAVE * DC_WAVES), 0, st, a);
+    const uint32_t gf = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + DC_FOLD_WAVES - 1) / DC_FOLD_WAVES, (uint64_t)cus * 32u));
+    hipLaunchKernelGGL(k_dc_fold, dim3(gf), dim3(WAVE * DC_FOLD_WAVES), 0, st, a);
   }
-  if (n_tiles) hipLaunchKernelGGL(k_dc_len, dim3(grid), dim3(WAVE * DC_WAVES), 0, st, a, n_tiles);
+  if (n_tiles) hipLaunchKernelGGL(k_dc_len, dim3(grid), dim3(WAVE * GS_ROW_WAVES), 0, st, a, n_tiles);
   GS_TRY(gs_prim_carved("gs_decode: scan of the tiles", tmp + t_scan, tb_scan, [&](void *t, size_t &tb) {
     return rocprim::exclusive_scan(t, tb, a.tile_sum, a.tile_off, 0ull, (size_t)n_tiles + 1, rocprim::plus<uint64_t>(), st);
   }));
@@ -948,7 +879,7 @@ gs_status gs_decode_run_device(gs_decoder *d, const gs_decode_batch_dev &db, uin
   }
   GS_TRY(gs_reserve(d->w_text, total + 16));
   a.out = (char *)d->w_text.p;
-  if (total) hipLaunchKernelGGL(k_dc_write, dim3(grid), dim3(WAVE * DC_WAVES), 0, st, a, n_tiles);
+  if (total) hipLaunchKernelGGL(k_dc_write, dim3(grid), dim3(WAVE * GS_ROW_WAVES), 0, st, a, n_tiles);
   GS_HIP(hipStreamSynchronize(st));
   GS_HIP(hipGetLastError());
   *d_text = d->w_text.p;

@@ -22,8 +22,9 @@
  *                         k_ds_cut     keep = marked && rank - rank of the group's head < N
  *                         (rocprim exclusive scan of the keeps: the places)
  *                         k_ds_gather  the kept records into a fresh gs_kmers                 (k + P + 13 B each way)
- *                         k_ds_text_len / (64-bit scan) / k_ds_text_write: the ids "{prefix}{group}:{chr}:{pos}:{sense}"
- *                         or the kmers-file rows, names read from one uploaded table
+ *                         gs_km_encode_text (gs_kmers.hip: k_km_text_len / 64-bit scan / k_km_text_write over the row of
+ *                         gs_rowtext.h): the ids "{prefix}{group}:{chr}:{pos}:{sense}" or the kmers-file rows, names read
+ *                         from one uploaded table
  * Every kernel is one record per lane over 4- and 8-byte arrays; they are bound by memory and by the two sorts.
  */
 #include "gs_common.h"
@@ -665,96 +666,22 @@ __global__ __launch_bounds__(DS_BLOCK) void k_ds_gather(gs_ds_gather_args a) {
   if (a.place_of) a.place_of[r] = (uint32_t)o;
 }
 
-struct gs_ds_text_args {
-  const uint8_t *seqs, *pams, *sense;
-  const uint32_t *pos, *group, *chr;
-  const uint8_t *names;      /* prefix, the group names, the chromosome names */
-  const uint32_t *goff, *coff; /* where each name begins in `names`; one more entry closes each table */
-  uint64_t *lens;            /* m + 1 */
-  const uint64_t *off;       /* m + 1 */
-  uint8_t *text, *sense01;
-  uint64_t m;
-  uint32_t k, P, prefix_len, rows;
-};
-__device__ __forceinline__ uint32_t ds_digits(uint32_t v) {
-  uint32_t d = 1;
-  while (v >= 10u) {
-    v /= 10u;
-    d++;
-  }
-  return d;
-}
-__global__ __launch_bounds__(DS_BLOCK) void k_ds_text_len(gs_ds_text_args a) {
-  const uint64_t j = (uint64_t)blockIdx.x * DS_BLOCK + threadIdx.x;
-  if (j > a.m) return;
-  if (j == a.m) {
-    a.lens[j] = 0;
-    return;
-  }
-  const uint32_t g = a.group[j], c = a.chr[j];
-  const uint32_t gl = a.goff[g + 1] - a.goff[g], cl = a.coff[c + 1] - a.coff[c], dg = ds_digits(a.pos[j]);
-  const uint32_t id = a.prefix_len + gl + 1u + cl + 1u + dg + 2u;
-  a.lens[j] = a.rows ? (uint64_t)id + 1u + a.k + 1u + a.P + 1u + cl + 1u + dg + 3u : (uint64_t)id;
-}
-__device__ __forceinline__ uint8_t *ds_put(uint8_t *o, const uint8_t *s, uint32_t n) {
-  for (uint32_t i = 0; i < n; i++) o[i] = s[i];
-  return o + n;
-}
-__device__ __forceinline__ uint8_t *ds_put_u32(uint8_t *o, uint32_t v) {
-  const uint32_t d = ds_digits(v);
-  uint8_t *q = o + d;
-  do {
-    *--q = (uint8_t)('0' + v % 10u);
-    v /= 10u;
-  } while (v);
-  return o + d;
-}
-__global__ __launch_bounds__(DS_BLOCK) void k_ds_text_write(gs_ds_text_args a) {
-  const uint64_t j = (uint64_t)blockIdx.x * DS_BLOCK + threadIdx.x;
-  if (j >= a.m) return;
-  const uint32_t g = a.group[j], c = a.chr[j], pos = a.pos[j];
-  const uint8_t sense = a.sense[j];
-  uint8_t *o = a.text + a.off[j];
-  o = ds_put(o, a.names, a.prefix_len);
-  o = ds_put(o, a.names + a.goff[g], a.goff[g + 1] - a.goff[g]);
-  *o++ = ':';
-  o = ds_put(o, a.names + a.coff[c], a.coff[c + 1] - a.coff[c]);
-  *o++ = ':';
-  o = ds_put_u32(o, pos);
-  *o++ = ':';
-  *o++ = sense;
-  if (!a.rows) {
-    a.sense01[j] = sense == '+' ? 1 : 0;
-    return;
-  }
-  *o++ = ',';
-  o = ds_put(o, a.seqs + j * a.k, a.k);
-  *o++ = ',';
-  o = ds_put(o, a.pams + j * a.P, a.P);
-  *o++ = ',';
-  o = ds_put(o, a.names + a.coff[c], a.coff[c + 1] - a.coff[c]);
-  *o++ = ',';
-  o = ds_put_u32(o, pos);
-  *o++ = ',';
-  *o++ = sense;
-  *o++ = '\n';
-}
-
-static void km_release_own(gs_kmers *km) { gs_kmers_free(km); }
-
-/* prefix, group names and chromosome names back to back, and where each begins */
-static void ds_name_table(const gs_regions *rg, const char *prefix, std::string &names, std::vector<uint32_t> &goff, std::vector<uint32_t> &coff) {
-  names = prefix;
+/* prefix, group names and chromosome names back to back, and where each begins (gs_km_names, gs_kmers_obj.h) */
+static gs_km_names ds_name_table(const gs_regions *rg, const char *prefix) {
+  gs_km_names nt;
+  nt.names = prefix;
+  nt.prefix_len = (uint32_t)nt.names.size();
   for (const std::string &s : rg->group_names) {
-    goff.push_back((uint32_t)names.size());
-    names += s;
+    nt.goff.push_back((uint32_t)nt.names.size());
+    nt.names += s;
   }
-  goff.push_back((uint32_t)names.size());
+  nt.goff.push_back((uint32_t)nt.names.size());
   for (const std::string &s : rg->chr_names) {
-    coff.push_back((uint32_t)names.size());
-    names += s;
+    nt.coff.push_back((uint32_t)nt.names.size());
+    nt.names += s;
   }
-  coff.push_back((uint32_t)names.size());
+  nt.coff.push_back((uint32_t)nt.names.size());
+  return nt;
 }
 static void ds_group_tally(gs_design *d, uint64_t kept, const std::vector<uint32_t> &kept_of_group, uint32_t per_region) {
   d->last[0] = d->n;
@@ -776,7 +703,7 @@ gs_status gs_ds_select(gs_design *d, const char *prefix, const gs_ds_select_rule
   const uint64_t n = d->n;
   const uint32_t k = d->k, P = d->P;
   const size_t n_groups = d->rg->group_names.size();
-  std::unique_ptr<gs_kmers, void (*)(gs_kmers *)> own(new gs_kmers(), km_release_own);
+  std::unique_ptr<gs_kmers, void (*)(gs_kmers *)> own(new gs_kmers(), km_release);
   gs_kmers *km = own.get();
   km->device = d->device;
   km->k = k;
@@ -884,65 +811,15 @@ gs_status gs_ds_select(gs_design *d, const char *prefix, const gs_ds_select_rule
   }
   if (rule.tally) ds_group_tally(d, m, kept_of_group, per_region);
   km->n = m;
-  /* the text: ids or rows */
-  std::string names;
-  std::vector<uint32_t> goff, coff;
-  ds_name_table(d->rg, prefix, names, goff, coff);
-  uint8_t *d_names = nullptr, *text = nullptr, *s01 = nullptr;
-  uint32_t *d_goff = nullptr, *d_coff = nullptr;
-  uint64_t *lens = nullptr, *off = nullptr;
-  GS_TRY(mem.get(names.size(), &d_names));
-  GS_TRY(mem.get(4 * goff.size(), &d_goff));
-  GS_TRY(mem.get(4 * coff.size(), &d_coff));
-  GS_HIP(hipMemcpyAsync(d_names, names.data(), names.size(), hipMemcpyHostToDevice, st));
-  GS_HIP(hipMemcpyAsync(d_goff, goff.data(), 4 * goff.size(), hipMemcpyHostToDevice, st));
-  GS_HIP(hipMemcpyAsync(d_coff, coff.data(), 4 * coff.size(), hipMemcpyHostToDevice, st));
-  GS_TRY(mem.get(8 * (m + 1), &lens));
-  GS_TRY(mem.get(8 * (m + 1), &off));
-  gs_ds_text_args ta;
-  memset(&ta, 0, sizeof ta);
-  ta.seqs = (const uint8_t *)km->d_seqs;
-  ta.pams = (const uint8_t *)km->d_pams;
-  ta.sense = (const uint8_t *)km->d_sense;
-  ta.pos = (const uint32_t *)km->d_pos;
-  ta.group = o_group;
-  ta.chr = o_chr;
-  ta.names = d_names;
-  ta.goff = d_goff;
-  ta.coff = d_coff;
-  ta.lens = lens;
-  ta.off = off;
-  ta.m = m;
-  ta.k = k;
-  ta.P = P;
-  ta.prefix_len = (uint32_t)strlen(prefix);
-  ta.rows = rows ? 1u : 0u;
-  hipLaunchKernelGGL(k_ds_text_len, dim3((unsigned)((m + 1 + DS_BLOCK - 1) / DS_BLOCK)), dim3(DS_BLOCK), 0, st, ta);
-  GS_TRY(gs_prim("design text: scan of the lengths", mem, tmp, [&](void *p, size_t &b) {
-    return rocprim::exclusive_scan(p, b, lens, off, 0ull, (size_t)m + 1, rocprim::plus<uint64_t>(), st);
-  }));
+  /* the text: ids or rows, by the writer of gs_kmers.hip over the table of all names */
   uint64_t total = 0;
-  GS_HIP(hipMemcpyAsync(&total, off + m, 8, hipMemcpyDeviceToHost, st));
-  GS_HIP(hipStreamSynchronize(st));
-  GS_TRY(mem.get(total, &text));
-  if (!rows) GS_TRY(mem.get(m, &s01));
-  ta.text = text;
-  ta.sense01 = s01;
-  if (m) hipLaunchKernelGGL(k_ds_text_write, dim3((unsigned)((m + DS_BLOCK - 1) / DS_BLOCK)), dim3(DS_BLOCK), 0, st, ta);
-  GS_HIP(hipStreamSynchronize(st));
-  GS_HIP(hipGetLastError());
-  mem.keep(text);
+  void *text = nullptr;
+  GS_TRY(gs_km_encode_text(km, ds_name_table(d->rg, prefix), o_group, o_chr, rows, "design text: scan of the lengths", st, &text, &total));
   if (rows) {
     *d_text = text;
     *text_bytes = total;
     return GS_OK; /* the object is dropped: the rows are the result */
   }
-  mem.keep(off);
-  mem.keep(s01);
-  km->d_ids = text;
-  km->d_id_off = off;
-  km->d_sense01 = s01;
-  km->id_bytes = total;
   *out = own.release();
   return GS_OK;
 }
@@ -1061,7 +938,7 @@ extern "C" gs_status gs_debug_design_host(const gs_regions *rg, uint32_t n_parts
       }
       if (marked) rank++;
     }
-    std::unique_ptr<gs_kmers, void (*)(gs_kmers *)> own(new gs_kmers(), km_release_own);
+    std::unique_ptr<gs_kmers, void (*)(gs_kmers *)> own(new gs_kmers(), km_release);
     gs_kmers *km = own.get();
     km->device = -1;
     km->k = k;

@@ -15,8 +15,10 @@
  *                position, sense, PAM pattern.
  * The output arrays stay in HBM in exactly the layout gs_enumerate_device takes.
  *
- * The records as text, also in HBM (the shape of gs_textdev.hip: a length per record, an exclusive scan, a write):
- *   k_km_text_len    bytes of every record's id "{prefix}{chromosome}:{position}:{sense}" or of its kmers-file row
+ * The records as text, also in HBM (a length per record, an exclusive scan, a write; gs_km_encode_text, which gs_design.hip
+ * calls too, with a group and a chromosome per record and a table of their names).  The id and the row are stated once, as
+ * gs_guide_row of gs_rowtext.h: the length kernel runs it over the counting sink, the write kernel over the writing one.
+ *   k_km_text_len    bytes of every record's id "{prefix}[{group}:]{chromosome}:{position}:{sense}" or of its kmers-file row
  *                    "id,sequence,pam,chromosome,position,sense\n" (scripts/generate_kmers.py:120-125)   (4 B read, 8 B written)
  *   (rocprim 64-bit exclusive scan of the n + 1 lengths: the offsets)
  *   k_km_text_write  one thread per record composes its bytes at its offset (a row: 4 + 8 + k + 1 B read, ~2k + 2P + 40 B
@@ -27,6 +29,7 @@
 #include "gs_common.h"
 #include "gs_scratch.h"
 #include "gs_kmers_obj.h"
+#include "gs_rowtext.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -153,7 +156,7 @@ static gs_status km_alloc(size_t bytes, void **out) {
   one.keep(*out);
   return GS_OK;
 }
-static void km_release(gs_kmers *km) {
+void km_release(gs_kmers *km) { /* gs_kmers_obj.h */
   if (!km) return;
   bool any = false; /* an empty object never touched a device */
   for (void *p : {km->d_seqs, km->d_pams, km->d_pos, km->d_sense, km->d_ids, km->d_id_off, km->d_sense01}) any = any || p;
@@ -320,89 +323,61 @@ extern "C" gs_status gs_kmers_get(gs_kmers *km, int on_device, uint64_t *n, cons
 struct gs_km_text_args {
   const uint8_t *seqs, *pams, *sense;
   const uint32_t *pos;
-  const uint8_t *names; /* prefix, then the chromosome name */
-  uint64_t *lens;       /* n + 1 */
-  const uint64_t *off;  /* n + 1 */
+  const uint32_t *group, *chr; /* per record, or nullptr: no group in the id; chromosome 0 */
+  const uint8_t *names;        /* prefix, the group names, the chromosome names */
+  const uint32_t *goff, *coff; /* where each name begins in `names`; one more entry closes each table */
+  uint64_t *lens;              /* n + 1 */
+  const uint64_t *off;         /* n + 1 */
   uint8_t *text, *sense01;
   uint64_t n;
-  uint32_t k, P, prefix_len, name_len, rows;
+  uint32_t k, P, prefix_len, rows;
 };
-__device__ __forceinline__ uint32_t km_digits(uint32_t v) { /* 1 .. 10: 4,294,967,295 has ten */
-  uint32_t d = 1;
-  while (v >= 10u) {
-    v /= 10u;
-    d++;
+/* record j through gs_guide_row: the length kernel runs it over the counting sink, the write kernel over the writing one */
+template <class S>
+__device__ __forceinline__ void km_text_row(S &o, const gs_km_text_args &a, uint64_t j) {
+  const uint32_t c = a.chr ? a.chr[j] : 0u;
+  gs_rt_span group{nullptr, 0u};
+  if (a.group) {
+    const uint32_t g = a.group[j];
+    group = gs_rt_span{a.names + a.goff[g], a.goff[g + 1] - a.goff[g]};
   }
-  return d;
+  gs_guide_row(o, a.names, a.prefix_len, group, gs_rt_span{a.names + a.coff[c], a.coff[c + 1] - a.coff[c]}, a.pos[j], a.sense[j],
+               a.seqs + j * a.k, a.pams + j * a.P, a.k, a.P, a.rows != 0u);
 }
 __global__ __launch_bounds__(KM_BLOCK) void k_km_text_len(gs_km_text_args a) {
   const uint64_t j = (uint64_t)blockIdx.x * KM_BLOCK + threadIdx.x;
   if (j > a.n) return;
-  if (j == a.n) {
-    a.lens[j] = 0;
-    return;
-  }
-  const uint32_t id = a.prefix_len + a.name_len + 1u + km_digits(a.pos[j]) + 2u;
-  /* id , sequence , pam , chromosome , position , sense \n */
-  a.lens[j] = a.rows ? (uint64_t)id + 1u + a.k + 1u + a.P + 1u + a.name_len + 1u + km_digits(a.pos[j]) + 3u : (uint64_t)id;
-}
-__device__ __forceinline__ uint8_t *km_put(uint8_t *o, const uint8_t *s, uint32_t n) {
-  for (uint32_t i = 0; i < n; i++) o[i] = s[i];
-  return o + n;
-}
-__device__ __forceinline__ uint8_t *km_put_u32(uint8_t *o, uint32_t v) {
-  const uint32_t d = km_digits(v);
-  uint8_t *q = o + d;
-  do {
-    *--q = (uint8_t)('0' + v % 10u);
-    v /= 10u;
-  } while (v);
-  return o + d;
+  gs_row_count o;
+  if (j < a.n) km_text_row(o, a, j); /* one more entry closes the scan */
+  a.lens[j] = o.n;
 }
 __global__ __launch_bounds__(KM_BLOCK) void k_km_text_write(gs_km_text_args a) {
   const uint64_t j = (uint64_t)blockIdx.x * KM_BLOCK + threadIdx.x;
   if (j >= a.n) return;
-  const uint32_t pos = a.pos[j];
-  const uint8_t sense = a.sense[j];
-  uint8_t *o = a.text + a.off[j];
-  o = km_put(o, a.names, a.prefix_len + a.name_len);
-  *o++ = ':';
-  o = km_put_u32(o, pos);
-  *o++ = ':';
-  *o++ = sense;
-  if (!a.rows) {
-    a.sense01[j] = sense == '+' ? 1 : 0;
-    return;
-  }
-  *o++ = ',';
-  o = km_put(o, a.seqs + j * a.k, a.k);
-  *o++ = ',';
-  o = km_put(o, a.pams + j * a.P, a.P);
-  *o++ = ',';
-  o = km_put(o, a.names + a.prefix_len, a.name_len);
-  *o++ = ',';
-  o = km_put_u32(o, pos);
-  *o++ = ',';
-  *o++ = sense;
-  *o++ = '\n';
+  gs_row_write o;
+  o.p = (char *)a.text + a.off[j];
+  km_text_row(o, a, j);
+  if (!a.rows) a.sense01[j] = a.sense[j] == '+' ? 1 : 0;
 }
 __global__ __launch_bounds__(KM_BLOCK) void k_km_rebase(const uint64_t *in, uint64_t n, uint64_t base, uint64_t *out) {
   const uint64_t j = (uint64_t)blockIdx.x * KM_BLOCK + threadIdx.x;
   if (j < n) out[j] = in[j] + base;
 }
 
-/* ids (rows == 0, kept in the object) or kmers-file rows (*d_text: the caller frees it) of all records */
-static gs_status km_encode(gs_kmers *km, const char *prefix, const char *chr_name, bool rows, hipStream_t st, void **d_text,
-                           void **d_off, uint64_t *bytes) {
-  const size_t pl = strlen(prefix), nl = strlen(chr_name);
-  if (pl >= (1u << 20) || nl >= (1u << 20)) return GS_ERR_ARG;
-  GS_HIP(hipSetDevice(km->device));
+/* gs_kmers_obj.h: ids (rows == false, kept in the object) or kmers-file rows (*d_text: the caller frees it) of all records */
+gs_status gs_km_encode_text(gs_kmers *km, const gs_km_names &nt, const uint32_t *d_group, const uint32_t *d_chr, bool rows, const char *what,
+                            hipStream_t st, void **d_text, uint64_t *bytes) {
   const uint64_t n = km->n;
   gs_scratch mem;
-  void *d_names = nullptr, *d_lens = nullptr, *off = nullptr, *text = nullptr, *s01 = nullptr;
-  std::string names = std::string(prefix) + chr_name;
-  GS_TRY(mem.get(names.size(), &d_names));
-  GS_HIP(hipMemcpyAsync(d_names, names.data(), names.size(), hipMemcpyHostToDevice, st));
+  void *d_tab = nullptr, *d_lens = nullptr, *off = nullptr, *text = nullptr, *s01 = nullptr;
+  /* one upload: the offsets of the group names, those of the chromosome names, the names */
+  const size_t ng = nt.goff.size(), nc = nt.coff.size();
+  std::vector<uint8_t> tab(4 * (ng + nc) + nt.names.size());
+  if (ng) memcpy(tab.data(), nt.goff.data(), 4 * ng);
+  memcpy(tab.data() + 4 * ng, nt.coff.data(), 4 * nc);
+  memcpy(tab.data() + 4 * (ng + nc), nt.names.data(), nt.names.size());
+  GS_TRY(mem.get(tab.size(), &d_tab));
+  GS_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
   GS_TRY(mem.get(8 * (n + 1), &d_lens));
   GS_TRY(mem.get(8 * (n + 1), &off));
   gs_km_text_args a;
@@ -411,24 +386,27 @@ static gs_status km_encode(gs_kmers *km, const char *prefix, const char *chr_nam
   a.pams = (const uint8_t *)km->d_pams;
   a.sense = (const uint8_t *)km->d_sense;
   a.pos = (const uint32_t *)km->d_pos;
-  a.names = (const uint8_t *)d_names;
+  a.group = d_group;
+  a.chr = d_chr;
+  a.goff = (const uint32_t *)d_tab;
+  a.coff = a.goff + ng;
+  a.names = (const uint8_t *)(a.coff + nc);
   a.lens = (uint64_t *)d_lens;
   a.off = (const uint64_t *)off;
   a.n = n;
   a.k = km->k;
   a.P = km->P;
-  a.prefix_len = (uint32_t)pl;
-  a.name_len = (uint32_t)nl;
+  a.prefix_len = nt.prefix_len;
   a.rows = rows ? 1u : 0u;
   const unsigned grid = (unsigned)((n + 1 + KM_BLOCK - 1) / KM_BLOCK);
   hipLaunchKernelGGL(k_km_text_len, dim3(grid), dim3(KM_BLOCK), 0, st, a);
   gs_prim_tmp tmp;
-  GS_TRY(gs_prim("kmers text: scan of the lengths", mem, tmp, [&](void *t, size_t &tb) {
+  GS_TRY(gs_prim(what, mem, tmp, [&](void *t, size_t &tb) {
     return rocprim::exclusive_scan(t, tb, (uint64_t *)d_lens, (uint64_t *)off, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st);
   }));
   uint64_t total = 0;
   GS_HIP(hipMemcpyAsync(&total, (uint64_t *)off + n, 8, hipMemcpyDeviceToHost, st));
-  GS_HIP(hipStreamSynchronize(st));
+  GS_HIP(hipStreamSynchronize(st)); /* `tab` is a local */
   GS_TRY(mem.get(total, &text));
   if (!rows) GS_TRY(mem.get(n, &s01));
   a.text = (uint8_t *)text;
@@ -451,9 +429,20 @@ static gs_status km_encode(gs_kmers *km, const char *prefix, const char *chr_nam
     km->have_ids = true;
     km->have_host_ids = false;
   }
-  if (d_off) *d_off = off;
   *bytes = total;
   return GS_OK;
+}
+
+/* a scan's records: no group, one chromosome */
+static gs_status km_encode(gs_kmers *km, const char *prefix, const char *chr_name, bool rows, hipStream_t st, void **d_text, uint64_t *bytes) {
+  const size_t pl = strlen(prefix), nl = strlen(chr_name);
+  if (pl >= (1u << 20) || nl >= (1u << 20)) return GS_ERR_ARG;
+  GS_HIP(hipSetDevice(km->device));
+  gs_km_names nt;
+  nt.names = std::string(prefix) + chr_name;
+  nt.prefix_len = (uint32_t)pl;
+  nt.coff = {(uint32_t)pl, (uint32_t)(pl + nl)};
+  return gs_km_encode_text(km, nt, nullptr, nullptr, rows, "kmers text: scan of the lengths", st, d_text, bytes);
 }
 
 extern "C" gs_status gs_kmers_encode_ids(gs_kmers *km, const char *prefix, const char *chr_name, void *stream) {
@@ -468,7 +457,7 @@ extern "C" gs_status gs_kmers_encode_ids(gs_kmers *km, const char *prefix, const
   }
   uint64_t bytes = 0;
   try {
-    return km_encode(km, prefix, chr_name, false, (hipStream_t)stream, nullptr, nullptr, &bytes);
+    return km_encode(km, prefix, chr_name, false, (hipStream_t)stream, nullptr, &bytes);
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;
   }
@@ -520,7 +509,7 @@ extern "C" gs_status gs_kmers_csv(gs_kmers *km, const char *prefix, const char *
   uint64_t bytes = 0;
   gs_status rc;
   try {
-    rc = km_encode(km, prefix, chr_name, true, nullptr, &d_text, nullptr, &bytes);
+    rc = km_encode(km, prefix, chr_name, true, nullptr, &d_text, &bytes);
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;
   }

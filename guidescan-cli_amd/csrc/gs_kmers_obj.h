@@ -3,8 +3,9 @@
 #ifndef GS_KMERS_OBJ_H
 #define GS_KMERS_OBJ_H
 
-#include <stdint.h>
+#include "gs_common.h"
 
+#include <string>
 #include <vector>
 
 struct gs_kmers {
@@ -28,5 +29,23 @@ struct gs_kmers {
   std::vector<uint8_t> h_ids, h_sense01;
   std::vector<uint64_t> h_id_off;
 };
+
+/* frees the object and its arrays in HBM (gs_kmers_free; the deleter of an object under construction) */
+void km_release(gs_kmers *km);
+
+/* The id and kmers-file row writer of gs_kmers.hip (the row itself: gs_guide_row, gs_rowtext.h).  The name table: the prefix,
+ * then the group names, then the chromosome names back to back; goff / coff say where each name begins, one more entry closes
+ * each.  goff empty: the ids name no group. */
+struct gs_km_names {
+  std::string names;
+  std::vector<uint32_t> goff, coff;
+  uint32_t prefix_len = 0;
+};
+/* The ids "{prefix}[{group}:]{chromosome}:{position}:{sense}" of km's records (rows == false: they become the object's
+ * d_ids, d_id_off and d_sense01) or their kmers-file rows in HBM (*d_text, the caller's to free).  d_group / d_chr: uint32[n]
+ * in HBM, the group and chromosome of every record, or nullptr: no group (goff empty), chromosome 0.  what: names the scan
+ * in an error message.  The caller has set the device. */
+gs_status gs_km_encode_text(gs_kmers *km, const gs_km_names &nt, const uint32_t *d_group, const uint32_t *d_chr, bool rows, const char *what,
+                            hipStream_t st, void **d_text, uint64_t *bytes);
 
 #endif

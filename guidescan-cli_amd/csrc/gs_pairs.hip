@@ -285,8 +285,6 @@ __global__ __launch_bounds__(PR_BLOCK) void k_pr_finish(gs_pr_args a, const uint
 
 static dim3 pr_grid(uint64_t n) { return dim3((unsigned)((n + PR_BLOCK - 1) / PR_BLOCK)); }
 
-static void km_release_own(gs_kmers *km) { gs_kmers_free(km); }
-
 static gs_status pr_device(gs_design *d, const char *prefix, const gs_pair_rule *rule, bool filter, hipStream_t st, gs_kmers **guides,
                            gs_pairs *pr) {
   const uint64_t n = d->n;
@@ -474,7 +472,7 @@ static gs_status pr_device(gs_design *d, const char *prefix, const gs_pair_rule 
   GS_TRY(laps.lap(-1));
   const gs_ds_select_rule sel{flag, 0u, false, -1.0f, place_of, false};
   GS_TRY(gs_ds_select(d, prefix, sel, st, false, &km, nullptr, nullptr));
-  std::unique_ptr<gs_kmers, void (*)(gs_kmers *)> own(km, km_release_own);
+  std::unique_ptr<gs_kmers, void (*)(gs_kmers *)> own(km, km_release);
 
   const size_t K = (size_t)plan.kept;
   pr->n = K;

@@ -13,7 +13,9 @@
  *               streams the tile's contiguous span out with 16-byte stores (LDS and HBM addresses are congruent mod 16;
  *               only the span's ragged head and tail are byte stores).  A tile whose span outgrows the slice (very long
  *               ids or chromosome names, long of:H: fields) is composed in HBM directly.
- * Both kernels run ONE row routine over two sinks, a counting one and a writing one: the lengths cannot disagree.
+ * Both kernels run ONE row routine over two sinks, a counting one and a writing one: the lengths cannot disagree.  The
+ * sinks and the two tile passes themselves (gs_tile_len, gs_tile_write) are gs_rowtext.h's, shared with gs_decode.hip: this
+ * file keeps the rows, the SAM tables and the host driver; k_tx_len and k_tx_write hand tx_slot_row to the templates.
  * SAM needs three per-guide facts first (k_tx_sam_ok, k_tx_sam_guide): the unfiltered count per distance, the hits kept
  * per distance (the cap counts kept hits, after the boundary drop: printer.hpp:129 - the CSV cap counts raw indices,
  * :259), and the of:H: field, which is composed once per guide into a scratch span (k_tx_sam_hex) and copied into each
@@ -22,6 +24,7 @@
  * block host/bam_writer.hpp makes of it (tx_bam_row); GS_TEXT_BGZF hands the blocks to gs_bgzf.hip.
  */
 #include "gs_device.h"
+#include "gs_rowtext.h"
 #include "gs_bgzf_huff.h"
 #include "gs_scratch.h"
 #include "gs_resolve.h"
@@ -31,9 +34,6 @@
 
 #include <algorithm>
 
-#define TX_WAVES 4
-#define TX_LDS 12288u            /* bytes of a wave's slice */
-#define TX_MAX_ROW (1u << 25)    /* a row of this many bytes or more is refused: 64 of them stay below 2^31 */
 #define TX_ERR_ARG 1u
 #define TX_ERR_BIG 2u
 #define TX_ERR_ID 4u /* BAM: an id of more than 254 bytes (l_read_name is one byte and counts the NUL) */
@@ -83,22 +83,6 @@ __device__ __forceinline__ uint32_t tx_comp(uint32_t c) { /* src/genomics/sequen
     default: return c;
   }
 }
-__device__ __forceinline__ uint32_t tx_digits(uint64_t v) {
-  uint32_t k = 1;
-  if (v < (1ull << 32)) {
-    uint32_t w = (uint32_t)v;
-    while (w >= 10u) {
-      w /= 10u;
-      k++;
-    }
-    return k;
-  }
-  while (v >= 10ull) {
-    v /= 10ull;
-    k++;
-  }
-  return k;
-}
 
 /* "%f" of a float in [0, 1] as round(f * 10^6) under round-half-even on the exact value (what glibc prints):
  * f = m * 2^e with m < 2^24, so m * 10^6 < 2^44; shifted right by -e with the exact remainder deciding. */
@@ -147,57 +131,7 @@ __device__ __forceinline__ uint64_t tx_first_at(const gs_hit *hits, uint64_t b, 
   return b;
 }
 
-/* ---- the two sinks ------------------------------------------------------------------------------------------- */
-struct tx_count {
-  uint64_t n = 0;
-  __device__ __forceinline__ void ch(uint32_t) { n++; }
-  __device__ __forceinline__ void put(const uint8_t *, uint32_t k) { n += k; }
-  __device__ __forceinline__ void lit(const char *, uint32_t k) { n += k; }
-  __device__ __forceinline__ void u64(uint64_t v) { n += tx_digits(v); }
-  __device__ __forceinline__ void span(const char *, uint64_t k) { n += k; }
-};
-struct tx_write {
-  char *p;
-  /* the of:H: field of a SAM line is copied by the whole wave afterwards */
-  char *sp_dst = nullptr;
-  const char *sp_src = nullptr;
-  uint64_t sp_n = 0;
-  __device__ __forceinline__ void ch(uint32_t c) { *p++ = (char)c; }
-  __device__ __forceinline__ void put(const uint8_t *s, uint32_t k) {
-    for (uint32_t i = 0; i < k; i++) p[i] = (char)s[i];
-    p += k;
-  }
-  __device__ __forceinline__ void lit(const char *s, uint32_t k) {
-    for (uint32_t i = 0; i < k; i++) p[i] = s[i];
-    p += k;
-  }
-  __device__ __forceinline__ void u64(uint64_t v) {
-    const uint32_t k = tx_digits(v);
-    char *q = p + k;
-    if (v < (1ull << 32)) {
-      uint32_t w = (uint32_t)v;
-      do {
-        *--q = (char)('0' + w % 10u);
-        w /= 10u;
-      } while (w);
-    } else {
-      do {
-        *--q = (char)('0' + (uint32_t)(v % 10ull));
-        v /= 10ull;
-      } while (v);
-    }
-    p += k;
-  }
-  __device__ __forceinline__ void span(const char *s, uint64_t k) {
-    sp_dst = p;
-    sp_src = s;
-    sp_n = k;
-    p += k;
-  }
-};
-#define TX_LIT(o, s) (o).lit(s, (uint32_t)sizeof(s) - 1u)
-
-/* ---- the rows ------------------------------------------------------------------------------------------------ */
+/* ---- the rows: templates over the sinks of gs_rowtext.h (the of:H: field of a SAM line is a `span`) ------------ */
 template <class S>
 __device__ __forceinline__ void tx_id(S &o, const tx_args &a, uint32_t g) {
   const uint64_t b = a.id_off[g], e = a.id_off[g + 1u];
@@ -233,7 +167,7 @@ __device__ __forceinline__ void tx_features(S &o, const tx_args &a, uint64_t i) 
   o.ch(',');
   const uint64_t b = a.feat_off[i], e = a.feat_off[i + 1u];
   if (b == e) {
-    TX_LIT(o, "NA");
+    GS_ROW_LIT(o, "NA");
     return;
   }
   for (uint64_t x = b; x < e; x++) {
@@ -260,12 +194,12 @@ __device__ __forceinline__ void tx_guide_row(S &o, const tx_args &a, uint32_t g,
   tx_id(o, a, g);
   o.ch(',');
   tx_sequence(o, a, g);
-  TX_LIT(o, ",NA,NA,NA,0");
-  if (a.complete) TX_LIT(o, ",NA,NA,NA");
+  GS_ROW_LIT(o, ",NA,NA,NA,0");
+  if (a.complete) GS_ROW_LIT(o, ",NA,NA,NA");
   if (a.features)
-    TX_LIT(o, ",1.0,NA\n");
+    GS_ROW_LIT(o, ",1.0,NA\n");
   else
-    TX_LIT(o, ",1.0\n");
+    GS_ROW_LIT(o, ",1.0\n");
 }
 
 /* one CSV row (printer.hpp:245-300 as format_csv_fast restates it) */
@@ -325,7 +259,7 @@ __device__ __forceinline__ void tx_csv_row(S &o, const tx_args &a, uint32_t g, u
       }
       o.ch(code == 0u ? 'T' : code == 1u ? 'G' : code == 2u ? 'C' : code == 3u ? 'N' : 'A'); /* complement of A,C,G,N,T */
     }
-    TX_LIT(o, ",0,0"); /* rna_bulges, dna_bulges */
+    GS_ROW_LIT(o, ",0,0"); /* rna_bulges, dna_bulges */
   }
   o.ch(',');
   tx_specificity(o, tx_spec_q(__float_as_uint(a.spec[g])));
@@ -346,14 +280,14 @@ __device__ __forceinline__ void tx_sam_row(S &o, const tx_args &a, uint32_t g, u
   if (pos_sense)
     o.ch('0');
   else
-    TX_LIT(o, "16");
+    GS_ROW_LIT(o, "16");
   o.ch('\t');
   if (loc.c >= 0) tx_chr_name(o, a, loc.c); /* no sentinel check in the reference: empty RNAME */
   o.ch('\t');
   o.u64(loc.c >= 0 ? (uint64_t)loc.s : 0ull);
-  TX_LIT(o, "\t100\t");
+  GS_ROW_LIT(o, "\t100\t");
   o.u64((uint64_t)a.L + a.P);
-  TX_LIT(o, "M\t*\t0\t0\t");
+  GS_ROW_LIT(o, "M\t*\t0\t0\t");
   if (pos_sense) {
     tx_sequence(o, a, g);
   } else { /* reverse_complement(sequence) */
@@ -365,18 +299,18 @@ __device__ __forceinline__ void tx_sam_row(S &o, const tx_args &a, uint32_t g, u
       o.ch(tx_comp(c));
     }
   }
-  TX_LIT(o, "\t*");
+  GS_ROW_LIT(o, "\t*");
   for (uint32_t d = 0; d <= a.m; d++) {
-    TX_LIT(o, "\tk");
+    GS_ROW_LIT(o, "\tk");
     o.ch('0' + d);
-    TX_LIT(o, ":i:");
+    GS_ROW_LIT(o, ":i:");
     o.u64(a.cnt[(size_t)g * 8u + d]); /* unfiltered */
   }
   if (a.complete) {
-    TX_LIT(o, "\tof:H:");
+    GS_ROW_LIT(o, "\tof:H:");
     o.span(a.hex + 16u * a.hex_off[g], 16u * (a.hex_off[g + 1u] - a.hex_off[g]));
   }
-  TX_LIT(o, "\tsp:f:");
+  GS_ROW_LIT(o, "\tsp:f:");
   tx_specificity(o, tx_spec_q(__float_as_uint(a.spec[g])));
   o.ch('\n');
 }
@@ -467,11 +401,11 @@ __device__ __forceinline__ void tx_bam_row(S &o, const tx_args &a, uint32_t g, u
     tx_le(o, v, v <= 255u ? 1u : v <= 65535u ? 2u : 4u);
   }
   if (a.complete) {
-    TX_LIT(o, "ofH");
+    GS_ROW_LIT(o, "ofH");
     o.span(a.hex + 16u * a.hex_off[g], hexn);
     o.ch(0);
   }
-  TX_LIT(o, "spf");
+  GS_ROW_LIT(o, "spf");
   tx_le(o, gb_sp_float_bits(tx_spec_q(__float_as_uint(a.spec[g]))), 4);
 }
 
@@ -490,77 +424,23 @@ __device__ __forceinline__ void tx_slot_row(S &o, const tx_args &a, uint64_t s0,
 }
 
 /* ---- kernels ------------------------------------------------------------------------------------------------- */
-__global__ __launch_bounds__(WAVE *TX_WAVES) void k_tx_len(tx_args a, uint32_t n_tiles) {
-  const uint32_t lane = threadIdx.x & (WAVE - 1u);
-  const uint32_t wave0 = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE, n_waves = gridDim.x * blockDim.x / WAVE;
-  for (uint32_t tile = wave0; tile < n_tiles; tile += n_waves) {
-    const uint64_t s0 = (uint64_t)tile * WAVE, s = s0 + lane;
-    uint32_t len = 0, err = 0;
-    if (s < a.slots) {
-      tx_count o;
-      tx_slot_row(o, a, s0, s, err);
-      if (o.n >= TX_MAX_ROW) {
-        err |= TX_ERR_BIG;
-        o.n = 0;
-      }
-      len = err ? 0u : (uint32_t)o.n;
-      a.lens[s] = len;
-    }
-    if (err) atomicOr(a.err, err);
-    const uint32_t incl = wave_incl_sum(len);
-    if (lane == WAVE - 1u) a.tile_sum[tile] = incl;
-  }
+/* the tile composer of gs_rowtext.h over tx_slot_row; a slot's flags are ORed into the error word, and its row is left out */
+__global__ __launch_bounds__(WAVE *GS_ROW_WAVES) void k_tx_len(tx_args a, uint32_t n_tiles) {
+  gs_tile_len(
+      a, a.slots, n_tiles, a.lens, a.tile_sum,
+      [](const tx_args &a, gs_row_count &o, uint64_t s, uint64_t s0, uint32_t &err) { tx_slot_row(o, a, s0, s, err); },
+      [](const tx_args &a, uint64_t, uint32_t err, bool too_long) {
+        if (too_long) err |= TX_ERR_BIG;
+        if (err) atomicOr(a.err, err);
+        return err == 0u;
+      });
 }
 
-__global__ __launch_bounds__(WAVE *TX_WAVES) void k_tx_write(tx_args a, uint32_t n_tiles) {
-  __shared__ __attribute__((aligned(16))) char s_buf[TX_WAVES][TX_LDS];
-  const uint32_t lane = threadIdx.x & (WAVE - 1u);
-  char *buf = s_buf[threadIdx.x / WAVE];
-  const uint32_t wave0 = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE, n_waves = gridDim.x * blockDim.x / WAVE;
-  for (uint32_t tile = wave0; tile < n_tiles; tile += n_waves) {
-    const uint64_t s0 = (uint64_t)tile * WAVE, s = s0 + lane;
-    const uint32_t len = s < a.slots ? a.lens[s] : 0u;
-    const uint32_t incl = wave_incl_sum(len);
-    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
-    if (total == 0u) continue;
-    const uint64_t base = a.tile_off[tile];
-    const uint32_t a0 = (uint32_t)(base & 15u); /* the slice holds the span at the same address mod 16 as HBM does */
-    const bool in_lds = a0 + total <= TX_LDS;
-    uint32_t err = 0;
-    tx_write o;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); /* (the tile before has been read out of the slice) */
-    if (in_lds) {
-      o.p = buf + a0 + (incl - len);
-      if (len) tx_slot_row(o, a, s0, s, err);
-    } else {
-      o.p = a.text + base + (incl - len);
-      if (len) tx_slot_row(o, a, s0, s, err);
-    }
-    /* the of:H: fields: one line after the other, 64 bytes per step */
-    uint64_t todo = __ballot(o.sp_n != 0ull);
-    while (todo) {
-      const int l = __ffsll((long long)todo) - 1;
-      todo &= todo - 1ull;
-      char *dst = (char *)(((uint64_t)(uint32_t)__shfl((int)((uint64_t)o.sp_dst >> 32), l) << 32) |
-                           (uint32_t)__shfl((int)(uint32_t)(uint64_t)o.sp_dst, l));
-      const char *src = (const char *)(((uint64_t)(uint32_t)__shfl((int)((uint64_t)o.sp_src >> 32), l) << 32) |
-                                       (uint32_t)__shfl((int)(uint32_t)(uint64_t)o.sp_src, l));
-      const uint64_t k = ((uint64_t)(uint32_t)__shfl((int)(o.sp_n >> 32), l) << 32) | (uint32_t)__shfl((int)(uint32_t)o.sp_n, l);
-      for (uint64_t i = lane; i < k; i += WAVE) dst[i] = src[i];
-    }
-    if (!in_lds) continue;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    char *out = a.text + (base - a0); /* 16-byte aligned */
-    const uint32_t end = a0 + total, c_first = (a0 + 15u) >> 4, c_last = end >> 4; /* whole 16-byte chunks [c_first, c_last) */
-    if (c_first >= c_last) {
-      for (uint32_t i = a0 + lane; i < end; i += WAVE) out[i] = buf[i];
-    } else {
-      for (uint32_t i = a0 + lane; i < c_first * 16u; i += WAVE) out[i] = buf[i];
-      for (uint32_t c = c_first + lane; c < c_last; c += WAVE) ((uint4 *)out)[c] = ((const uint4 *)buf)[c];
-      for (uint32_t i = c_last * 16u + lane; i < end; i += WAVE) out[i] = buf[i];
-    }
-  }
+__global__ __launch_bounds__(WAVE *GS_ROW_WAVES) void k_tx_write(tx_args a, uint32_t n_tiles) {
+  gs_tile_write<gs_row_write_span>(a, a.slots, n_tiles, a.lens, a.tile_off, a.text, [](const tx_args &a, gs_row_write_span &o, uint64_t s, uint64_t s0) {
+    uint32_t err = 0; /* k_tx_len has had the verdict */
+    tx_slot_row(o, a, s0, s, err);
+  });
 }
 
 /* SAM: 1 = the hit survives resolve_absolute */
@@ -608,8 +488,9 @@ __device__ __forceinline__ uint4 tx_hex_le(uint64_t v) { /* printer.hpp:18-79: t
   }
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
-/* SAM: the of:H: field of every guide that has lines, once, in the scratch span hex[16 * hex_off[g] ...) */
-__global__ __launch_bounds__(WAVE *TX_WAVES) void k_tx_sam_hex(tx_args a, uint32_t n_tiles) {
+/* SAM: the of:H: field of every guide that has lines, once, in the scratch span hex[16 * hex_off[g] ...).  No client of the
+ * composer, but it walks the same tiles under the same grid (gs_tile_grid): hence its blocks of GS_ROW_WAVES waves */
+__global__ __launch_bounds__(WAVE *GS_ROW_WAVES) void k_tx_sam_hex(tx_args a, uint32_t n_tiles) {
   const uint32_t lane = threadIdx.x & (WAVE - 1u);
   const uint32_t wave0 = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE, n_waves = gridDim.x * blockDim.x / WAVE;
   uint4 *hex = (uint4 *)a.hex;
@@ -800,7 +681,7 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
     }
 
     const uint32_t cus = (uint32_t)gs_num_cus(ix->device);
-    const uint32_t grid = std::max(1u, std::min((n_tiles + TX_WAVES - 1) / TX_WAVES, cus * 32u));
+    const uint32_t grid = gs_tile_grid(n_tiles, cus);
     GS_HIP(hipMemsetAsync(tmp + t_err, 0, 16, st));
     GS_HIP(hipMemsetAsync(a.tile_sum + n_tiles, 0, 8, st));
     if (sam) {
@@ -819,10 +700,10 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
       if (units) {
         GS_TRY(gs_reserve(ix->w_text.hex, 16 * units + 16));
         a.hex = (char *)ix->w_text.hex.p;
-        hipLaunchKernelGGL(k_tx_sam_hex, dim3(grid), dim3(WAVE * TX_WAVES), 0, st, a, n_tiles);
+        hipLaunchKernelGGL(k_tx_sam_hex, dim3(grid), dim3(WAVE * GS_ROW_WAVES), 0, st, a, n_tiles);
       }
     }
-    hipLaunchKernelGGL(k_tx_len, dim3(grid), dim3(WAVE * TX_WAVES), 0, st, a, n_tiles);
+    hipLaunchKernelGGL(k_tx_len, dim3(grid), dim3(WAVE * GS_ROW_WAVES), 0, st, a, n_tiles);
     GS_TRY(gs_prim_carved("gs_format_device: scan of the tiles", tmp + t_scan, tb_scan, [&](void *t, size_t &b) {
       return rocprim::exclusive_scan(t, b, a.tile_sum, a.tile_off, 0ull, (size_t)n_tiles + 1, rocprim::plus<uint64_t>(), st);
     }));
@@ -848,7 +729,7 @@ static gs_status format_device(gs_index *ix, const gs_genome_structure *gs, cons
     GS_TRY(gs_reserve(ix->w_text.text, total + 16));
     a.text = (char *)ix->w_text.text.p;
     GS_TRY(gs_reserve(ix->w_text.goff, 8 * (n + 1) + 16));
-    if (total) hipLaunchKernelGGL(k_tx_write, dim3(grid), dim3(WAVE * TX_WAVES), 0, st, a, n_tiles);
+    if (total) hipLaunchKernelGGL(k_tx_write, dim3(grid), dim3(WAVE * GS_ROW_WAVES), 0, st, a, n_tiles);
     /* where each guide's lines begin (gs_index_last_text_offsets): 8 bytes per guide, kept beside the text */
     hipLaunchKernelGGL(k_tx_guide_off, dim3((uint32_t)((n + 256) / 256)), dim3(256), 0, st, a.offsets, a.off0, a.n, (const uint32_t *)a.lens,
                        (const uint64_t *)a.tile_off, (uint64_t *)ix->w_text.goff.p);

@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 api = import_module("guidescan-cli_amd.api")
 decode = dg.decode
 CLI = dg.ROOT / "guidescan-cli_amd" / "bin" / "guidescan"
-DC_LDS = 12288   # the bytes of a wave's slice in k_dc_write (gs_decode.hip)
+DC_LDS = 12288   # the bytes of a wave's slice in k_dc_write (GS_ROW_LDS, csrc/gs_rowtext.h)
 HEADER = {"succinct": decode.SUCCINCT_HEADER + "\n", "complete": decode.COMPLETE_HEADER + "\n"}   # the script's, without the option
 
 
@@ -338,3 +338,50 @@ def test_enumerate_annotate_and_decode_annotate_agree(tmp_path):
     assert any(k[3].startswith("first_") for _, c in records for k in c) and any("last_" in k[3] for _, c in records for k in c)
     for i, c in records:
         assert c == by_enumerate[i], i
+
+
+def test_a_tile_at_the_border_of_the_lds_slice(small):
+    """A tile is composed in the wave's slice while a0 + total <= 12288 (a0: the tile's offset in the text mod 16) and
+    straight in HBM beyond.  Three records of 62 off-targets each are three tiles of 64 words; one off-target of the second
+    lies under 46 groups with names of 200 bytes and one more whose name grows byte by byte over 48 values, so that its
+    tile's total passes from 12288 - 24 to 12288 + 23 and crosses the border whatever a0 is.  The rows without the option are
+    the Python model's, the column is annot_model's."""
+    rng = np.random.default_rng(21)
+    guide = "ACGTTGCAAGCTTGCATGCAAGG"
+
+    def rec(name, d, first):
+        ws = [first] + [dac.word("cA", int(x), "+-"[int(s)]) for x, s in zip(rng.integers(30, 90, 61), rng.integers(0, 2, 61))]
+        r = decode.Record(name, guide, False, "cA", 3, dac.hex_list([(d, ws)]))
+        assert len(r.hex) == 64 * 16
+        return r
+
+    recs = [rec("before", 0, dac.word("cA", 40, "+")), rec("wide", 1, dac.word("cD", 25, "+")), rec("behind", 2, dac.word("cB", 5, "-"))]
+    model = decode.Decoder(dac.SQ, small["fasta"], dg.TABLES)
+    plain = (HEADER["complete"] + "".join(r + "\n" for r in model.rows(recs, complete=True))).encode("latin-1")
+    assert plain.count(b"\n") == 1 + 3 * 62
+    fixed = "".join(f"cD\t25\t26\tf{i:02d}_" + "x" * 196 + "\n" for i in range(46)) + "cA\t35\t37\tshort\n"
+
+    def expected(length):
+        bed = fixed + "cD\t25\t26\t" + "s" * length + "\n"
+        want, feats = dac.expected_complete(plain, dac.SQ, recs, bed)
+        rows = want.split(b"\n")[1:-1]
+        assert len(feats[62]) == 47 and {len(f) for f in feats[63:124]} == {0, 1}   # one wide row; `short` touches some others
+        return bed, want, sum(len(r) + 1 for r in rows[62:124])
+
+    start = 1 + DC_LDS - 24 - expected(1)[2]
+    assert 1 <= start and start + 47 <= 230   # the parser admits names of 238 bytes here
+    dec = api.Decoder(dac.SQ, small["fasta"], device=0)
+    totals = []
+    try:
+        for length in range(start, start + 48):
+            bed, want, total = expected(length)
+            totals.append(total)
+            an = annotation(bed)
+            dec.set_annotation(an)
+            got = dec.decode_records(recs, complete=True, features=True)
+            dec.set_annotation(None)
+            an.close()
+            assert got == body(want), f"a name of {length} bytes"
+    finally:
+        dec.close()
+    assert totals == list(range(DC_LDS - 24, DC_LDS + 24))

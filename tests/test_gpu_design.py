@@ -193,3 +193,76 @@ def test_a_shape_outside_the_fast_path_s_key_is_unsupported(scored_gpu):
     assert e.value.status == 3
     d.close()
     rg.close()
+
+
+# ---- ids and rows through the id writer the design shares with the candidate scan (gs_km_encode_text, gs_kmers.hip) --------
+WRITER_CHROMOSOMES = ("c", "the_second_chromosome")   # names of different length
+WRITER_COUNTS = (1, 255, 256, 257)                    # the writer's workgroups hold 256 records
+
+
+@pytest.fixture(scope="module")
+def writer_genome():
+    """1.2 Mb and 3 kb over A,C,G,T: positions of one to seven digits; the scan of both, once, on the host"""
+    rng = np.random.default_rng(41)
+    lengths = [1_200_000, 3_000]
+    chromosomes = [rng.choice(np.frombuffer(b"ACGT", np.uint8), ln) for ln in lengths]
+    chromosomes[0][:30] = np.frombuffer(b"ACGTACGTACGTACGTACGTAGGTTACCAT", np.uint8)   # a site at position 1, whatever follows
+    scans = []
+    for chrm in chromosomes:
+        km = api.generate_kmers(chrm, "NGG", 20)
+        seqs, _, pos, sense = km.to_host()
+        km.close()
+        scans.append((np.asarray(seqs).reshape(-1, 20), np.asarray(pos), np.asarray(sense)))
+    return lengths, chromosomes, scans
+
+
+def _window(q, first, n, w):
+    """q: the sorted 0-based starts of a chromosome's candidates -> the interval that holds exactly those of
+    q[first:first + n] (a footprint is [q, q + w) and must lie inside), or None where an equal start stands next to them"""
+    last = first + n - 1
+    if (first and q[first - 1] == q[first]) or (last + 1 < len(q) and q[last + 1] == q[last]):
+        return None
+    return int(q[first]), int(q[last]) + w
+
+
+@pytest.mark.parametrize("prefix", ["", "p" * 200], ids=["no_prefix", "prefix200"])
+@pytest.mark.parametrize("count", WRITER_COUNTS)
+def test_ids_and_rows_through_the_shared_writer(writer_genome, count, prefix):
+    lengths, chromosomes, scans = writer_genome
+    w = 23
+    # the longest group name the parser admits under this prefix: an id with ten position digits has 254 bytes
+    longest = "G" * (254 - len(prefix) - 1 - max(map(len, WRITER_CHROMOSOMES)) - 1 - 10 - 2)
+    q0 = np.sort(scans[0][1].astype(np.int64) - 1)
+    bed, singles = [], 0
+    if count > 1:
+        # one record per digit count 1 .. 6 on the first chromosome, one on the second, the rest from one stretch
+        for digits in range(1, 7):
+            first = next(i for i in range(int(np.searchsorted(q0, 10 ** (digits - 1) - 1)), len(q0)) if _window(q0, i, 1, w))
+            assert len(str(q0[first] + 1)) == digits
+            bed.append((0, *_window(q0, first, 1, w), f"d{digits}"))
+        q1 = np.sort(scans[1][1].astype(np.int64) - 1)
+        first = next(i for i in range(len(q1)) if _window(q1, i, 1, w))
+        bed.append((1, *_window(q1, first, 1, w), "g"))   # a name of one byte
+        singles = len(bed)
+    # ... and positions of seven digits under the longest name
+    at = int(np.searchsorted(q0, 1_000_000))
+    first = next(i for i in range(at, len(q0)) if _window(q0, i, count - singles, w))
+    bed.append((0, *_window(q0, first, count - singles, w), longest))
+    text = "".join(f"{WRITER_CHROMOSOMES[c]}\t{a}\t{b}\t{name}\n" for c, a, b, name in bed)
+    rg = api.Regions.parse(text.encode(), (list(WRITER_CHROMOSOMES), lengths), prefix=prefix)
+    parts = []
+    for c, chrm in enumerate(chromosomes):
+        km = api.generate_kmers(chrm, "NGG", 20)
+        parts.append(km.restrict(rg, c))
+        km.close()
+    d = api.Design.concat(parts)
+    want = api.design_host_model(rg, [(c, *scans[c], None, None) for c in range(2)], "NGG", 20, prefix, rows=True)
+    assert want["n"] == count
+    digits = {len(str(int(p))) for p in want["pos"]}
+    assert digits == ({7} if count == 1 else set(range(1, 8))) and (count == 1 or set(want["sense_chars"].tolist()) == {ord("+"), ord("-")})
+    assert want["ids"].startswith((prefix + longest + ":c:1").encode() if count == 1 else (prefix + "d1:c:").encode())
+    km = d.select(prefix)
+    assert_same(selected(km), want)
+    assert km.n == count and d.rows(prefix) == want["rows"] and want["rows"].count(b"\n") == count
+    for x in (km, d, rg, *parts):
+        x.close()

@@ -337,3 +337,32 @@ def test_a_guide_outside_the_fast_path_is_left_to_the_caller(toy, handle):
         handle.enumerate_text(seqs, pams, ["a", "b", "c", "n"], [True] * 4, gs, mismatches=2)
     assert e.value.status == 3  # GS_ERR_UNSUPPORTED: nothing is returned
     assert handle.enumerate_text(seqs[:3], pams[:3], ["a", "b", "c"], [True] * 3, gs, mismatches=2).count(b"\n") >= 3
+
+
+TILE_LDS = 12288   # the bytes of a wave's slice (GS_ROW_LDS, csrc/gs_rowtext.h)
+
+
+@pytest.mark.parametrize("cfg", [dict(), dict(sam=True)], ids=cfg_id)
+def test_a_tile_at_the_border_of_the_lds_slice(handle, cfg):
+    """A tile is composed in the wave's slice while a0 + total <= 12288 (a0: the tile's offset in the text mod 16) and
+    straight in HBM beyond.  The second tile of a batch of one-hit guides - 32 rows, a row per hit slot - is padded with
+    long ids to 12288 - 24 bytes; then one guide's id grows byte by byte over 48 values, so the tile's total passes the
+    border whatever a0 is.  With sam=True every line carries an of:H: field, the span the wave copies afterwards."""
+    n, lo, swept = 74, 32, 45   # tiles of 32 guides: [0, 32) short rows, [32, 64) the padded tile, [64, 74) a partial tile
+    gs, ids, seqs, pams, senses, offs, hits, spec = _one_hit_batch(np.linspace(0.0, 1.0, n))
+
+    def rows_of_tile(ids):
+        lines = api.format_guides(gs, ids, seqs, pams, senses, offs, hits, spec, 3, **cfg).split(b"\n")[:-1]
+        assert len(lines) == n
+        return sum(len(x) + 1 for x in lines[lo:lo + 32])
+
+    extra = TILE_LDS - 24 - rows_of_tile(ids)   # an id stands once in its row
+    assert extra > 32 * 100
+    ids = [x + "p" * (extra // 32 + (extra % 32 if i == swept else 0)) if lo <= i < lo + 32 else x for i, x in enumerate(ids)]
+    totals = []
+    for j in range(48):
+        grown = [x + "q" * j if i == swept else x for i, x in enumerate(ids)]
+        want = api.format_guides(gs, grown, seqs, pams, senses, offs, hits, spec, 3, **cfg)
+        totals.append(rows_of_tile(grown))
+        assert device_text(handle, gs, grown, seqs, pams, senses, offs, hits, spec, 3, **cfg) == want, f"id grown by {j}"
+    assert totals == list(range(TILE_LDS - 24, TILE_LDS + 24))
