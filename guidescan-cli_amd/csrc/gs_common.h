@@ -303,6 +303,7 @@ struct gs_pairtab_host {
   uint32_t deep_P = 0, deep_kb = 0;
   bool spaced = false;             /* both strands' spaced tables exist, keyed by the first sp_x and the last sp_g guide symbols */
   uint32_t sp_x = 0, sp_g = 0;
+  uint32_t sp_forced_d = 0;        /* GS_SPACED_BITS when they were built (0: the offsets' bits came from the row count) */
   uint64_t sp_rows[2] = {0, 0};
   uint64_t sp_bytes() const { return own.bytes_of(d[0].sp_off) + own.bytes_of(d[0].sp_rows) + own.bytes_of(d[1].sp_off) + own.bytes_of(d[1].sp_rows); }
   uint64_t n_slots[2] = {0, 0};    /* slots of each strand's row arrays (rows + the big entries' header slots) */

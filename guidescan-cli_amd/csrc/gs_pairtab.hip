@@ -442,16 +442,19 @@ bool gs_pairtab_free_spaced(gs_index *ix, uint32_t slot) {
 
 /* the direct part's bits for a table of `rows` rows whose keys have key_bits bits and whose payload keeps obits bits of O:
  * 2^d >= rows, at most 2^28 offsets, and what the payload's second word has to hold (O, the other key bits) fits 32 bits;
- * 0: no such d */
-static uint32_t sp_direct_bits(uint64_t rows, uint32_t key_bits, uint32_t obits) {
+ * 0: no such d.  forced != 0 (GS_SPACED_BITS): that d instead of the one the row count gives, under the same three limits - a
+ * small genome then gets the key split of a large one (d = the whole key, no key bits with the row) or the smallest legal d */
+static uint32_t sp_direct_bits(uint64_t rows, uint32_t key_bits, uint32_t obits, uint32_t forced) {
   uint32_t d = 8;
   while (d < 28 && (1ull << d) < rows) d++;
+  if (forced) d = forced < 28u ? forced : 28u;
   if (d > key_bits) d = key_bits;
   if (key_bits - d + obits > 32u) d = key_bits + obits - 32u;
   return d >= 1 && d <= 28 && d <= key_bits ? d : 0u;
 }
 
-static gs_status build_spaced(gs_index *ix, gs_pairtab_host &p, int s, uint32_t k, uint32_t x_len, uint32_t g, hipStream_t st) {
+static gs_status build_spaced(gs_index *ix, gs_pairtab_host &p, int s, uint32_t k, uint32_t x_len, uint32_t g, uint32_t forced_d,
+                              hipStream_t st) {
   const uint64_t entries = 1ull << (2 * k);
   const uint32_t key_bits = 2u * (x_len + g), obits = 2u * (k - x_len);
   gs_scratch mem; /* the temporaries, and both arrays until the slot has them */
@@ -476,7 +479,7 @@ static gs_status build_spaced(gs_index *ix, gs_pairtab_host &p, int s, uint32_t 
   uint64_t rows = 0;
   GS_TRY(scan_counts(mem, d_count, d_start, entries, st, &rows));
   if (p.n_slots[s] >= 0xFFFFFFFFull || rows > p.n_slots[s]) return GS_ERR_UNSUPPORTED;
-  const uint32_t d = sp_direct_bits(rows, key_bits, obits);
+  const uint32_t d = sp_direct_bits(rows, key_bits, obits, forced_d);
   if (!d) return GS_ERR_UNSUPPORTED;
   const uint32_t rem = key_bits - d;
   GS_TRY(mem.get(4 * rows, &d_keys));
@@ -515,7 +518,10 @@ gs_status gs_pairtab_ensure_spaced(gs_index *ix, uint32_t slot, uint32_t x_len, 
   gs_pairtab_host &p = ix->pairtab[slot];
   const uint32_t k = ix->pt_k;
   if (!p.valid) return GS_OK;
-  if (p.spaced && p.sp_x == x_len && p.sp_g == g) return GS_OK;
+  /* GS_SPACED_BITS: the direct part's bits asked for (0: from the row count); tables built under another value are built anew */
+  uint32_t forced_d = 0;
+  if (const char *e = gs_opt(ix, "GS_SPACED_BITS")) forced_d = (uint32_t)std::min(32l, std::max(1l, atol(e)));
+  if (p.spaced && p.sp_x == x_len && p.sp_g == g && p.sp_forced_d == forced_d) return GS_OK;
   gs_pairtab_free_spaced(ix, slot);
   if (k < 4 || x_len < 1 || x_len + 2 > k || g < 1 || 2 * (x_len + g) > 32 || g > 16) return GS_OK;
   /* what the finished tables take (8 bytes per row and the offsets, both strands) and the sort's buffers while one is built */
@@ -540,7 +546,7 @@ gs_status gs_pairtab_ensure_spaced(gs_index *ix, uint32_t slot, uint32_t x_len, 
   const bool timed = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
   if (timed) (void)hipEventRecord(ev[0], st);
   gs_status rc = GS_OK;
-  for (int s = 0; s < 2 && rc == GS_OK; s++) rc = build_spaced(ix, p, s, k, x_len, g, st);
+  for (int s = 0; s < 2 && rc == GS_OK; s++) rc = build_spaced(ix, p, s, k, x_len, g, forced_d, st);
   if (timed) {
     float ms = 0.f;
     (void)hipEventRecord(ev[1], st);
@@ -558,6 +564,7 @@ gs_status gs_pairtab_ensure_spaced(gs_index *ix, uint32_t slot, uint32_t x_len, 
   p.spaced = true;
   p.sp_x = x_len;
   p.sp_g = g;
+  p.sp_forced_d = forced_d;
   if (gs_opt(ix, "GS_DEBUG")) fprintf(stderr, "[gs] spaced tables of pair %u: %.2f GB, built in %.1f ms\n", p.code, 1e-9 * (double)p.sp_bytes(), p.sp_build_ms);
   return GS_OK;
 }

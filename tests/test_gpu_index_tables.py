@@ -439,6 +439,22 @@ def test_pair_deep_and_spaced_tables_start_ttn(pair_world):
         hits_equal_oracle(w, seqs, result, "TTN", (), True)
 
 
+@pytest.mark.parametrize("bits,rem", [("32", 0), ("1", 23)], ids=["whole-key", "smallest"])
+def test_pair_deep_and_spaced_tables_key_split(pair_world, bits, rem):
+    """the same comparison under GS_SPACED_BITS: the whole 24-bit key of this geometry (|X| = 7, |R| = 5) in the offsets and
+    no key bits with the row - what a genome of hg38's size gets -, and one bit in the offsets, the other 23 with the row"""
+    w = pair_world
+    with built(dict(text=w["text"]), GS_PREFIX_K=str(PK)) as gidx:
+        gidx.set_option("GS_SPACED_BITS", bits)
+        seqs, result = pair_batch(gidx, w, "TTN", (), L_START, True, PK - 2)
+        for strand in (0, 1):
+            lay = gidx.debug_layout(strand, slot=0)
+            assert lay["spaced"] and (lay["sp_rem"], lay["d"]) == (rem, 24 - rem), lay
+        check_slots(gidx, w, (CODE["TTN"],), PK - 2, L_START, {}, {})
+        assert gidx.last_counters()["spaced_items"] == 2 * seqs.shape[0]
+        hits_equal_oracle(w, seqs, result, "TTN", (), True)
+
+
 def test_every_array_was_compared():
     """a table that silently was not built fails here: every array name, both strands, was present and equal at least once"""
     missing = [(kind, name, s) for kind, names in (("strand", STRAND_NAMES), ("slot", SLOT_NAMES)) for name in names

@@ -162,6 +162,7 @@ def test_long_keys_on_a_repeat_rich_genome():
         (offr, hitsr), ctr, forms = three_settings(gidx, seqs[pick], pams[pick], mismatches=3)
         assert forms == (3, 3)
         assert ctr["spaced_rows_max"] > 64, ctr
+        assert ctr["spaced_matches"] > 0, ctr   # rows that passed the lookup's filter: what runs behind a match ran
         # a k-mer entry of 63 rows and more: under the key of the heaviest guide's own site that many rows share their O
         info = gidx.spaced_rows(0, 0, 0)[2]
         assert info["built"] == 1, info
