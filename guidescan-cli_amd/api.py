@@ -93,6 +93,11 @@ class GsRegionsReport(C.Structure):
                 ("bad_text", C.c_void_p)]
 
 
+class GsSeqRule(C.Structure):
+    _fields_ = [("gc_min", C.c_uint32), ("gc_max", C.c_uint32), ("max_run", C.c_uint32), ("n_motifs", C.c_uint32),
+                ("motif_len", C.c_uint8 * 16), ("motif_set", (C.c_uint8 * 16) * 16)]
+
+
 class GsPairRule(C.Structure):
     _fields_ = [("min_span", C.c_uint64), ("max_span", C.c_uint64), ("cut_offset", C.c_uint32), ("orientation", C.c_uint32),
                 ("per_region", C.c_uint32), ("flags", C.c_uint32), ("min_specificity", C.c_float), ("pad", C.c_uint32)]
@@ -399,6 +404,27 @@ def lib():
     L.gs_debug_pairs_host.argtypes = [u64, vp, vp, vp, vp, vp, vp, u32, u32, u32, C.POINTER(GsPairRule), C.POINTER(vp)]
     L.gs_debug_pairs_chunk.restype = u64
     L.gs_debug_pairs_chunk.argtypes = [u64]
+    L.gs_seq_rule_init.restype = i32
+    L.gs_seq_rule_init.argtypes = [C.POINTER(GsSeqRule)]
+    L.gs_seq_rule_add_motif.restype = i32
+    L.gs_seq_rule_add_motif.argtypes = [C.POINTER(GsSeqRule), C.c_char_p, C.c_int]
+    L.gs_kmers_filter.restype = i32
+    L.gs_kmers_filter.argtypes = [vp, C.POINTER(GsSeqRule), vp, C.POINTER(vp), vp]
+    L.gs_debug_kmers_filter_ms.restype = i32
+    L.gs_debug_kmers_filter_ms.argtypes = [vp, vp]
+    L.gs_debug_kmers_filter_host.restype = i32
+    L.gs_debug_kmers_filter_host.argtypes = [vp, u64, u32, C.POINTER(GsSeqRule), vp, vp]
+    L.gs_design_set_spacing.restype = i32
+    L.gs_design_set_spacing.argtypes = [vp, u32, u32, u32]
+    L.gs_design_last_spacing.restype = i32
+    L.gs_design_last_spacing.argtypes = [vp, vp]
+    L.gs_debug_design_space_ms.restype = i32
+    L.gs_debug_design_space_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.gs_debug_design_host_spaced.restype = i32
+    L.gs_debug_design_host_spaced.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, C.c_char_p, u32, C.c_char_p, u32, f32, u32, u32, u32,
+                                              C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), vp]
+    L.gs_debug_design_set_scores.restype = i32
+    L.gs_debug_design_set_scores.argtypes = [vp, vp, vp]
     L.gs_decoder_set_annotation.restype = i32
     L.gs_decoder_set_annotation.argtypes = [vp, vp]
     L.gs_debug_decode_annot_ms.restype = i32
@@ -447,7 +473,10 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_design_set_feature_rule", "gs_design_get_feature_hits",
            "gs_decoder_set_annotation", "gs_debug_decode_annot_ms",
            "gs_design_pairs", "gs_pairs_get", "gs_pairs_rows", "gs_pairs_last", "gs_pairs_ms", "gs_pairs_free", "gs_debug_pairs_host",
-           "gs_debug_pairs_chunk"]
+           "gs_debug_pairs_chunk",
+           "gs_seq_rule_init", "gs_seq_rule_add_motif", "gs_kmers_filter", "gs_debug_kmers_filter_ms", "gs_debug_kmers_filter_host",
+           "gs_design_set_spacing", "gs_design_last_spacing", "gs_debug_design_space_ms", "gs_debug_design_host_spaced",
+           "gs_debug_design_set_scores"]
 
 
 def _check(rc):
@@ -736,6 +765,45 @@ def _bytes_or_none(x, n):
     return a
 
 
+class SeqRule:
+    """The sequence rules on the candidates of a scan (csrc/gs_select_scan.h): gc=(MIN, MAX) integer percentages,
+    max_run >= 1, exclude_motifs and exclude_sites IUPAC motifs over ACGTRYSWKMBDHVN - a site also excludes its reverse
+    complement.  At most 16 motifs after that expansion, 1 to 32 letters each; ValueError names the motif refused."""
+
+    def __init__(self, gc=None, max_run=None, exclude_motifs=(), exclude_sites=()):
+        self.c = GsSeqRule()
+        _check(lib().gs_seq_rule_init(C.byref(self.c)))
+        if gc is not None:
+            lo, hi = gc
+            if int(lo) != lo or int(hi) != hi or not 0 <= lo <= hi <= 100:
+                raise ValueError("gc: (MIN, MAX), integer percentages with 0 <= MIN <= MAX <= 100")
+            self.c.gc_min, self.c.gc_max = int(lo), int(hi)
+        if max_run is not None:
+            if int(max_run) != max_run or max_run < 1:
+                raise ValueError("max_run >= 1")
+            self.c.max_run = int(max_run)
+        for motifs, both in ((exclude_motifs, 0), (exclude_sites, 1)):
+            for m in motifs:
+                rc = lib().gs_seq_rule_add_motif(C.byref(self.c), m.encode(), both)
+                if rc != 0:
+                    raise ValueError(lib().gs_status_string(rc).decode())
+
+    @property
+    def n_motifs(self):
+        return int(self.c.n_motifs)
+
+
+def seq_rule_host(seqs, k, rule):
+    """the rule on the host through the kernels' shared header, no GPU (gs_debug_kmers_filter_host).  seqs: uint8[n, k] ->
+    (charge uint8[n]: 0 passes, 1 GC, 2 run, 3 motif; counts: dict(scanned, gc, run, motif))"""
+    a = np.ascontiguousarray(seqs, dtype=np.uint8).reshape(-1, k)
+    n = a.shape[0]
+    charge = np.zeros(n, dtype=np.uint8)
+    counts = (C.c_uint64 * 4)()
+    _check(lib().gs_debug_kmers_filter_host(a.ctypes.data if n else None, n, k, C.byref(rule.c), charge.ctypes.data if n else None, counts))
+    return charge, dict(zip(("scanned", "gc", "run", "motif"), (int(x) for x in counts)))
+
+
 class DeviceKmers:
     """Candidate guides of one chromosome, resident in HBM (gs_kmers_generate).  `seqs_ptr` /
     `pams_ptr` are raw device addresses in the layout GenomeIndex.enumerate_device takes."""
@@ -822,6 +890,17 @@ class DeviceKmers:
         s = C.string_at(out, ln.value)
         lib().gs_free(out)
         return s
+
+    def filter(self, rule):
+        """the candidates that pass a SeqRule, in the scan's order, as a fresh DeviceKmers (gs_kmers_filter); before
+        encode_ids.  .filter_counts: dict(scanned, gc, run, motif); .filter_ms: the three passes between stream events"""
+        h, counts, ms = C.c_void_p(), (C.c_uint64 * 4)(), (C.c_double * 3)()
+        _check(lib().gs_kmers_filter(self._h, C.byref(rule.c), None, C.byref(h), counts))
+        km = DeviceKmers(h, self.k, self.P)
+        km.filter_counts = dict(zip(("scanned", "gc", "run", "motif"), (int(x) for x in counts)))
+        _check(lib().gs_debug_kmers_filter_ms(h, ms))
+        km.filter_ms = dict(zip(("rule", "scan", "gather"), (float(x) for x in ms)))
+        return km
 
     def restrict(self, regions, chr_index):
         """the records of this scan - of chromosome chr_index of the regions' structure - that lie in a group of
@@ -1005,6 +1084,36 @@ class Design:
         self._rule = annotation   # keeps it alive through score()
         return self
 
+    def set_spacing(self, min_spacing, cut_offset=3, start=False):
+        """the picks of a group lie min_spacing bases apart or more, by the cut that leaves cut_offset protospacer bases
+        between it and the PAM (gs_design_set_spacing; the rule is csrc/gs_select_scan.h's).  0 takes the rule off.
+        select() and rows() then need 1 <= per_region <= 1024, and pairs() is refused."""
+        _check(lib().gs_design_set_spacing(self._h, int(min_spacing), int(cut_offset), GS_FLAG_PAM_AT_START if start else 0))
+        return self
+
+    def last_spacing(self):
+        """of the last select() / rows() under set_spacing (gs_design_last_spacing)"""
+        out = (C.c_uint64 * 2)()
+        _check(lib().gs_design_last_spacing(self._h, out))
+        return {"passed_over": int(out[0]), "groups_short_for_spacing": int(out[1])}
+
+    def space_ms(self):
+        """the milliseconds of that selection's walk kernel alone (gs_debug_design_space_ms)"""
+        ms = C.c_double()
+        _check(lib().gs_debug_design_space_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def set_scores(self, spec, eligible=None):
+        """specificities (float32[n]) and eligibility bytes (uint8[n], None: all) from the host, in record order; the
+        design then counts as scored (gs_debug_design_set_scores).  For tests of the selection."""
+        n = self.info()[0]
+        s = np.ascontiguousarray(spec, dtype=np.float32)
+        e = None if eligible is None else np.ascontiguousarray(eligible, dtype=np.uint8)
+        if s.shape != (n,) or (e is not None and e.shape != (n,)):
+            raise ValueError("one entry per record")
+        _check(lib().gs_debug_design_set_scores(self._h, s.ctypes.data if n else None, e.ctypes.data if e is not None and n else None))
+        return self
+
     def select(self, prefix="", per_region=None, min_specificity=None):
         """the records in order, cut to the first per_region eligible ones of each group with specificity >=
         min_specificity (gs_design_select) -> DeviceKmers with ids"""
@@ -1168,15 +1277,21 @@ def pairs_host(group, chr, pos, sense, spec, eligible, k, P, n_groups, max_span,
 
 
 def design(index, regions, pam, k, per_region=None, min_specificity=None, *, chromosomes, mismatches=3, alt_pams=(),
-           start=False, threshold=-1, prefix="", device=0):
-    """Guides for regions in one call: scan, restrict, (score,) select -> DeviceKmers with ids.  chromosomes: iterable of
-    (index in the regions' structure, the chromosome's bytes).  `index` (a GenomeIndex) may be None when neither
-    per_region, min_specificity nor threshold asks for scores."""
+           start=False, threshold=-1, prefix="", device=0, seq_rule=None, min_spacing=0, cut_offset=3):
+    """Guides for regions in one call: scan, (filter,) restrict, (score,) select -> DeviceKmers with ids.  chromosomes:
+    iterable of (index in the regions' structure, the chromosome's bytes).  `index` (a GenomeIndex) may be None when neither
+    per_region, min_specificity nor threshold asks for scores.  seq_rule: a SeqRule, applied to every scan before it is
+    restricted, so a candidate it drops is never scored.  min_spacing > 0 (with per_region <= 1024): the picks of a group
+    lie that many bases apart or more, by the cut at cut_offset (Design.set_spacing)."""
     parts = []
     try:
         for ci, chrm in chromosomes:
             km = generate_kmers(chrm, pam, k, start, device)
             try:
+                if seq_rule is not None:
+                    kept = km.filter(seq_rule)
+                    km.close()
+                    km = kept
                 parts.append(km.restrict(regions, ci))
             finally:
                 km.close()
@@ -1187,15 +1302,19 @@ def design(index, regions, pam, k, per_region=None, min_specificity=None, *, chr
     try:
         if per_region is not None or min_specificity is not None or threshold >= 0:
             whole.score(index, mismatches, alt_pams, start, threshold)
+        if min_spacing:
+            whole.set_spacing(min_spacing, cut_offset, start)
         return whole.select(prefix, per_region, min_specificity)
     finally:
         whole.close()
 
 
-def design_host_model(regions, parts, pam, k, prefix="", per_region=None, min_specificity=None, rows=False):
+def design_host_model(regions, parts, pam, k, prefix="", per_region=None, min_specificity=None, rows=False, min_spacing=None,
+                      cut_offset=3, start=False):
     """the stages of Design on the host through the kernels' shared header, no GPU (gs_debug_design_host).  parts: list of
     (chr_index, seqs uint8[n,k], positions uint32[n], senses uint8[n], specificity float32[n] or None, eligible
-    uint8[n] or None) -> dict as kmers_arrays plus pos, and rows bytes when asked for"""
+    uint8[n] or None) -> dict as kmers_arrays plus pos, and rows bytes when asked for.  min_spacing not None: through
+    gs_debug_design_host_spaced, and the dict also holds last_select and last_spacing as Design gives them"""
     npart = len(parts)
     keep = []
 
@@ -1219,15 +1338,26 @@ def design_host_model(regions, parts, pam, k, prefix="", per_region=None, min_sp
     elig, have_elig = col(5, np.uint8)
     n, s = _select_args(per_region, min_specificity)
     h, text, ln = C.c_void_p(), C.c_void_p(), C.c_uint64()
-    _check(lib().gs_debug_design_host(regions._h, npart, chr_index.ctypes.data, counts.ctypes.data, seqs, pos, sense,
-                                      spec if have_spec else None, elig if have_elig else None, pam.encode(), k,
-                                      prefix.encode(), n, s, C.byref(h), C.byref(text) if rows else None, C.byref(ln)))
+    report = (C.c_uint64 * 6)()
+    if min_spacing is None:
+        _check(lib().gs_debug_design_host(regions._h, npart, chr_index.ctypes.data, counts.ctypes.data, seqs, pos, sense,
+                                          spec if have_spec else None, elig if have_elig else None, pam.encode(), k,
+                                          prefix.encode(), n, s, C.byref(h), C.byref(text) if rows else None, C.byref(ln)))
+    else:
+        _check(lib().gs_debug_design_host_spaced(regions._h, npart, chr_index.ctypes.data, counts.ctypes.data, seqs, pos, sense,
+                                                 spec if have_spec else None, elig if have_elig else None, pam.encode(), k,
+                                                 prefix.encode(), n, s, int(min_spacing), int(cut_offset),
+                                                 GS_FLAG_PAM_AT_START if start else 0, C.byref(h),
+                                                 C.byref(text) if rows else None, C.byref(ln), report))
     km = _selected_kmers(h, k, len(pam))
     try:
         sq, pm, ps, sn = km.to_host()
         ids, off, sp = km.ids_to_host()
         out = {"n": km.n, "seqs": sq.tobytes(), "pams": pm.tobytes(), "pos": ps, "sense_chars": sn, "ids": ids,
                "id_off": off, "sense": sp}
+        if min_spacing is not None:
+            out["last_select"] = dict(zip(("records", "kept", "groups_empty", "groups_short"), (int(x) for x in report[:4])))
+            out["last_spacing"] = {"passed_over": int(report[4]), "groups_short_for_spacing": int(report[5])}
         if rows:
             out["rows"] = C.string_at(text, ln.value)
             lib().gs_free(text)

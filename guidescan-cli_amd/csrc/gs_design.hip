@@ -20,6 +20,10 @@
  *                         (rocprim exclusive scan of the marks: a record's rank among the marked ones before it)
  *                         k_ds_heads   the first record of every group leaves its rank in the group's slot
  *                         k_ds_cut     keep = marked && rank - rank of the group's head < N
+ *                         with gs_design_set_spacing, in place of the two (gs_select_scan.h, no counterpart in the reference):
+ *                         k_ds_bounds  the first and last record of every group leave its begin and end place
+ *                         k_ds_space   one wave per group walks its records in order, 64 a step, against the kept cuts in
+ *                                      LDS: keep = marked && no kept record within D && fewer than N kept  (17 B read, 4 written)
  *                         (rocprim exclusive scan of the keeps: the places)
  *                         k_ds_gather  the kept records into a fresh gs_kmers                 (k + P + 13 B each way)
  *                         gs_km_encode_text (gs_kmers.hip: k_km_text_len / 64-bit scan / k_km_text_write over the row of
@@ -34,6 +38,7 @@
 #include "gs_regions_obj.h"
 #include "gs_annot_obj.h"
 #include "gs_design_obj.h"
+#include "gs_select_scan.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -644,6 +649,81 @@ __global__ __launch_bounds__(DS_BLOCK) void k_ds_cut(const uint64_t *hi_sorted, 
   }
   keep[j] = kp;
 }
+/* ---- spacing between the picks of a group (gs_select_scan.h) ---------------------------------------------------------- */
+/* where every group begins and ends in the sorted order; a group with no record keeps begin == end (both 0) */
+__global__ __launch_bounds__(DS_BLOCK) void k_ds_bounds(const uint64_t *hi_sorted, uint64_t n, uint32_t *begin, uint32_t *end) {
+  const uint64_t j = (uint64_t)blockIdx.x * DS_BLOCK + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t g = (uint32_t)(hi_sorted[j] >> 32);
+  if (j == 0 || (uint32_t)(hi_sorted[j - 1] >> 32) != g) begin[g] = (uint32_t)j;
+  if (j + 1 == n || (uint32_t)(hi_sorted[j + 1] >> 32) != g) end[g] = (uint32_t)(j + 1);
+}
+struct gs_ds_space_args {
+  const uint32_t *chr, *pos;
+  const uint8_t *sense;
+  const uint32_t *order, *mark, *begin, *end;
+  uint32_t *keep, *kept_of_group, *passed_of_group, *marked_of_group;
+  uint32_t n_groups, per_region, min_spacing, cut_offset, start, k, P;
+};
+#define DS_WAVE 64
+/* One wave walks one group, 64 records a step, lane i holding record i of the step with its mark and chr << 32 | cut.
+ * Phase 1: every lane tests its record against the group's kept list in LDS, all lanes reading the same entry at the same
+ * time.  Phase 2: the survivors are resolved in order among themselves - the lowest lane of the ballot is kept and
+ * appended to the list, the later lanes within D of it on its chromosome drop out, and the ballot is taken again above
+ * it, until it is empty or N is reached.  Control flow is uniform across the wave; the only atomic is the group's final
+ * count.  keep[] is written for every record of the group. */
+__global__ __launch_bounds__(DS_WAVE) void k_ds_space(gs_ds_space_args a) {
+  __shared__ uint64_t list[GS_SL_MAX_PER_REGION];
+  const uint32_t g = blockIdx.x, lane = threadIdx.x;
+  if (g >= a.n_groups) return;
+  const uint32_t b = a.begin[g], e = a.end[g];
+  const uint32_t N = a.per_region < GS_SL_MAX_PER_REGION ? a.per_region : GS_SL_MAX_PER_REGION;
+  uint32_t kept = 0, passed = 0, marked = 0;
+  for (uint32_t base = b; base < e; base += DS_WAVE) {
+    const uint32_t j = base + lane;
+    const bool valid = j < e;
+    if (kept >= N) { /* uniform: the group is full, the rest is cut (its marks are not counted: the group is not short) */
+      if (valid) a.keep[j] = 0u;
+      continue;
+    }
+    uint64_t key = 0;
+    bool m = false;
+    if (valid) {
+      const uint32_t r = a.order[j];
+      m = a.mark[j] != 0u;
+      key = gs_sl_key(a.chr[r], a.pos[r], a.sense[r], a.k, a.P, a.cut_offset, a.start != 0u);
+    }
+    marked += (uint32_t)__popcll(__ballot(m));
+    bool kp = false, alive = m;
+    for (uint32_t t = 0; t < kept; t++) alive = alive && !gs_sl_conflict(list[t], key, a.min_spacing);
+    unsigned long long cand = __ballot(alive);
+    uint32_t stop = DS_WAVE; /* the lane of the N-th pick, where the walk ends */
+    while (cand) {
+      const uint32_t l = (uint32_t)__ffsll(cand) - 1u;
+      const uint64_t picked = ((uint64_t)(uint32_t)__shfl((int)(key >> 32), (int)l) << 32) | (uint32_t)__shfl((int)(uint32_t)key, (int)l);
+      if (lane == l) {
+        kp = true;
+        list[kept] = key;
+      }
+      kept++;
+      if (kept >= N) {
+        stop = l;
+        break;
+      }
+      alive = alive && lane > l && !gs_sl_conflict(picked, key, a.min_spacing);
+      cand = __ballot(alive);
+    }
+    passed += (uint32_t)__popcll(__ballot(m && !kp && lane < stop));
+    __syncthreads(); /* the list's new entries, before the next step reads them */
+    if (valid) a.keep[j] = kp ? 1u : 0u;
+  }
+  if (lane == 0) {
+    if (kept) atomicAdd(&a.kept_of_group[g], kept);
+    a.passed_of_group[g] = passed;
+    a.marked_of_group[g] = marked;
+  }
+}
+
 struct gs_ds_gather_args {
   const uint8_t *seqs, *pams, *sense;
   const uint32_t *pos, *group, *chr, *order, *keep, *place;
@@ -714,8 +794,19 @@ gs_status gs_ds_select(gs_design *d, const char *prefix, const gs_ds_select_rule
   gs_prim_tmp tmp;
   uint64_t m = 0;
   uint32_t *o_group = nullptr, *o_chr = nullptr;
-  std::vector<uint32_t> kept_of_group(n_groups, 0);
+  std::vector<uint32_t> kept_of_group(n_groups, 0), space_of_group; /* the latter: passed over, then marked, per group */
+  struct marks { /* around k_ds_space, where the rule is set */
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~marks() {
+      for (hipEvent_t x : e)
+        if (x) hipEventDestroy(x);
+    }
+  } evs;
+  hipEvent_t *ev = evs.e;
+  if (rule.min_spacing && rule.tally && n)
+    for (int i = 0; i < 2; i++) GS_HIP(hipEventCreate(&evs.e[i]));
   if (n) {
+    uint32_t *d_space = nullptr;
     uint64_t *hi = nullptr, *lo = nullptr, *key2 = nullptr, *hi_g = nullptr;
     uint32_t *idx = nullptr, *idx1 = nullptr, *idx2 = nullptr, *mark = nullptr, *rank = nullptr, *keep = nullptr, *place = nullptr,
              *head_rank = nullptr, *d_kept = nullptr;
@@ -767,16 +858,57 @@ gs_status gs_ds_select(gs_design *d, const char *prefix, const gs_ds_select_rule
     GS_TRY(gs_prim("design: ranks of the marked records", mem, tmp, [&](void *p, size_t &b) {
       return rocprim::exclusive_scan(p, b, mark, rank, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st);
     }));
-    hipLaunchKernelGGL(k_ds_heads, grid, block, 0, st, hi_sorted, (const uint32_t *)rank, n, head_rank);
-    hipLaunchKernelGGL(k_ds_cut, grid1, block, 0, st, hi_sorted, (const uint32_t *)mark, (const uint32_t *)rank,
-                       (const uint32_t *)head_rank, n, per_region, keep, d_kept);
+    if (rule.min_spacing) { /* the walk of every group by one wave in place of the cut by rank */
+      uint32_t *bounds = nullptr;
+      GS_TRY(mem.get(16 * n_groups, &bounds));
+      GS_HIP(hipMemsetAsync(bounds, 0, 16 * n_groups, st));
+      GS_HIP(hipMemsetAsync(keep + n, 0, 4, st));
+      d_space = bounds + 2 * n_groups;
+      hipLaunchKernelGGL(k_ds_bounds, grid, block, 0, st, hi_sorted, n, bounds, bounds + n_groups);
+      gs_ds_space_args sa;
+      memset(&sa, 0, sizeof sa);
+      sa.chr = a.chr;
+      sa.pos = a.pos;
+      sa.sense = a.sense;
+      sa.order = idx2;
+      sa.mark = mark;
+      sa.begin = bounds;
+      sa.end = bounds + n_groups;
+      sa.keep = keep;
+      sa.kept_of_group = d_kept;
+      sa.passed_of_group = d_space;
+      sa.marked_of_group = d_space + n_groups;
+      sa.n_groups = (uint32_t)n_groups;
+      sa.per_region = per_region;
+      sa.min_spacing = rule.min_spacing;
+      sa.cut_offset = rule.cut_offset;
+      sa.start = rule.pam_at_start ? 1u : 0u;
+      sa.k = k;
+      sa.P = P;
+      if (ev[0]) GS_HIP(hipEventRecord(ev[0], st));
+      hipLaunchKernelGGL(k_ds_space, dim3((unsigned)n_groups), dim3(DS_WAVE), 0, st, sa);
+      if (ev[1]) GS_HIP(hipEventRecord(ev[1], st));
+    } else {
+      hipLaunchKernelGGL(k_ds_heads, grid, block, 0, st, hi_sorted, (const uint32_t *)rank, n, head_rank);
+      hipLaunchKernelGGL(k_ds_cut, grid1, block, 0, st, hi_sorted, (const uint32_t *)mark, (const uint32_t *)rank,
+                         (const uint32_t *)head_rank, n, per_region, keep, d_kept);
+    }
     GS_TRY(gs_prim("design: places of the kept records", mem, tmp, [&](void *p, size_t &b) {
       return rocprim::exclusive_scan(p, b, keep, place, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st);
     }));
     uint32_t m32 = 0;
     GS_HIP(hipMemcpyAsync(&m32, place + n, 4, hipMemcpyDeviceToHost, st));
     if (n_groups) GS_HIP(hipMemcpyAsync(kept_of_group.data(), d_kept, 4 * n_groups, hipMemcpyDeviceToHost, st));
+    if (d_space) {
+      space_of_group.resize(2 * n_groups);
+      GS_HIP(hipMemcpyAsync(space_of_group.data(), d_space, 8 * n_groups, hipMemcpyDeviceToHost, st));
+    }
     GS_HIP(hipStreamSynchronize(st));
+    if (ev[0]) {
+      float ms = 0;
+      GS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+      d->space_ms = ms;
+    }
     m = m32;
     if (m) {
       GS_TRY(gs_ds_array((size_t)m * k, &km->d_seqs));
@@ -809,7 +941,14 @@ gs_status gs_ds_select(gs_design *d, const char *prefix, const gs_ds_select_rule
       hipLaunchKernelGGL(k_ds_gather, grid, block, 0, st, ga);
     }
   }
-  if (rule.tally) ds_group_tally(d, m, kept_of_group, per_region);
+  if (rule.tally) {
+    ds_group_tally(d, m, kept_of_group, per_region);
+    d->last_spacing[0] = d->last_spacing[1] = 0;
+    for (size_t g = 0; g < n_groups && !space_of_group.empty(); g++) {
+      d->last_spacing[0] += space_of_group[g];
+      if (kept_of_group[g] < per_region && space_of_group[n_groups + g] >= per_region) d->last_spacing[1]++;
+    }
+  }
   km->n = m;
   /* the text: ids or rows, by the writer of gs_kmers.hip over the table of all names */
   uint64_t total = 0;
@@ -832,6 +971,62 @@ static gs_status ds_select_args(const gs_design *d, const char *prefix, uint32_t
     gs_set_error("a selection by specificity before gs_design_score");
     return GS_ERR_ARG;
   }
+  if (d->space_d && (per_region < 1 || per_region > GS_SL_MAX_PER_REGION)) {
+    gs_set_error("a minimum spacing needs per_region from 1 to 1024: a group's kept cuts live in LDS");
+    return GS_ERR_ARG;
+  }
+  if (d->space_d && d->space_c > d->k) {
+    gs_set_error("the cut offset lies beyond the k-mer length");
+    return GS_ERR_ARG;
+  }
+  return GS_OK;
+}
+/* the rule of a selection on the design's own eligibility bytes, with the design's spacing */
+static gs_ds_select_rule ds_own_rule(const gs_design *d, uint32_t per_region, bool filter, float min_specificity) {
+  gs_ds_select_rule rule{(const uint8_t *)d->d_elig, per_region, filter, min_specificity, nullptr, true};
+  rule.min_spacing = d->space_d;
+  rule.cut_offset = d->space_c;
+  rule.pam_at_start = d->space_start;
+  return rule;
+}
+
+extern "C" gs_status gs_design_set_spacing(gs_design *d, uint32_t min_spacing, uint32_t cut_offset, uint32_t flags) {
+  if (!d || (flags & ~GS_FLAG_PAM_AT_START)) return GS_ERR_ARG;
+  if (min_spacing && cut_offset > d->k) {
+    gs_set_error("gs_design_set_spacing: the cut offset lies beyond the k-mer length");
+    return GS_ERR_ARG;
+  }
+  d->space_d = min_spacing;
+  d->space_c = cut_offset;
+  d->space_start = (flags & GS_FLAG_PAM_AT_START) != 0;
+  return GS_OK;
+}
+
+extern "C" gs_status gs_design_last_spacing(const gs_design *d, uint64_t out[2]) {
+  if (!d || !out) return GS_ERR_ARG;
+  out[0] = d->last_spacing[0];
+  out[1] = d->last_spacing[1];
+  return GS_OK;
+}
+
+extern "C" gs_status gs_debug_design_space_ms(const gs_design *d, double *ms) {
+  if (!d || !ms) return GS_ERR_ARG;
+  *ms = d->space_ms;
+  return GS_OK;
+}
+
+extern "C" gs_status gs_debug_design_set_scores(gs_design *d, const float *specificity, const uint8_t *eligible) {
+  if (!d || d->device < 0 || (d->n && !specificity)) return GS_ERR_ARG;
+  if (d->n) {
+    GS_HIP(hipSetDevice(d->device));
+    GS_HIP(hipMemcpy(d->d_spec, specificity, 4 * (size_t)d->n, hipMemcpyHostToDevice));
+    if (eligible)
+      GS_HIP(hipMemcpy(d->d_elig, eligible, (size_t)d->n, hipMemcpyHostToDevice));
+    else
+      GS_HIP(hipMemset(d->d_elig, 1, (size_t)d->n));
+  }
+  d->scored = true;
+  d->have_host = false;
   return GS_OK;
 }
 
@@ -843,7 +1038,7 @@ extern "C" gs_status gs_design_select(gs_design *d, const char *prefix, uint32_t
   if (d->device < 0) return GS_ERR_ARG;
   *out = nullptr;
   try {
-    const gs_ds_select_rule rule{(const uint8_t *)d->d_elig, per_region, filter, min_specificity, nullptr, true};
+    const gs_ds_select_rule rule = ds_own_rule(d, per_region, filter, min_specificity);
     return gs_ds_select(d, prefix, rule, (hipStream_t)stream, false, out, nullptr, nullptr);
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;
@@ -862,7 +1057,7 @@ extern "C" gs_status gs_design_rows(gs_design *d, const char *prefix, uint32_t p
   uint64_t bytes = 0;
   gs_status rc;
   try {
-    const gs_ds_select_rule rule{(const uint8_t *)d->d_elig, per_region, filter, min_specificity, nullptr, true};
+    const gs_ds_select_rule rule = ds_own_rule(d, per_region, filter, min_specificity);
     rc = gs_ds_select(d, prefix, rule, (hipStream_t)stream, true, nullptr, &d_text, &bytes);
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;
@@ -876,12 +1071,13 @@ extern "C" gs_status gs_design_rows(gs_design *d, const char *prefix, uint32_t p
 
 /* ---- the same stages on the host, through the shared header ----------------------------------------------------------- */
 
-extern "C" gs_status gs_debug_design_host(const gs_regions *rg, uint32_t n_parts, const uint32_t *chr_index, const uint64_t *n,
-                                          const uint8_t *const *seqs, const uint32_t *const *positions, const uint8_t *const *senses,
-                                          const float *const *specificity, const uint8_t *const *eligible, const char *pam, uint32_t k,
-                                          const char *prefix, uint32_t per_region, float min_specificity, gs_kmers **out, char **rows,
-                                          uint64_t *rows_len) {
+static gs_status ds_host_model(const gs_regions *rg, uint32_t n_parts, const uint32_t *chr_index, const uint64_t *n,
+                               const uint8_t *const *seqs, const uint32_t *const *positions, const uint8_t *const *senses,
+                               const float *const *specificity, const uint8_t *const *eligible, const char *pam, uint32_t k,
+                               const char *prefix, uint32_t per_region, float min_specificity, uint32_t min_spacing, uint32_t cut_offset,
+                               uint32_t flags, gs_kmers **out, char **rows, uint64_t *rows_len, uint64_t *report) {
   if (!rg || !out || !pam || !prefix || (n_parts && (!chr_index || !n || !seqs || !positions || !senses))) return GS_ERR_ARG;
+  if (flags & ~GS_FLAG_PAM_AT_START) return GS_ERR_ARG;
   const uint32_t P = (uint32_t)strlen(pam);
   if (k < 1 || k > 64 || P < 1 || P > 8) return GS_ERR_ARG;
   for (uint32_t i = 0; i < n_parts; i++)
@@ -895,6 +1091,9 @@ extern "C" gs_status gs_debug_design_host(const gs_regions *rg, uint32_t n_parts
     d.k = k;
     d.P = P;
     d.scored = specificity != nullptr;
+    d.space_d = min_spacing;
+    d.space_c = cut_offset;
+    d.space_start = (flags & GS_FLAG_PAM_AT_START) != 0;
     bool filter = false;
     GS_TRY(ds_select_args(&d, prefix, per_region, min_specificity, filter));
     /* restrict */
@@ -928,7 +1127,7 @@ extern "C" gs_status gs_debug_design_host(const gs_regions *rg, uint32_t n_parts
     /* mark, rank the marked, cut */
     std::vector<uint32_t> kept, kept_of_group(rg->group_names.size(), 0);
     uint32_t rank = 0;
-    for (uint64_t j = 0; j < d.n; j++) {
+    for (uint64_t j = 0; j < d.n && !min_spacing; j++) {
       const uint32_t r = order[j];
       if (j == 0 || d.h_group[order[j - 1]] != d.h_group[r]) rank = 0;
       const bool marked = d.h_elig[r] && (!filter || d.h_spec[r] >= min_specificity);
@@ -937,6 +1136,31 @@ extern "C" gs_status gs_debug_design_host(const gs_regions *rg, uint32_t n_parts
         kept_of_group[d.h_group[r]]++;
       }
       if (marked) rank++;
+    }
+    /* with a minimum spacing: the walk of gs_select_scan.h over every group's stretch of the order */
+    for (uint64_t b = 0, e = 0; b < d.n && min_spacing; b = e) {
+      const uint32_t g = d.h_group[order[b]];
+      for (e = b; e < d.n && d.h_group[order[e]] == g;) e++;
+      const uint32_t len = (uint32_t)(e - b);
+      std::vector<uint64_t> key(len), list(std::min(len, per_region));
+      std::vector<uint8_t> mark(len), keep(len);
+      for (uint32_t i = 0; i < len; i++) {
+        const uint32_t r = order[b + i];
+        key[i] = gs_sl_key(d.h_chr[r], d.h_pos[r], d.h_sense[r], k, P, cut_offset, d.space_start);
+        mark[i] = d.h_elig[r] && (!filter || d.h_spec[r] >= min_specificity) ? 1 : 0;
+      }
+      uint32_t passed = 0, marked = 0;
+      kept_of_group[g] = gs_sl_walk(key.data(), mark.data(), len, min_spacing, per_region, list.data(), keep.data(), &passed, &marked);
+      for (uint32_t i = 0; i < len; i++)
+        if (keep[i]) kept.push_back(order[b + i]);
+      d.last_spacing[0] += passed;
+      if (kept_of_group[g] < per_region && marked >= per_region) d.last_spacing[1]++;
+    }
+    if (report) {
+      ds_group_tally(&d, kept.size(), kept_of_group, per_region);
+      for (int i = 0; i < 4; i++) report[i] = d.last[i];
+      report[4] = d.last_spacing[0];
+      report[5] = d.last_spacing[1];
     }
     std::unique_ptr<gs_kmers, void (*)(gs_kmers *)> own(new gs_kmers(), km_release);
     gs_kmers *km = own.get();
@@ -975,4 +1199,23 @@ extern "C" gs_status gs_debug_design_host(const gs_regions *rg, uint32_t n_parts
   } catch (const std::bad_alloc &) {
     return GS_ERR_NOMEM;
   }
+}
+
+extern "C" gs_status gs_debug_design_host(const gs_regions *rg, uint32_t n_parts, const uint32_t *chr_index, const uint64_t *n,
+                                          const uint8_t *const *seqs, const uint32_t *const *positions, const uint8_t *const *senses,
+                                          const float *const *specificity, const uint8_t *const *eligible, const char *pam, uint32_t k,
+                                          const char *prefix, uint32_t per_region, float min_specificity, gs_kmers **out, char **rows,
+                                          uint64_t *rows_len) {
+  return ds_host_model(rg, n_parts, chr_index, n, seqs, positions, senses, specificity, eligible, pam, k, prefix, per_region,
+                       min_specificity, 0, 0, 0, out, rows, rows_len, nullptr);
+}
+
+extern "C" gs_status gs_debug_design_host_spaced(const gs_regions *rg, uint32_t n_parts, const uint32_t *chr_index, const uint64_t *n,
+                                                 const uint8_t *const *seqs, const uint32_t *const *positions,
+                                                 const uint8_t *const *senses, const float *const *specificity,
+                                                 const uint8_t *const *eligible, const char *pam, uint32_t k, const char *prefix,
+                                                 uint32_t per_region, float min_specificity, uint32_t min_spacing, uint32_t cut_offset,
+                                                 uint32_t flags, gs_kmers **out, char **rows, uint64_t *rows_len, uint64_t *report) {
+  return ds_host_model(rg, n_parts, chr_index, n, seqs, positions, senses, specificity, eligible, pam, k, prefix, per_region,
+                       min_specificity, min_spacing, cut_offset, flags, out, rows, rows_len, report);
 }

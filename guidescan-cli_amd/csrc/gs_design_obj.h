@@ -29,6 +29,13 @@ struct gs_design {
   void *d_fhits = nullptr;
   bool have_fhits = false;
   std::vector<uint32_t> h_fhits;
+  /* gs_design_set_spacing: the picks of a group lie space_d bases apart or more (0: no rule), by the cut that leaves
+   * space_c protospacer bases between it and the PAM; of the last select under the rule: marked records passed over, and
+   * groups short of N that hold N marked records */
+  uint32_t space_d = 0, space_c = 3;
+  bool space_start = false;
+  uint64_t last_spacing[2] = {0, 0};
+  double space_ms = 0; /* k_ds_space of that select, between stream events */
 };
 
 /* The ordering, gather and id passes of gs_design_select over the eligibility bytes d_elig (uint8[n] in HBM, the
@@ -42,6 +49,10 @@ struct gs_ds_select_rule {
   float min_spec;
   uint32_t *d_place;
   bool tally;
+  /* min_spacing > 0: k_ds_space takes the place of k_ds_cut (1 <= per_region <= 1024), the cut by cut_offset and
+   * pam_at_start; with tally the design's last_spacing[] is updated too */
+  uint32_t min_spacing = 0, cut_offset = 0;
+  bool pam_at_start = false;
 };
 gs_status gs_ds_select(gs_design *d, const char *prefix, const gs_ds_select_rule &rule, hipStream_t st, bool rows, gs_kmers **out,
                        void **d_text, uint64_t *text_bytes);

@@ -30,6 +30,7 @@
 #include "gs_scratch.h"
 #include "gs_kmers_obj.h"
 #include "gs_rowtext.h"
+#include "gs_select_scan.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -582,6 +583,215 @@ extern "C" gs_status gs_kmers_concat(gs_kmers *const *parts, uint32_t n_parts, g
   GS_HIP(hipStreamSynchronize(nullptr));
   GS_HIP(hipGetLastError());
   *out = own.release();
+  return GS_OK;
+}
+
+/* ---- sequence rules on a scan's candidates (no counterpart in the reference; the rule is gs_select_scan.h's) ----------
+ *   k_km_rule   one lane per candidate: the rule over its k bytes -> a 64-bit flag and the charged rule; a wave's failures
+ *               go to the three counters with one atomic each                     (k B read, 9 B written)
+ *   (rocprim 64-bit exclusive scan of the n + 1 flags: the places)
+ *   k_km_keep   the passing candidates into a fresh object at their places: stable   (k + P + 5 + 16 B read, k + P + 5 written) */
+struct gs_km_filter_args {
+  const uint8_t *seqs, *pams, *sense;
+  const uint32_t *pos;
+  uint64_t *flag;        /* n + 1 */
+  const uint64_t *place; /* n + 1 */
+  uint8_t *charge;
+  unsigned long long *failed; /* by GC, run, motif */
+  uint8_t *o_seqs, *o_pams, *o_sense;
+  uint32_t *o_pos;
+  uint64_t n;
+  uint32_t k, P;
+};
+__global__ __launch_bounds__(KM_BLOCK) void k_km_rule(gs_km_filter_args a, gs_seq_rule rule) {
+  const uint64_t j = (uint64_t)blockIdx.x * KM_BLOCK + threadIdx.x;
+  const bool in = j < a.n;
+  uint32_t ch = GS_SL_PASS;
+  if (in) {
+    ch = gs_sl_charge(rule, a.seqs + j * a.k, a.k);
+    a.charge[j] = (uint8_t)ch;
+  }
+  if (j <= a.n) a.flag[j] = in && ch == GS_SL_PASS ? 1ull : 0ull; /* one more entry closes the scan */
+  for (uint32_t r = GS_SL_GC; r <= GS_SL_MOTIF; r++) {
+    const unsigned long long b = __ballot(in && ch == r);
+    if ((threadIdx.x & 63u) == 0u && b) atomicAdd(&a.failed[r - 1u], (unsigned long long)__popcll(b));
+  }
+}
+__global__ __launch_bounds__(KM_BLOCK) void k_km_keep(gs_km_filter_args a) {
+  const uint64_t j = (uint64_t)blockIdx.x * KM_BLOCK + threadIdx.x;
+  if (j >= a.n || !a.flag[j]) return;
+  const uint64_t o = a.place[j];
+  for (uint32_t u = 0; u < a.k; u++) a.o_seqs[o * a.k + u] = a.seqs[j * a.k + u];
+  for (uint32_t u = 0; u < a.P; u++) a.o_pams[o * a.P + u] = a.pams[j * a.P + u];
+  a.o_pos[o] = a.pos[j];
+  a.o_sense[o] = a.sense[j];
+}
+
+extern "C" gs_status gs_seq_rule_init(gs_seq_rule *rule) {
+  if (!rule) return GS_ERR_ARG;
+  memset(rule, 0, sizeof *rule);
+  rule->gc_max = 100;
+  return GS_OK;
+}
+
+extern "C" gs_status gs_seq_rule_add_motif(gs_seq_rule *rule, const char *motif, int both_strands) {
+  if (!rule || !motif) return GS_ERR_ARG;
+  const size_t len = strlen(motif);
+  auto refuse = [&](const std::string &why) {
+    gs_set_error("motif '" + std::string(motif) + "': " + why);
+    return GS_ERR_FORMAT;
+  };
+  if (len == 0) return refuse("an empty motif");
+  if (len > GS_SEQ_MOTIF_LETTERS) return refuse("more than 32 letters");
+  for (size_t p = 0; p < len; p++)
+    if (!gs_sl_iupac((uint8_t)motif[p])) return refuse(std::string("the letter '") + motif[p] + "' is not one of ACGTRYSWKMBDHVN");
+  bool twin = false; /* the reverse complement, where it is another motif */
+  for (size_t p = 0; p < len && both_strands; p++)
+    twin = twin || gs_sl_complement(gs_sl_iupac((uint8_t)motif[len - 1 - p])) != gs_sl_iupac((uint8_t)motif[p]);
+  if (rule->n_motifs > GS_SEQ_MOTIFS || rule->n_motifs + (twin ? 2u : 1u) > GS_SEQ_MOTIFS) return refuse("more than 16 motifs");
+  for (uint32_t t = 0; t < (twin ? 2u : 1u); t++) {
+    const uint32_t m = rule->n_motifs++;
+    rule->motif_len[m] = (uint8_t)len;
+    memset(rule->motif_set[m], 0, sizeof rule->motif_set[m]);
+    for (size_t p = 0; p < len; p++) {
+      const uint32_t set = gs_sl_iupac((uint8_t)motif[t ? len - 1 - p : p]);
+      gs_sl_motif_put(*rule, m, (uint32_t)p, t ? gs_sl_complement(set) : set);
+    }
+  }
+  return GS_OK;
+}
+
+static gs_status km_rule_args(const gs_seq_rule *rule) {
+  if (!rule) return GS_ERR_ARG;
+  if (!gs_sl_rule_ok(*rule)) {
+    gs_set_error("sequence rule: 0 <= gc_min <= gc_max <= 100, at most 16 motifs of 1 to 32 IUPAC letters");
+    return GS_ERR_ARG;
+  }
+  return GS_OK;
+}
+
+extern "C" gs_status gs_kmers_filter(gs_kmers *km, const gs_seq_rule *rule, void *stream, gs_kmers **out, uint64_t counts[4]) {
+  if (!km || !out) return GS_ERR_ARG;
+  GS_TRY(km_rule_args(rule));
+  if (km->parsed || km->device < 0) {
+    gs_set_error("gs_kmers_filter takes the candidates of a scan on a device");
+    return GS_ERR_ARG;
+  }
+  if (km->have_ids) {
+    gs_set_error("gs_kmers_filter after gs_kmers_encode_ids: the ids would name candidates that are gone");
+    return GS_ERR_ARG;
+  }
+  *out = nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t n = km->n;
+  const uint32_t k = km->k, P = km->P;
+  uint64_t failed[3] = {0, 0, 0}, kept = 0;
+  struct events { /* around the rule and the scan, and around the gather */
+    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~events() {
+      for (hipEvent_t x : e)
+        if (x) hipEventDestroy(x);
+    }
+  } ev;
+  try {
+    GS_HIP(hipSetDevice(km->device));
+    std::unique_ptr<gs_kmers, void (*)(gs_kmers *)> own(new gs_kmers(), km_release);
+    gs_kmers *f = own.get();
+    f->device = km->device;
+    f->k = k;
+    f->P = P;
+    if (n) {
+      gs_scratch mem;
+      gs_prim_tmp tmp;
+      uint64_t *d_flag = nullptr, *d_place = nullptr;
+      uint8_t *d_charge = nullptr;
+      unsigned long long *d_failed = nullptr;
+      GS_TRY(mem.get(8 * (n + 1), &d_flag));
+      GS_TRY(mem.get(8 * (n + 1), &d_place));
+      GS_TRY(mem.get(n, &d_charge));
+      GS_TRY(mem.get(24, &d_failed));
+      GS_HIP(hipMemsetAsync(d_failed, 0, 24, st));
+      for (hipEvent_t &x : ev.e) GS_HIP(hipEventCreate(&x));
+      gs_km_filter_args a;
+      memset(&a, 0, sizeof a);
+      a.seqs = (const uint8_t *)km->d_seqs;
+      a.pams = (const uint8_t *)km->d_pams;
+      a.sense = (const uint8_t *)km->d_sense;
+      a.pos = (const uint32_t *)km->d_pos;
+      a.flag = d_flag;
+      a.place = d_place;
+      a.charge = d_charge;
+      a.failed = d_failed;
+      a.n = n;
+      a.k = k;
+      a.P = P;
+      GS_HIP(hipEventRecord(ev.e[0], st));
+      hipLaunchKernelGGL(k_km_rule, dim3((unsigned)((n + 1 + KM_BLOCK - 1) / KM_BLOCK)), dim3(KM_BLOCK), 0, st, a, *rule);
+      GS_HIP(hipEventRecord(ev.e[1], st));
+      GS_TRY(gs_prim("kmers filter: scan of the flags", mem, tmp, [&](void *t, size_t &tb) {
+        return rocprim::exclusive_scan(t, tb, d_flag, d_place, 0ull, (size_t)n + 1, rocprim::plus<uint64_t>(), st);
+      }));
+      GS_HIP(hipEventRecord(ev.e[2], st));
+      GS_HIP(hipMemcpyAsync(&kept, d_place + n, 8, hipMemcpyDeviceToHost, st));
+      GS_HIP(hipMemcpyAsync(failed, d_failed, 24, hipMemcpyDeviceToHost, st));
+      GS_HIP(hipStreamSynchronize(st));
+      if (kept > n) {
+        gs_set_error("gs_kmers_filter: more candidates kept than scanned");
+        return GS_ERR_DEVICE;
+      }
+      float ms = 0;
+      GS_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+      f->filter_ms[0] = ms;
+      GS_HIP(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
+      f->filter_ms[1] = ms;
+      f->n = kept;
+      if (kept) {
+        GS_TRY(km_alloc((size_t)kept * k, &f->d_seqs));
+        GS_TRY(km_alloc((size_t)kept * P, &f->d_pams));
+        GS_TRY(km_alloc(4 * (size_t)kept, &f->d_pos));
+        GS_TRY(km_alloc((size_t)kept, &f->d_sense));
+        a.o_seqs = (uint8_t *)f->d_seqs;
+        a.o_pams = (uint8_t *)f->d_pams;
+        a.o_sense = (uint8_t *)f->d_sense;
+        a.o_pos = (uint32_t *)f->d_pos;
+        GS_HIP(hipEventRecord(ev.e[3], st));
+        hipLaunchKernelGGL(k_km_keep, dim3((unsigned)((n + KM_BLOCK - 1) / KM_BLOCK)), dim3(KM_BLOCK), 0, st, a);
+        GS_HIP(hipEventRecord(ev.e[4], st));
+        GS_HIP(hipStreamSynchronize(st));
+        GS_HIP(hipEventElapsedTime(&ms, ev.e[3], ev.e[4]));
+        f->filter_ms[2] = ms;
+      }
+      GS_HIP(hipGetLastError());
+    }
+    if (counts) {
+      counts[0] = n;
+      for (int i = 0; i < 3; i++) counts[1 + i] = failed[i];
+    }
+    *out = own.release();
+    return GS_OK;
+  } catch (const std::bad_alloc &) {
+    return GS_ERR_NOMEM;
+  }
+}
+
+extern "C" gs_status gs_debug_kmers_filter_ms(const gs_kmers *filtered, double out[3]) {
+  if (!filtered || !out) return GS_ERR_ARG;
+  for (int i = 0; i < 3; i++) out[i] = filtered->filter_ms[i];
+  return GS_OK;
+}
+
+extern "C" gs_status gs_debug_kmers_filter_host(const uint8_t *seqs, uint64_t n, uint32_t k, const gs_seq_rule *rule, uint8_t *charge,
+                                                uint64_t counts[4]) {
+  if ((n && (!seqs || !charge)) || k < 1 || k > 64) return GS_ERR_ARG;
+  GS_TRY(km_rule_args(rule));
+  uint64_t c[4] = {n, 0, 0, 0};
+  for (uint64_t j = 0; j < n; j++) {
+    const uint32_t ch = gs_sl_charge(*rule, seqs + j * k, k);
+    charge[j] = (uint8_t)ch;
+    if (ch) c[ch]++;
+  }
+  if (counts)
+    for (int i = 0; i < 4; i++) counts[i] = c[i];
   return GS_OK;
 }
 

@@ -28,6 +28,7 @@ struct gs_kmers {
   bool have_ids = false, have_host_ids = false;
   std::vector<uint8_t> h_ids, h_sense01;
   std::vector<uint64_t> h_id_off;
+  double filter_ms[3] = {0, 0, 0}; /* made by gs_kmers_filter: its rule, scan and gather passes between stream events */
 };
 
 /* frees the object and its arrays in HBM (gs_kmers_free; the deleter of an object under construction) */

@@ -506,6 +506,10 @@ extern "C" gs_status gs_design_pairs(gs_design *d, const char *prefix, const gs_
     gs_set_error("pairs are ranked by specificity: gs_design_score first");
     return GS_ERR_ARG;
   }
+  if (d->space_d) {
+    gs_set_error("gs_design_pairs on a design with a minimum spacing: pairs have their own span rule");
+    return GS_ERR_ARG;
+  }
   *guides = nullptr;
   *pairs = nullptr;
   try {

@@ -132,6 +132,77 @@ inline bool candidate_option(const std::string &a, int &i, int argc, char **argv
   return true;
 }
 
+/* the sequence rules on the candidates of a scan (`kmers`, `enumerate --all-candidates`; csrc/gs_select_scan.h, no
+ * counterpart in the reference): --gc MIN:MAX, --max-run R, --exclude-motif M1,M2,..., --exclude-site M1,M2,... */
+struct seq_rule_opts {
+  gs_seq_rule rule;
+  bool given = false;
+  seq_rule_opts() { gs_seq_rule_init(&rule); }
+};
+/* one of them? (i advances over its value); a value that is refused is one line on stderr and `bad` */
+inline bool seq_rule_option(const std::string &a, int &i, int argc, char **argv, seq_rule_opts &so, bool &bad) {
+  if (a != "--gc" && a != "--max-run" && a != "--exclude-motif" && a != "--exclude-site") return false;
+  so.given = true;
+  if (i + 1 >= argc) {
+    std::cerr << "error: " << a << " needs a value\n";
+    bad = true;
+    return true;
+  }
+  const std::string v = argv[++i];
+  auto digits = [](const std::string &s, unsigned long &out) {
+    if (s.empty() || s.size() > 9 || s.find_first_not_of("0123456789") != std::string::npos) return false;
+    out = strtoul(s.c_str(), nullptr, 10);
+    return true;
+  };
+  if (a == "--gc") {
+    const size_t colon = v.find(':');
+    unsigned long lo = 0, hi = 0;
+    if (colon == std::string::npos || !digits(v.substr(0, colon), lo) || !digits(v.substr(colon + 1), hi) || lo > hi || hi > 100) {
+      std::cerr << "error: --gc " << v << ": MIN:MAX, integer percentages with 0 <= MIN <= MAX <= 100\n";
+      bad = true;
+      return true;
+    }
+    so.rule.gc_min = (uint32_t)lo;
+    so.rule.gc_max = (uint32_t)hi;
+  } else if (a == "--max-run") {
+    unsigned long r = 0;
+    if (!digits(v, r) || r < 1) {
+      std::cerr << "error: --max-run " << v << ": the longest run of one letter, at least 1\n";
+      bad = true;
+      return true;
+    }
+    so.rule.max_run = (uint32_t)r;
+  } else {
+    std::vector<std::string> motifs = split_commas(v);
+    if (motifs.empty() || v.back() == ',') motifs.push_back(""); /* refused below, as an empty motif */
+    for (const std::string &m : motifs)
+      if (gs_seq_rule_add_motif(&so.rule, m.c_str(), a == "--exclude-site") != GS_OK) {
+        std::cerr << "error: " << a << ": " << gs_status_string(GS_ERR_FORMAT) << "\n";
+        bad = true;
+        return true;
+      }
+  }
+  return true;
+}
+/* "Sequence rules: kept K of N candidate(s); F failed --gc, F --max-run, F a motif" */
+inline std::string seq_rule_line(const uint64_t counts[4]) {
+  return "Sequence rules: kept " + std::to_string(counts[0] - counts[1] - counts[2] - counts[3]) + " of " + std::to_string(counts[0]) +
+         " candidate(s); " + std::to_string(counts[1]) + " failed --gc, " + std::to_string(counts[2]) + " --max-run, " +
+         std::to_string(counts[3]) + " a motif\n";
+}
+/* the scan's candidates through the rule on the scan's device: *km becomes the filtered object, counts add up */
+inline gs_status apply_seq_rule(const seq_rule_opts &so, gs_kmers **km, uint64_t counts[4]) {
+  if (!so.given) return GS_OK;
+  gs_kmers *f = nullptr;
+  uint64_t c[4] = {0, 0, 0, 0};
+  const gs_status rc = gs_kmers_filter(*km, &so.rule, nullptr, &f, c);
+  if (rc != GS_OK) return rc;
+  gs_kmers_free(*km);
+  *km = f;
+  for (int i = 0; i < 4; i++) counts[i] += c[i];
+  return GS_OK;
+}
+
 struct kmer_row {
   std::string id, sequence, pam, chromosome, sense;
   long long position;

@@ -74,6 +74,11 @@ struct options {
    * guides are those of the best --per-region pairs of each group (gs_design_pairs), and FILE is the table of the pairs */
   std::string pairs, pair_orientation;
   long long max_span = -1, min_span = -1, cut_offset = -1; /* -1: not given */
+  /* --gc, --max-run, --exclude-motif, --exclude-site (with --all-candidates): candidates dropped for their own sequence,
+   * before they are restricted or scored (gs_kmers_filter); --min-spacing D [--cut-offset C] (with --regions --per-region N):
+   * the picks of a group lie D bases apart or more (gs_design_set_spacing) */
+  cli::seq_rule_opts seq;
+  long long min_spacing = -1; /* -1: not given */
   bool selects() const { return per_region > 0 || min_spec >= 0.0f || max_feature_hits >= 0 || !pairs.empty(); }
 };
 
@@ -86,6 +91,10 @@ inline int parse_options(int argc, char **argv, int (*usage)(), options &o) {
     if (cli::candidate_option(a, i, argc, argv, o.co, bad)) {
       if (bad) return 2;
       candidate_opts_given = true;
+      continue;
+    }
+    if (cli::seq_rule_option(a, i, argc, argv, o.seq, bad)) {
+      if (bad) return 2;
       continue;
     }
     auto need = [&](const char *what) -> const char * {
@@ -146,15 +155,15 @@ inline int parse_options(int argc, char **argv, int (*usage)(), options &o) {
       (a == "--max-feature-hits" ? o.max_feature_hits : o.feature_distance) = k;
     }
     else if (a == "--pairs") o.pairs = need("--pairs");
-    else if (a == "--max-span" || a == "--min-span" || a == "--cut-offset") {
+    else if (a == "--max-span" || a == "--min-span" || a == "--cut-offset" || a == "--min-spacing") {
       const char *v = need(a.c_str());
       char *end = nullptr;
       const long long k = v[0] >= '0' && v[0] <= '9' && strlen(v) <= 18 ? strtoll(v, &end, 10) : -1;
-      if (k < 0 || !end || *end) {
+      if (k < 0 || !end || *end || (a == "--min-spacing" && k > 0xFFFFFFFFll)) {
         std::cerr << "error: " << a << " " << v << ": a number, 0 or more\n";
         return 2;
       }
-      (a == "--max-span" ? o.max_span : a == "--min-span" ? o.min_span : o.cut_offset) = k;
+      (a == "--max-span" ? o.max_span : a == "--min-span" ? o.min_span : a == "--cut-offset" ? o.cut_offset : o.min_spacing) = k;
     } else if (a == "--pair-orientation") {
       o.pair_orientation = need("--pair-orientation");
       if (o.pair_orientation != "any" && o.pair_orientation != "pam-out" && o.pair_orientation != "pam-in") {
@@ -165,9 +174,27 @@ inline int parse_options(int argc, char **argv, int (*usage)(), options &o) {
     else if (!a.empty() && a[0] != '-' && o.prefix.empty()) o.prefix = a;
     else return usage();
   }
-  if (o.pairs.empty() && (o.max_span >= 0 || o.min_span >= 0 || o.cut_offset >= 0 || !o.pair_orientation.empty())) {
+  if (o.pairs.empty() && (o.max_span >= 0 || o.min_span >= 0 || (o.cut_offset >= 0 && o.min_spacing < 0) || !o.pair_orientation.empty())) {
     std::cerr << "error: --max-span, --min-span, --cut-offset and --pair-orientation describe the pairs of --pairs FILE\n";
     return 2;
+  }
+  if (o.min_spacing >= 0 || o.seq.given) { /* refused with one line each, before the genome is read */
+    const char *why = nullptr;
+    if (o.seq.given && !o.kmers_file.empty())
+      why = "--gc, --max-run, --exclude-motif and --exclude-site drop candidates of the scan of --all-candidates; with -f the kmers file is "
+            "the user's own choice of guides";
+    else if (o.seq.given && !o.all_candidates)
+      why = "--gc, --max-run, --exclude-motif and --exclude-site drop candidates of the scan of --all-candidates";
+    else if (o.min_spacing >= 0 && !o.pairs.empty()) why = "--min-spacing spaces single guides; the pairs of --pairs have their own span rule";
+    else if (o.min_spacing >= 0 && (o.regions.empty() || !o.all_candidates))
+      why = "--min-spacing spaces the picks within the groups of --all-candidates --regions BED";
+    else if (o.min_spacing >= 0 && (o.per_region < 1 || o.per_region > 1024))
+      why = "--min-spacing needs --per-region N with N from 1 to 1024: the picks of a group are spaced one after the other";
+    else if (o.min_spacing >= 0 && o.cut_offset > (long long)o.co.k) why = "--cut-offset lies beyond the k-mer length";
+    if (why) {
+      std::cerr << "error: " << why << "\n";
+      return 2;
+    }
   }
   if (!o.pairs.empty()) { /* refused with one line each, before the genome is read */
     const char *why = nullptr;
@@ -891,7 +918,7 @@ inline bool select_design(const options &o, enumerate_job &job, candidate_set &c
     }
   }
   const bool paired = !o.pairs.empty();
-  uint64_t last[4] = {0, 0, 0, 0}, plast[6] = {0, 0, 0, 0, 0, 0};
+  uint64_t last[4] = {0, 0, 0, 0}, plast[6] = {0, 0, 0, 0, 0, 0}, spaced[2] = {0, 0};
   if (rc == GS_OK && paired) { /* --per-region counts pairs: the guides are the members of the kept ones */
     gs_pair_rule rule;
     memset(&rule, 0, sizeof rule);
@@ -920,8 +947,12 @@ inline bool select_design(const options &o, enumerate_job &job, candidate_set &c
       if (!ok) return false;
     }
   } else if (rc == GS_OK) {
-    rc = gs_design_select(cand.design, o.co.prefix.c_str(), (uint32_t)o.per_region, o.min_spec, nullptr, &cand.all);
+    if (o.min_spacing > 0)
+      rc = gs_design_set_spacing(cand.design, (uint32_t)o.min_spacing, o.cut_offset >= 0 ? (uint32_t)o.cut_offset : 3,
+                                 o.co.start ? GS_FLAG_PAM_AT_START : 0u);
+    if (rc == GS_OK) rc = gs_design_select(cand.design, o.co.prefix.c_str(), (uint32_t)o.per_region, o.min_spec, nullptr, &cand.all);
     if (rc == GS_OK) gs_design_last_select(cand.design, last);
+    if (rc == GS_OK) gs_design_last_spacing(cand.design, spaced);
   }
   if (rc == GS_OK) rc = view_kmers(cand.all, 1, &cand.n, cand.d);
   if (rc != GS_OK) {
@@ -945,6 +976,9 @@ inline bool select_design(const options &o, enumerate_job &job, candidate_set &c
             << std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count() << " s\n";
   if (o.verbose)
     std::cout << "Regions: " << last[2] << " group(s) left without a guide, " << last[3] << " group(s) short of --per-region\n";
+  if (o.min_spacing > 0)
+    std::cout << "Spacing: " << spaced[0] << " record(s) passed over within " << o.min_spacing << " base(s) of a pick, " << spaced[1]
+              << " group(s) short of --per-region for it\n";
   return true;
 }
 
@@ -964,11 +998,14 @@ inline bool scan_candidates(const options &o, const std::string &text, enumerate
   std::vector<gs_kmers *> parts;
   std::vector<gs_design *> dparts;
   gs_status rc = GS_OK;
+  uint64_t rule_counts[4] = {0, 0, 0, 0};
   if (!o.regions.empty() && !read_regions(o.regions, job.gs, co.prefix, cand)) return false;
   for (size_t c : sel) {
     gs_kmers *km = nullptr;
     rc = gs_kmers_generate(o.device, (const uint8_t *)text.data() + begin[c], job.gs.lengths[c], 0, co.pam.c_str(), (uint32_t)co.k,
                            co.start ? GS_FLAG_PAM_AT_START : 0u, nullptr, &km);
+    /* the sequence rules, on the scan's device and before anything is restricted or scored */
+    if (rc == GS_OK && (rc = cli::apply_seq_rule(o.seq, &km, rule_counts)) != GS_OK) gs_kmers_free(km);
     if (rc != GS_OK) break;
     if (cand.regions) { /* the chromosome's candidates inside the intervals; the scan itself is dropped */
       gs_design *dp = nullptr;
@@ -1002,6 +1039,10 @@ inline bool scan_candidates(const options &o, const std::string &text, enumerate
     cand.P = (uint32_t)co.pam.size();
     uint64_t n_rec = 0;
     gs_design_info(cand.design, &n_rec, nullptr);
+    if (o.seq.given) {
+      cand.n_scanned = rule_counts[0];
+      std::cout << cli::seq_rule_line(rule_counts);
+    }
     std::cout << "Scanned " << cand.n_scanned << " candidate(s) of " << sel.size() << " chromosome(s), " << n_rec
               << " record(s) inside the regions, in " << std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count() << " s\n";
     /* a selection by specificity waits for the index (select_design); otherwise the records are ordered now, and -t is the
@@ -1029,6 +1070,7 @@ inline bool scan_candidates(const options &o, const std::string &text, enumerate
   job.cand = &cand;
   /* 2L + 3P > 59: no batch fits the fast path's key, every one takes the host route */
   job.cand_device = (o.encoder == "gpu" || o.bgzf == "gpu") && o.gpus == 1 && cand.L <= 31 && 2 * cand.L + 3 * cand.P <= 59;
+  if (o.seq.given) std::cout << cli::seq_rule_line(rule_counts);
   std::cout << "Scanned " << cand.n << " candidate(s) of " << sel.size() << " chromosome(s) in "
             << std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count() << " s\n";
   return true;

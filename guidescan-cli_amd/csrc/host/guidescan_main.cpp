@@ -55,6 +55,13 @@
  *       --min-specificity, -t and --max-feature-hits say which guides may pair.  PAIRS.csv is the table
  *       group,id_a,id_b,chromosome,cut_a,cut_b,span,specificity_a,specificity_b,pair_specificity; the guides of the kept
  *       pairs are the guides of the command, so OUT is their database in any format.  The score phase always runs.
+ *       --gc MIN:MAX, --max-run R, --exclude-motif M1,..., --exclude-site M1,... (`kmers` too; no counterpart in the
+ *       reference): candidates dropped for their own protospacer, on the scan's device and before anything is restricted
+ *       or scored (gs_kmers_filter; the rule is csrc/gs_select_scan.h's).  One line reports kept of scanned and the three
+ *       counts.  With -f they are refused: a given file is the user's own choice of guides.
+ *       --min-spacing D [--cut-offset C] (with --regions --per-region N, N <= 1024; no counterpart in the reference): best
+ *       first, a guide whose cut lies fewer than D bases from one already picked for the group on the same chromosome is
+ *       passed over (gs_design_set_spacing; one wave walks a group).  Not with --pairs, which has its own span rule.
  *       With -t and neither selection option there is no score phase: the pipeline's own threshold pass drops the guides.
  *       -f KMERS.csv --kmers gpu: the kmers file is parsed on the first device (gs_kmers_parse_file, the rules of
  *       cli::read_kmers) and the command goes on as --all-candidates does from its scan: sequences, PAMs, ids and
@@ -167,6 +174,10 @@ int usage() {
                "                 [--start] [--chromosomes a,b,...] [--device D] [--regions BED]\n"
                "                 --regions BED: only candidates inside the file's intervals (chromosome, start, end, [group]),\n"
                "                 one row per group, ids {prefix}{group}:{chr}:{position}:{sense}, ordered by group\n"
+               "                 [--gc MIN:MAX] [--max-run R] [--exclude-motif M1,M2,...] [--exclude-site M1,M2,...]\n"
+               "                 sequence rules on the protospacer as the sequence column prints it (the PAM is not looked at):\n"
+               "                 G+C percentage within MIN:MAX, no letter more than R times in a row, none of the IUPAC motifs\n"
+               "                 (at most 16 of 1 to 32 letters); --exclude-site also excludes each reverse complement\n"
                "       guidescan enumerate PREFIX (-f KMERS | --all-candidates) -o OUT [-m N] [-a PAM]... [--format csv|sam|bam]\n"
                "                 [--mode succinct|complete] [--max-off-targets N] [--start]\n"
                "                 [--rna-bulges N] [--dna-bulges N] [--bulge-form walk|seeded] [-t THRESHOLD] [-n FORMAT_THREADS]\n"
@@ -183,6 +194,11 @@ int usage() {
                "                 to X bases apart, the cut C (default 3) protospacer bases from the PAM; pam-out: the PAMs face\n"
                "                 away from each other.  Ranked by the smaller specificity of the two; --per-region N keeps the best\n"
                "                 N pairs of each group.  PAIRS.csv is their table, OUT the database of their guides.\n"
+               "                 [--gc MIN:MAX] [--max-run R] [--exclude-motif M1,M2,...] [--exclude-site M1,M2,...]\n"
+               "                 (with --all-candidates) the sequence rules of `kmers`: a candidate they drop is never scored\n"
+               "                 [--min-spacing D [--cut-offset C]] (with --regions --per-region N, N <= 1024, not with --pairs):\n"
+               "                 best first, a guide is skipped when its cut lies fewer than D bases from a guide already\n"
+               "                 picked for the group on the same chromosome\n"
                "                 [--annotate BED [--max-feature-hits K [--feature-distance D]]]\n"
                "                 --annotate (CSV only): a match_features column, the groups of the BED file that each printed\n"
                "                 off-target overlaps, joined by ';', or NA.  --max-feature-hits K (with --regions): a candidate\n"
@@ -301,17 +317,19 @@ int do_index(int argc, char **argv) {
 int do_kmers(int argc, char **argv) {
   std::string prefix, output, regions;
   candidate_opts co;
+  cli::seq_rule_opts so;
+  uint64_t rule_counts[4] = {0, 0, 0, 0};
   int device = 0;
   for (int i = 0; i < argc; i++) {
     const std::string a = argv[i];
     bool bad = false;
-    if (candidate_option(a, i, argc, argv, co, bad)) {
+    if (candidate_option(a, i, argc, argv, co, bad) || cli::seq_rule_option(a, i, argc, argv, so, bad)) {
       if (bad) return 2;
     } else if ((a == "-o" || a == "--output") && i + 1 < argc)
       output = argv[++i];
     else if (a == "--regions" && i + 1 < argc)
       regions = argv[++i];
-    else if (a == "--per-region" || a == "--min-specificity" || a == "--pairs") {
+    else if (a == "--per-region" || a == "--min-specificity" || a == "--pairs" || a == "--min-spacing") {
       std::cerr << "error: " << a << " ranks guides by specificity, which takes the index: use guidescan enumerate --all-candidates --regions\n";
       return 2;
     }
@@ -365,6 +383,7 @@ int do_kmers(int argc, char **argv) {
     gs_kmers *km = nullptr;
     rc = gs_kmers_generate(device, (const uint8_t *)text.data() + begin[c], gs.lengths[c], 0, co.pam.c_str(), (uint32_t)co.k,
                            co.start ? GS_FLAG_PAM_AT_START : 0u, nullptr, &km);
+    if (rc == GS_OK && (rc = cli::apply_seq_rule(so, &km, rule_counts)) != GS_OK) gs_kmers_free(km);
     if (rc != GS_OK) break;
     auto t2 = std::chrono::steady_clock::now();
     s_scan += std::chrono::duration<double>(t2 - t1).count();
@@ -427,6 +446,7 @@ int do_kmers(int argc, char **argv) {
   }
   std::cout << "Wrote " << total << " candidate(s) of " << sel.size() << " chromosome(s) to " << output << " in "
             << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s\n";
+  if (so.given) std::cout << cli::seq_rule_line(rule_counts);
   std::cout << "Stages: scan " << s_scan << " s, rows " << s_rows << " s, file writes " << s_write << " s\n";
   return 0;
 }

@@ -972,6 +972,68 @@ gs_status gs_debug_pairs_host(uint64_t n, const uint32_t *group, const uint32_t 
  * value.  For tests */
 uint64_t gs_debug_pairs_chunk(uint64_t set);
 
+/* ---- library selection: sequence rules on the candidates, spacing between the picks of a group ------------------------ */
+/* The reference has no counterpart for anything in this section: its users filter the genome-wide table in a script.  The
+ * rules, stated once (gs_select_scan.h).  Sequence rule: over the k protospacer bytes of a candidate as the kmers file's
+ * `sequence` column prints them (guide orientation, both senses, with and without --start; the PAM is not looked at; any
+ * case).  With g the number of G and C the candidate passes iff gc_min * k <= 100 * g <= gc_max * k; iff no letter stands
+ * more than max_run times in a row (0: no bound); and iff no motif matches at any offset, a position matching when the
+ * base is in the IUPAC letter's set.  A failing candidate is charged to the first rule it fails: GC, run, motif. */
+#define GS_SEQ_MOTIFS 16u        /* at most, after the expansion of sites */
+#define GS_SEQ_MOTIF_LETTERS 32u /* of one motif, at most */
+typedef struct gs_seq_rule {
+  uint32_t gc_min, gc_max; /* percent, 0 <= gc_min <= gc_max <= 100; 0 and 100: no bound */
+  uint32_t max_run;        /* 0: no bound */
+  uint32_t n_motifs;
+  uint8_t motif_len[GS_SEQ_MOTIFS];
+  /* one 4-bit set per position (A = 1, C = 2, G = 4, T = 8), two positions to a byte, the even one in the low half */
+  uint8_t motif_set[GS_SEQ_MOTIFS][GS_SEQ_MOTIF_LETTERS / 2];
+} gs_seq_rule;
+/* the rule that passes everything (no counterpart in the reference): gc 0:100, no run bound, no motif */
+gs_status gs_seq_rule_init(gs_seq_rule *rule);
+/* One more motif over ACGTRYSWKMBDHVN, either case (no counterpart in the reference); both_strands != 0 adds its reverse
+ * complement too, the IUPAC complement letter by letter, unless that is the motif itself.  GS_ERR_FORMAT, and
+ * gs_status_string(GS_ERR_FORMAT) reads as one line that names the motif: an empty motif, one of more than
+ * GS_SEQ_MOTIF_LETTERS letters, a letter outside the alphabet, or a motif beyond GS_SEQ_MOTIFS; the rule is then unchanged. */
+gs_status gs_seq_rule_add_motif(gs_seq_rule *rule, const char *motif, int both_strands);
+/* The candidates of a scan that pass the rule, as a fresh object in HBM on the scan's device, in the scan's order (no
+ * counterpart in the reference): one lane per candidate evaluates the rule, a 64-bit scan of the flags, a gather.  counts:
+ * candidates in, failed by GC, by run, by motif.  Called before gs_kmers_encode_ids: GS_ERR_ARG on an object that has ids,
+ * on the rows of a kmers file, and for a rule outside its bounds.  `km` is unchanged and still the caller's. */
+gs_status gs_kmers_filter(gs_kmers *km, const gs_seq_rule *rule, void *stream, gs_kmers **out, uint64_t counts[4]);
+/* the milliseconds of the three passes that made a gs_kmers_filter's result, between events on its stream (no counterpart
+ * in the reference): rule, scan, gather */
+gs_status gs_debug_kmers_filter_ms(const gs_kmers *filtered, double out[3]);
+/* Host only: the rule through gs_select_scan.h on n sequences of k bytes back to back, with no device (no counterpart in
+ * the reference).  charge[i]: 0 where sequence i passes, else 1, 2 or 3 for GC, run, motif; counts as above. */
+gs_status gs_debug_kmers_filter_host(const uint8_t *seqs, uint64_t n, uint32_t k, const gs_seq_rule *rule, uint8_t *charge,
+                                     uint64_t counts[4]);
+
+/* Spacing (no counterpart in the reference), over the order of gs_design_select: walk a group's marked records (eligible
+ * and specificity >= min_specificity) in that order and keep a record iff every record already kept in this group on the
+ * same chromosome has its cut at least min_spacing bases away; stop at per_region kept.  The cut is that of the pairs
+ * section with cut_offset and flags (GS_FLAG_PAM_AT_START).  min_spacing 0 takes the rule off: the selection is then the
+ * code and the bytes it was.  With the rule set gs_design_select and gs_design_rows need 1 <= per_region <= 1024
+ * (GS_ERR_ARG otherwise, with a message), and gs_design_pairs is GS_ERR_ARG.  GS_ERR_ARG: cut_offset > k, another flag. */
+gs_status gs_design_set_spacing(gs_design *design, uint32_t min_spacing, uint32_t cut_offset, uint32_t flags);
+/* of the last gs_design_select / gs_design_rows under the rule (no counterpart in the reference): the marked records the
+ * walks passed over for spacing, and the groups left short of per_region that hold at least per_region marked records */
+gs_status gs_design_last_spacing(const gs_design *design, uint64_t out[2]);
+/* the milliseconds of that selection's walk kernel alone, between events on its stream (no counterpart in the reference) */
+gs_status gs_debug_design_space_ms(const gs_design *design, double *ms);
+/* Host only: gs_debug_design_host with the rule's three arguments, through gs_select_scan.h (no counterpart in the
+ * reference).  report (or NULL): what gs_design_last_select and gs_design_last_spacing would give, six numbers. */
+gs_status gs_debug_design_host_spaced(const gs_regions *regions, uint32_t n_parts, const uint32_t *chr_index, const uint64_t *n,
+                                      const uint8_t *const *seqs, const uint32_t *const *positions, const uint8_t *const *senses,
+                                      const float *const *specificity, const uint8_t *const *eligible, const char *pam, uint32_t k,
+                                      const char *prefix, uint32_t per_region, float min_specificity, uint32_t min_spacing,
+                                      uint32_t cut_offset, uint32_t flags, gs_kmers **out, char **rows, uint64_t *rows_len,
+                                      uint64_t *report);
+/* Specificities and eligibility bytes of a design's n records from host arrays, in record order; the design then counts
+ * as scored (no counterpart in the reference).  eligible NULL: every record.  For tests: the selection kernels run on
+ * chosen ranks and ties without a search. */
+gs_status gs_debug_design_set_scores(gs_design *design, const float *specificity, const uint8_t *eligible);
+
 /* The column (no counterpart in the reference).  GS_TEXT_FEATURES: the CSV header ends in ",match_features" and every CSV
  * row ends in ',' and the names of the row's features joined by ';', or "NA" if it has none; the `NA` row of a guide without
  * hits ends in ",NA" too.  Both modes.  Together with GS_TEXT_SAM or GS_TEXT_BAM: GS_ERR_ARG, in every entry point below
