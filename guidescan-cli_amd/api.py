@@ -98,6 +98,18 @@ class GsSeqRule(C.Structure):
                 ("motif_len", C.c_uint8 * 16), ("motif_set", (C.c_uint8 * 16) * 16)]
 
 
+class GsControlsRule(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("first", C.c_uint64), ("n", C.c_uint64), ("max_candidates", C.c_uint64), ("round", C.c_uint64),
+                ("L", C.c_uint32), ("n_alt", C.c_uint32), ("mismatches", C.c_uint32), ("flags", C.c_uint32),
+                ("min_distance", C.c_uint32), ("pad", C.c_uint32), ("pam", C.c_char_p), ("alt_pams", C.c_char_p),
+                ("seq_rule", C.POINTER(GsSeqRule)), ("id_prefix", C.c_char_p)]
+
+
+class GsControlsReport(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("kept", "looked_at", "gc", "run", "motif", "targeting", "close", "last_counter", "rounds")] + \
+               [("ms", C.c_double * 5)]
+
+
 class GsPairRule(C.Structure):
     _fields_ = [("min_span", C.c_uint64), ("max_span", C.c_uint64), ("cut_offset", C.c_uint32), ("orientation", C.c_uint32),
                 ("per_region", C.c_uint32), ("flags", C.c_uint32), ("min_specificity", C.c_float), ("pad", C.c_uint32)]
@@ -425,6 +437,19 @@ def lib():
                                               C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), vp]
     L.gs_debug_design_set_scores.restype = i32
     L.gs_debug_design_set_scores.argtypes = [vp, vp, vp]
+    L.gs_controls_generate.restype = i32
+    L.gs_controls_generate.argtypes = [vp, C.POINTER(GsControlsRule), vp, C.POINTER(vp), C.POINTER(GsControlsReport)]
+    L.gs_controls_rows.restype = i32
+    L.gs_controls_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.gs_controls_counters.restype = i32
+    L.gs_controls_counters.argtypes = [vp, C.POINTER(u64), C.POINTER(vp)]
+    L.gs_debug_controls_host.restype = i32
+    L.gs_debug_controls_host.argtypes = [C.POINTER(GsControlsRule), vp, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64),
+                                         C.POINTER(GsControlsReport)]
+    L.gs_debug_controls_sequences.restype = i32
+    L.gs_debug_controls_sequences.argtypes = [u64, u64, u64, u32, vp]
+    L.gs_debug_controls_round.restype = u64
+    L.gs_debug_controls_round.argtypes = [u64]
     L.gs_decoder_set_annotation.restype = i32
     L.gs_decoder_set_annotation.argtypes = [vp, vp]
     L.gs_debug_decode_annot_ms.restype = i32
@@ -476,7 +501,9 @@ EXPORTS = ["gs_index_build", "gs_index_build_with_sa", "gs_index_open_sdsl", "gs
            "gs_debug_pairs_chunk",
            "gs_seq_rule_init", "gs_seq_rule_add_motif", "gs_kmers_filter", "gs_debug_kmers_filter_ms", "gs_debug_kmers_filter_host",
            "gs_design_set_spacing", "gs_design_last_spacing", "gs_debug_design_space_ms", "gs_debug_design_host_spaced",
-           "gs_debug_design_set_scores"]
+           "gs_debug_design_set_scores",
+           "gs_controls_generate", "gs_controls_rows", "gs_controls_counters", "gs_debug_controls_host",
+           "gs_debug_controls_sequences", "gs_debug_controls_round"]
 
 
 def _check(rc):
@@ -902,6 +929,20 @@ class DeviceKmers:
         km.filter_ms = dict(zip(("rule", "scan", "gather"), (float(x) for x in ms)))
         return km
 
+    def controls_rows(self) -> bytes:
+        """the kmers-file rows "id,sequence,pam,NA,0,+" of the controls api.controls made, no header (gs_controls_rows)"""
+        out, ln = C.c_void_p(), C.c_uint64()
+        _check(lib().gs_controls_rows(self._h, C.byref(out), C.byref(ln)))
+        s = C.string_at(out, ln.value)
+        lib().gs_free(out)
+        return s
+
+    def control_counters(self):
+        """the counters of the controls api.controls made, in order (gs_controls_counters) -> uint64[n]"""
+        n, p = C.c_uint64(), C.c_void_p()
+        _check(lib().gs_controls_counters(self._h, C.byref(n), C.byref(p)))
+        return np.frombuffer(C.string_at(p, 8 * n.value), dtype=np.uint64).copy() if n.value else np.empty(0, np.uint64)
+
     def restrict(self, regions, chr_index):
         """the records of this scan - of chromosome chr_index of the regions' structure - that lie in a group of
         `regions` (gs_design_restrict) -> Design"""
@@ -929,6 +970,84 @@ def _selected_kmers(h, k, P):
     _check(lib().gs_kmers_get(h, 0, C.byref(n), None, None, None, None))
     km.n = int(n.value)
     return km
+
+
+CONTROLS_COUNTS = ("kept", "looked_at", "gc", "run", "motif", "targeting", "close", "last_counter", "rounds")
+CONTROLS_STAGES = ("generate", "search", "keep", "distance", "ids")
+
+
+def _controls_rule(n, L, pam, seed, first, mismatches, alt_pams, start, seq_rule, min_distance, max_candidates, round, prefix,
+                   no_new_tables=False):
+    """-> (GsControlsRule, what it points to: keep alive for the call)"""
+    alts = "".join(alt_pams).encode()
+    if any(len(p) != len(pam) for p in alt_pams):
+        raise ValueError("an alt PAM has the PAM's length")
+    keep = (pam.encode(), alts, prefix.encode(), seq_rule)
+    r = GsControlsRule(seed=seed, first=first, n=n, max_candidates=max_candidates, round=round, L=L, n_alt=len(alt_pams),
+                       mismatches=mismatches, flags=(1 if start else 0) | (16 if no_new_tables else 0), min_distance=min_distance,
+                       pam=keep[0], alt_pams=keep[1] if alt_pams else None,
+                       seq_rule=C.pointer(seq_rule.c) if seq_rule is not None else None, id_prefix=keep[2])
+    return r, keep
+
+
+def _controls_report(rep):
+    out = {k: int(getattr(rep, k)) for k in CONTROLS_COUNTS}
+    out["ms"] = dict(zip(CONTROLS_STAGES, (float(x) for x in rep.ms)))
+    return out
+
+
+def controls(index, n, L=20, pam="NGG", seed=0, first=0, mismatches=3, alt_pams=(), start=False, seq_rule=None, min_distance=1,
+             max_candidates=1 << 32, round=0, prefix="control_", no_new_tables=False):
+    """Non-targeting controls (gs_controls_generate; the rules are csrc/gs_controls_scan.h's): the first n candidates of
+    the seed's counter sequence from `first` that pass seq_rule (a SeqRule), have no site within `mismatches` under pam and
+    alt_pams, and lie min_distance mismatches or more from every control kept before them; at most max_candidates are
+    looked at.  -> (DeviceKmers with ids "{prefix}{counter}" from the start, as a parsed object: .controls_rows() its
+    kmers-file rows, .control_counters() the kept counters; report: dict of kept, looked_at, gc, run, motif, targeting,
+    close, last_counter, rounds and ms by stage).  Fewer than n kept is no error: report["kept"] says so.  round: counters
+    per device round (0: the default); the result does not depend on it."""
+    r, keep = _controls_rule(n, L, pam, seed, first, mismatches, alt_pams, start, seq_rule, min_distance, max_candidates, round, prefix,
+                             no_new_tables)
+    h, rep = C.c_void_p(), GsControlsReport()
+    _check(lib().gs_controls_generate(index._h, C.byref(r), None, C.byref(h), C.byref(rep)))
+    km = DeviceKmers.__new__(DeviceKmers)
+    km._h, km.k, km.P, km.pos_ptr = h, L, len(pam), None
+    a, b, d, m = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+    _check(lib().gs_kmers_get(h, 1, C.byref(m), C.byref(a), C.byref(b), None, C.byref(d)))
+    km.n, km.seqs_ptr, km.pams_ptr, km.sense_ptr = int(m.value), a.value, b.value, d.value
+    _check(lib().gs_kmers_get_ids(h, 1, C.byref(a), C.byref(b), C.byref(d)))
+    km.ids_ptr, km.id_offsets_ptr, km.sense_positive_ptr = a.value, b.value, d.value
+    km.report = _controls_report(rep)                      # as a parsed object: no positions
+    return km, km.report
+
+
+def controls_round(set_to=0) -> int:
+    """the counters of a device round where the call says 0 (gs_debug_controls_round); set_to != 0 sets it"""
+    return int(lib().gs_debug_controls_round(set_to))
+
+
+def controls_host_model(targeting, n, L=20, pam="NGG", seed=0, first=0, seq_rule=None, min_distance=1, max_candidates=1 << 32,
+                        prefix="control_", round=0):
+    """the walk on the host through the kernels' shared header, no GPU and no search (gs_debug_controls_host).  targeting:
+    one byte per candidate from `first`, nonzero where it has a hit; round != 0: the walk cut into rounds as the device cuts it
+    -> (kept counters uint64[kept], rows bytes, report)"""
+    t = np.ascontiguousarray(np.asarray(targeting) != 0, dtype=np.uint8)
+    r, keep = _controls_rule(n, L, pam, seed, first, 0, (), False, seq_rule, min_distance, max_candidates, round, prefix)
+    kc, rows, ln, rep = C.c_void_p(), C.c_void_p(), C.c_uint64(), GsControlsReport()
+    _check(lib().gs_debug_controls_host(C.byref(r), t.ctypes.data if t.size else None, t.size, C.byref(kc), C.byref(rows), C.byref(ln),
+                                        C.byref(rep)))
+    report = _controls_report(rep)
+    counters = np.frombuffer(C.string_at(kc, 8 * report["kept"]), dtype=np.uint64).copy()
+    text = C.string_at(rows, ln.value)
+    lib().gs_free(kc)
+    lib().gs_free(rows)
+    return counters, text, report
+
+
+def control_sequences(seed, first, n, L):
+    """the generator alone (gs_debug_controls_sequences) -> uint8[n, L], candidates first .. first + n - 1"""
+    out = np.empty((n, L), dtype=np.uint8)
+    _check(lib().gs_debug_controls_sequences(seed, first, n, L, out.ctypes.data if n else None))
+    return out
 
 
 class RegionsFileError(GsError):

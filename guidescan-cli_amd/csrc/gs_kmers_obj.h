@@ -29,6 +29,11 @@ struct gs_kmers {
   std::vector<uint8_t> h_ids, h_sense01;
   std::vector<uint64_t> h_id_off;
   double filter_ms[3] = {0, 0, 0}; /* made by gs_kmers_filter: its rule, scan and gather passes between stream events */
+  /* made by gs_controls_generate (gs_controls.hip): a parsed object in every respect, plus the kept counters and the id
+   * prefix its rows are written with */
+  bool controls = false;
+  std::vector<uint64_t> h_counters;
+  std::string ct_prefix;
 };
 
 /* frees the object and its arrays in HBM (gs_kmers_free; the deleter of an object under construction) */

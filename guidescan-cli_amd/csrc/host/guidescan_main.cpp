@@ -3,7 +3,7 @@
  * (src/guidescan.cxx:28-95, 316-358) and database output, and calls the MI355X path through the
  * C-ABI (include/guidescan_amd.h).  Control plane only: no search logic lives here.
  * Here: the dispatch, usage, `index`, `kmers` and `sam2bam`.  `enumerate` is enumerate_cmd.hpp over the ordered batch
- * pipeline of batch_pipeline.hpp, `decode` is decode_cmd.hpp, the readers and candidate options the commands share are
+ * pipeline of batch_pipeline.hpp, `decode` is decode_cmd.hpp, `controls` is controls_cmd.hpp, the readers and candidate options the commands share are
  * cli_common.hpp, the BAM records and BGZF blocks of the host are bam_writer.hpp.
  *
  *   guidescan index  [--index PREFIX] [--store-sa] [--sdsl] [--device D] [--fasta host|gpu] [--verbose] GENOME.fa
@@ -96,6 +96,7 @@
 #include "guidescan_amd.h"
 #include "bam_writer.hpp"
 #include "cli_common.hpp"
+#include "controls_cmd.hpp"
 #include "decode_cmd.hpp"
 #include "enumerate_cmd.hpp"
 #include "fasta_names.hpp"
@@ -203,6 +204,14 @@ int usage() {
                "                 --annotate (CSV only): a match_features column, the groups of the BED file that each printed\n"
                "                 off-target overlaps, joined by ';', or NA.  --max-feature-hits K (with --regions): a candidate\n"
                "                 with more than K off-targets within D mismatches (default: -m) inside a feature is not eligible\n"
+               "       guidescan controls PREFIX -o KMERS -n N [--seed S] [--first I] [--pam NGG] [--kmer-length 20] [--start]\n"
+               "                 [-m 3] [-a PAM]... [--gc MIN:MAX] [--max-run R] [--exclude-motif M1,...] [--exclude-site M1,...]\n"
+               "                 [--min-distance H] [--max-candidates C] [--allow-short] [--prefix control_] [--device D] [--verbose]\n"
+               "                 non-targeting controls as a kmers file for enumerate -f: candidate I of seed S is a fixed random\n"
+               "                 protospacer; it is dropped by the sequence rules, by any site within -m mismatches (the -a PAMs\n"
+               "                 included), or by fewer than H (default 1) mismatches to a control already kept; the first N that\n"
+               "                 remain are written, ids {prefix}{I}.  Fewer than N after C (default 2^32) candidates: exit 1 and no\n"
+               "                 file, unless --allow-short.  A smaller N (at most 16384) gives the head of the same file.\n"
                "       guidescan decode [--mode succinct|complete] [--device D] [-o OUT] [--batch-size RECORDS] [--verbose]\n"
                "                 [--bgzf host|gpu] [--fasta host|gpu] [--annotate BED [--features-only]] DATABASE GENOME.fa\n"
                "                 --annotate: the features of a BED file, read against the database's @SQ lines, in the pass that\n"
@@ -511,6 +520,7 @@ int main(int argc, char **argv) {
   if (!strcmp(argv[1], "index")) return do_index(argc - 2, argv + 2);
   if (!strcmp(argv[1], "kmers")) return do_kmers(argc - 2, argv + 2);
   if (!strcmp(argv[1], "enumerate")) return enumerate_cmd::run(argc - 2, argv + 2, usage);
+  if (!strcmp(argv[1], "controls")) return controls_cmd::run(argc - 2, argv + 2, usage);
   if (!strcmp(argv[1], "decode")) {
     const int rc = decode_cmd::run(argc - 2, argv + 2);
     return rc == 2 ? usage() : rc;

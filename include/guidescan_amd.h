@@ -1034,6 +1034,79 @@ gs_status gs_debug_design_host_spaced(const gs_regions *regions, uint32_t n_part
  * chosen ranks and ties without a search. */
 gs_status gs_debug_design_set_scores(gs_design *design, const float *specificity, const uint8_t *eligible);
 
+/* ---- non-targeting controls for a library: `guidescan controls` ------------------------------------------------------- */
+/* The reference has no counterpart for anything in this section: its manual strips the CTRL guides out of its example
+ * library before analysing it (manual/manual.tex:403-411), and the only way to make them is to draw random protospacers
+ * and search each.  The rules, stated once (gs_controls_scan.h).  Candidate i is a 64-bit counter from `first`; for seed s
+ * its protospacer is a pure function of (s, i, L): with mix(x) the splitmix64 finaliser (x += 0x9E3779B97F4A7C15, two
+ * xor-shift-multiplies by 0xBF58476D1CE4E5B9 and 0x94D049BB133111EB, x ^ x >> 31), w = mix(mix(s) ^ i) and base j of the
+ * sequence column is "ACGT"[(w >> 2j) & 3]; the PAM column is the pattern.  Candidates are walked in ascending i and each
+ * is charged to the first thing it fails: the sequence rule (GC, run, motif, as above), targeting (its hit list on the
+ * fast path under `mismatches`, the pattern, the alt PAMs and GS_FLAG_PAM_AT_START is not empty - before positions are
+ * resolved, so a site across a chromosome boundary disqualifies too), close (fewer than min_distance mismatches to a
+ * control already kept).  Otherwise it is kept.  The walk stops at the candidate that makes n kept or after
+ * max_candidates.  The kept list, its order and every count depend on these arguments and the genome only, never on the
+ * round size or the device; the controls for n = a are the first a of those for n = b > a. */
+typedef struct gs_controls_rule {
+  uint64_t seed, first;
+  uint64_t n;              /* controls wanted, 1 .. 16,384 (the walk keeps a round's controls in LDS) */
+  uint64_t max_candidates; /* 0: 2^32 */
+  uint64_t round;          /* counters generated per round, at most 2^24; 0: the default (2^20, gs_debug_controls_round) */
+  uint32_t L;              /* 1 .. 31, and 2L + 3P <= 59 where the device searches */
+  uint32_t n_alt;
+  uint32_t mismatches;
+  /* GS_FLAG_PAM_AT_START; GS_FLAG_NO_NEW_TABLES: never build derived tables.  Without it the call still builds none before it
+   * has searched 5 candidates per 1,000 genome bases, the tables' break-even; tables the handle holds already are used */
+  uint32_t flags;
+  uint32_t min_distance;   /* 1 drops exact repeats only, 0 nothing */
+  uint32_t pad;
+  const char *pam;                /* the pattern, P <= 8 symbols, NUL terminated */
+  const char *alt_pams;           /* n_alt * P bytes, or NULL */
+  const gs_seq_rule *seq_rule;    /* NULL: none */
+  const char *id_prefix;          /* NULL: "control_"; at most 255 bytes */
+} gs_controls_rule;
+typedef struct gs_controls_report {
+  uint64_t kept;         /* controls kept */
+  uint64_t looked_at;    /* candidates from `first` to the last one looked at, inclusive */
+  uint64_t gc, run, motif; /* of those: charged to the sequence rule */
+  uint64_t targeting;    /* charged for a hit list that is not empty */
+  uint64_t close;        /* charged to the distance rule */
+  uint64_t last_counter; /* counter of the last candidate looked at (`first` when none was) */
+  uint64_t rounds;       /* rounds run */
+  /* milliseconds between events in the stream, summed over the rounds: generate + rule + compaction, search, keep +
+   * compaction, distance (both kernels and the count of the charges), ids */
+  double ms[5];
+} gs_controls_report;
+/* The controls as a gs_kmers object in HBM on the handle's device, ids "{prefix}{i}" (i in decimal) from the start (no
+ * counterpart in the reference).  Its positions and ids behave as a parsed object's: gs_kmers_get gives NULL positions and
+ * '+' senses, gs_kmers_encode_ids and gs_kmers_csv are GS_ERR_ARG, and its arrays are what gs_enumerate_text_device /
+ * gs_format_device_ids take.  Per round: k_ct_generate (one lane per counter: word, sequence rule), a scan and a gather
+ * into the layout gs_enumerate_device takes, the search under the handle's lock, k_ct_keep (empty hit list?), a scan and a
+ * gather, k_ct_old (against the controls of earlier rounds), k_ct_walk (one wave, in counter order, 64 a step).  Fewer than
+ * n kept is still GS_OK and an object: report->kept says so.  GS_ERR_UNSUPPORTED with a message: 2L + 3P > 59, or a
+ * candidate the fast path does not take (a PAM symbol outside A,C,G,T,N).  GS_ERR_ARG: a rule outside its bounds,
+ * first + max_candidates beyond 2^64. */
+gs_status gs_controls_generate(gs_index *ix, const gs_controls_rule *rule, void *stream, gs_kmers **out, gs_controls_report *report);
+/* the kmers-file rows "id,sequence,pam,NA,0,+\n" of such an object (no counterpart in the reference; the reference's reader
+ * wants the three location columns, src/genomics/kmer.cxx:9-25, its printers never look at them): rows only, no header;
+ * *text is malloc'ed (NUL terminated, *len bytes before the terminator): release with gs_free.  GS_ERR_ARG on any other object */
+gs_status gs_controls_rows(gs_kmers *controls, char **text, uint64_t *len);
+/* the kept counters in order, n entries owned by the object (no counterpart in the reference) */
+gs_status gs_controls_counters(gs_kmers *controls, uint64_t *n, const uint64_t **counters);
+/* Host only: the walk through gs_controls_scan.h with no device and no search (no counterpart in the reference).
+ * targeting[j] != 0: candidate first + j has a hit - the caller says, the tests take it from the oracle; the walk looks at
+ * min(n_candidates, max_candidates) candidates at most.  *counters (the kept counters, report->kept of them) and *rows are
+ * malloc'ed: release with gs_free.  rule->round != 0: the walk is cut into rounds of that many candidates the way the
+ * device cuts it (earlier rounds' controls first, then the round's own walk), which must change nothing.  flags, mismatches
+ * and alt PAMs are not looked at; ms stays 0, rounds 0. */
+gs_status gs_debug_controls_host(const gs_controls_rule *rule, const uint8_t *targeting, uint64_t n_candidates, uint64_t **counters, char **rows,
+                                 uint64_t *rows_len, gs_controls_report *report);
+/* Host only: the generator alone (no counterpart in the reference): out gets n * L ASCII bytes, candidates first .. first + n - 1 */
+gs_status gs_debug_controls_sequences(uint64_t seed, uint64_t first, uint64_t n, uint32_t L, uint8_t *out);
+/* the counters of a round where the rule says 0 (no counterpart in the reference): set != 0 sets it (at most 2^24) for every
+ * later call of the process; -> the value.  For tests */
+uint64_t gs_debug_controls_round(uint64_t set);
+
 /* The column (no counterpart in the reference).  GS_TEXT_FEATURES: the CSV header ends in ",match_features" and every CSV
  * row ends in ',' and the names of the row's features joined by ';', or "NA" if it has none; the `NA` row of a guide without
  * hits ends in ",NA" too.  Both modes.  Together with GS_TEXT_SAM or GS_TEXT_BAM: GS_ERR_ARG, in every entry point below
